@@ -236,6 +236,55 @@ def test_every_emitted_fraction_follows_and_none_exceeds_one(tmp_path, monkeypat
     assert bench.sanitize_fractions(line) == []
 
 
+def test_full_and_dump_outputs_flags():
+    """A plain run is the headline alone; --full adds the measurements with runs of their own; --dump-outputs names a directory."""
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+    # a train dump replays the last timed step on one rank: a data-parallel run is refused before anything starts
+    for extra in (["--gpus", "2"], ["--dp-single"]):
+        env = dict(os.environ)
+        env.pop("WORLD_SIZE", None)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "out", *extra], capture_output=True,
+                           text=True, env=env, timeout=300)
+        assert p.returncode != 0 and "replays a train step on one rank" in p.stderr, extra
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    import collections
+    import types
+    import numpy as np
+    import torch
+    # the same seeded rows every time, in increasing order; every row when there are few
+    n = bench.DUMP_ROWS * 3 + 5
+    rows = bench.sample_rows(n)
+    assert len(rows) == bench.DUMP_ROWS and np.array_equal(rows, bench.sample_rows(n)) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(bench.sample_rows(10), np.arange(10))
+    # train: the loss trainStep returned, the render of the step's forward and the parameters of the model
+    Model = collections.namedtuple("Model", "getParams")
+    params = {"xyz": torch.arange(n * 3, dtype=torch.float32).reshape(n, 3), "opacity": torch.ones(n, 1)}
+    arrays = bench.step_outputs("train", torch.tensor([1.0, 2.0, 3.0, 4.0]), Model(lambda: params),
+                                types.SimpleNamespace(_fused={"color": torch.zeros(20, 3)}, H=4, W=5))
+    nbytes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert set(got) == {"loss", "render", "xyz", "opacity", "rows"} and nbytes <= bench.DUMP_BYTES
+    assert got["render"].shape == (4, 5, 3)
+    assert got["xyz"].dtype == np.float32 and got["xyz"].shape == (bench.DUMP_ROWS, 3) and got["rows"].dtype == np.float64
+    assert np.array_equal(got["xyz"], params["xyz"].numpy()[rows]) and np.array_equal(got["rows"], rows)
+    assert np.array_equal(got["loss"], [1, 2, 3, 4])
+    # fwdbwd: the render of the step and the gradients
+    Res = collections.namedtuple("Res", "render depth alpha")
+    res = Res(torch.zeros(4, 5, 3), None, torch.ones(4, 5, 1))
+    arrays = bench.step_outputs("fwdbwd", (res, {"xyz": torch.zeros(7, 3)}), None)
+    assert set(arrays) == {"render", "alpha", "grad_xyz"}
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert sorted(f.name for f in (tmp_path / "b").iterdir()) == ["alpha.npy", "grad_xyz.npy", "render.npy"]
+    assert set(bench.step_outputs("forward", res, None)) == {"render", "alpha"}
+    with pytest.raises(SystemExit):
+        bench.step_outputs("forward", None, None)
+
+
 def test_physical_cores_counts_smt_siblings_once():
     threads = sorted(os.sched_getaffinity(0))
     n = bench.physical_cores(threads)

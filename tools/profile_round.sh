@@ -12,7 +12,7 @@ root=$GRAFT_REPO_ROOT
 out=$root/gpurun_out/prof_$tag
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $root/bench.py --config $config --no-cpu-baseline $extra"
+B="python3 $root/bench.py --full --config $config --no-cpu-baseline $extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- $B --steps 30 --warmup 5 > $out/stats_bench.json 2> $out/stats.log || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_$c -o p -- $B --steps 6 --warmup 2 > $out/pmc_$c.json 2> $out/pmc_$c.log || exit 1
