@@ -127,6 +127,7 @@ _SIGS = {
     "gs_copy_overflow_flag": (C.c_int, [_vp, _vp]),
     "gs_set_update_gate": (C.c_int, [_vp, _vp]),
     "gs_set_overflow_rider": (C.c_int, [_vp, _vp]),
+    "gs_set_pose_correction": (C.c_int, [_vp, _vp, _vp]),
     "gs_set_gathered_gate": (C.c_int, [_vp, C.c_longlong, C.c_int, _vp]),
     "gs_set_gate_seen": (C.c_int, [_vp, _vp]),
     "gs_dp_cc_floats": (C.c_longlong, [C.c_int]),

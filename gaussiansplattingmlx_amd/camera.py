@@ -58,6 +58,7 @@ class Camera:
         self.projectionMatrix = np.ascontiguousarray(
             getProjectionMatrix(znear, zfar, float(self.FoVx), float(self.FoVy)).astype(np.float32))
         self.cameraCenter = c2w[:3, 3].copy()
+        self.c2w = c2w.copy()
 
     def as_dict(self):
         return dict(view=self.worldViewTransform, proj=self.projectionMatrix, fovX=float(self.FoVx),
@@ -79,3 +80,43 @@ def look_at_c2w(eye, target=(0.0, 0.0, 0.0), up=(0.0, 0.0, 1.0)) -> np.ndarray:
     c2w = np.eye(4)
     c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = right, down, fwd, eye
     return c2w
+
+
+def _skew(w) -> np.ndarray:
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def rodrigues(w) -> np.ndarray:
+    """R(w) = I + A [w]x + B [w]x^2, A = sin t / t, B = (1 - cos t) / t^2, t = |w|; their series below t^2 = 1e-3, so that
+    R(0) is exactly I (include/gsplat.h gs_set_pose_correction)."""
+    w = np.asarray(w, np.float64).reshape(3)
+    t2 = float(w @ w)
+    if t2 < 1e-3:
+        A, B = 1.0 - t2 / 6.0 + t2 * t2 / 120.0, 0.5 - t2 / 24.0 + t2 * t2 / 720.0
+    else:
+        t = np.sqrt(t2)
+        A, B = np.sin(t) / t, 2.0 * np.sin(0.5 * t) ** 2 / t2
+    K = _skew(w)
+    return np.eye(3) + A * K + B * (K @ K)
+
+
+def pose_delta_matrix(delta) -> np.ndarray:
+    """dT(delta) = [[R(w), tau], [0, 1]] for delta = (w, tau) in R^6."""
+    d = np.asarray(delta, np.float64).reshape(6)
+    T = np.eye(4)
+    T[:3, :3] = rodrigues(d[:3])
+    T[:3, 3] = d[3:]
+    return T
+
+
+def apply_pose_correction(camera: Camera, delta) -> Camera:
+    """The camera with its pose corrected by delta = (w, tau), in float64: c2w' = c2w dT(delta), the correction acting in the
+    camera's own OpenCV frame (x right, y down, z forward).  Intrinsics and the projection matrix are the camera's own.  What
+    the renderer composes on the device while a correction is set (GaussianRenderer.setPoseCorrection), and how a trainer's
+    refined cameras are exported (GaussianTrainer.refinedCamera)."""
+    c2w = getattr(camera, "c2w", None)
+    if c2w is None:
+        c2w = np.linalg.inv(np.asarray(camera.worldViewTransform, np.float64).T)
+    out = Camera(camera.imageWidth, camera.imageHeight, camera.focalX, camera.focalY, np.asarray(c2w, np.float64) @ pose_delta_matrix(delta))
+    out.projectionMatrix = camera.projectionMatrix.copy()
+    return out

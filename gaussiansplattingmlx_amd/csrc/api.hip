@@ -426,6 +426,7 @@ int gs_ctx_destroy(gs_ctx* c)
     if (c->densifyDone) (void)hipEventDestroy(c->densifyDone);
     if (c->densifyPlanHost) (void)hipHostFree(c->densifyPlanHost);
     dev_free(c->densifyPlan);
+    dev_free(c->poseCam); dev_free(c->posePartials);
     dev_free(c->densifyTable);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -760,6 +761,17 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.missChecked = !c->fwd.cutsActive;
     if (c->fwd.cutsActive) c->missHost[0] = 0;
     const CamParams cp = make_cam(cam, c->W, c->H);
+    if (c->poseDelta) {         // pose refinement: the corrected camera, composed on the device, for every kernel of this step
+        const long long need = pose_partials_floats(N);
+        if (need > c->posePartialsCap) {
+            GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+            dev_free(c->posePartials);
+            c->posePartialsCap = 0;
+            if (const int arc = dev_alloc(c, &c->posePartials, (size_t)need)) return arc;
+            c->posePartialsCap = need;
+        }
+        if (const int prc = launch_pose_camera(c, cp, c->poseDelta)) return prc;
+    }
     c->segBaseWanted = c->fast16 && N > 0;
     c->segBaseDone = false;
     c->fwdPairNow = c->fast16 && blend_forward_v2_pair_decide(c);
@@ -790,6 +802,18 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.rot = rotation; c->fwd.opacity = opacity;
     c->fwd.outColor = out_color; c->fwd.outDepth = out_depth; c->fwd.outAlpha = out_alpha;
     c->fwd.cam = cp;
+    c->fwd.poseDelta = c->poseDelta;
+    c->fwd.poseGrad = c->poseGrad;
+    return GS_OK;
+}
+
+int gs_set_pose_correction(gs_ctx* c, const float* delta, float* grad_delta)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!delta != !grad_delta) return fail(c, GS_ERR_INVALID_ARG, "gs_set_pose_correction: delta and grad_delta are both set or both NULL");
+    if (delta && !c->poseCam) { const int arc = dev_alloc(c, &c->poseCam, 1); if (arc) return arc; }
+    c->poseDelta = delta;
+    c->poseGrad = grad_delta;
     return GS_OK;
 }
 
@@ -852,6 +876,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
                                 float* color_cot)
 {
     if (!c) return GS_ERR_INVALID_ARG;
+    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: a pose correction is set (single-device steps only)");
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && !color_cot)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: null buffer");
@@ -871,6 +896,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
 int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity)
 {
     if (!c) return GS_ERR_INVALID_ARG;
+    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_finish: a pose correction is set (single-device steps only)");
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N, K = c->fwd.K;
@@ -887,6 +913,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
                                       float* xyz_own)
 {
     if (!c) return GS_ERR_INVALID_ARG;
+    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_finish_geom: a pose correction is set (single-device steps only)");
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish_geom: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N;
@@ -902,6 +929,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
                                float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity, float* xyz_own)
 {
     if (!c) return GS_ERR_INVALID_ARG;
+    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_geom: a pose correction is set (single-device steps only)");
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && (!color_cot || !grad_xyz || !grad_scales || !grad_rotation || !grad_opacity || !xyz_own)))

@@ -190,6 +190,13 @@ struct gs_ctx {
     uint32_t* missDev = nullptr;         // device address of missHost
     hipEvent_t fwdDone = nullptr;        // recorded after the forward blend when cuts were active
     const uint32_t* workHint = nullptr;  // = the caller's block-work buffer: sweep lengths of an earlier forward of this view
+    // pose refinement (gs_set_pose_correction): caller-owned device delta[6] / grad_delta[6], nullptr = off; the composed
+    // camera of the last posed forward (pose_camera_kernel) and the backward's wave partials ([16 x waves], grown on demand)
+    const float* poseDelta = nullptr;
+    float* poseGrad = nullptr;
+    gs::CamParams* poseCam = nullptr;
+    float* posePartials = nullptr;
+    long long posePartialsCap = 0;
     float* gradNormAccum = nullptr;      // caller-owned [N]: the projection backward adds |grad xyz| (gs_set_grad_norm_accum)
     uint32_t* segBase = nullptr;     // [numPixBlocks] first saved-state slot of each block
     float* segState = nullptr;       // [qslotCap][5][64] running (T, C, D) of an 8x8 quadrant, saved every GS_SEG_LEN splats
@@ -294,6 +301,8 @@ struct gs_ctx {
                     *opacity = nullptr;
         const float *outColor = nullptr, *outDepth = nullptr, *outAlpha = nullptr;
         gs::CamParams cam;
+        const float* poseDelta = nullptr;  // the correction this forward was composed with (nullptr: none) ...
+        float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
         uint32_t* cutStore = nullptr;  // the view's cut words at the time of this forward (nullptr: none kept)
         bool cutsActive = false;     // this forward binned under depth cuts
         bool missChecked = true;     // ... and gs_forward_missed has been asked since
@@ -373,6 +382,9 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
                                           const float* opacity, const CamParams& cam, const float* pBase, float* mBase,
                                           float* vBase, const float lr[6], float b1, float b2, float eps, float gscale);
 bool depth_sort_takes_splitters(const gs_ctx* c, int N);      // binning.hip
+int launch_pose_camera(gs_ctx* c, const gs::CamParams& host, const float* delta);   // projection.hip, pose refinement
+int launch_pose_grad(gs_ctx* c, int N);
+long long pose_partials_floats(int N);
 int launch_colour_rest(gs_ctx* c);      // gs_rider.h: the colour units the binning kernels have not taken along
 int launch_color_cot(gs_ctx* c, int N, float* out);
 int launch_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, const float* mgAll,

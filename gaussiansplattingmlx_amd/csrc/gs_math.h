@@ -342,9 +342,14 @@ struct GeomGrads {
 
 // Reverse mode of the geometry part: cotangents of means2d, depth, cov2d, conic
 // -> gradients of means3d, scales, rotations (activated values).
+// POSE (camera pose refinement, DESIGN.md "Pose refinement"): also dV[3 k + a] = dL/dV[k][a], k < 4 (x, y, z, 1), a < 3 --
+// the gradient of the 3 x 4 affine part of the view matrix as this function reads it, through the view-space point
+// (means, depth, J) and through W = V[:3, :3] in J W.
+template <bool POSE = false>
 __device__ __forceinline__ void project_geometry_bwd(const float m[3], const float s[3], const float rq[4],
                                                      const CamParams& cam, const float cotM2d[2], float cotDepth,
-                                                     const float cotCov[4], const float cotCon[4], GeomGrads& g)
+                                                     const float cotCov[4], const float cotCon[4], GeomGrads& g,
+                                                     float* dV = nullptr)
 {
     const float* V = cam.V;
     const float* P = cam.P;
@@ -432,6 +437,24 @@ __device__ __forceinline__ void project_geometry_bwd(const float m[3], const flo
 #pragma unroll
     for (int a = 0; a < 3; a++)
         g.dm[a] += V[a * 4 + 0] * dpv[0] + V[a * 4 + 1] * dpv[1] + V[a * 4 + 2] * dpv[2] + V[a * 4 + 3] * dpv[3];
+    if constexpr (POSE) {
+        // p_view[a] = sum_k [m, 1][k] V[k][a]: the total cotangent of the view-space point is (dt0 + dpv0, dt1 + dpv1, dt2 + dpv2)
+        const float dp[3] = {dt0 + dpv[0], dt1 + dpv[1], dt2 + dpv[2]};
+        const float mh[4] = {m[0], m[1], m[2], 1.0f};
+        // J W with J = ((jxx, 0, jxz), (0, jyy, jyz)): b[k] = jxx V[k][0] + jxz V[k][2], b[3 + k] = jyy V[k][1] + jyz V[k][2]
+        const float jxx = cam.focalX / tz, jyy = cam.focalY / tz;
+        const float jxz = -cc.tx * cam.focalX / tz2, jyz = -cc.ty * cam.focalY / tz2;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int a = 0; a < 3; a++) dV[3 * k + a] = mh[k] * dp[a];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            dV[3 * k + 0] += db[k] * jxx;
+            dV[3 * k + 1] += db[3 + k] * jyy;
+            dV[3 * k + 2] += db[k] * jxz + db[3 + k] * jyz;
+        }
+    }
 
     // Sigma = L L^T, L = R diag(s)
     float L[9], dL[9];

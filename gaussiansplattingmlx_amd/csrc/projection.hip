@@ -229,170 +229,23 @@ __device__ __forceinline__ void sh_rows_out(const float* __restrict__ lds, float
 #ifndef GS_DEGENERATE_INVISIBLE
 #define GS_DEGENERATE_INVISIBLE 1
 #endif
-template <bool TWO_PHASE, bool COLOUR, bool SELF = false>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_fwd_fused_kernel(
-    int N, int K, int degree, CamParams cam, int tileW, int tileH, int gridW, int gridH,
-    const float* __restrict__ xyz, const float* __restrict__ fdc, const float* __restrict__ frest,
-    const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw, const float* __restrict__ opacityRaw,
-    float* __restrict__ packed12, float* __restrict__ radiiOut, ushort4* __restrict__ tileRect,
-    uint32_t* __restrict__ tilesTouched, uint32_t* __restrict__ depthKey, uint32_t* __restrict__ depthVal,
-    uint32_t* __restrict__ visPerBlock, uint32_t* __restrict__ counters, int flags, ColourRider self,
-    GsVirtGeom vg, GsCutCoarse cc, uint4* __restrict__ tilePieces)
-{
-    const int noKeyForUntouched = flags & 1;
-    const bool trimRects = (flags & 2) && !vg.nbx && tileW == 16 && tileH == 16;
-    extern __shared__ float shLds[];
-    __shared__ uint32_t sDropped;
-    if (cc.superCut) {           // (uniform)
-        if (threadIdx.x == 0) sDropped = 0u;
-        __syncthreads();
-    }
-    // first kernel of a forward: clears the ctx counters for the kernels behind it (no memset launch)
-    if (blockIdx.x == 0 && threadIdx.x < GS_CNT_COUNT) counters[threadIdx.x] = 0;
-    const int p = blockIdx.x * PROJ_FUSED_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int L = (K - 1) * 3;
-    // K = 25 (L = 72): the rows go through LDS in two halves of 12 coefficients (see sh_half_load); otherwise whole
-    const bool twoPhase = TWO_PHASE;
-    const int LH = L >> 1, kSplit = 1 + (K - 1) / 2;          // second half starts at coefficient kSplit
-    const int rowW = twoPhase ? LH + 1 : L + 1;
-    float* myRows = shLds + wv * 64 * rowW;
-    const int row0 = blockIdx.x * PROJ_FUSED_THREADS + wv * 64;
-    const int rows = min(64, N - row0);
-    float4 halfB[SH_HALF_MAX4];
-    if (COLOUR && rows > 0 && L > 0) {
-        if (twoPhase) {
-            float4 halfA[SH_HALF_MAX4];
-            sh_half_load(frest + (size_t)row0 * L, rows, L, 0, LH, lane, halfA);
-            sh_half_load(frest + (size_t)row0 * L, rows, L, LH, LH, lane, halfB);
-            sh_half_to_lds(myRows, rows, LH, lane, halfA);
-        } else {
-            sh_rows_in(myRows, frest + (size_t)row0 * L, rows, L, lane);
-        }
-    }
-    // each wave reads back only what it staged itself: DS operations of one wave complete in order
-    bool visible = false;
-    uint32_t myTouched = 0;       // (SELF)
-    ProjOut o;
-    float opacity = 0.f, colA[3] = {0.f, 0.f, 0.f}, dirv[3] = {0.f, 0.f, 0.f};
-    if (p < N) {
-        const float m[3] = {xyz[3 * p], xyz[3 * p + 1], xyz[3 * p + 2]};
-        const float s[3] = {expf(scalesRaw[3 * p]), expf(scalesRaw[3 * p + 1]), expf(scalesRaw[3 * p + 2])};
-        const float r0 = rotRaw[4 * p], r1 = rotRaw[4 * p + 1], r2 = rotRaw[4 * p + 2], r3 = rotRaw[4 * p + 3];
-        const float den = sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3) + 1e-8f;
-        const float q[4] = {r0 / den, r1 / den, r2 / den, r3 / den};
-        opacity = 1.0f / (1.0f + expf(-opacityRaw[p]));
-        project_geometry(m, s, q, cam, o);
-        // A 2-D covariance whose float32 determinant is not positive -- the true one always is (the +0.3 blur), so this is
-        // cancellation: a needle tens of thousands of pixels long, cov2d = (4.2e7, -3.8e7; -3.8e7, 3.5e7) -- has a conic that is not
-        // positive definite: q < 0 without bound, "weights" above 1, a 0.99-alpha blob over its whole 3-sigma square.  The reference's
-        // training kernels have no guard (slang/gaussian_projection_screen_shared.slang:248-254; its viewer's shaders do:
-        // Metal/GaussianRender.metal:153-154), and there the splat's gradients are 0 x inf = NaN, which takes it out of the picture for
-        // good.  Here it is out of the picture while it is degenerate: radius 0, not binned, zero gradient (the fused path's second
-        // deliberate deviation; the op-level gs_projection_forward keeps the 1:1 arithmetic).
-        if (GS_DEGENERATE_INVISIBLE && !(o.cov2d[0] * o.cov2d[3] - o.cov2d[1] * o.cov2d[2] > 0.0f)) o.radius = 0.0f;
+#define GS_FWD_KERNEL proj_fwd_fused_kernel
+#define GS_FWD_CAM_PARAM CamParams cam
+#define GS_FWD_CAM_INIT
+#include "gs_proj_fwd_kernel.h"
+#undef GS_FWD_KERNEL
+#undef GS_FWD_CAM_PARAM
+#undef GS_FWD_CAM_INIT
 
-        const float x = m[0] - cam.cam[0], y = m[1] - cam.cam[1], z = m[2] - cam.cam[2];
-        const float* d0 = fdc + (size_t)p * 3;
-        const float* rest = myRows + lane * rowW;
-        float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-        if (!COLOUR) {
-        } else if (!twoPhase) {
-            sh_foreach(degree, x, y, z, [&](int k, float b, float, float, float) {
-                if (k == 0) { c0 = b * d0[0]; c1 = b * d0[1]; c2 = b * d0[2]; }
-                else {
-                    const float* r = rest + (k - 1) * 3;
-                    c0 += b * r[0]; c1 += b * r[1]; c2 += b * r[2];
-                }
-            });
-        } else {
-            // same sum, same order (k ascending); coefficients 1 .. kSplit-1 are staged now
-            sh_foreach(degree, x, y, z, [&](int k, float b, float, float, float) {
-                if (k == 0) { c0 = b * d0[0]; c1 = b * d0[1]; c2 = b * d0[2]; }
-                else if (k < kSplit) {
-                    const float* r = rest + (k - 1) * 3;
-                    c0 += b * r[0]; c1 += b * r[1]; c2 += b * r[2];
-                }
-            });
-        }
-        colA[0] = c0; colA[1] = c1; colA[2] = c2;
-        dirv[0] = x; dirv[1] = y; dirv[2] = z;
-        }
-        if (COLOUR && twoPhase && rows > 0 && L > 0) sh_half_to_lds(myRows, rows, LH, lane, halfB);     // the wave's first half is consumed
-        if (p < N) {
-        float c0 = colA[0], c1 = colA[1], c2 = colA[2];
-        if (COLOUR && twoPhase) {
-            const float* rest = myRows + lane * rowW;
-            sh_foreach(degree, dirv[0], dirv[1], dirv[2], [&](int k, float b, float, float, float) {
-                if (k >= kSplit) {
-                    const float* r = rest + (k - kSplit) * 3;
-                    c0 += b * r[0]; c1 += b * r[1]; c2 += b * r[2];
-                }
-            });
-        }
-        // 12th float: per channel, which side of the max(., 0) the colour fell on (2 bits: 0 below, 1 tie, 2 above), so
-        // that the colour cotangent can be gated right after the blend backward (color_cot_kernel)
-        uint32_t gate = 0u;
-        if (COLOUR) {
-            c0 += 0.5f; c1 += 0.5f; c2 += 0.5f;
-            gate = colour_gate(c0, c1, c2);
-        }
-
-        float4* out = reinterpret_cast<float4*>(packed12 + (size_t)p * 12);
-        out[0] = make_float4(o.sx, o.sy, o.conic[0], o.conic[1]);
-        out[1] = make_float4(o.conic[2], o.conic[3], c0, c1);
-        out[2] = make_float4(c2, opacity, o.depth, __uint_as_float(gate));
-        if (radiiOut) radiiOut[p] = o.radius;
-
-        uint32_t touched = 0;
-        ushort4 tr = make_ushort4(0, 0, 0, 0);
-        uint32_t pc[4] = {0u, 0u, 0u, 0u};      // (trimmed rects: the rect's four row groups, first column | columns << 16)
-        if (o.radius > 0.0f) {
-            int x0, y0, x1, y1;
-            if (vg.nbx)        // block lists: tileW .. gridH describe the grid of 16 x 16 blocks enumerated per tile
-                block_rect_of_splat(o.rect, o.sx, o.sy, o.cov2d[0], o.cov2d[3], vg.nbx, vg.nby, vg.tw, vg.th, gridW / vg.nbx,
-                                    gridH / vg.nby, (int)cam.W, (int)cam.H, x0, y0, x1, y1);
-            else if (trimRects)   // 16 x 16 tiles, GS_TUNE_TRIM_RECTS: the reference's 3-sigma square cut by the box of q <= 40.3, beyond
-                                  // which the blend's staging drops the entry for every quadrant anyway (block_rect_of_splat)
-                block_rect_of_splat(o.rect, o.sx, o.sy, o.cov2d[0], o.cov2d[3], 1, 1, 16, 16, gridW, gridH, (int)cam.W, (int)cam.H,
-                                    x0, y0, x1, y1);
-            else
-                tile_rect(o.rect[0], o.rect[1], o.rect[2], o.rect[3], tileW, tileH, gridW, gridH, x0, y0, x1, y1);
-            touched = (uint32_t)((x1 - x0) * (y1 - y0));
-            // ... and inside that box only the columns the ellipse reaches, row group by row group (rect_row_groups4)
-            if (trimRects && tilePieces && touched)
-                touched = rect_row_groups4(o.sx, o.sy, o.cov2d[0], o.cov2d[1], o.cov2d[3], x0, y0, x1, y1, (int)cam.H, pc);
-            tr = make_ushort4((unsigned short)x0, (unsigned short)y0, (unsigned short)x1, (unsigned short)y1);
-            visible = true;
-            // A view under depth cuts: a Gaussian that lies beyond the deepest cut of every 4 x 4 tiles its rect touches would
-            // lose all its pairs in the cut expansion one by one (binning.hip, cut_super_kernel).  Dropped here it touches no
-            // tile at all: no SH rows fetched for its colour, no candidates enumerated, its depth key sorted behind the rest.
-            // Exact as the cuts are: a forward that needed more is detected and repeated without them.
-            if (cc.superCut && touched) {
-                const uint32_t key = __float_as_uint(o.depth);
-                bool reach = false;
-                const int sx1 = (x1 - 1) / GS_CUT_SUPER, sy1 = (y1 - 1) / GS_CUT_SUPER;
-                for (int sy = y0 / GS_CUT_SUPER; sy <= sy1 && !reach; sy++)
-                    for (int sx = x0 / GS_CUT_SUPER; sx <= sx1; sx++)
-                        if (key <= 0xFFFFFFFFu - cc.superCut[sy * cc.superW + sx]) { reach = true; break; }
-                if (!reach) { atomicAdd(&sDropped, touched); touched = 0; tr = make_ushort4(0, 0, 0, 0); pc[0] = pc[1] = pc[2] = pc[3] = 0u; }
-            }
-        }
-        tileRect[p] = tr;
-        if (trimRects && tilePieces) tilePieces[p] = make_uint4(pc[0], pc[1], pc[2], pc[3]);
-        tilesTouched[p] = touched;
-        myTouched = touched;
-        depthKey[p] = (touched || !noKeyForUntouched) ? __float_as_uint(o.depth) : GS_SORT_NO_KEY;     // binning.hip, bin_prep_kernel
-        depthVal[p] = (uint32_t)p;
-    }
-    // visible count: one plain store per block, summed when somebody asks (gs_last_stats).  A same-address atomic per
-    // wave here cost a third of the kernel (4700 atomics on one counter: 82 -> 55 us).
-    const int nvis = __syncthreads_count(visible);
-    if (threadIdx.x == 0) visPerBlock[blockIdx.x] = (uint32_t)nvis;
-    if (cc.superCut && threadIdx.x == 0) cc.dropPerBlock[blockIdx.x] = sDropped;       // (behind the barrier of the count above)
-    // (every lane reads tilesTouched / writes the colour floats of ITS OWN record: program order is all that is needed)
-    if (SELF) colour_rider_wave(self, blockIdx.x * (PROJ_FUSED_THREADS / 64) + wv, shLds + wv * 64 * GS_RIDER_ROW, lane, (int)myTouched);
-}
+// Pose refinement (gs_set_pose_correction): the same kernel reading the camera pose_camera_kernel composed on the device,
+// instantiated with COLOUR only -- no riders: the binning kernels and colour_rest_kernel see only the host camera
+#define GS_FWD_KERNEL proj_fwd_fused_pose_kernel
+#define GS_FWD_CAM_PARAM const CamParams* __restrict__ dcam
+#define GS_FWD_CAM_INIT const CamParams cam = *dcam;
+#include "gs_proj_fwd_kernel.h"
+#undef GS_FWD_KERNEL
+#undef GS_FWD_CAM_PARAM
+#undef GS_FWD_CAM_INIT
 
 // ---------------------------------------------------------------------------------------------
 // fused backward: gradAcc16 (d packed) + raw parameters -> raw-parameter gradients
@@ -569,13 +422,24 @@ __device__ __forceinline__ void drop_nonfinite_row(float4& g0, float4& g1, float
     }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
-    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
+// A deterministic wave64 sum (butterfly, the same order on every run): every lane ends with the total.
+__device__ __forceinline__ float wave_sum_xor(float v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// POSE: besides its own gradients the kernel writes the wave's share of dL/dV' (12 floats [3 k + a], project_geometry_bwd<true>)
+// and of dL/dcam_center' (3 floats: minus the colour path's d) to posePartials[16 w .. 16 w + 14] (16 w + 15: 0), w the wave's index;
+// pose_grad_kernel sums them.  A row with an all-zero cotangent contributes exactly 0 (as its own gradients do).
+template <int MODE, bool POSE>
+__device__ __forceinline__ void proj_bwd_fused_body(
+    int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
     const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
     float* gFdc, float* gFrest, float* gScales, float* gRot,
-    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam)
+    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials)
 {
     constexpr bool EMIT_MG = MODE == 1, ADAM = MODE == 2;
     extern __shared__ float shLds[];
@@ -600,6 +464,11 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
         sh_rows_load4(frest + (size_t)row0 * L, total4, 0, lane, keptRows);
         sh_rows_to_lds4(myRows, total4, L, 0, lane, keptRows);
     } else if (rows > 0 && L > 0) sh_rows_in(myRows, frest + (size_t)row0 * L, rows, L, lane);
+    float pose[POSE ? 15 : 1];
+    if constexpr (POSE) {
+#pragma unroll
+        for (int j = 0; j < 15; j++) pose[j] = 0.f;
+    }
     if (p < N) {
     const float4* ga = reinterpret_cast<const float4*>(gradAcc16 + (size_t)p * 16);
     float4 g0 = ga[0], g1 = ga[1], g2 = ga[2];
@@ -621,7 +490,7 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
     const float q[4] = {rr[0] / den, rr[1] / den, rr[2] / den, rr[3] / den};
 
     GeomGrads g;
-    project_geometry_bwd(m, s, q, cam, cm, cotDepth, ccov, ccon, g);
+    project_geometry_bwd<POSE>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr);
     // A Gaussian no pixel blended (not visible, or off every tile) arrives with an all-zero cotangent row and its
     // gradient is exactly zero.  The reference's arithmetic evaluates J^T 0 term by term, which is 0 * inf = NaN when
     // the point sits within ~1e-3 of the camera plane (1 / t_z^2 overflows); one such NaN poisons Adam for good.
@@ -632,6 +501,10 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
         for (int a = 0; a < 3; a++) { g.dm[a] = 0.f; g.ds[a] = 0.f; }
 #pragma unroll
         for (int a = 0; a < 4; a++) g.dq[a] = 0.f;
+        if constexpr (POSE) {
+#pragma unroll
+            for (int j = 0; j < 12; j++) pose[j] = 0.f;
+        }
     }
 
     const float x = m[0] - cam.cam[0], y = m[1] - cam.cam[1], z = m[2] - cam.cam[2];
@@ -687,6 +560,22 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
         if (ADAM) { sg_[11] = gdc[0]; sg_[12] = gdc[1]; sg_[13] = gdc[2]; }
     }
     if (ADAM && GS_PROJ_LATE_MOMENTS) small_moments();
+    if constexpr (POSE) {
+        // xyz - cam' is the SH view direction's argument: dL/dcam' = -d (a zero row has d = 0 up to 0 x inf: selected away)
+        const bool live = (g0.x != 0.f || g0.y != 0.f || g0.z != 0.f || g0.w != 0.f || g1.x != 0.f ||
+                                                 g1.y != 0.f || g1.z != 0.f || g1.w != 0.f || g2.x != 0.f || g2.y != 0.f ||
+                                                 g2.z != 0.f);
+        pose[12] = live ? -d[0] : 0.f; pose[13] = live ? -d[1] : 0.f; pose[14] = live ? -d[2] : 0.f;
+        // a row whose pose share is not finite (a point at the camera plane) is dropped from the view's sum, as
+        // drop_nonfinite_row drops a cotangent row: one Gaussian must not poison the view's correction and its moments
+        bool fin = true;
+#pragma unroll
+        for (int j = 0; j < 15; j++) fin = fin && (pose[j] - pose[j]) == 0.0f;
+        if (!fin) {
+#pragma unroll
+            for (int j = 0; j < 15; j++) pose[j] = 0.f;
+        }
+    }
     const float gx = g.dm[0] + d[0], gy = g.dm[1] + d[1], gz = g.dm[2] + d[2];
     if (ADAM) { sg_[0] = gx; sg_[1] = gy; sg_[2] = gz; }
     else { gXyz[3 * p] = gx; gXyz[3 * p + 1] = gy; gXyz[3 * p + 2] = gz; }
@@ -737,6 +626,42 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
         if (kept) adam_rows_kept(adam, frest, row0, total4, L, myRows, lane, adam.lr[2], keptRows);
         else adam_rows(adam, frest, row0, rows, L, myRows, lane, adam.lr[2]);
     }
+    if constexpr (POSE) {
+        float* out = posePartials + 16 * ((size_t)blockIdx.x * (PROJ_FUSED_THREADS / 64) + wv);
+#pragma unroll
+        for (int j = 0; j < 15; j++) {
+            const float t = wave_sum_xor(pose[j]);
+            if (lane == j) out[j] = t;
+        }
+        if (lane == 15) out[15] = 0.f;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
+    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
+    float* gFdc, float* gFrest, float* gScales, float* gRot,
+    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam)
+{
+    proj_bwd_fused_body<MODE, false>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
+                                     gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, nullptr);
+}
+
+// Pose refinement: the camera pose_camera_kernel composed, and the pose partials (MODE 0 and 2 only)
+template <int MODE>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_kernel(
+    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
+    float* gFdc, float* gFrest, float* gScales, float* gRot,
+    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials)
+{
+    static_assert(MODE == 0 || MODE == 2, "no pose refinement in the data-parallel form");
+    const CamParams cam = *dcam;
+    proj_bwd_fused_body<MODE, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
+                                    gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1067,12 +992,14 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
     // -- where those kernels have room for them: the three launches of the splitter depth sort and the tile sort's prefix
     // kernel (16385 .. 655 k Gaussians, not the context's first forward).  Elsewhere the split costs more than it hides
     // (measured): one projection kernel as before.  GS_TUNE_COLOUR_RIDERS = 2 forces the split (A/B).
-    c->rider.on = K == GS_RIDER_K && (c->colourRiders == 2 || (c->colourRiders == 1 && depth_sort_takes_splitters(c, N)));
+    // pose refinement: the camera lives on the device, and only this kernel reads it -- no riders, no self-colour split
+    const bool posed = c->poseDelta != nullptr;
+    c->rider.on = !posed && K == GS_RIDER_K && (c->colourRiders == 2 || (c->colourRiders == 1 && depth_sort_takes_splitters(c, N)));
     // where no rider travels (the LSD depth sort's and the one-workgroup sort's kernels are no hosts): geometry first, then
     // the wave's own colours with the rows of unseen Gaussians left out -- faster than the interleaved one-kernel form at
     // every size measured (2 M garden 0.168 -> 0.129 ms, 300 k 0.035 -> 0.031, 10 k 0.0116 -> 0.0098; same bits).
     // GS_TUNE_COLOUR_RIDERS = 3 forces this form, 0 the interleaved one
-    const bool selfColour = K == GS_RIDER_K && !c->rider.on && (c->colourRiders == 3 || c->colourRiders == 1);
+    const bool selfColour = !posed && K == GS_RIDER_K && !c->rider.on && (c->colourRiders == 3 || c->colourRiders == 1);
     // a view under depth cuts: its cuts in coarse form first (binning.hip), for the kernel to drop the Gaussians that lie beyond
     // all of theirs (block lists and 16 x 16 tiles alike: the context's grid is the grid the cuts are kept on)
     GsCutCoarse cc;
@@ -1102,7 +1029,17 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
                            0, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
                            scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
                            c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
-    } else if (selfColour)
+    } else if (posed && twoPhase)
+        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<true, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    else if (posed)
+        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<false, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    else if (selfColour)
         hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW, c->stream, N, K, c->degree, cam, c->tileW,
                            c->tileH, c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
@@ -1148,10 +1085,17 @@ int launch_projection_fused_backward(gs_ctx* c, int N, int K, const float* xyz, 
                                      const float* opacity, const CamParams& cam, float* gXyz, float* gFdc,
                                      float* gFrest, float* gScales, float* gRot, float* gOpacity, bool emitColorCot)
 {
-    if (N == 0) return GS_OK;
+    if (N == 0) return c->fwd.poseDelta && !emitColorCot ? launch_pose_grad(c, 0) : GS_OK;
     const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
     AdamFuse none = {};
     if (!emitColorCot) { none.ovf = c->counters + GS_CNT_OVERFLOW; none.rider = c->overflowRider; }
+    if (c->fwd.poseDelta && !emitColorCot) {
+        hipLaunchKernelGGL(proj_bwd_fused_pose_kernel<0>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
+                           gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum, none, c->posePartials);
+        GS_HIP_CHECK(c, hipGetLastError());
+        return launch_pose_grad(c, N);
+    }
     if (!emitColorCot)
         hipLaunchKernelGGL(proj_bwd_fused_kernel<0>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
@@ -1169,13 +1113,20 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
                                           const float* opacity, const CamParams& cam, const float* pBase, float* mBase,
                                           float* vBase, const float lr[6], float b1, float b2, float eps, float gscale)
 {
-    if (N == 0) return GS_OK;
+    if (N == 0) return c->fwd.poseDelta ? launch_pose_grad(c, 0) : GS_OK;
     const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
     AdamFuse a;
     a.pBase = pBase; a.mBase = mBase; a.vBase = vBase;
     for (int i = 0; i < 6; i++) a.lr[i] = lr[i];
     a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale;
     a.gate = c->adamGate;
+    if (c->fwd.poseDelta) {
+        hipLaunchKernelGGL(proj_bwd_fused_pose_kernel<2>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
+                           c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, c->gradNormAccum, a, c->posePartials);
+        GS_HIP_CHECK(c, hipGetLastError());
+        return launch_pose_grad(c, N);
+    }
     hipLaunchKernelGGL(proj_bwd_fused_kernel<2>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
                        c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr,
                        nullptr, nullptr, nullptr, nullptr, c->gradNormAccum, a);
@@ -1294,6 +1245,177 @@ int launch_pack_gaussians(gs_ctx* c, int N, const float* means2d, const float* c
     if (N == 0) return GS_OK;
     hipLaunchKernelGGL(pack_gaussians_kernel, dim3(gs_div_up(N, 256)), dim3(256), 0, c->stream, N, means2d, conic,
                        color, opacity, depths, packed11);
+    GS_HIP_CHECK(c, hipGetLastError());
+    return GS_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// pose refinement (gs_set_pose_correction; DESIGN.md "Pose refinement")
+// ---------------------------------------------------------------------------------------------
+// R(w) = I + A K + B K^2, K = [w]x, t = |w|: A = sin t / t, B = (1 - cos t) / t^2; the Jacobian needs C = A'(t) / t =
+// (t cos t - sin t) / t^3 and D = B'(t) / t = (t sin t - 2 (1 - cos t)) / t^4.  Taylor series below t^2 = 1e-3 (the first
+// omitted terms are under 1e-12 there), so that R(0) is exactly I; 1 - cos t as 2 sin^2(t / 2) above it.
+__device__ void rodrigues_coeffs(double t2, double& A, double& B, double& C, double& D)
+{
+    if (t2 < 1e-3) {
+        A = 1.0 - t2 / 6.0 + t2 * t2 / 120.0;
+        B = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
+        C = -1.0 / 3.0 + t2 / 30.0 - t2 * t2 / 840.0;
+        D = -1.0 / 12.0 + t2 / 180.0 - t2 * t2 / 6720.0;
+    } else {
+        const double t = sqrt(t2), s = sin(t), h = sin(0.5 * t), omc = 2.0 * h * h;
+        A = s / t;
+        B = omc / t2;
+        C = (t * cos(t) - s) / (t2 * t);
+        D = (t * s - 2.0 * omc) / (t2 * t2);
+    }
+}
+
+__device__ void skew(const double w[3], double K[3][3])
+{
+    K[0][0] = 0.0;   K[0][1] = -w[2]; K[0][2] = w[1];
+    K[1][0] = w[2];  K[1][1] = 0.0;   K[1][2] = -w[0];
+    K[2][0] = -w[1]; K[2][1] = w[0];  K[2][2] = 0.0;
+}
+
+__device__ void matmul3(const double X[3][3], const double Y[3][3], double Z[3][3])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Z[i][j] = X[i][0] * Y[0][j] + X[i][1] * Y[1][j] + X[i][2] * Y[2][j];
+}
+
+__device__ void rodrigues(const double w[3], double R[3][3])
+{
+    double A, B, C, D, K[3][3], K2[3][3];
+    rodrigues_coeffs(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], A, B, C, D);
+    skew(w, K);
+    matmul3(K, K, K2);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R[i][j] = (i == j ? 1.0 : 0.0) + A * K[i][j] + B * K2[i][j];
+}
+
+// The corrected camera: c2w' = c2w [[R, tau], [0, 1]], so w2c' = [[R^T Rw, R^T (tw - tau)], [0, 1]] with w2c = [[Rw, tw], [0, 1]]
+// = V^T (p_view = [p, 1] V), and cam' = cam + Rw^T tau.  A delta of six zero words copies the host camera bit for bit.
+__global__ __launch_bounds__(64) void pose_camera_kernel(CamParams host, const float* __restrict__ delta, CamParams* __restrict__ out)
+{
+    if (threadIdx.x != 0) return;
+    CamParams o = host;
+    bool zero = true;
+    for (int i = 0; i < 6; i++) zero = zero && __float_as_uint(delta[i]) == 0u;
+    if (!zero) {
+        const double w[3] = {delta[0], delta[1], delta[2]}, tau[3] = {delta[3], delta[4], delta[5]};
+        double R[3][3];
+        rodrigues(w, R);
+        for (int a = 0; a < 3; a++)
+            for (int k = 0; k < 4; k++) {
+                double acc = 0.0;
+                for (int j = 0; j < 3; j++) acc += R[j][a] * ((double)host.V[4 * k + j] - (k == 3 ? tau[j] : 0.0));
+                o.V[4 * k + a] = (float)acc;
+            }
+        for (int i = 0; i < 3; i++) {
+            double acc = host.cam[i];
+            for (int j = 0; j < 3; j++) acc += (double)host.V[4 * i + j] * tau[j];
+            o.cam[i] = (float)acc;
+        }
+    }
+    *out = o;
+}
+
+// dL/d delta from the wave partials of proj_bwd_fused_pose_kernel: one workgroup, sums in a fixed order (no atomics), the
+// chain rule in float64.  G[k][a] = dL/dV'[k][a] = part [3 k + a] (k < 4, a < 3), gc = dL/dcam' = parts [12 .. 14].  With dA = G^T (dL/d w2c'[:3, :4]),
+// B = [Rw | tw - tau]:  dL/dtau = -(R dA)[:, 3] + Rw gc,  dL/dw_i = sum_ja (B dA^T)[j][a] dR[j][a]/dw_i,
+// dR/dw_i = C w_i K + A E_i + D w_i K^2 + B (E_i K + K E_i), E_i = [e_i]x.
+__global__ __launch_bounds__(256) void pose_grad_kernel(int nParts, const float* __restrict__ parts, CamParams host,
+                                                        const float* __restrict__ delta, float* __restrict__ gradDelta)
+{
+    // thread (g, q): columns 4 q .. 4 q + 3 of rows g, g + 64, g + 128, ...; eight rows' loads in flight at a time, added in
+    // row order; then the 64 groups pairwise in a fixed tree.  Column 15 is a zero pad.
+    __shared__ double acc[64][16];
+    const int q = threadIdx.x & 3, grp = threadIdx.x >> 2;
+    const float4* p4 = reinterpret_cast<const float4*>(parts);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    constexpr int B = 8;
+    for (int r0 = grp; r0 < nParts; r0 += 64 * B) {
+        float4 v[B];
+#pragma unroll
+        for (int b = 0; b < B; b++) {
+            const int r = r0 + 64 * b;
+            v[b] = r < nParts ? p4[4 * (size_t)r + q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int b = 0; b < B; b++) { s0 += v[b].x; s1 += v[b].y; s2 += v[b].z; s3 += v[b].w; }
+    }
+    acc[grp][4 * q] = s0; acc[grp][4 * q + 1] = s1; acc[grp][4 * q + 2] = s2; acc[grp][4 * q + 3] = s3;
+    for (int h = 32; h > 0; h >>= 1) {
+        __syncthreads();
+        if (grp < h)
+            for (int k = 0; k < 4; k++) acc[grp][4 * q + k] += acc[grp + h][4 * q + k];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double tot[15];
+    for (int k = 0; k < 15; k++) tot[k] = acc[0][k];
+    const double w[3] = {delta[0], delta[1], delta[2]}, tau[3] = {delta[3], delta[4], delta[5]};
+    double A, Bc, C, D, K[3][3], K2[3][3], R[3][3];
+    rodrigues_coeffs(w[0] * w[0] + w[1] * w[1] + w[2] * w[2], A, Bc, C, D);
+    skew(w, K);
+    matmul3(K, K, K2);
+    for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 3; k++) R[i][k] = (i == k ? 1.0 : 0.0) + A * K[i][k] + Bc * K2[i][k];
+    double dA[3][4], Bm[3][4];
+    for (int a = 0; a < 3; a++)
+        for (int k = 0; k < 4; k++) {
+            dA[a][k] = tot[3 * k + a];
+            Bm[a][k] = (double)host.V[4 * k + a] - (k == 3 ? tau[a] : 0.0);
+        }
+    double g[6];
+    for (int r = 0; r < 3; r++) {
+        double t = 0.0;
+        for (int a = 0; a < 3; a++) t -= R[r][a] * dA[a][3];
+        for (int i = 0; i < 3; i++) t += (double)host.V[4 * i + r] * tot[12 + i];
+        g[3 + r] = t;
+    }
+    double Gam[3][3];
+    for (int jj = 0; jj < 3; jj++)
+        for (int a = 0; a < 3; a++) {
+            double t = 0.0;
+            for (int k = 0; k < 4; k++) t += Bm[jj][k] * dA[a][k];
+            Gam[jj][a] = t;
+        }
+    for (int i = 0; i < 3; i++) {
+        double e[3] = {0.0, 0.0, 0.0}, E[3][3], EK[3][3], KE[3][3];
+        e[i] = 1.0;
+        skew(e, E);
+        matmul3(E, K, EK);
+        matmul3(K, E, KE);
+        double t = 0.0;
+        for (int jj = 0; jj < 3; jj++)
+            for (int a = 0; a < 3; a++)
+                t += Gam[jj][a] * (C * w[i] * K[jj][a] + A * E[jj][a] + D * w[i] * K2[jj][a] + Bc * (EK[jj][a] + KE[jj][a]));
+        g[i] = t;
+    }
+    for (int q = 0; q < 6; q++) gradDelta[q] = (float)g[q];
+}
+
+int launch_pose_camera(gs_ctx* c, const CamParams& host, const float* delta)
+{
+    hipLaunchKernelGGL(pose_camera_kernel, dim3(1), dim3(64), 0, c->stream, host, delta, c->poseCam);
+    GS_HIP_CHECK(c, hipGetLastError());
+    return GS_OK;
+}
+
+// floats of the backward's pose partials: a row of 16 per wave of proj_bwd_fused_pose_kernel
+long long pose_partials_floats(int N)
+{
+    return 16LL * gs_div_up(N, PROJ_FUSED_THREADS) * (PROJ_FUSED_THREADS / 64);
+}
+
+int launch_pose_grad(gs_ctx* c, int N)
+{
+    const int parts = (int)(pose_partials_floats(N) / 16);
+    hipLaunchKernelGGL(pose_grad_kernel, dim3(1), dim3(256), 0, c->stream, N > 0 ? parts : 0, c->posePartials, c->fwd.cam,
+                       c->fwd.poseDelta, c->fwd.poseGrad);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }

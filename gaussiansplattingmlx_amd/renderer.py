@@ -473,6 +473,18 @@ class GaussianRenderer:
                                                 _p(g["rotation"]), _p(g["opacity"])))
         return g
 
+    def setPoseCorrection(self, delta=None, grad=None):
+        """gs_set_pose_correction: delta / grad float32 device tensors of 6 elements (w, tau), or both None (off, the default).
+        The following renderForward renders the camera c2w [[R(w), tau], [0, 1]] (camera.apply_pose_correction), and its
+        renderBackward / renderBackwardAdam overwrite grad with dL/d delta."""
+        if (delta is None) != (grad is None):
+            raise ValueError("setPoseCorrection: delta and grad are both given or both None")
+        for t in (delta, grad):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != 6 or not t.is_contiguous() or t.device.type != "cuda"):
+                raise ValueError("setPoseCorrection: delta and grad are contiguous float32 device tensors of 6 elements")
+        self._check(self.lib.gs_set_pose_correction(self.ctx, None if delta is None else _p(delta), None if grad is None else _p(grad)))
+        self._pose = (delta, grad)        # (kept alive while the library holds their addresses)
+
     def renderBackwardAdam(self, cotColor, arena, m, v, lrs, beta1=0.9, beta2=0.999, eps=1e-15, grad_scale=1.0,
                            cotDepth=None, cotAlpha=None):
         """Backward with the Adam step fused into the projection backward (single-device steps): the parameters the

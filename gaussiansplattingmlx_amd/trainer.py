@@ -355,7 +355,8 @@ class GaussianTrainer:
     def __init__(self, model: GaussModel, gaussRender: GaussianRenderer, iterationCount: int = 30000,
                  lambda_dssim: float = 0.2, process_group=None, dp_exchange: str = "sh_compressed",
                  exchange_when_single: bool = False, densify: bool = True, fuse_adam: bool = True,
-                 exchange_impl: str = "torch", dp_bootstrap=None, views_per_rank: int = 1):
+                 exchange_impl: str = "torch", dp_bootstrap=None, views_per_rank: int = 1, pose_opt: bool = False,
+                 pose_lr=(1e-4, 1e-4), n_views: int | None = None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -369,7 +370,27 @@ class GaussianTrainer:
         IS the gathered one: the collective replaced by addressing), the geometry gradients are summed over the rank's views
         before the all-reduce, the SH rebuild runs over all world x V blocks and Adam at grad_scale 1 / (world x V).  With
         world = 1, V = 8 this is BASELINE config 4's arithmetic -- eight views, one update -- on one card.  sh_compressed
-        exchange, torch issuer (or no group at all); world x V <= 16."""
+        exchange, torch issuer (or no group at all); world x V <= 16.
+
+        pose_opt: per-view camera pose refinement (include/gsplat.h gs_set_pose_correction).  Every training view v has a
+        correction delta_v = (w, tau) of its camera-to-world pose, c2w' = c2w [[R(w), tau], [0, 1]] in the camera's own frame,
+        zero at the start and trained by the loss with its own Adam step (the project's Adam, no bias correction) at
+        pose_lr = (rotation rate in radians, translation rate in scene units) -- each moves a component by about its rate per
+        step (about three times that on a view's first steps: no bias correction); the defaults (1e-4, 1e-4) keep a correct
+        camera within ~0.1 px of where it is at 800 px and a focal of ~1000, and reach a degree in a few hundred visits of a view.
+        Raise them for poses known to be far off.  Needs
+        n_views (the view keys are 0 .. n_views - 1) and a viewKey on every step; single-device steps only (one view per step,
+        no process group, no native exchange).  Off (the default): no kernel, buffer or result differs."""
+        self.pose_opt = bool(pose_opt)
+        if self.pose_opt:
+            if views_per_rank != 1:
+                raise ValueError("pose_opt: one view per step only (views_per_rank > 1 is not supported)")
+            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
+                raise ValueError("pose_opt: single-device steps only (no process group, dp_bootstrap or native exchange)")
+            if n_views is None or int(n_views) < 1:
+                raise ValueError("pose_opt needs n_views >= 1 (view keys 0 .. n_views - 1)")
+            if len(pose_lr) != 2:
+                raise ValueError("pose_lr = (rotation rate, translation rate)")
         if dp_exchange not in ("sh_compressed", "allreduce"):
             raise ValueError(f"unknown dp_exchange {dp_exchange!r}")
         if exchange_impl not in ("torch", "native"):
@@ -484,6 +505,11 @@ class GaussianTrainer:
             self._seen = torch.zeros(1, dtype=torch.int32, device=r.device)
             self._need = torch.zeros(1, dtype=torch.int64, device=r.device)
         self._alloc_exchange_buffers()
+        if self.pose_opt:
+            self.nViews, self.poseLr = int(n_views), (float(pose_lr[0]), float(pose_lr[1]))
+            # rows of 8 floats (the first 6 used): gs_adam_step takes 16-byte aligned arenas
+            z = lambda: torch.zeros((self.nViews, 8), dtype=torch.float32, device=r.device)[:, :6]      # noqa: E731
+            self._pose_delta, self._pose_m, self._pose_v, self._pose_grad = z(), z(), z(), z()
         if self._exchange:
             # the replicas must START identical too -- and the check's first call pays for the collective's set-up (a first
             # float64 max-reduce cost the torch exchange ~35 ms at the first densify event of a run) here, not there
@@ -1010,8 +1036,11 @@ class GaussianTrainer:
         r = self.gaussRender
         # knobs of the caller's renderer that this step changes, put back whatever happens
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
+        row = self._pose_row(viewKey) if self.pose_opt else None
         try:
             r.setTuning(depth_gradient=0)
+            if self.pose_opt:      # the view's correction, for every forward of this step (repeats included) and its backward
+                r.setPoseCorrection(self._pose_delta[row], self._pose_grad[row])
             if self._exchange:
                 r.setTuning(host_overflow_errors=0)
                 if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
@@ -1025,6 +1054,35 @@ class GaussianTrainer:
                     self._recover_overflow()      # (every regrow is by half at least: a few rounds reach any need)
         finally:
             r.setTuning(**restore)
+            if self.pose_opt:
+                r.setPoseCorrection(None, None)
+
+    def _pose_row(self, viewKey) -> int:
+        if viewKey is None or isinstance(viewKey, (list, tuple)):
+            raise ValueError("pose_opt: every trainStep needs the viewKey of its one view")
+        row = int(viewKey)
+        if row != viewKey or not 0 <= row < self.nViews:
+            raise ValueError(f"pose_opt: viewKey {viewKey!r} is not one of 0 .. {self.nViews - 1}")
+        return row
+
+    def _poseAdam(self, viewKey):
+        """Adam on the view's six pose floats (gs_adam_step, two segments: rotation, translation): gated like the step's other
+        optimizer kernels, so a step from a blank render moves no pose either."""
+        r, row = self.gaussRender, int(viewKey)
+        r._check(r.lib.gs_adam_step(r.ctx, 6, _p(self._pose_delta[row]), _p(self._pose_grad[row]), _p(self._pose_m[row]),
+                                    _p(self._pose_v[row]), 2, (C.c_longlong * 2)(3, 6), (C.c_float * 2)(*self.poseLr),
+                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0)))
+
+    def poseCorrections(self) -> np.ndarray:
+        """The views' pose corrections delta = (w, tau), host float32 [n_views, 6] (waits for the device)."""
+        if not self.pose_opt:
+            raise ValueError("poseCorrections: the trainer was built without pose_opt")
+        return self._pose_delta.cpu().numpy()
+
+    def refinedCamera(self, viewKey, camera):
+        """The view's camera with its learned correction applied (camera.apply_pose_correction, float64)."""
+        from .camera import apply_pose_correction
+        return apply_pose_correction(camera, self.poseCorrections()[self._pose_row(viewKey)])
 
     def _profiledStep(self, camera, targetRGB, stepCameras, viewKey):
         """One iteration under the reference's IntervalProfiler: host sections by wall clock, device stages by the
@@ -1260,6 +1318,8 @@ class GaussianTrainer:
             lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
             r._check(r.lib.gs_adam_step(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
                                         C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0 / self.world)))
+        if self.pose_opt:
+            self._poseAdam(viewKey)
         return self._finishIteration()
 
     def _finishIteration(self):

@@ -237,6 +237,22 @@ int gs_render_backward_adam(gs_ctx* ctx, const float* cot_color, const float* co
                             float* params_base, float* m_base, float* v_base, long long n_arena, const float lr[6],
                             float beta1, float beta2, float eps, float grad_scale);
 
+/* Per-view camera pose refinement (not in the reference; DESIGN.md "Pose refinement").  delta DEVICE [6] = (w, tau), float32,
+ * a correction of the camera-to-world pose in the camera's own OpenCV frame (x right, y down, z forward):
+ *   c2w' = c2w [[R(w), tau], [0, 1]],  R(w) Rodrigues' rotation (its series near w = 0: R(0) = I exactly),
+ *   view' = inv(c2w')^T (row-major, as gs_camera.view),  cam_center' = c2w'[:3, 3];
+ * proj, the fovs and the focals are unchanged.  While a correction is set, each gs_render_forward composes its camera on the
+ * device from the host gs_camera and *delta (six zero words: the host camera bit for bit), and the gs_render_backward /
+ * gs_render_backward_adam of that forward OVERWRITE grad_delta DEVICE [6] with dL/d delta: the exact chain rule at the current
+ * delta through the means, the 2-D covariance, the depth cotangent and the SH view direction, summed in a fixed order (the same
+ * bits on every run).  A Gaussian whose cotangent row is all zero contributes exactly 0.  The backward uses the correction its
+ * forward was composed with.  delta and grad_delta are both set or both NULL; NULL (the default) is the behaviour without
+ * pose refinement, kernel for kernel.  While a correction is set gs_render_backward_dp* and gs_dp_step return
+ * GS_ERR_INVALID_ARG (single-device steps only).  The op-level entry points (gs_projection_*, gs_blend_*) take explicit
+ * matrices and are not affected.  Optimise delta with gs_adam_step on its six floats: it is gated with the step's other
+ * optimizer kernels. */
+int gs_set_pose_correction(gs_ctx* ctx, const float* delta /*DEVICE [6] or NULL*/, float* grad_delta /*DEVICE [6] or NULL*/);
+
 /* Data-parallel form of gs_render_backward (not in the reference, which is single-device): identical, except that
  * instead of the two SH gradient tensors it returns color_cot[N,3] = the cotangent of the SH colour after the
  * max(., 0) gate.  One view's SH gradient is basis_k(xyz - cam_center) x color_cot, so ranks exchange 12 B per
