@@ -128,6 +128,7 @@ _SIGS = {
     "gs_set_update_gate": (C.c_int, [_vp, _vp]),
     "gs_set_overflow_rider": (C.c_int, [_vp, _vp]),
     "gs_set_pose_correction": (C.c_int, [_vp, _vp, _vp]),
+    "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
     "gs_set_gathered_gate": (C.c_int, [_vp, C.c_longlong, C.c_int, _vp]),
     "gs_set_gate_seen": (C.c_int, [_vp, _vp]),
     "gs_dp_cc_floats": (C.c_longlong, [C.c_int]),

@@ -804,6 +804,15 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.cam = cp;
     c->fwd.poseDelta = c->poseDelta;
     c->fwd.poseGrad = c->poseGrad;
+    c->fwd.antialias = c->antialias;
+    return GS_OK;
+}
+
+int gs_set_antialiasing(gs_ctx* c, int enable)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_antialiasing: enable is 0 or 1");
+    c->antialias = enable == 1;
     return GS_OK;
 }
 

@@ -197,6 +197,7 @@ struct gs_ctx {
     gs::CamParams* poseCam = nullptr;
     float* posePartials = nullptr;
     long long posePartialsCap = 0;
+    bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
     float* gradNormAccum = nullptr;      // caller-owned [N]: the projection backward adds |grad xyz| (gs_set_grad_norm_accum)
     uint32_t* segBase = nullptr;     // [numPixBlocks] first saved-state slot of each block
     float* segState = nullptr;       // [qslotCap][5][64] running (T, C, D) of an 8x8 quadrant, saved every GS_SEG_LEN splats
@@ -303,6 +304,7 @@ struct gs_ctx {
         gs::CamParams cam;
         const float* poseDelta = nullptr;  // the correction this forward was composed with (nullptr: none) ...
         float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
+        bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
         uint32_t* cutStore = nullptr;  // the view's cut words at the time of this forward (nullptr: none kept)
         bool cutsActive = false;     // this forward binned under depth cuts
         bool missChecked = true;     // ... and gs_forward_missed has been asked since

@@ -142,6 +142,7 @@ struct Cov2Ctx {
     float t0, t1, t2, clipX, clipY, tx, ty;
     float b[6];
     float t[6];
+    float u[4];             // the entries before the + 0.3 blur (the anti-aliased mode's det Sigma, aa_opacity_scale)
 };
 
 __device__ __forceinline__ void build_cov2d(const float m[3], const float c[9], const CamParams& cam, float out[4],
@@ -187,6 +188,7 @@ __device__ __forceinline__ void build_cov2d(const float m[3], const float c[9], 
             acc = acc + M[r][1] * JW[q][1];
             acc = acc + M[r][2] * JW[q][2];
             out[2 * r + q] = r == q ? acc + 0.3f : acc;
+            cc.u[2 * r + q] = acc;
         }
     cc.t0 = pv[0]; cc.t1 = pv[1]; cc.t2 = depth; cc.clipX = zLimX; cc.clipY = zLimY; cc.tx = xs; cc.ty = ys;
 #pragma unroll
@@ -196,6 +198,7 @@ __device__ __forceinline__ void build_cov2d(const float m[3], const float c[9], 
 struct ProjOut {
     float sx, sy, depth;
     float cov2d[4], conic[4];
+    float cov2dRaw[4];  // cov2d before the + 0.3 blur (anti-aliased mode)
     float radius;  // already multiplied by the visibility mask
     float rect[4]; // minX minY maxX maxY
 };
@@ -224,6 +227,8 @@ __device__ __forceinline__ void project_geometry(const float m[3], const float s
     build_cov3d(s, rq, c3, rc);
     Cov2Ctx cc;
     build_cov2d(m, c3, cam, o.cov2d, cc);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o.cov2dRaw[k] = cc.u[k];
     const float det = o.cov2d[0] * o.cov2d[3] - o.cov2d[1] * o.cov2d[2];
     o.conic[0] = o.cov2d[3] / det;
     o.conic[1] = -o.cov2d[1] / det;
@@ -336,6 +341,32 @@ __device__ __forceinline__ uint32_t rect_row_groups4(float sx, float sy, float s
     return total;
 }
 
+// Anti-aliased mode (gs_set_antialiasing; Mip-Splatting's 2-D filter as Inria's and gsplat's rasterizers
+// offer it): the blend sees sigma(o) rho instead of sigma(o), rho = sqrt(det Sigma / det Sigma_b), Sigma the projected 2-D
+// covariance before the + 0.3 blur (u: Cov2Ctx::u, in float32 from the unblurred entries -- det Sigma_b minus correction terms
+// would cancel for a sub-pixel splat), Sigma_b = Sigma + 0.3 I the blurred one (cb) the conic, radius and rects come from.
+// Returns rho, or 0 for a splat whose det Sigma (or det Sigma_b) is not > 0 or not finite: such a splat is invisible while it
+// is so (radius 0, no pairs, a zero gradient; the GS_DEGENERATE_INVISIBLE convention), which also keeps the derivative of the
+// square root out of its singularity.  VJP: d rho / d Sigma_b = (rho / 2) (Sigma^-T - Sigma_b^-T) in the four-independent-entries
+// convention of project_geometry_bwd's cotCov (d det A / d A = det A A^-T), times cot = dL/d(packed opacity) sigma(o), added to
+// dCb.  Forward and backward call this one function: the same arithmetic, the same rho and the same degenerate set.
+template <bool VJP = false>
+__device__ __forceinline__ float aa_opacity_scale(const float u[4], const float cb[4], float cot = 0.0f, float* dCb = nullptr)
+{
+    const float detU = u[0] * u[3] - u[1] * u[2];
+    const float detB = cb[0] * cb[3] - cb[1] * cb[2];
+    if (!(detU > 0.0f && (detU - detU) == 0.0f && detB > 0.0f && (detB - detB) == 0.0f)) return 0.0f;
+    const float rho = sqrtf(detU / detB);
+    if constexpr (VJP) {
+        const float h = 0.5f * cot * rho, iu = h / detU, ib = h / detB;
+        dCb[0] += u[3] * iu - cb[3] * ib;
+        dCb[1] += -u[2] * iu + cb[2] * ib;
+        dCb[2] += -u[1] * iu + cb[1] * ib;
+        dCb[3] += u[0] * iu - cb[0] * ib;
+    }
+    return rho;
+}
+
 struct GeomGrads {
     float dm[3], ds[3], dq[4];
 };
@@ -345,11 +376,13 @@ struct GeomGrads {
 // POSE (camera pose refinement, DESIGN.md "Pose refinement"): also dV[3 k + a] = dL/dV[k][a], k < 4 (x, y, z, 1), a < 3 --
 // the gradient of the 3 x 4 affine part of the view matrix as this function reads it, through the view-space point
 // (means, depth, J) and through W = V[:3, :3] in J W.
-template <bool POSE = false>
+// AA (anti-aliased mode): aaCot = dL/d(packed opacity) sigma(o); the VJP of rho (aa_opacity_scale) joins the covariance
+// cotangent ahead of everything downstream of it (the pose share included), and *aaRho receives rho.
+template <bool POSE = false, bool AA = false>
 __device__ __forceinline__ void project_geometry_bwd(const float m[3], const float s[3], const float rq[4],
                                                      const CamParams& cam, const float cotM2d[2], float cotDepth,
                                                      const float cotCov[4], const float cotCon[4], GeomGrads& g,
-                                                     float* dV = nullptr)
+                                                     float* dV = nullptr, float aaCot = 0.0f, float* aaRho = nullptr)
 {
     const float* V = cam.V;
     const float* P = cam.P;
@@ -373,6 +406,7 @@ __device__ __forceinline__ void project_geometry_bwd(const float m[3], const flo
     dC[0] = det * S29 + c2[3] * S33;
 #pragma unroll
     for (int k = 0; k < 4; k++) dC[k] += cotCov[k];
+    if constexpr (AA) *aaRho = aa_opacity_scale<true>(cc.u, c2, aaCot, dC);
 
     const float* b = cc.b;
     const float* t = cc.t;

@@ -2,7 +2,8 @@
 // a kernel argument, and as proj_fwd_fused_pose_kernel, the camera the one pose_camera_kernel composed on the device (pose
 // refinement, gs_set_pose_correction).  One text, so that the default kernels compile exactly as they did before the pose
 // form existed.  The includer defines GS_FWD_KERNEL, GS_FWD_CAM_PARAM and GS_FWD_CAM_INIT.
-template <bool TWO_PHASE, bool COLOUR, bool SELF = false>
+// AA: the anti-aliased mode (gs_set_antialiasing): the packed opacity is sigma(o) rho (aa_opacity_scale, gs_math.h).
+template <bool TWO_PHASE, bool COLOUR, bool SELF = false, bool AA = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void GS_FWD_KERNEL(
     int N, int K, int degree, GS_FWD_CAM_PARAM, int tileW, int tileH, int gridW, int gridH,
     const float* __restrict__ xyz, const float* __restrict__ fdc, const float* __restrict__ frest,
@@ -65,6 +66,11 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void GS_FWD_KERNEL(
         // good.  Here it is out of the picture while it is degenerate: radius 0, not binned, zero gradient (the fused path's second
         // deliberate deviation; the op-level gs_projection_forward keeps the 1:1 arithmetic).
         if (GS_DEGENERATE_INVISIBLE && !(o.cov2d[0] * o.cov2d[3] - o.cov2d[1] * o.cov2d[2] > 0.0f)) o.radius = 0.0f;
+        if constexpr (AA) {     // (rho = 0: det Sigma not > 0 -- invisible while it is so, as above)
+            const float rho = aa_opacity_scale(o.cov2dRaw, o.cov2d);
+            opacity *= rho;
+            if (!(rho > 0.0f)) o.radius = 0.0f;
+        }
 
         const float x = m[0] - cam.cam[0], y = m[1] - cam.cam[1], z = m[2] - cam.cam[2];
         const float* d0 = fdc + (size_t)p * 3;

@@ -433,7 +433,9 @@ __device__ __forceinline__ float wave_sum_xor(float v)
 // POSE: besides its own gradients the kernel writes the wave's share of dL/dV' (12 floats [3 k + a], project_geometry_bwd<true>)
 // and of dL/dcam_center' (3 floats: minus the colour path's d) to posePartials[16 w .. 16 w + 14] (16 w + 15: 0), w the wave's index;
 // pose_grad_kernel sums them.  A row with an all-zero cotangent contributes exactly 0 (as its own gradients do).
-template <int MODE, bool POSE>
+// AA (anti-aliased mode, gs_set_antialiasing): the forward blended sigma(o) rho; dop is the cotangent of that product, so
+// dL/do_raw = dop rho sigma (1 - sigma) and the covariance cotangent gains the VJP of rho (project_geometry_bwd<., true>).
+template <int MODE, bool POSE, bool AA = false>
 __device__ __forceinline__ void proj_bwd_fused_body(
     int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
@@ -490,7 +492,9 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     const float q[4] = {rr[0] / den, rr[1] / den, rr[2] / den, rr[3] / den};
 
     GeomGrads g;
-    project_geometry_bwd<POSE>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr);
+    float aaRho = 1.0f;
+    const float aaSg = AA ? 1.0f / (1.0f + expf(-opacityRaw[p])) : 0.0f;
+    project_geometry_bwd<POSE, AA>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr, cotOpacity * aaSg, &aaRho);
     // A Gaussian no pixel blended (not visible, or off every tile) arrives with an all-zero cotangent row and its
     // gradient is exactly zero.  The reference's arithmetic evaluates J^T 0 term by term, which is 0 * inf = NaN when
     // the point sits within ~1e-3 of the camera plane (1 / t_z^2 overflows); one such NaN poisons Adam for good.
@@ -595,7 +599,7 @@ __device__ __forceinline__ void proj_bwd_fused_body(
         if (ADAM) sg_[6 + a] = v; else gRot[4 * p + a] = v;
     }
     const float sg = 1.0f / (1.0f + expf(-opr));
-    const float gop = cotOpacity * sg * (1.0f - sg);
+    const float gop = (AA ? cotOpacity * aaRho : cotOpacity) * sg * (1.0f - sg);
     if (ADAM) sg_[10] = gop; else gOpacity[p] = gop;
     if (ADAM && !gateWord) {
         // the 14 small elements: values and moments were loaded at the top; one burst of stores here
@@ -637,7 +641,7 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     }
 }
 
-template <int MODE>
+template <int MODE, bool AA = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
     int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
@@ -645,12 +649,12 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
     float* gFdc, float* gFrest, float* gScales, float* gRot,
     float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam)
 {
-    proj_bwd_fused_body<MODE, false>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
+    proj_bwd_fused_body<MODE, false, AA>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
                                      gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, nullptr);
 }
 
 // Pose refinement: the camera pose_camera_kernel composed, and the pose partials (MODE 0 and 2 only)
-template <int MODE>
+template <int MODE, bool AA = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_kernel(
     int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
@@ -660,7 +664,7 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_kernel
 {
     static_assert(MODE == 0 || MODE == 2, "no pose refinement in the data-parallel form");
     const CamParams cam = *dcam;
-    proj_bwd_fused_body<MODE, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
+    proj_bwd_fused_body<MODE, true, AA>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
                                     gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials);
 }
 
@@ -778,8 +782,9 @@ struct ViewCentersOwn {
     int n;
 };
 
-__global__ __launch_bounds__(256) void proj_bwd_geom_kernel(
-    int N, CamParams cam, const float* __restrict__ xyz, const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw,
+template <bool AA>       // (the anti-aliased mode: proj_bwd_fused_body's AA)
+__device__ __forceinline__ void proj_bwd_geom_body(
+    int N, const CamParams& cam, const float* __restrict__ xyz, const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw,
     const float* __restrict__ opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gXyz,
     float* __restrict__ gScales, float* __restrict__ gRot, float* __restrict__ gOpacity, float* __restrict__ xyzOwn,
     const float* __restrict__ packed12, float* __restrict__ ccOut, const uint32_t* __restrict__ ovf, float* __restrict__ rider)
@@ -815,7 +820,9 @@ __global__ __launch_bounds__(256) void proj_bwd_geom_kernel(
     const float den = nrm + 1e-8f;
     const float q[4] = {rr[0] / den, rr[1] / den, rr[2] / den, rr[3] / den};
     GeomGrads g;
-    project_geometry_bwd(m, s, q, cam, cm, cotDepth, ccov, ccon, g);
+    float aaRho = 1.0f;
+    const float aaSg = AA ? 1.0f / (1.0f + expf(-opacityRaw[p])) : 0.0f;
+    project_geometry_bwd<false, AA>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, nullptr, cotOpacity * aaSg, &aaRho);
     // (a Gaussian no pixel blended: the exact zero instead of the reference's 0 * inf, as proj_bwd_fused_kernel)
     if (g0.x == 0.f && g0.y == 0.f && g0.z == 0.f && g0.w == 0.f && g1.x == 0.f && g1.y == 0.f && g1.z == 0.f &&
         g1.w == 0.f && g2.x == 0.f && g2.y == 0.f && g2.z == 0.f) {
@@ -837,8 +844,19 @@ __global__ __launch_bounds__(256) void proj_bwd_geom_kernel(
 #pragma unroll
     for (int a = 0; a < 4; a++) gRot[4 * p + a] = g.dq[a] / den + 2.0f * rr[a] * dn2;
     const float sg = 1.0f / (1.0f + expf(-opacityRaw[p]));
-    gOpacity[p] = cotOpacity * sg * (1.0f - sg);
+    gOpacity[p] = (AA ? cotOpacity * aaRho : cotOpacity) * sg * (1.0f - sg);
 }
+
+#define GS_GEOM_PARAMS                                                                                                             \
+    int N, CamParams cam, const float* __restrict__ xyz, const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw,   \
+        const float* __restrict__ opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gXyz,                      \
+        float* __restrict__ gScales, float* __restrict__ gRot, float* __restrict__ gOpacity, float* __restrict__ xyzOwn,          \
+        const float* __restrict__ packed12, float* __restrict__ ccOut, const uint32_t* __restrict__ ovf, float* __restrict__ rider
+#define GS_GEOM_ARGS N, cam, xyz, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gScales, gRot, gOpacity, xyzOwn, packed12, ccOut, ovf, rider
+__global__ __launch_bounds__(256) void proj_bwd_geom_kernel(GS_GEOM_PARAMS) { proj_bwd_geom_body<false>(GS_GEOM_ARGS); }
+__global__ __launch_bounds__(256) void proj_bwd_geom_aa_kernel(GS_GEOM_PARAMS) { proj_bwd_geom_body<true>(GS_GEOM_ARGS); }
+#undef GS_GEOM_PARAMS
+#undef GS_GEOM_ARGS
 
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void sh_views_dir_adam_kernel(
     int N, int K, int degree, ViewCentersOwn views, const float* __restrict__ xyz, const float* __restrict__ mgAll,
@@ -980,6 +998,46 @@ int launch_projection_backward(gs_ctx* c, int N, int K, const float* scales, con
     return GS_OK;
 }
 
+// the forward's kernel, in the anti-aliased mode's form (AA: gs_set_antialiasing) or the default one
+template <bool AA>
+static void launch_fwd_fused_kernel(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
+                                    const float* scales, const float* rot, const float* opacity, const CamParams& cam,
+                                    float* radii, bool posed, bool twoPhase, bool selfColour, size_t lds, int pflags,
+                                    const ColourRider& a, const GsCutCoarse& cc, uint4* pieces)
+{
+    if (c->rider.on)
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           0, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    else if (posed && twoPhase)
+        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<true, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    else if (posed)
+        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<false, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    else if (selfColour)
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, true, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW, c->stream, N, K, c->degree, cam, c->tileW,
+                           c->tileH, c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
+                           c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters,
+                           pflags, a, c->virt, cc, pieces);
+    else if (twoPhase)
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    else
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<false, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+                           lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
+                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+}
+
 int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
                                     const float* scales, const float* rot, const float* opacity,
                                     const CamParams& cam, float* radii)
@@ -1025,36 +1083,13 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
         c->rider.args.units = 0;
         c->rider.next = 0;
         c->rider.total = gs_div_up(N, 64);
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           0, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
-    } else if (posed && twoPhase)
-        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<true, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
-    else if (posed)
-        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<false, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
-    else if (selfColour)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW, c->stream, N, K, c->degree, cam, c->tileW,
-                           c->tileH, c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
-                           c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters,
-                           pflags, a, c->virt, cc, pieces);
-    else if (twoPhase)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+    }
+    if (c->antialias)
+        launch_fwd_fused_kernel<true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
+                                      lds, pflags, a, cc, pieces);
     else
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<false, true>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+        launch_fwd_fused_kernel<false>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
+                                       lds, pflags, a, cc, pieces);
     c->visBlocks = gs_div_up(N, PROJ_FUSED_THREADS);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
@@ -1087,21 +1122,22 @@ int launch_projection_fused_backward(gs_ctx* c, int N, int K, const float* xyz, 
 {
     if (N == 0) return c->fwd.poseDelta && !emitColorCot ? launch_pose_grad(c, 0) : GS_OK;
     const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
+    const bool aa = c->fwd.antialias;       // (the mode this backward's forward ran in)
     AdamFuse none = {};
     if (!emitColorCot) { none.ovf = c->counters + GS_CNT_OVERFLOW; none.rider = c->overflowRider; }
     if (c->fwd.poseDelta && !emitColorCot) {
-        hipLaunchKernelGGL(proj_bwd_fused_pose_kernel<0>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
-                           gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum, none, c->posePartials);
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_kernel<0, true> : proj_bwd_fused_pose_kernel<0>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
+                           dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity,
+                           c->gradAcc16, gXyz, gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum, none, c->posePartials);
         GS_HIP_CHECK(c, hipGetLastError());
         return launch_pose_grad(c, N);
     }
     if (!emitColorCot)
-        hipLaunchKernelGGL(proj_bwd_fused_kernel<0>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_kernel<0, true> : proj_bwd_fused_kernel<0>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
                            gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum, none);
     else   // data-parallel variant: gFdc receives mg[N,3]
-        hipLaunchKernelGGL(proj_bwd_fused_kernel<1>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_kernel<1, true> : proj_bwd_fused_kernel<1>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
                            gFdc, nullptr, gScales, gRot, gOpacity, c->gradNormAccum, none);
     GS_HIP_CHECK(c, hipGetLastError());
@@ -1120,14 +1156,15 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
     for (int i = 0; i < 6; i++) a.lr[i] = lr[i];
     a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale;
     a.gate = c->adamGate;
+    const bool aa = c->fwd.antialias;
     if (c->fwd.poseDelta) {
-        hipLaunchKernelGGL(proj_bwd_fused_pose_kernel<2>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_kernel<2, true> : proj_bwd_fused_pose_kernel<2>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
                            c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr,
                            nullptr, nullptr, nullptr, nullptr, nullptr, c->gradNormAccum, a, c->posePartials);
         GS_HIP_CHECK(c, hipGetLastError());
         return launch_pose_grad(c, N);
     }
-    hipLaunchKernelGGL(proj_bwd_fused_kernel<2>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
+    hipLaunchKernelGGL((aa ? proj_bwd_fused_kernel<2, true> : proj_bwd_fused_kernel<2>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
                        c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr,
                        nullptr, nullptr, nullptr, nullptr, c->gradNormAccum, a);
     GS_HIP_CHECK(c, hipGetLastError());
@@ -1197,7 +1234,8 @@ int launch_projection_geom_backward(gs_ctx* c, int N, const float* xyz, const fl
                                     float* gOpacity, float* xyzOwn, float* colorCot)
 {
     if (N == 0) return GS_OK;
-    hipLaunchKernelGGL(proj_bwd_geom_kernel, dim3(gs_div_up(N, 256)), dim3(256), 0, c->stream, N, cam, xyz, scales, rot, opacity,
+    hipLaunchKernelGGL((c->fwd.antialias ? proj_bwd_geom_aa_kernel : proj_bwd_geom_kernel), dim3(gs_div_up(N, 256)), dim3(256), 0,
+                       c->stream, N, cam, xyz, scales, rot, opacity,
                        c->gradAcc16, gXyz, gScales, gRot, gOpacity, xyzOwn, c->packed12, colorCot, c->counters + GS_CNT_OVERFLOW,
                        c->overflowRider);
     GS_HIP_CHECK(c, hipGetLastError());

@@ -69,7 +69,8 @@ class CutPolicy:
 
 class GaussianRenderer:
     def __init__(self, active_sh_degree: int, W: int, H: int, TILE_SIZE=TILE_SIZE_H_W(16, 16),
-                 whiteBackground: bool = False, useScreenSpaceCustomOp: bool = True, device: int = 0):
+                 whiteBackground: bool = False, useScreenSpaceCustomOp: bool = True, device: int = 0,
+                 antialiased: bool = False):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("GaussianRenderer needs a GPU: the HIP path has no CPU fallback")
@@ -106,6 +107,9 @@ class GaussianRenderer:
         self.targetStatsCache = True   # lossForwardBackward(targetKey=...) keeps the target's SSIM statistics per key
         self._target_cache = OrderedDict()
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
+        self._antialiased = False
+        if antialiased:
+            self.setAntialiased(True)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -484,6 +488,22 @@ class GaussianRenderer:
                 raise ValueError("setPoseCorrection: delta and grad are contiguous float32 device tensors of 6 elements")
         self._check(self.lib.gs_set_pose_correction(self.ctx, None if delta is None else _p(delta), None if grad is None else _p(grad)))
         self._pose = (delta, grad)        # (kept alive while the library holds their addresses)
+
+    def setAntialiased(self, enable: bool = True):
+        """gs_set_antialiasing: the anti-aliased mode (Mip-Splatting's 2-D filter; include/gsplat.h) for the
+        following renderForward calls, off by default.  Every backward uses the mode of its forward, so a GaussianTrainer
+        trains in whatever mode its renderer is in.  All ranks of a data-parallel job must agree (a rank that does not shows
+        up as a replica mismatch).  PLY snapshots do not record the mode: render a model in the mode it was trained in."""
+        self._check(self.lib.gs_set_antialiasing(self.ctx, 1 if enable else 0))
+        self._antialiased = bool(enable)
+
+    @property
+    def antialiased(self) -> bool:
+        return self._antialiased
+
+    @antialiased.setter
+    def antialiased(self, enable: bool):
+        self.setAntialiased(enable)
 
     def renderBackwardAdam(self, cotColor, arena, m, v, lrs, beta1=0.9, beta2=0.999, eps=1e-15, grad_scale=1.0,
                            cotDepth=None, cotAlpha=None):

@@ -253,6 +253,26 @@ int gs_render_backward_adam(gs_ctx* ctx, const float* cot_color, const float* co
  * optimizer kernels. */
 int gs_set_pose_correction(gs_ctx* ctx, const float* delta /*DEVICE [6] or NULL*/, float* grad_delta /*DEVICE [6] or NULL*/);
 
+/* Anti-aliased mode (not in the reference; DESIGN.md "Anti-aliased mode"): Mip-Splatting's 2-D filter, as Inria's rasterizer
+ * (antialiasing) and gsplat (rasterize_mode="antialiased") offer it.  With Sigma a splat's projected 2-D covariance BEFORE the
+ * reference's blur (J W Sigma3 W^T J^T) and Sigma_b = Sigma + 0.3 I the blurred one, each following gs_render_forward writes
+ *   sigma(o) rho,  rho = sqrt(det Sigma / det Sigma_b)
+ * as the packed opacity: the blur stays, and the splat's opacity shrinks by the share its footprint was inflated by.  Conic,
+ * means, depth, colour, radius and rect are unchanged; colour, depth and alpha see only the compensated opacity.  det Sigma is
+ * formed in float32 from the unblurred entries.  A splat whose det Sigma is not > 0 (or not finite) is invisible while it is so:
+ * radius 0, no pairs, an exactly zero gradient (the fused path's GS_DEGENERATE_INVISIBLE convention; Inria's rasterizer
+ * clamps the ratio at 2.5e-5 instead, which keeps such a splat faintly visible with the square root's derivative at its
+ * singularity).  Backward, with c = dL/d(packed opacity): dL/do_raw = c rho sigma (1 - sigma), and the cotangent of Sigma_b
+ * gains c sigma(o) (rho / 2) (Sigma^-T - Sigma_b^-T) in the four-independent-entries convention.  enable: 0 (the default, the
+ * reference's semantics, kernel for kernel) or 1; any other value returns GS_ERR_INVALID_ARG and leaves the mode as it was.
+ * The mode is the context's; a backward uses the mode its forward ran in.  It composes with every fused entry point:
+ * gs_render_backward, gs_render_backward_adam, gs_render_backward_dp*, gs_dp_step, pose refinement, depth cuts and view hints,
+ * trimmed rects and block lists (the lists are built from the geometry alone: M does not change).  All ranks of a
+ * data-parallel job must agree on it (a rank that does not shows up as a replica mismatch).  The op-level entry points
+ * (gs_projection_*, gs_pack_gaussians, gs_blend_*) keep the reference's arithmetic and ignore the mode.  PLY snapshots do not
+ * record it: render a model in the mode it was trained in. */
+int gs_set_antialiasing(gs_ctx* ctx, int enable);
+
 /* Data-parallel form of gs_render_backward (not in the reference, which is single-device): identical, except that
  * instead of the two SH gradient tensors it returns color_cot[N,3] = the cotangent of the SH colour after the
  * max(., 0) gate.  One view's SH gradient is basis_k(xyz - cam_center) x color_cot, so ranks exchange 12 B per
