@@ -37,6 +37,12 @@ class gs_dp_step_args(C.Structure):
                 ("cam_centers", C.c_void_p), ("color_cot_local", C.c_void_p), ("color_cot_all", C.c_void_p)]
 
 
+class gs_mcmc_params(C.Structure):
+    _fields_ = [("noise_lr", C.c_double), ("opacity_reg", C.c_double), ("scale_reg", C.c_double),
+                ("min_opacity", C.c_double), ("grow_rate", C.c_double), ("cap_max", C.c_longlong), ("n_max", C.c_int),
+                ("iteration", C.c_int), ("seed", C.c_ulonglong)]
+
+
 GS_DP_ALLREDUCE, GS_DP_SH_COMPRESSED = 0, 1
 GS_DP_UNIQUE_ID_BYTES = 128
 
@@ -129,6 +135,12 @@ _SIGS = {
     "gs_set_overflow_rider": (C.c_int, [_vp, _vp]),
     "gs_set_pose_correction": (C.c_int, [_vp, _vp, _vp]),
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
+    "gs_set_mcmc": (C.c_int, [_vp, _vp]),
+    "gs_mcmc_regularizer_grad": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
+    "gs_mcmc_inject_noise": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [C.c_float, _vp]),
+    "gs_mcmc_random": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "gs_mcmc_relocate": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 11),
+    "gs_mcmc_grow": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int] + [_vp] * 11),
     "gs_set_gathered_gate": (C.c_int, [_vp, C.c_longlong, C.c_int, _vp]),
     "gs_set_gate_seen": (C.c_int, [_vp, _vp]),
     "gs_dp_cc_floats": (C.c_longlong, [C.c_int]),

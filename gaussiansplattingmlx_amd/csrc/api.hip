@@ -428,6 +428,7 @@ int gs_ctx_destroy(gs_ctx* c)
     dev_free(c->densifyPlan);
     dev_free(c->poseCam); dev_free(c->posePartials);
     dev_free(c->densifyTable);
+    mcmc_free(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return GS_OK;
@@ -814,6 +815,101 @@ int gs_set_antialiasing(gs_ctx* c, int enable)
     if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_antialiasing: enable is 0 or 1");
     c->antialias = enable == 1;
     return GS_OK;
+}
+
+// ---- the MCMC strategy (include/gsplat.h gs_set_mcmc; mcmc.hip, projection.hip proj_bwd_fused_*mcmc_kernel) ----------------
+static const char* mcmc_params_error(const gs_mcmc_params* p)
+{
+    if (!p) return "null gs_mcmc_params";
+    auto fin = [](double v) { return v - v == 0.0; };
+    if (!fin(p->noise_lr) || p->noise_lr < 0 || !fin(p->opacity_reg) || p->opacity_reg < 0 || !fin(p->scale_reg) || p->scale_reg < 0)
+        return "noise_lr, opacity_reg and scale_reg are finite and >= 0";
+    if (!(p->min_opacity > 0.0 && p->min_opacity < 1.0)) return "min_opacity is in (0, 1)";
+    if (!(p->grow_rate >= 0.0 && p->grow_rate <= 1.0)) return "grow_rate is in [0, 1]";
+    if (p->n_max < 1 || p->n_max > 51) return "n_max is in 1 .. 51";
+    if (p->cap_max < 1 || p->cap_max > 0x7fffffffLL) return "cap_max is in 1 .. 2^31 - 1";
+    if (p->iteration < 0) return "iteration >= 0";
+    return nullptr;
+}
+
+int gs_set_mcmc(gs_ctx* c, const gs_mcmc_params* params)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!params) { c->mcmcOn = false; return GS_OK; }
+    if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
+    c->mcmc = *params;
+    c->mcmcOn = true;
+    return GS_OK;
+}
+
+int gs_mcmc_regularizer_grad(gs_ctx* c, int N, const float* scales, const float* opacity, float* grad_scales, float* grad_opacity,
+                             const gs_mcmc_params* params)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
+    if (N < 0 || (N > 0 && (!scales || !opacity || !grad_scales || !grad_opacity)))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_mcmc_regularizer_grad: bad arguments");
+    return launch_mcmc_regularizer(c, N, scales, opacity, grad_scales, grad_opacity, *params);
+}
+
+int gs_mcmc_inject_noise(gs_ctx* c, int N, float* xyz, const float* scales, const float* rotation, const float* opacity,
+                         float lr_xyz, const gs_mcmc_params* params)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
+    if (N < 0 || (N > 0 && (!xyz || !scales || !rotation || !opacity)))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_mcmc_inject_noise: bad arguments");
+    return launch_mcmc_noise(c, N, xyz, scales, rotation, opacity, lr_xyz, *params);
+}
+
+int gs_mcmc_random(gs_ctx* c, unsigned long long seed, int iteration, int stream, int n, uint32_t* words, float* normals,
+                   double* uniforms)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n < 0 || iteration < 0 || stream < 0 || stream > 2) return fail(c, GS_ERR_INVALID_ARG, "gs_mcmc_random: bad arguments");
+    return launch_mcmc_random(c, seed, iteration, stream, n, words, normals, uniforms);
+}
+
+static int mcmc_rows(gs_ctx* c, const char* who, int N, int K, float* xyz, float* fdc, float* frest, float* scales, float* rot,
+                     float* opacity, const float* pBase, float* m, float* v, const gs_mcmc_params* params, McmcRows& rows)
+{
+    if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
+    if (N < 0 || K < 1 || K > 25) return fail(c, GS_ERR_INVALID_ARG, who);
+    if (N > 0 && (!xyz || !fdc || (K > 1 && !frest) || !scales || !rot || !opacity || !pBase || !m || !v))
+        return fail(c, GS_ERR_INVALID_ARG, who);
+    float* t[6] = {xyz, fdc, K > 1 ? frest : fdc, scales, rot, opacity};
+    for (int k = 0; k < 6; k++) {
+        if (N > 0 && t[k] < pBase) return fail(c, GS_ERR_INVALID_ARG, who);
+        rows.t[k] = t[k];
+    }
+    rows.pBase = pBase; rows.mBase = m; rows.vBase = v;
+    return GS_OK;
+}
+
+int gs_mcmc_relocate(gs_ctx* c, int N, int K, float* xyz, float* features_dc, float* features_rest, float* scales, float* rotation,
+                     float* opacity, const float* param_base, float* exp_avg, float* exp_avg_sq, const gs_mcmc_params* params,
+                     long long stats[4])
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!stats) return fail(c, GS_ERR_INVALID_ARG, "gs_mcmc_relocate: null stats");
+    McmcRows rows;
+    const int rc = mcmc_rows(c, "gs_mcmc_relocate: bad arguments", N, K, xyz, features_dc, features_rest, scales, rotation,
+                             opacity, param_base, exp_avg, exp_avg_sq, params, rows);
+    if (rc) return rc;
+    return mcmc_relocate(c, N, K, rows, *params, stats);
+}
+
+int gs_mcmc_grow(gs_ctx* c, int N, int capacity, int K, float* xyz, float* features_dc, float* features_rest, float* scales,
+                 float* rotation, float* opacity, const float* param_base, float* exp_avg, float* exp_avg_sq,
+                 const gs_mcmc_params* params, int* N_out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!N_out || capacity < N) return fail(c, GS_ERR_INVALID_ARG, "gs_mcmc_grow: bad arguments");
+    McmcRows rows;
+    const int rc = mcmc_rows(c, "gs_mcmc_grow: bad arguments", N, K, xyz, features_dc, features_rest, scales, rotation, opacity,
+                             param_base, exp_avg, exp_avg_sq, params, rows);
+    if (rc) return rc;
+    return mcmc_grow(c, N, capacity, K, rows, *params, N_out);
 }
 
 int gs_set_pose_correction(gs_ctx* c, const float* delta, float* grad_delta)

@@ -198,6 +198,11 @@ struct gs_ctx {
     float* posePartials = nullptr;
     long long posePartialsCap = 0;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
+    bool mcmcOn = false;                 // gs_set_mcmc: the MCMC strategy's step in gs_render_backward_adam, with these parameters
+    gs_mcmc_params mcmc = {};
+    void* mcmcWs = nullptr;              // mcmc.hip: the event's scratch (grown on demand) and its pinned read-back words
+    size_t mcmcWsBytes = 0;
+    long long* mcmcHost = nullptr;
     float* gradNormAccum = nullptr;      // caller-owned [N]: the projection backward adds |grad xyz| (gs_set_grad_norm_accum)
     uint32_t* segBase = nullptr;     // [numPixBlocks] first saved-state slot of each block
     float* segState = nullptr;       // [qslotCap][5][64] running (T, C, D) of an 8x8 quadrant, saved every GS_SEG_LEN splats
@@ -466,6 +471,22 @@ int launch_densify_gather_planned_packed(gs_ctx* c, int cap, int K, const float*
                                          const float* scales, const float* rot, const float* opacity, const int* gather,
                                          const int* noiseMode, unsigned long long noiseSeed, float* outBase, const int order[6]);
 int launch_densify_noise(gs_ctx* c, unsigned long long seed, int rows, float* out);
+// mcmc.hip (include/gsplat.h gs_set_mcmc and the gs_mcmc_* entry points; arguments checked by api.hip)
+struct McmcRows {            // the six tensors of rows [0, capacity) and where their moments lie
+    float* t[6];             // xyz, f_dc, f_rest, scales, rotation, opacity
+    const float* pBase;
+    float* mBase;
+    float* vBase;
+};
+int launch_mcmc_regularizer(gs_ctx* c, int N, const float* scales, const float* opacity, float* gScales, float* gOpacity,
+                            const gs_mcmc_params& p);
+int launch_mcmc_noise(gs_ctx* c, int N, float* xyz, const float* scales, const float* rot, const float* opacity, float lrXyz,
+                      const gs_mcmc_params& p);
+int launch_mcmc_random(gs_ctx* c, unsigned long long seed, int iteration, int stream, int n, uint32_t* words, float* normals,
+                       double* uniforms);
+int mcmc_relocate(gs_ctx* c, int N, int K, const McmcRows& rows, const gs_mcmc_params& p, long long stats[4]);
+int mcmc_grow(gs_ctx* c, int N, int capacity, int K, const McmcRows& rows, const gs_mcmc_params& p, int* nOut);
+void mcmc_free(gs_ctx* c);
 // knn.hip
 int launch_dist_topk(gs_ctx* c, int N, int k, int qBegin, int qCount, const float* xyz, float* out);
 // ply.hip

@@ -12,6 +12,7 @@
 //    the per-Gaussian data crosses HBM once.
 // One lane per Gaussian; HBM-bound (408 B/Gaussian forward, 728 B backward at K=25).
 #include "gs_ctx.h"
+#include "gs_mcmc.h"
 #include "gs_rider.h"
 
 namespace gs {
@@ -435,14 +436,19 @@ __device__ __forceinline__ float wave_sum_xor(float v)
 // pose_grad_kernel sums them.  A row with an all-zero cotangent contributes exactly 0 (as its own gradients do).
 // AA (anti-aliased mode, gs_set_antialiasing): the forward blended sigma(o) rho; dop is the cotangent of that product, so
 // dL/do_raw = dop rho sigma (1 - sigma) and the covariance cotangent gains the VJP of rho (project_geometry_bwd<., true>).
-template <int MODE, bool POSE, bool AA = false>
+// MCMC (the MCMC strategy's per-step part, gs_set_mcmc; MODE 2 only): the regularisers' gradients join the opacity and scale
+// gradients in front of adam_step, and the position noise (gs_mcmc.h mcmc_noise) of the updated parameters joins the
+// updated xyz in front of the stores.
+template <int MODE, bool POSE, bool AA = false, bool MCMC = false>
 __device__ __forceinline__ void proj_bwd_fused_body(
     int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
     const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
     float* gFdc, float* gFrest, float* gScales, float* gRot,
-    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials)
+    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials,
+    McmcFuse mc = McmcFuse{})
 {
+    static_assert(!MCMC || MODE == 2, "the MCMC step is fused into the Adam form only");
     constexpr bool EMIT_MG = MODE == 1, ADAM = MODE == 2;
     extern __shared__ float shLds[];
     // no update from a forward that did not render (gs_ctx.h adamGate).  The word is requested here and looked at only
@@ -601,6 +607,11 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     const float sg = 1.0f / (1.0f + expf(-opr));
     const float gop = (AA ? cotOpacity * aaRho : cotOpacity) * sg * (1.0f - sg);
     if (ADAM) sg_[10] = gop; else gOpacity[p] = gop;
+    if constexpr (MCMC) {      // + the gradients of opacity_reg mean(sigma(o)) and scale_reg mean(exp(s)) (mcmc_reg_kernel's sums)
+        sg_[10] = sg_[10] + mc.oCoef * mcmc_sigmoid_slope(opr);
+#pragma unroll
+        for (int a = 0; a < 3; a++) sg_[3 + a] = sg_[3 + a] + mc.sCoef * s[a];
+    }
     if (ADAM && !gateWord) {
         // the 14 small elements: values and moments were loaded at the top; one burst of stores here
         float sp[14] = {m[0], m[1], m[2], sr[0], sr[1], sr[2], rr[0], rr[1], rr[2], rr[3], opr, d0v[0], d0v[1], d0v[2]};
@@ -608,6 +619,11 @@ __device__ __forceinline__ void proj_bwd_fused_body(
                                adam.lr[4], adam.lr[4], adam.lr[4], adam.lr[5], adam.lr[1], adam.lr[1], adam.lr[1]};
 #pragma unroll
         for (int i = 0; i < 14; i++) adam_step(adam, sg_[i], slr[i], sp[i], sm_[i], sv_[i]);
+        if constexpr (MCMC) {
+            float dn[3];
+            mcmc_noise(mc, (uint32_t)p, sp + 3, sp + 6, sp[10], dn);
+            sp[0] = sp[0] + dn[0]; sp[1] = sp[1] + dn[1]; sp[2] = sp[2] + dn[2];
+        }
         float* pB = const_cast<float*>(adam.pBase);
         auto out3 = [&](int i0) {
             const size_t o = small_off(i0);
@@ -666,6 +682,30 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_kernel
     const CamParams cam = *dcam;
     proj_bwd_fused_body<MODE, true, AA>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
                                     gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials);
+}
+
+// The MCMC strategy's step (gs_set_mcmc): MODE 2 with the regularisers and the noise, plain and posed.  Kernels of their own,
+// so that the default ones above keep their code.
+template <bool AA>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_mcmc_kernel(
+    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
+    McmcFuse mc)
+{
+    proj_bwd_fused_body<2, false, AA, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam, nullptr, mc);
+}
+template <bool AA>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_mcmc_kernel(
+    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
+    float* __restrict__ posePartials, McmcFuse mc)
+{
+    const CamParams cam = *dcam;
+    proj_bwd_fused_body<2, true, AA, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, nullptr,
+                                           nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam, posePartials, mc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1157,6 +1197,22 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
     a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale;
     a.gate = c->adamGate;
     const bool aa = c->fwd.antialias;
+    if (c->mcmcOn) {
+        const McmcFuse mc = mcmc_fuse(c->mcmc, N, lr[0]);
+        if (c->fwd.poseDelta) {
+            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_mcmc_kernel<true> : proj_bwd_fused_pose_mcmc_kernel<false>),
+                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree,
+                               c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a,
+                               c->posePartials, mc);
+            GS_HIP_CHECK(c, hipGetLastError());
+            return launch_pose_grad(c, N);
+        }
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_mcmc_kernel<true> : proj_bwd_fused_mcmc_kernel<false>),
+                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam,
+                           xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a, mc);
+        GS_HIP_CHECK(c, hipGetLastError());
+        return GS_OK;
+    }
     if (c->fwd.poseDelta) {
         hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_kernel<2, true> : proj_bwd_fused_pose_kernel<2>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
                            c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr,

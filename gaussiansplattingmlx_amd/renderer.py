@@ -505,6 +505,55 @@ class GaussianRenderer:
     def antialiased(self, enable: bool):
         self.setAntialiased(enable)
 
+    # -- the MCMC strategy (include/gsplat.h gs_set_mcmc; mcmc.MCMCConfig.params builds the gs_mcmc_params) -----------------
+    def setMCMC(self, params=None):
+        """gs_set_mcmc: the MCMC strategy's per-step part (regularisers, noise) in the following renderBackwardAdam calls, or
+        None (off, the default)."""
+        self._check(self.lib.gs_set_mcmc(self.ctx, None if params is None else C.byref(params)))
+
+    def mcmcRegularizerGrad(self, scales, opacity, gradScales, gradOpacity, params):
+        """gs_mcmc_regularizer_grad: gradOpacity / gradScales += the regularisers' gradients (in place)."""
+        N = int(scales.shape[0])
+        self._check(self.lib.gs_mcmc_regularizer_grad(self.ctx, N, _p(scales), _p(opacity), _p(gradScales), _p(gradOpacity),
+                                                      C.byref(params)))
+
+    def mcmcInjectNoise(self, xyz, scales, rotation, opacity, lr_xyz: float, params):
+        """gs_mcmc_inject_noise: xyz += the step's noise (in place; gated like the optimizer kernels)."""
+        N = int(xyz.shape[0])
+        self._check(self.lib.gs_mcmc_inject_noise(self.ctx, N, _p(xyz), _p(scales), _p(rotation), _p(opacity),
+                                                  C.c_float(lr_xyz), C.byref(params)))
+
+    def mcmcRandom(self, seed: int, iteration: int, stream: int, n: int):
+        """gs_mcmc_random: (words uint32 [n,4] as int32, normals [n,3], uniforms float64 [n]) of stream 0 noise / 1 relocation
+        draws / 2 growth draws."""
+        words = self._empty(max(n, 1), 4, dtype=torch.int32)[:n]
+        normals = self._empty(max(n, 1), 3)[:n]
+        uniforms = self._empty(max(n, 1), dtype=torch.float64)[:n]
+        self._check(self.lib.gs_mcmc_random(self.ctx, C.c_ulonglong(int(seed)).value, int(iteration), int(stream), int(n),
+                                            _p(words), _p(normals), _p(uniforms)))
+        return words, normals, uniforms
+
+    def _mcmc_rows(self, params: dict):
+        K = int(params["features_rest"].shape[1]) + 1
+        return K, [_p(params[k]) for k in ("xyz", "features_dc", "features_rest", "scales", "rotation", "opacity")]
+
+    def mcmcRelocate(self, params: dict, arena, m, v, mcmcParams) -> dict:
+        """gs_mcmc_relocate over the rows of `params` (views into arena; m / v its moment arenas).  Waits for the counts."""
+        K, t = self._mcmc_rows(params)
+        st = (C.c_longlong * 4)()
+        self._check(self.lib.gs_mcmc_relocate(self.ctx, int(params["xyz"].shape[0]), K, *t, _p(arena), _p(m), _p(v),
+                                              C.byref(mcmcParams), st))
+        return dict(dead=int(st[0]), relocated=int(st[1]), live=int(st[2]), N=int(st[3]))
+
+    def mcmcGrow(self, params: dict, capacity: int, arena, m, v, mcmcParams) -> int:
+        """gs_mcmc_grow: appends the grown rows behind the N rows of `params` (each tensor must have room for `capacity`
+        rows); returns the new count.  Waits for the counts."""
+        K, t = self._mcmc_rows(params)
+        n = C.c_int()
+        self._check(self.lib.gs_mcmc_grow(self.ctx, int(params["xyz"].shape[0]), int(capacity), K, *t, _p(arena), _p(m), _p(v),
+                                          C.byref(mcmcParams), C.byref(n)))
+        return int(n.value)
+
     def renderBackwardAdam(self, cotColor, arena, m, v, lrs, beta1=0.9, beta2=0.999, eps=1e-15, grad_scale=1.0,
                            cotDepth=None, cotAlpha=None):
         """Backward with the Adam step fused into the projection backward (single-device steps): the parameters the

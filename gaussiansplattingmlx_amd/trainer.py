@@ -350,13 +350,34 @@ class GaussModel:
         self.m.zero_()
         self.v.zero_()
 
+    def restride(self, capacity: int):
+        """Lays the model out at stride = capacity >= N rows per tensor segment in fresh buffers, parameters and moments kept:
+        rows can then be appended in place up to `capacity` (setCount) with no pointer moving (the MCMC strategy's growth)."""
+        capacity = max(int(capacity), self.N)
+        if self.stride == capacity and self.capacity == capacity:
+            return
+        old = {name: self._carve(getattr(self, name), self.N, self.stride) for name in ("arena", "m", "v")}
+        self._pbuf[self._cur] = self._gbuf = self._mbuf = self._vbuf = None
+        self._pbuf[1 - self._cur] = None
+        self._layout(self.N, capacity, stride=capacity)
+        for name in ("arena", "m", "v"):
+            new = self._carve(getattr(self, name), self.N, self.stride)
+            for k in ARENA_ORDER:
+                new[k].copy_(old[name][k])
+
+    def setCount(self, N: int):
+        """The count after rows were appended in place at the current stride (N <= stride): the views are carved anew."""
+        if not self.N <= int(N) <= self.stride:
+            raise ValueError(f"setCount: {N} is not in [{self.N}, {self.stride}]")
+        self._layout(int(N), self.capacity, pads=(), stride=self.stride)
+
 
 class GaussianTrainer:
     def __init__(self, model: GaussModel, gaussRender: GaussianRenderer, iterationCount: int = 30000,
                  lambda_dssim: float = 0.2, process_group=None, dp_exchange: str = "sh_compressed",
                  exchange_when_single: bool = False, densify: bool = True, fuse_adam: bool = True,
                  exchange_impl: str = "torch", dp_bootstrap=None, views_per_rank: int = 1, pose_opt: bool = False,
-                 pose_lr=(1e-4, 1e-4), n_views: int | None = None):
+                 pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -380,7 +401,37 @@ class GaussianTrainer:
         camera within ~0.1 px of where it is at 800 px and a focal of ~1000, and reach a degree in a few hundred visits of a view.
         Raise them for poses known to be far off.  Needs
         n_views (the view keys are 0 .. n_views - 1) and a viewKey on every step; single-device steps only (one view per step,
-        no process group, no native exchange).  Off (the default): no kernel, buffer or result differs."""
+        no process group, no native exchange).  Off (the default): no kernel, buffer or result differs.
+
+        strategy: "reference" (the default: the reference's densification -- clone / split by accumulated |grad xyz|, prune,
+        optimizer reset every 100 steps -- when densify is on) or "mcmc": the MCMC strategy (mcmc.MCMCConfig, include/gsplat.h
+        gs_set_mcmc) with the settings `mcmc` (None: MCMCConfig()).  Every step adds the regularisers'
+        gradients and, behind Adam, the position noise; behind steps refine_start < t < refine_stop, t % refine_every == 0, dead
+        Gaussians are relocated onto live ones and the count grows by grow_rate up to cap_max.  The reference strategy is then
+        off (densify is ignored).  The model is laid out at stride = capacity >= cap_max on construction, so growth appends in
+        place; lastMCMCStats holds the last event's counts.  Single-device steps only (no process group, dp_bootstrap, native
+        exchange or views_per_rank > 1, no referenceParamReload); composes with pose_opt and an anti-aliased renderer."""
+        if strategy not in ("reference", "mcmc"):
+            raise ValueError(f"unknown strategy {strategy!r} (\"reference\" or \"mcmc\")")
+        self.strategy = strategy
+        self.mcmc = None
+        self.lastMCMCStats = None
+        if strategy == "mcmc":
+            from .mcmc import MCMCConfig
+            cfg = MCMCConfig() if mcmc is None else mcmc
+            if not isinstance(cfg, MCMCConfig):
+                raise ValueError("mcmc must be an MCMCConfig")
+            cfg.validate()
+            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
+                raise ValueError("strategy='mcmc': single-device steps only (no process group, dp_bootstrap or native exchange)")
+            if views_per_rank != 1:
+                raise ValueError("strategy='mcmc': one view per step only (views_per_rank > 1 is not supported)")
+            if cfg.cap_max < model.N:
+                raise ValueError(f"strategy='mcmc': cap_max = {cfg.cap_max} is below the model's N = {model.N}")
+            self.mcmc = cfg
+            densify = False
+        elif mcmc is not None:
+            raise ValueError("mcmc settings need strategy='mcmc'")
         self.pose_opt = bool(pose_opt)
         if self.pose_opt:
             if views_per_rank != 1:
@@ -463,7 +514,7 @@ class GaussianTrainer:
         # commit (:900-905): outside the densify window, and at every cadence without a change, its training falls back to
         # the last committed state.  False (default): not mirrored -- training keeps what it has learnt.  True: the
         # reference's trajectory (a copy of the parameters is kept at every commit and restored at those points).
-        self.referenceParamReload = False
+        self._referenceParamReload = False
         self._committed_params = None
         self.overflowRecoveries = 0                    # times the reserved pair capacity had to be regrown (see trainStep)
         self._checked_views = set()                    # views whose first forward has been checked for overflow
@@ -505,6 +556,9 @@ class GaussianTrainer:
             self._seen = torch.zeros(1, dtype=torch.int32, device=r.device)
             self._need = torch.zeros(1, dtype=torch.int64, device=r.device)
         self._alloc_exchange_buffers()
+        if self.mcmc is not None:
+            model.restride(max(self.mcmc.cap_max, model.capacity))
+            self._seg_end = (C.c_longlong * 6)(*[int(x) for x in model.seg_end])
         if self.pose_opt:
             self.nViews, self.poseLr = int(n_views), (float(pose_lr[0]), float(pose_lr[1]))
             # rows of 8 floats (the first 6 used): gs_adam_step takes 16-byte aligned arenas
@@ -516,6 +570,37 @@ class GaussianTrainer:
             self.checkReplicas()
             if self._plans_events():      # ... likewise the plan check's side stream and its 16-word collective
                 self.checkPlans(dict(zip(PLAN_WORDS, (model.N, 0, model.N, model.N, 0, 0, 0, model.N))))
+
+    @property
+    def referenceParamReload(self):
+        return self._referenceParamReload
+
+    @referenceParamReload.setter
+    def referenceParamReload(self, value):
+        if value and self.mcmc is not None:
+            raise ValueError("referenceParamReload mirrors the reference strategy's commits: not with strategy='mcmc'")
+        self._referenceParamReload = value
+
+    def _mcmcParams(self, iteration=None):
+        """The gs_mcmc_params of step `iteration` (default: the coming one)."""
+        return self.mcmc.params(self.iteration if iteration is None else iteration, self.noise_seed)
+
+    def _mcmcEvent(self, it: int):
+        """The MCMC strategy's event behind step `it` (include/gsplat.h gs_mcmc_relocate, gs_mcmc_grow): relocation, then
+        growth into the rows behind N (the model is laid out at stride = capacity >= cap_max: nothing moves)."""
+        r, m = self.gaussRender, self.model
+        prm = self._mcmcParams(it)
+        st = r.mcmcRelocate(m.getParams(), m.arena, m.m, m.v, prm)
+        N0 = m.N
+        N_new = r.mcmcGrow(m.getParams(), m.stride, m.arena, m.m, m.v, prm)
+        if N_new != N0:
+            m.setCount(N_new)
+        self.lastMCMCStats = dict(dead=st["dead"], relocated=st["relocated"], added=N_new - N0, N=N_new)
+        if st["relocated"] > 0 or N_new != N0:
+            r.dropDepthCuts()         # rows moved or were added: the views' depth cuts no longer describe the scene
+        if r.reserved is not None and N_new > r.reserved[0]:
+            r.reserve(N_new, int(r.reserved[1] * (N_new / max(r.reserved[0], 1)) * 1.1))
+        return self.lastMCMCStats
 
     def _dp_connect(self, bootstrap):
         """gs_dp_init: rank 0 draws the RCCL id, every rank gets it (through process_group, whatever its backend), and the
@@ -1039,6 +1124,8 @@ class GaussianTrainer:
         row = self._pose_row(viewKey) if self.pose_opt else None
         try:
             r.setTuning(depth_gradient=0)
+            if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
+                r.setMCMC(self._mcmcParams())
             if self.pose_opt:      # the view's correction, for every forward of this step (repeats included) and its backward
                 r.setPoseCorrection(self._pose_delta[row], self._pose_grad[row])
             if self._exchange:
@@ -1054,6 +1141,8 @@ class GaussianTrainer:
                     self._recover_overflow()      # (every regrow is by half at least: a few rounds reach any need)
         finally:
             r.setTuning(**restore)
+            if self.mcmc is not None:
+                r.setMCMC(None)
             if self.pose_opt:
                 r.setPoseCorrection(None, None)
 
@@ -1265,6 +1354,10 @@ class GaussianTrainer:
             fused = True
         elif not self._exchange:
             r.renderBackward(self._cot, out=m.getGrads())
+            if self.mcmc is not None:
+                g = m.getGrads()
+                r.mcmcRegularizerGrad(m.getParams()["scales"], m.getParams()["opacity"], g["scales"], g["opacity"],
+                                      self._mcmcParams())
             if self.densify:
                 self.addGradientAccumulation()
         elif self.dp_exchange == "allreduce":
@@ -1318,6 +1411,10 @@ class GaussianTrainer:
             lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
             r._check(r.lib.gs_adam_step(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
                                         C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0 / self.world)))
+            if self.mcmc is not None:
+                p = m.getParams()
+                r.mcmcInjectNoise(p["xyz"], p["scales"], p["rotation"], p["opacity"],
+                                  getLearningRates(self.iteration, self.iterationCount)[0], self._mcmcParams())
         if self.pose_opt:
             self._poseAdam(viewKey)
         return self._finishIteration()
@@ -1328,6 +1425,11 @@ class GaussianTrainer:
         self.iteration += 1
         if self.outputDirectory is not None and it % self.save_snapshot_per_iteration == 0:
             self.save_snapshot(it)
+        if self.mcmc is not None and self.mcmc.is_event(it):
+            self._mcmcEvent(it)
+            # the event has just waited for the device (its count reads): the overflow flag is cheap to look at now
+            if self._overflow_reported():
+                self.checkOverflow()
         if self.densify and it % self.split_and_prune_per_iteration == 0:
             self._committed = False
             self.split_and_prune(it)

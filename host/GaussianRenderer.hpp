@@ -136,6 +136,34 @@ public:
                                         oXyz, oFdc, oFrest, oScales, oRot, oOpacity));
     }
     void densifyNoise(unsigned long long seed, int rows, float* out) { check(gs_densify_noise(ctx_, seed, rows, out)); }
+    // The MCMC strategy (include/gsplat.h gs_set_mcmc): the per-step part in backwardAdam while set (nullptr = off), the
+    // stand-alone ops of the unfused step, and the event (relocation, then growth into the rows behind N).
+    void setMCMC(const gs_mcmc_params* p) { check(gs_set_mcmc(ctx_, p)); }
+    void mcmcRegularizerGrad(int N, const float* scales, const float* opacity, float* gScales, float* gOpacity, const gs_mcmc_params& p)
+    {
+        check(gs_mcmc_regularizer_grad(ctx_, N, scales, opacity, gScales, gOpacity, &p));
+    }
+    void mcmcInjectNoise(int N, float* xyz, const float* scales, const float* rot, const float* opacity, float lrXyz,
+                         const gs_mcmc_params& p)
+    {
+        check(gs_mcmc_inject_noise(ctx_, N, xyz, scales, rot, opacity, lrXyz, &p));
+    }
+    void mcmcRandom(unsigned long long seed, int iteration, int stream, int n, uint32_t* words, float* normals, double* uniforms)
+    {
+        check(gs_mcmc_random(ctx_, seed, iteration, stream, n, words, normals, uniforms));
+    }
+    void mcmcRelocate(int N, int K, float* xyz, float* fdc, float* frest, float* scales, float* rot, float* opacity,
+                      const float* paramBase, float* m, float* v, const gs_mcmc_params& p, long long stats[4])
+    {
+        check(gs_mcmc_relocate(ctx_, N, K, xyz, fdc, frest, scales, rot, opacity, paramBase, m, v, &p, stats));
+    }
+    int mcmcGrow(int N, int capacity, int K, float* xyz, float* fdc, float* frest, float* scales, float* rot, float* opacity,
+                 const float* paramBase, float* m, float* v, const gs_mcmc_params& p)
+    {
+        int n = N;
+        check(gs_mcmc_grow(ctx_, N, capacity, K, xyz, fdc, frest, scales, rot, opacity, paramBase, m, v, &p, &n));
+        return n;
+    }
     // Rank 0 draws the RCCL id (dpUniqueId) and hands its 128 bytes to every rank by whatever channel the launcher has;
     // dpInit is collective.  After forwardWithCameraParams + loss on this rank's view, dpStep runs backward, gradient
     // exchange (RCCL on the library's own side stream) and Adam with grad_scale = 1 / world; replicas stay identical.

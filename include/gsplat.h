@@ -273,6 +273,73 @@ int gs_set_pose_correction(gs_ctx* ctx, const float* delta /*DEVICE [6] or NULL*
  * record it: render a model in the mode it was trained in. */
 int gs_set_antialiasing(gs_ctx* ctx, int enable);
 
+/* MCMC densification strategy (not in the reference; DESIGN.md "MCMC strategy"): "3D Gaussian Splatting as Markov Chain Monte
+ * Carlo" (Kheradmand et al. 2024), gsplat's MCMCStrategy, with its defaults in brackets.  Notation: o = sigmoid(opacity_raw),
+ * s = exp(scales_raw), R the rotation of q / (|q| + 1e-8), Sigma = R diag(s^2) R^T, N the Gaussian count.
+ *   Every step (a step the overflow gate skips changes nothing, noise included):
+ *     regularisers: the gradient gains opacity_reg o (1 - o) / N on every opacity_raw and scale_reg s_j / (3 N) on every
+ *       scales_raw element, visible or not (the gradients of opacity_reg mean(o) + scale_reg mean(s));
+ *     Adam, unchanged (the project's, no bias correction);
+ *     noise, from the parameters AFTER the update: xyz += Sigma eps noise_lr lr_xyz / (1 + exp(-100 ((1 - o) - 0.995))),
+ *       eps ~ N(0, I3) from Philox4x32-10 with counter (row, iteration, "mcmc", "nois") and key seed (gs_mcmc_random stream 0),
+ *       lr_xyz the xyz learning rate of the step's Adam.
+ *   Every event (the host's cadence), after that step's Adam and noise: gs_mcmc_relocate, then gs_mcmc_grow.
+ * The four float64 scalars are rounded to float32 where a kernel uses them; opacity_reg / N, scale_reg / (3 N) and
+ * noise_lr lr_xyz are formed in float64 first. */
+typedef struct gs_mcmc_params {
+    double noise_lr;          /* 5e5 */
+    double opacity_reg;       /* 0.01 */
+    double scale_reg;         /* 0.01 */
+    double min_opacity;       /* 0.005: a row with o <= min_opacity, or o not finite, is dead */
+    double grow_rate;         /* 0.05: growth to min(cap_max, floor((1 + grow_rate) N)) */
+    long long cap_max;        /* 1000000: the budget; N never exceeds it */
+    int n_max;                /* 51: the relocation formula's largest n, 1 .. 51 */
+    int iteration;            /* t: keys the step's noise and the event's draws */
+    unsigned long long seed;  /* key of every stream of the strategy */
+} gs_mcmc_params;
+
+/* The strategy's per-step part for gs_render_backward_adam (NULL = off, the default): while set, that call adds the
+ * regularisers' gradients in front of its Adam update and the noise behind it, in the same kernel (plain, posed, either
+ * anti-aliasing mode).  The struct is copied; set it again when `iteration` changes.  A per-context setting as
+ * gs_set_antialiasing is; gs_render_backward, the data-parallel entry points and the op-level ones ignore it. */
+int gs_set_mcmc(gs_ctx* ctx, const gs_mcmc_params* params /*HOST or NULL*/);
+/* The regularisers alone (the unfused step: gs_render_backward, this, gs_adam_step, gs_mcmc_inject_noise):
+ * grad_opacity[i] += opacity_reg o (1 - o) / N, grad_scales[i, j] += scale_reg s_j / (3 N), over all N rows. */
+int gs_mcmc_regularizer_grad(gs_ctx* ctx, int N, const float* scales, const float* opacity, float* grad_scales,
+                             float* grad_opacity, const gs_mcmc_params* params /*HOST*/);
+/* The noise alone: xyz += the step's noise of the parameters as they are now (call it behind the step's gs_adam_step).
+ * lr_xyz: that step's xyz learning rate.  Gated like the optimizer kernels (gs_set_update_gate). */
+int gs_mcmc_inject_noise(gs_ctx* ctx, int N, float* xyz, const float* scales, const float* rotation, const float* opacity,
+                         float lr_xyz, const gs_mcmc_params* params /*HOST*/);
+/* The generator, raw: for i in [0, n), Philox4x32-10 with counter (i, iteration, 0x6d636d63, tag) and key seed, tag by
+ * stream: 0 noise 0x6e6f6973, 1 relocation draws 0x72656c6f, 2 growth draws 0x67726f77.  words[n,4] the four output words;
+ * normals[n,3] = (r_a cos 2 pi u1, r_a sin 2 pi u1, r_b cos 2 pi u3), r_a = sqrt(-2 ln u0), r_b = sqrt(-2 ln u2),
+ * u_k = ((w_k >> 8) + 1/2) 2^-24, in float32; uniforms[n] = ((w0 >> 5) 2^26 + (w1 >> 6) + 1/2) 2^-53 in float64.  Any
+ * output may be NULL. */
+int gs_mcmc_random(gs_ctx* ctx, unsigned long long seed, int iteration, int stream, int n, uint32_t* words,
+                   float* normals, double* uniforms);
+/* Relocation.  Rows [0, N) of the six tensors (raw; features_rest [N, K-1, 3]), whose Adam moments lie at the same offsets
+ * from exp_avg / exp_avg_sq as the tensors from param_base (gs_render_backward_adam's arenas).  If there is at least one
+ * dead and one live row: n_dead sources are drawn from the live rows with replacement, probability proportional to o (the
+ * inverse CDF over a float64 prefix sum of the live rows in index order, uniforms from stream 1 keyed by `iteration`); a
+ * source drawn c times gets n = min(c + 1, n_max),
+ *   o' = clamp(1 - (1 - o)^(1/n), min_opacity, 1 - 2^-23),
+ *   s' = s o / sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1)       (float64),
+ * opacity_raw = logit(o'), scales_raw = log(s'); the k-th dead row (index order) receives the k-th draw's modified source
+ * row, all six tensors.  The moments of sources and destinations are zeroed; every other row and moment is left alone.
+ * Deterministic (no float atomics).  stats HOST [4] = dead, relocated, live, N.  [sync: one read of the counts] */
+int gs_mcmc_relocate(gs_ctx* ctx, int N, int K, float* xyz, float* features_dc, float* features_rest, float* scales,
+                     float* rotation, float* opacity, const float* param_base, float* exp_avg, float* exp_avg_sq,
+                     const gs_mcmc_params* params /*HOST*/, long long stats[4] /*HOST*/);
+/* Growth.  n_add = min(cap_max, floor((1 + grow_rate) N)) - N if positive; n_add sources are drawn from all N rows with
+ * probability proportional to o (rows whose opacity_raw is not finite weigh 0; stream 2), modified as gs_mcmc_relocate's sources are,
+ * and their modified rows appended at [N, N + n_add) with zero moments.  The tensors must have room for `capacity` rows
+ * (GS_ERR_SIZE_MISMATCH if N + n_add would exceed it).  No row weighs anything: nothing is added.  *N_out = the new count.
+ * [sync: one read of the counts] */
+int gs_mcmc_grow(gs_ctx* ctx, int N, int capacity, int K, float* xyz, float* features_dc, float* features_rest,
+                 float* scales, float* rotation, float* opacity, const float* param_base, float* exp_avg, float* exp_avg_sq,
+                 const gs_mcmc_params* params /*HOST*/, int* N_out /*HOST*/);
+
 /* Data-parallel form of gs_render_backward (not in the reference, which is single-device): identical, except that
  * instead of the two SH gradient tensors it returns color_cot[N,3] = the cotangent of the SH colour after the
  * max(., 0) gate.  One view's SH gradient is basis_k(xyz - cam_center) x color_cot, so ranks exchange 12 B per
