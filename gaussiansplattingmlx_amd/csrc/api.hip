@@ -427,6 +427,7 @@ int gs_ctx_destroy(gs_ctx* c)
     if (c->densifyPlanHost) (void)hipHostFree(c->densifyPlanHost);
     dev_free(c->densifyPlan);
     dev_free(c->poseCam); dev_free(c->posePartials);
+    dev_free(c->expoImage); dev_free(c->expoPartials);
     dev_free(c->densifyTable);
     mcmc_free(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -922,6 +923,26 @@ int gs_set_pose_correction(gs_ctx* c, const float* delta, float* grad_delta)
     return GS_OK;
 }
 
+int gs_set_exposure(gs_ctx* c, const float* M, float* grad)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!M != !grad) return fail(c, GS_ERR_INVALID_ARG, "gs_set_exposure: M and grad are both set or both NULL");
+    // (once per ctx, here: a step never allocates)
+    if (M && !c->expoPartials) { const int arc = dev_alloc(c, &c->expoPartials, (size_t)exposure_partials_doubles()); if (arc) return arc; }
+    if (M && !c->expoImage) { const int arc = dev_alloc(c, &c->expoImage, (size_t)3 * c->H * c->W); if (arc) return arc; }
+    c->expoM = M;
+    c->expoGrad = grad;
+    return GS_OK;
+}
+
+int gs_apply_exposure(gs_ctx* c, long long n_pixels, const float* M, const float* in, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_exposure: negative n_pixels");
+    if (n_pixels > 0 && (!M || !in || !out)) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_exposure: null buffer");
+    return launch_exposure_apply(c, n_pixels, M, in, out);
+}
+
 int gs_render_backward(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha,
                        float* grad_xyz, float* grad_features_dc, float* grad_features_rest, float* grad_scales,
                        float* grad_rotation, float* grad_opacity)
@@ -1132,8 +1153,17 @@ int gs_loss_forward_backward(gs_ctx* c, const float* render, const float* target
         return fail(c, GS_ERR_INVALID_ARG, "gs_loss_forward_backward: depth loss needs depth buffers");
     { const int orc = deferred_overflow(c); if (orc) return orc; }
     GsStageTimer t(c, GS_STAGE_LOSS);
-    return launch_loss(c, render, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth, loss_out,
-                       cot_color, cot_depth);
+    if (!c->expoM)
+        return launch_loss(c, render, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth, loss_out,
+                           cot_color, cot_depth);
+    // exposure compensation: the loss of A r + b (the ctx's scratch image; the render itself is left alone), then
+    // cot_color <- A^T cot_color and grad <- dL/dM
+    const long long np = (long long)c->H * c->W;
+    if (const int rc = launch_exposure_apply(c, np, c->expoM, render, c->expoImage)) return rc;
+    if (const int rc = launch_loss(c, c->expoImage, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth,
+                                   loss_out, cot_color, cot_depth))
+        return rc;
+    return launch_exposure_backward(c, np, c->expoM, render, cot_color, c->expoPartials, c->expoGrad);
 }
 
 int gs_loss_target_cache_floats(gs_ctx* c, long long* n)

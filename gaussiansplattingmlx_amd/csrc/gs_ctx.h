@@ -197,6 +197,12 @@ struct gs_ctx {
     gs::CamParams* poseCam = nullptr;
     float* posePartials = nullptr;
     long long posePartialsCap = 0;
+    // exposure compensation (gs_set_exposure): caller-owned device M[12] / grad[12], nullptr = off; the corrected image the
+    // loss reads ([H, W, 3]) and the backward's per-workgroup float64 partials, both allocated at the first exposure set
+    const float* expoM = nullptr;
+    float* expoGrad = nullptr;
+    float* expoImage = nullptr;
+    double* expoPartials = nullptr;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
     bool mcmcOn = false;                 // gs_set_mcmc: the MCMC strategy's step in gs_render_backward_adam, with these parameters
     gs_mcmc_params mcmc = {};
@@ -392,6 +398,10 @@ bool depth_sort_takes_splitters(const gs_ctx* c, int N);      // binning.hip
 int launch_pose_camera(gs_ctx* c, const gs::CamParams& host, const float* delta);   // projection.hip, pose refinement
 int launch_pose_grad(gs_ctx* c, int N);
 long long pose_partials_floats(int N);
+int launch_exposure_apply(gs_ctx* c, long long n, const float* M, const float* in, float* out);      // exposure.hip
+int launch_exposure_backward(gs_ctx* c, long long n, const float* M, const float* render, float* cot, double* partials,
+                             float* grad);
+long long exposure_partials_doubles();
 int launch_colour_rest(gs_ctx* c);      // gs_rider.h: the colour units the binning kernels have not taken along
 int launch_color_cot(gs_ctx* c, int N, float* out);
 int launch_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, const float* mgAll,

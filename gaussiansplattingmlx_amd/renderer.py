@@ -108,6 +108,7 @@ class GaussianRenderer:
         self._target_cache = OrderedDict()
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
         self._antialiased = False
+        self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
         if antialiased:
             self.setAntialiased(True)
 
@@ -488,6 +489,29 @@ class GaussianRenderer:
                 raise ValueError("setPoseCorrection: delta and grad are contiguous float32 device tensors of 6 elements")
         self._check(self.lib.gs_set_pose_correction(self.ctx, None if delta is None else _p(delta), None if grad is None else _p(grad)))
         self._pose = (delta, grad)        # (kept alive while the library holds their addresses)
+
+    def setExposure(self, M=None, grad=None):
+        """gs_set_exposure: M / grad float32 device tensors of 12 elements (M = [A | b] row-major 3 x 4), or both None (off, the
+        default).  The following lossForwardBackward calls take the loss of A render + b, return dL/d render as the colour
+        cotangent and overwrite grad with dL/dM (include/gsplat.h)."""
+        if (M is None) != (grad is None):
+            raise ValueError("setExposure: M and grad are both given or both None")
+        for t in (M, grad):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != 12 or not t.is_contiguous() or t.device.type != "cuda"):
+                raise ValueError("setExposure: M and grad are contiguous float32 device tensors of 12 elements")
+        self._check(self.lib.gs_set_exposure(self.ctx, _p(M), _p(grad)))
+        self._exposure = (M, grad)        # (kept alive while the library holds their addresses)
+
+    def applyExposure(self, img, M, out=None):
+        """gs_apply_exposure: A img + b per pixel of an [..., 3] image (a new tensor; out=img works in place)."""
+        img, M = self._t(img), self._t(M)
+        if img.shape[-1] != 3 or M.numel() != 12:
+            raise ValueError("applyExposure: an [..., 3] image and a 12-element M")
+        out = torch.empty_like(img) if out is None else out
+        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("applyExposure: out is a contiguous float32 tensor of the image's shape")
+        self._check(self.lib.gs_apply_exposure(self.ctx, img.numel() // 3, _p(M), _p(img), _p(out)))
+        return out
 
     def setAntialiased(self, enable: bool = True):
         """gs_set_antialiasing: the anti-aliased mode (Mip-Splatting's 2-D filter; include/gsplat.h) for the

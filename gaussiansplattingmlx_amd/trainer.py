@@ -14,6 +14,7 @@ grad_scale = 1/world_size (loss = mean over the views of the step).  Two exchang
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -37,6 +38,13 @@ def arenaLearningRates(current: int, total: int):
     """getLearningRates permuted from PARAM_ORDER into ARENA_ORDER."""
     lr = dict(zip(PARAM_ORDER, getLearningRates(current, total)))
     return [lr[k] for k in ARENA_ORDER]
+
+
+def exposureLearningRate(current: int, total: int, lr=(0.01, 0.001)) -> float:
+    """The exposure's learning rate at step `current` of `total`: log-linear from lr[0] to lr[1], held at lr[1] from `total`
+    on -- Inria's schedule for its per-image exposures (get_expon_lr_func, no delay)."""
+    s = min(float(current) / float(total), 1.0) if total > 0 else 1.0
+    return math.exp((1.0 - s) * math.log(lr[0]) + s * math.log(lr[1]))
 
 
 def view_for(step: int, rank: int, world: int, n_views: int) -> int:
@@ -377,7 +385,8 @@ class GaussianTrainer:
                  lambda_dssim: float = 0.2, process_group=None, dp_exchange: str = "sh_compressed",
                  exchange_when_single: bool = False, densify: bool = True, fuse_adam: bool = True,
                  exchange_impl: str = "torch", dp_bootstrap=None, views_per_rank: int = 1, pose_opt: bool = False,
-                 pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None):
+                 pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None,
+                 exposure_opt: bool = False, exposure_lr=(0.01, 0.001)):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -402,6 +411,15 @@ class GaussianTrainer:
         Raise them for poses known to be far off.  Needs
         n_views (the view keys are 0 .. n_views - 1) and a viewKey on every step; single-device steps only (one view per step,
         no process group, no native exchange).  Off (the default): no kernel, buffer or result differs.
+
+        exposure_opt: per-view exposure compensation (include/gsplat.h gs_set_exposure).  Every training
+        view v has an affine colour transform M_v = [A | b] (3 x 4, the identity at the start); the loss of a step is taken of
+        A render + b, and M_v is trained with it by its own Adam step (the project's Adam: beta (0.9, 0.999), eps 1e-15, no bias
+        correction) at exposureLearningRate(t, iterationCount, exposure_lr), log-linear from exposure_lr[0] to exposure_lr[1]
+        (Inria's defaults 0.01 -> 0.001).  Only the visited view's row moves.  Needs n_views and a viewKey on every step, as
+        pose_opt does; single-device steps only.  Composes with pose_opt, strategy='mcmc', an anti-aliased renderer and
+        referenceParamReload (which restores the model, not the exposures).  exposures() returns the learned transforms,
+        exposedRender(render, viewKey) a render under one.  Off (the default): no kernel, buffer or result differs.
 
         strategy: "reference" (the default: the reference's densification -- clone / split by accumulated |grad xyz|, prune,
         optimizer reset every 100 steps -- when densify is on) or "mcmc": the MCMC strategy (mcmc.MCMCConfig, include/gsplat.h
@@ -442,6 +460,20 @@ class GaussianTrainer:
                 raise ValueError("pose_opt needs n_views >= 1 (view keys 0 .. n_views - 1)")
             if len(pose_lr) != 2:
                 raise ValueError("pose_lr = (rotation rate, translation rate)")
+        self.exposure_opt = bool(exposure_opt)
+        if self.exposure_opt:
+            if views_per_rank != 1:
+                raise ValueError("exposure_opt: one view per step only (views_per_rank > 1 is not supported)")
+            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
+                raise ValueError("exposure_opt: single-device steps only (no process group, dp_bootstrap or native exchange)")
+            if n_views is None or isinstance(n_views, bool) or int(n_views) != n_views or int(n_views) < 1:
+                raise ValueError("exposure_opt needs n_views >= 1 (view keys 0 .. n_views - 1)")
+            try:
+                elr = tuple(float(x) for x in exposure_lr)
+            except (TypeError, ValueError):
+                elr = ()
+            if len(elr) != 2 or not all(math.isfinite(x) and x > 0.0 for x in elr):
+                raise ValueError("exposure_lr = (initial rate, final rate), both positive and finite")
         if dp_exchange not in ("sh_compressed", "allreduce"):
             raise ValueError(f"unknown dp_exchange {dp_exchange!r}")
         if exchange_impl not in ("torch", "native"):
@@ -564,6 +596,11 @@ class GaussianTrainer:
             # rows of 8 floats (the first 6 used): gs_adam_step takes 16-byte aligned arenas
             z = lambda: torch.zeros((self.nViews, 8), dtype=torch.float32, device=r.device)[:, :6]      # noqa: E731
             self._pose_delta, self._pose_m, self._pose_v, self._pose_grad = z(), z(), z(), z()
+        if self.exposure_opt:
+            self.nViews, self.exposureLr = int(n_views), elr
+            # rows of 12 floats (48 bytes: each row 16-byte aligned, as gs_adam_step wants), the identity [I | 0] to start
+            self._expo = torch.eye(3, 4, dtype=torch.float32, device=r.device).reshape(1, 12).repeat(self.nViews, 1).contiguous()
+            self._expo_grad, self._expo_m, self._expo_v = (torch.zeros_like(self._expo) for _ in range(3))
         if self._exchange:
             # the replicas must START identical too -- and the check's first call pays for the collective's set-up (a first
             # float64 max-reduce cost the torch exchange ~35 ms at the first densify event of a run) here, not there
@@ -1122,12 +1159,15 @@ class GaussianTrainer:
         # knobs of the caller's renderer that this step changes, put back whatever happens
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
         row = self._pose_row(viewKey) if self.pose_opt else None
+        erow = self._view_row(viewKey, "exposure_opt") if self.exposure_opt else None
         try:
             r.setTuning(depth_gradient=0)
             if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
                 r.setMCMC(self._mcmcParams())
             if self.pose_opt:      # the view's correction, for every forward of this step (repeats included) and its backward
                 r.setPoseCorrection(self._pose_delta[row], self._pose_grad[row])
+            if self.exposure_opt:  # the view's exposure, for every loss of this step (repeats included)
+                r.setExposure(self._expo[erow], self._expo_grad[erow])
             if self._exchange:
                 r.setTuning(host_overflow_errors=0)
                 if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
@@ -1145,14 +1185,40 @@ class GaussianTrainer:
                 r.setMCMC(None)
             if self.pose_opt:
                 r.setPoseCorrection(None, None)
+            if self.exposure_opt:
+                r.setExposure(None, None)
 
-    def _pose_row(self, viewKey) -> int:
+    def _view_row(self, viewKey, feature: str) -> int:
         if viewKey is None or isinstance(viewKey, (list, tuple)):
-            raise ValueError("pose_opt: every trainStep needs the viewKey of its one view")
+            raise ValueError(f"{feature}: every trainStep needs the viewKey of its one view")
         row = int(viewKey)
         if row != viewKey or not 0 <= row < self.nViews:
-            raise ValueError(f"pose_opt: viewKey {viewKey!r} is not one of 0 .. {self.nViews - 1}")
+            raise ValueError(f"{feature}: viewKey {viewKey!r} is not one of 0 .. {self.nViews - 1}")
         return row
+
+    def _pose_row(self, viewKey) -> int:
+        return self._view_row(viewKey, "pose_opt")
+
+    def _exposureAdam(self, viewKey):
+        """Adam on the view's twelve exposure floats (gs_adam_step, one segment at exposureLearningRate): gated like the step's
+        other optimizer kernels.  The other views' rows and moments are left alone."""
+        r, row = self.gaussRender, int(viewKey)
+        lr = exposureLearningRate(self.iteration, self.iterationCount, self.exposureLr)
+        r._check(r.lib.gs_adam_step(r.ctx, 12, _p(self._expo[row]), _p(self._expo_grad[row]), _p(self._expo_m[row]),
+                                    _p(self._expo_v[row]), 1, (C.c_longlong * 1)(12), (C.c_float * 1)(lr),
+                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0)))
+
+    def exposures(self) -> np.ndarray:
+        """The views' exposures M = [A | b], host float32 [n_views, 3, 4] (waits for the device)."""
+        if not self.exposure_opt:
+            raise ValueError("exposures: the trainer was built without exposure_opt")
+        return self._expo.cpu().numpy().reshape(self.nViews, 3, 4)
+
+    def exposedRender(self, render, viewKey):
+        """A render of view `viewKey` under the view's learned exposure (A render + b; gs_apply_exposure), a new tensor."""
+        if not self.exposure_opt:
+            raise ValueError("exposedRender: the trainer was built without exposure_opt")
+        return self.gaussRender.applyExposure(render, self._expo[self._view_row(viewKey, "exposure_opt")])
 
     def _poseAdam(self, viewKey):
         """Adam on the view's six pose floats (gs_adam_step, two segments: rotation, translation): gated like the step's other
@@ -1417,6 +1483,8 @@ class GaussianTrainer:
                                   getLearningRates(self.iteration, self.iterationCount)[0], self._mcmcParams())
         if self.pose_opt:
             self._poseAdam(viewKey)
+        if self.exposure_opt:
+            self._exposureAdam(viewKey)
         return self._finishIteration()
 
     def _finishIteration(self):

@@ -107,6 +107,12 @@ public:
                                        cotColor, nullptr));
     }
 
+    // Per-view exposure compensation (include/gsplat.h gs_set_exposure): while M / grad (device [12] each) are set, loss()
+    // takes the loss of A render + b, writes dL/d render into cotColor and overwrites grad with dL/dM; nullptr, nullptr = off.
+    void setExposure(const float* M, float* grad) { check(gs_set_exposure(ctx_, M, grad)); }
+    // out = A in + b for nPixels RGB pixels (device; out may be in): a training view under its learned exposure
+    void applyExposure(long long nPixels, const float* M, const float* in, float* out) { check(gs_apply_exposure(ctx_, nPixels, M, in, out)); }
+
     // The target's windowed SSIM statistics per training view (include/gsplat.h: gs_set_loss_target_cache): cache = device
     // buffer of lossTargetCacheFloats() floats, one per view; filled = false at a view's first loss, true afterwards.
     long long lossTargetCacheFloats() { long long n = 0; check(gs_loss_target_cache_floats(ctx_, &n)); return n; }

@@ -253,6 +253,27 @@ int gs_render_backward_adam(gs_ctx* ctx, const float* cot_color, const float* co
  * optimizer kernels. */
 int gs_set_pose_correction(gs_ctx* ctx, const float* delta /*DEVICE [6] or NULL*/, float* grad_delta /*DEVICE [6] or NULL*/);
 
+/* Per-view exposure compensation (not in the reference; DESIGN.md "Exposure compensation"): the photometric counterpart of pose
+ * refinement, as Inria's 3DGS trains it per training image.  M DEVICE [12] float32 = [A | b], row-major 3 x 4:
+ * M[4c + j] = A[c][j] (j < 3), M[4c + 3] = b[c]; the identity is A = I, b = 0.  Inria applies its exposure E as
+ * img @ E[:3, :3] + E[:3, 3]: in this convention A = E[:3, :3]^T, b = E[:3, 3].  While an exposure is set, each
+ * gs_loss_forward_backward takes the loss of the corrected image c_p = A r_p + b of the render r (no clamp), per channel
+ *   c_p[c] = fmaf(A[c][0], r0, fmaf(A[c][1], r1, fmaf(A[c][2], r2, b[c]))),
+ * writes dL/dr into cot_color,
+ *   dL/dr_p[j] = fmaf(A[0][j], g0, fmaf(A[1][j], g1, A[2][j] * g2)),   g_p = dL/dc_p (the loss's own cotangent),
+ * and OVERWRITES grad DEVICE [12] with dL/dM: dL/dA[c][j] = sum_p g_p[c] r_p[j], dL/db[c] = sum_p g_p[c], summed in float64
+ * in a fixed order (the same bits on every run) and rounded to float32.  With the identity, the loss and cot_color are the
+ * plain ones bit for bit.  The render is not written: the corrected image lives in a ctx-owned [H, W, 3] buffer, allocated at
+ * the first non-NULL call (no step allocates), and cot_color must not alias the render.  The depth term, the target cache
+ * (gs_set_loss_target_cache) and every render / backward entry point are unchanged; the op-level gs_ssim_* ignore the
+ * setting.  A repeated forward is followed by a repeated loss, which writes grad again.  M and grad are both set or both NULL;
+ * NULL (the default) issues the loss's launches exactly as without it.  Optimise M with gs_adam_step on its twelve floats: it
+ * is gated with the step's other optimizer kernels. */
+int gs_set_exposure(gs_ctx* ctx, const float* M /*DEVICE [12] or NULL*/, float* grad /*DEVICE [12] or NULL*/);
+/* out[p] = A in[p] + b for n_pixels RGB pixels ([n_pixels, 3] float32, DEVICE), in gs_set_exposure's order of operations; out may
+ * be in.  Shows or scores a training view under its learned exposure.  Asynchronous on the ctx stream. */
+int gs_apply_exposure(gs_ctx* ctx, long long n_pixels, const float* M /*DEVICE [12]*/, const float* in, float* out);
+
 /* Anti-aliased mode (not in the reference; DESIGN.md "Anti-aliased mode"): Mip-Splatting's 2-D filter, as Inria's rasterizer
  * (antialiasing) and gsplat (rasterize_mode="antialiased") offer it.  With Sigma a splat's projected 2-D covariance BEFORE the
  * reference's blur (J W Sigma3 W^T J^T) and Sigma_b = Sigma + 0.3 I the blurred one, each following gs_render_forward writes
