@@ -136,6 +136,8 @@ _SIGS = {
     "gs_set_pose_correction": (C.c_int, [_vp, _vp, _vp]),
     "gs_set_exposure": (C.c_int, [_vp, _vp, _vp]),
     "gs_apply_exposure": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp]),
+    "gs_set_bilateral_grid": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "gs_apply_bilateral_grid": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
     "gs_set_mcmc": (C.c_int, [_vp, _vp]),
     "gs_mcmc_regularizer_grad": (C.c_int, [_vp, C.c_int] + [_vp] * 5),

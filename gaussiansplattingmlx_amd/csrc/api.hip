@@ -427,7 +427,7 @@ int gs_ctx_destroy(gs_ctx* c)
     if (c->densifyPlanHost) (void)hipHostFree(c->densifyPlanHost);
     dev_free(c->densifyPlan);
     dev_free(c->poseCam); dev_free(c->posePartials);
-    dev_free(c->expoImage); dev_free(c->expoPartials);
+    dev_free(c->expoImage); dev_free(c->expoPartials); dev_free(c->bgPartials);
     dev_free(c->densifyTable);
     mcmc_free(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -927,6 +927,7 @@ int gs_set_exposure(gs_ctx* c, const float* M, float* grad)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!M != !grad) return fail(c, GS_ERR_INVALID_ARG, "gs_set_exposure: M and grad are both set or both NULL");
+    if (M && c->bgGrid) return fail(c, GS_ERR_INVALID_ARG, "gs_set_exposure: a bilateral grid is set (the two corrections are exclusive)");
     // (once per ctx, here: a step never allocates)
     if (M && !c->expoPartials) { const int arc = dev_alloc(c, &c->expoPartials, (size_t)exposure_partials_doubles()); if (arc) return arc; }
     if (M && !c->expoImage) { const int arc = dev_alloc(c, &c->expoImage, (size_t)3 * c->H * c->W); if (arc) return arc; }
@@ -941,6 +942,52 @@ int gs_apply_exposure(gs_ctx* c, long long n_pixels, const float* M, const float
     if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_exposure: negative n_pixels");
     if (n_pixels > 0 && (!M || !in || !out)) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_exposure: null buffer");
     return launch_exposure_apply(c, n_pixels, M, in, out);
+}
+
+int gs_set_bilateral_grid(gs_ctx* c, const float* grid, float* grad, int grid_w, int grid_h, int grid_l, float tv_weight)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!grid != !grad) return fail(c, GS_ERR_INVALID_ARG, "gs_set_bilateral_grid: grid and grad are both set or both NULL");
+    if (grid) {
+        if (c->expoM) return fail(c, GS_ERR_INVALID_ARG, "gs_set_bilateral_grid: an exposure is set (the two corrections are exclusive)");
+        if (!bilateral_shape_ok(grid_w, grid_h, grid_l))
+            return fail(c, GS_ERR_INVALID_ARG, "gs_set_bilateral_grid: grid_w, grid_h in [2, 64] and grid_l in [2, 32]");
+        if (!(tv_weight >= 0.0f) || !isfinite(tv_weight))
+            return fail(c, GS_ERR_INVALID_ARG, "gs_set_bilateral_grid: tv_weight must be finite and >= 0");
+        // (here and only here: a step never allocates; a trainer that sets the same shape every step allocates once)
+        if (grid_w != c->bgChunksW || grid_h != c->bgChunksH) {
+            c->bgChunks = bilateral_chunks(c->W, c->H, grid_w, grid_h);
+            c->bgChunksW = grid_w;
+            c->bgChunksH = grid_h;
+        }
+        const long long need = bilateral_partials_floats(grid_w, grid_h, grid_l, c->bgChunks);
+        if (need > c->bgPartialsCap) {
+            GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+            dev_free(c->bgPartials);
+            c->bgPartialsCap = 0;
+            if (const int arc = dev_alloc(c, &c->bgPartials, (size_t)need)) return arc;
+            c->bgPartialsCap = need;
+        }
+        if (!c->expoImage) { const int arc = dev_alloc(c, &c->expoImage, (size_t)3 * c->H * c->W); if (arc) return arc; }
+    }
+    c->bgGrid = grid;
+    c->bgGrad = grad;
+    c->bgW = grid_w;
+    c->bgH = grid_h;
+    c->bgL = grid_l;
+    c->bgTv = tv_weight;
+    return GS_OK;
+}
+
+int gs_apply_bilateral_grid(gs_ctx* c, int W, int H, const float* grid, int grid_w, int grid_h, int grid_l, const float* in,
+                            float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (W < 0 || H < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_bilateral_grid: negative image size");
+    if (!bilateral_shape_ok(grid_w, grid_h, grid_l))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_apply_bilateral_grid: grid_w, grid_h in [2, 64] and grid_l in [2, 32]");
+    if ((long long)W * H > 0 && (!grid || !in || !out)) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_bilateral_grid: null buffer");
+    return launch_bilateral_apply(c, W, H, grid, grid_w, grid_h, grid_l, in, out);
 }
 
 int gs_render_backward(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha,
@@ -1153,6 +1200,16 @@ int gs_loss_forward_backward(gs_ctx* c, const float* render, const float* target
         return fail(c, GS_ERR_INVALID_ARG, "gs_loss_forward_backward: depth loss needs depth buffers");
     { const int orc = deferred_overflow(c); if (orc) return orc; }
     GsStageTimer t(c, GS_STAGE_LOSS);
+    if (c->bgGrid) {
+        // bilateral grid: the loss of the sliced transform's image (the ctx's scratch image, as for an exposure), then
+        // cot_color <- dL/dr and grad <- dL/dG
+        if (const int rc = launch_bilateral_apply(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, render, c->expoImage)) return rc;
+        if (const int rc = launch_loss(c, c->expoImage, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth,
+                                       loss_out, cot_color, cot_depth))
+            return rc;
+        return launch_bilateral_backward(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, c->bgChunks, c->bgTv, render, cot_color,
+                                         c->bgPartials, c->bgGrad);
+    }
     if (!c->expoM)
         return launch_loss(c, render, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth, loss_out,
                            cot_color, cot_depth);

@@ -10,6 +10,7 @@
 //                          fixed order, no atomics);
 //   exposure_final_kernel  one workgroup: the workgroups' partials in float64, in block order -> grad[12] as float32.
 #include "gs_ctx.h"
+#include "gs_expo.h"
 
 namespace gs {
 
@@ -18,21 +19,6 @@ constexpr int EXPO_BWD_BLOCKS = 512;            // the backward's grid: a consta
 constexpr int EXPO_SEGS = 16;                    // the final kernel: block segments summed side by side, then in order
 static_assert(EXPO_BWD_BLOCKS % EXPO_SEGS == 0, "segments cover the blocks");
 static_assert(12 * EXPO_SEGS <= EXPO_THREADS, "one thread per component and segment");
-
-// M row-major 3 x 4: m[4c + j] = A[c][j] (j < 3), m[4c + 3] = b[c]
-__device__ __forceinline__ void expo_apply(const float* m, float r0, float r1, float r2, float o[3])
-{
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-        o[c] = fmaf(m[4 * c], r0, fmaf(m[4 * c + 1], r1, fmaf(m[4 * c + 2], r2, m[4 * c + 3])));
-}
-
-// A^T g: dL/dr[j] = A[0][j] g0 + A[1][j] g1 + A[2][j] g2, in that nesting
-__device__ __forceinline__ void expo_vjp(const float* m, float g0, float g1, float g2, float o[3])
-{
-#pragma unroll
-    for (int j = 0; j < 3; j++) o[j] = fmaf(m[j], g0, fmaf(m[4 + j], g1, m[8 + j] * g2));
-}
 
 // Four pixels (12 floats) per thread: three float4 where the buffers are 16-byte aligned, twelve floats otherwise
 template <bool VEC>

@@ -203,6 +203,16 @@ struct gs_ctx {
     float* expoGrad = nullptr;
     float* expoImage = nullptr;
     double* expoPartials = nullptr;
+    // bilateral grid (gs_set_bilateral_grid): caller-owned device grid / grad of bgW x bgH x bgL nodes, nullptr = off (never
+    // together with an exposure: the loss reads the corrected image from expoImage); the backward's per-(cell, chunk) partials,
+    // grown only by gs_set_bilateral_grid, and the chunk count of the grid shape they were sized for
+    const float* bgGrid = nullptr;
+    float* bgGrad = nullptr;
+    int bgW = 0, bgH = 0, bgL = 0;
+    float bgTv = 0.0f;
+    int bgChunks = 0, bgChunksW = 0, bgChunksH = 0;
+    float* bgPartials = nullptr;
+    long long bgPartialsCap = 0;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
     bool mcmcOn = false;                 // gs_set_mcmc: the MCMC strategy's step in gs_render_backward_adam, with these parameters
     gs_mcmc_params mcmc = {};
@@ -402,6 +412,12 @@ int launch_exposure_apply(gs_ctx* c, long long n, const float* M, const float* i
 int launch_exposure_backward(gs_ctx* c, long long n, const float* M, const float* render, float* cot, double* partials,
                              float* grad);
 long long exposure_partials_doubles();
+bool bilateral_shape_ok(int gw, int gh, int gl);       // bilateral_grid.hip
+int bilateral_chunks(int W, int H, int gw, int gh);
+long long bilateral_partials_floats(int gw, int gh, int gl, int nch);
+int launch_bilateral_apply(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, const float* in, float* out);
+int launch_bilateral_backward(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, int nch, float tvWeight,
+                              const float* render, float* cot, float* partials, float* grad);
 int launch_colour_rest(gs_ctx* c);      // gs_rider.h: the colour units the binning kernels have not taken along
 int launch_color_cot(gs_ctx* c, int N, float* out);
 int launch_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, const float* mgAll,

@@ -8,6 +8,7 @@ reference's init preconditions do (GaussianRenderer.swift:721-733).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from collections import OrderedDict, namedtuple
 
@@ -109,6 +110,7 @@ class GaussianRenderer:
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
         self._antialiased = False
         self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
+        self._bilateral = (None, None)  # setBilateralGrid's, likewise
         if antialiased:
             self.setAntialiased(True)
 
@@ -511,6 +513,48 @@ class GaussianRenderer:
         if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("applyExposure: out is a contiguous float32 tensor of the image's shape")
         self._check(self.lib.gs_apply_exposure(self.ctx, img.numel() // 3, _p(M), _p(img), _p(out)))
+        return out
+
+    @staticmethod
+    def _grid_shape(shape, what):
+        try:
+            gw, gh, gl = (int(x) for x in shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: shape = (grid_w, grid_h, grid_l)") from None
+        if not (2 <= gw <= 64 and 2 <= gh <= 64 and 2 <= gl <= 32) or tuple(shape) != (gw, gh, gl):
+            raise ValueError(f"{what}: shape = (grid_w, grid_h, grid_l) with 2 <= grid_w, grid_h <= 64 and 2 <= grid_l <= 32")
+        return gw, gh, gl
+
+    def setBilateralGrid(self, grid=None, grad=None, shape=(16, 16, 8), tv_weight: float = 10.0):
+        """gs_set_bilateral_grid: grid / grad float32 device tensors of grid_h x grid_w x grid_l x 12 elements (shape = (grid_w,
+        grid_h, grid_l); G[y][x][z] holds a 12-float M = [A | b] as in setExposure), or both None (off, the default).  The
+        following lossForwardBackward calls take the loss of the render under the grid, return dL/d render as the colour
+        cotangent and overwrite grad with dL/dG plus tv_weight times the TV term's gradient (include/gsplat.h).  Exclusive with
+        setExposure."""
+        if (grid is None) != (grad is None):
+            raise ValueError("setBilateralGrid: grid and grad are both given or both None")
+        gw, gh, gl = self._grid_shape(shape, "setBilateralGrid")
+        tv = float(tv_weight)
+        if not (math.isfinite(tv) and tv >= 0.0):
+            raise ValueError("setBilateralGrid: tv_weight must be finite and >= 0")
+        n = gw * gh * gl * 12
+        for t in (grid, grad):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device.type != "cuda"):
+                raise ValueError(f"setBilateralGrid: grid and grad are contiguous float32 device tensors of {n} elements")
+        self._check(self.lib.gs_set_bilateral_grid(self.ctx, _p(grid), _p(grad), gw, gh, gl, C.c_float(tv)))
+        self._bilateral = (grid, grad)    # (kept alive while the library holds their addresses)
+
+    def applyBilateralGrid(self, img, grid, shape=(16, 16, 8), out=None):
+        """gs_apply_bilateral_grid: an [H, W, 3] image under the grid (a new tensor; out=img works in place)."""
+        img, grid = self._t(img), self._t(grid)
+        gw, gh, gl = self._grid_shape(shape, "applyBilateralGrid")
+        if img.dim() != 3 or img.shape[-1] != 3 or grid.numel() != gw * gh * gl * 12:
+            raise ValueError("applyBilateralGrid: an [H, W, 3] image and a grid of grid_h x grid_w x grid_l x 12 elements")
+        out = torch.empty_like(img) if out is None else out
+        if out.shape != img.shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("applyBilateralGrid: out is a contiguous float32 tensor of the image's shape")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        self._check(self.lib.gs_apply_bilateral_grid(self.ctx, W, H, _p(grid), gw, gh, gl, _p(img), _p(out)))
         return out
 
     def setAntialiased(self, enable: bool = True):

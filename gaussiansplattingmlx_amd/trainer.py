@@ -47,6 +47,13 @@ def exposureLearningRate(current: int, total: int, lr=(0.01, 0.001)) -> float:
     return math.exp((1.0 - s) * math.log(lr[0]) + s * math.log(lr[1]))
 
 
+def bilateralGridLearningRate(current: int, total: int, lr: float = 2e-3) -> float:
+    """The bilateral grids' learning rate at step `current` of `total`: a linear warm-up from 1 % of lr over the first 1000
+    steps, times an exponential decay to 1 % at `total` (held from there on) -- gsplat's schedule for its bilateral grids."""
+    s = min(float(current) / float(total), 1.0) if total > 0 else 1.0
+    return lr * (0.01 + 0.99 * min(current, 1000) / 1000.0) * 0.01 ** s
+
+
 def view_for(step: int, rank: int, world: int, n_views: int) -> int:
     """View sharding: at step s the job consumes views [s*world, (s+1)*world) of a shared permutation; rank r takes
     the r-th of them.  No data-path collective is needed for the forward/backward; only gradients are exchanged."""
@@ -386,7 +393,8 @@ class GaussianTrainer:
                  exchange_when_single: bool = False, densify: bool = True, fuse_adam: bool = True,
                  exchange_impl: str = "torch", dp_bootstrap=None, views_per_rank: int = 1, pose_opt: bool = False,
                  pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None,
-                 exposure_opt: bool = False, exposure_lr=(0.01, 0.001)):
+                 exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
+                 bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -420,6 +428,17 @@ class GaussianTrainer:
         pose_opt does; single-device steps only.  Composes with pose_opt, strategy='mcmc', an anti-aliased renderer and
         referenceParamReload (which restores the model, not the exposures).  exposures() returns the learned transforms,
         exposedRender(render, viewKey) a render under one.  Off (the default): no kernel, buffer or result differs.
+
+        bilateral_grid: per-view bilateral grid colour correction (include/gsplat.h gs_set_bilateral_grid, DESIGN.md section
+        13), exposure compensation that varies over the image and with the render's luminance.  Every training view v has a grid
+        of bilateral_grid_shape = (grid_w, grid_h, grid_l) nodes, each a 3 x 4 affine transform (the identity at the start);
+        the loss of a step is taken of the render under the view's grid, and the grid is trained with it (plus
+        bilateral_grid_tv times its total variation) by its own Adam step (the project's Adam: beta (0.9, 0.999), eps 1e-15, no
+        bias correction) at bilateralGridLearningRate(t, iterationCount, bilateral_grid_lr).  Only the visited view's grid moves
+        and only it is regularised (gsplat regularises all grids every step).  Needs n_views and a viewKey on every step;
+        single-device steps only; not together with exposure_opt.  Composes with pose_opt, strategy='mcmc', an anti-aliased
+        renderer and referenceParamReload.  bilateralGrids() returns the learned grids, bilateralRender(render, viewKey) a render
+        under one.  Off (the default): no kernel, buffer or result differs.
 
         strategy: "reference" (the default: the reference's densification -- clone / split by accumulated |grad xyz|, prune,
         optimizer reset every 100 steps -- when densify is on) or "mcmc": the MCMC strategy (mcmc.MCMCConfig, include/gsplat.h
@@ -474,6 +493,26 @@ class GaussianTrainer:
                 elr = ()
             if len(elr) != 2 or not all(math.isfinite(x) and x > 0.0 for x in elr):
                 raise ValueError("exposure_lr = (initial rate, final rate), both positive and finite")
+        self.bilateral_grid = bool(bilateral_grid)
+        if self.bilateral_grid:
+            if self.exposure_opt:
+                raise ValueError("bilateral_grid and exposure_opt are exclusive (a constant grid is an exposure)")
+            if views_per_rank != 1:
+                raise ValueError("bilateral_grid: one view per step only (views_per_rank > 1 is not supported)")
+            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
+                raise ValueError("bilateral_grid: single-device steps only (no process group, dp_bootstrap or native exchange)")
+            if n_views is None or isinstance(n_views, bool) or int(n_views) != n_views or int(n_views) < 1:
+                raise ValueError("bilateral_grid needs n_views >= 1 (view keys 0 .. n_views - 1)")
+            from .renderer import GaussianRenderer
+            bgs = GaussianRenderer._grid_shape(bilateral_grid_shape, "bilateral_grid_shape")
+            try:
+                blr, btv = float(bilateral_grid_lr), float(bilateral_grid_tv)
+            except (TypeError, ValueError):
+                blr, btv = float("nan"), float("nan")
+            if isinstance(bilateral_grid_lr, bool) or not (math.isfinite(blr) and blr > 0.0):
+                raise ValueError("bilateral_grid_lr must be positive and finite")
+            if isinstance(bilateral_grid_tv, bool) or not (math.isfinite(btv) and btv >= 0.0):
+                raise ValueError("bilateral_grid_tv must be finite and >= 0")
         if dp_exchange not in ("sh_compressed", "allreduce"):
             raise ValueError(f"unknown dp_exchange {dp_exchange!r}")
         if exchange_impl not in ("torch", "native"):
@@ -601,6 +640,16 @@ class GaussianTrainer:
             # rows of 12 floats (48 bytes: each row 16-byte aligned, as gs_adam_step wants), the identity [I | 0] to start
             self._expo = torch.eye(3, 4, dtype=torch.float32, device=r.device).reshape(1, 12).repeat(self.nViews, 1).contiguous()
             self._expo_grad, self._expo_m, self._expo_v = (torch.zeros_like(self._expo) for _ in range(3))
+        if self.bilateral_grid:
+            self.nViews, self.bilateralGridShape = int(n_views), bgs
+            self.bilateralGridLr, self.bilateralGridTv = blr, btv
+            gw, gh, gl = bgs
+            # rows [grid_h, grid_w, grid_l, 12] (a multiple of 48 bytes: every row 16-byte aligned for gs_adam_step), the
+            # identity [I | 0] at every node to start; one gradient buffer serves every view (only the visited one is set)
+            eye = torch.eye(3, 4, dtype=torch.float32, device=r.device).reshape(12)
+            self._bg = eye.repeat(self.nViews, gh, gw, gl, 1).contiguous()
+            self._bg_m, self._bg_v = torch.zeros_like(self._bg), torch.zeros_like(self._bg)
+            self._bg_grad = torch.zeros_like(self._bg[0])
         if self._exchange:
             # the replicas must START identical too -- and the check's first call pays for the collective's set-up (a first
             # float64 max-reduce cost the torch exchange ~35 ms at the first densify event of a run) here, not there
@@ -1160,6 +1209,7 @@ class GaussianTrainer:
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
         row = self._pose_row(viewKey) if self.pose_opt else None
         erow = self._view_row(viewKey, "exposure_opt") if self.exposure_opt else None
+        brow = self._view_row(viewKey, "bilateral_grid") if self.bilateral_grid else None
         try:
             r.setTuning(depth_gradient=0)
             if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
@@ -1168,6 +1218,8 @@ class GaussianTrainer:
                 r.setPoseCorrection(self._pose_delta[row], self._pose_grad[row])
             if self.exposure_opt:  # the view's exposure, for every loss of this step (repeats included)
                 r.setExposure(self._expo[erow], self._expo_grad[erow])
+            if self.bilateral_grid:  # the view's grid, likewise
+                r.setBilateralGrid(self._bg[brow], self._bg_grad, self.bilateralGridShape, self.bilateralGridTv)
             if self._exchange:
                 r.setTuning(host_overflow_errors=0)
                 if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
@@ -1187,6 +1239,8 @@ class GaussianTrainer:
                 r.setPoseCorrection(None, None)
             if self.exposure_opt:
                 r.setExposure(None, None)
+            if self.bilateral_grid:
+                r.setBilateralGrid(None, None)
 
     def _view_row(self, viewKey, feature: str) -> int:
         if viewKey is None or isinstance(viewKey, (list, tuple)):
@@ -1219,6 +1273,29 @@ class GaussianTrainer:
         if not self.exposure_opt:
             raise ValueError("exposedRender: the trainer was built without exposure_opt")
         return self.gaussRender.applyExposure(render, self._expo[self._view_row(viewKey, "exposure_opt")])
+
+    def _bilateralGridAdam(self, viewKey):
+        """Adam on the view's grid (gs_adam_step, one segment at bilateralGridLearningRate): gated like the step's other
+        optimizer kernels.  The other views' grids and moments are left alone."""
+        r, row = self.gaussRender, int(viewKey)
+        n = self._bg_grad.numel()
+        lr = bilateralGridLearningRate(self.iteration, self.iterationCount, self.bilateralGridLr)
+        r._check(r.lib.gs_adam_step(r.ctx, n, _p(self._bg[row]), _p(self._bg_grad), _p(self._bg_m[row]), _p(self._bg_v[row]), 1,
+                                    (C.c_longlong * 1)(n), (C.c_float * 1)(lr), C.c_float(0.9), C.c_float(0.999),
+                                    C.c_float(1e-15), C.c_float(1.0)))
+
+    def bilateralGrids(self) -> np.ndarray:
+        """The views' grids, host float32 [n_views, grid_h, grid_w, grid_l, 12] (each node an M = [A | b]; waits for the device)."""
+        if not self.bilateral_grid:
+            raise ValueError("bilateralGrids: the trainer was built without bilateral_grid")
+        return self._bg.cpu().numpy()
+
+    def bilateralRender(self, render, viewKey):
+        """A render of view `viewKey` under the view's learned grid (gs_apply_bilateral_grid), a new tensor."""
+        if not self.bilateral_grid:
+            raise ValueError("bilateralRender: the trainer was built without bilateral_grid")
+        row = self._view_row(viewKey, "bilateral_grid")
+        return self.gaussRender.applyBilateralGrid(render, self._bg[row], self.bilateralGridShape)
 
     def _poseAdam(self, viewKey):
         """Adam on the view's six pose floats (gs_adam_step, two segments: rotation, translation): gated like the step's other
@@ -1485,6 +1562,8 @@ class GaussianTrainer:
             self._poseAdam(viewKey)
         if self.exposure_opt:
             self._exposureAdam(viewKey)
+        if self.bilateral_grid:
+            self._bilateralGridAdam(viewKey)
         return self._finishIteration()
 
     def _finishIteration(self):

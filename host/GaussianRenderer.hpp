@@ -112,6 +112,18 @@ public:
     void setExposure(const float* M, float* grad) { check(gs_set_exposure(ctx_, M, grad)); }
     // out = A in + b for nPixels RGB pixels (device; out may be in): a training view under its learned exposure
     void applyExposure(long long nPixels, const float* M, const float* in, float* out) { check(gs_apply_exposure(ctx_, nPixels, M, in, out)); }
+    // Per-view bilateral grid (include/gsplat.h gs_set_bilateral_grid; exclusive with setExposure): while grid / grad (device,
+    // gridH x gridW x gridL x 12 each) are set, loss() takes the loss of the sliced transform of render, writes dL/d render into
+    // cotColor and overwrites grad with dL/dG (+ tvWeight times the TV term's gradient); nullptr, nullptr = off.
+    void setBilateralGrid(const float* grid, float* grad, int gridW = 16, int gridH = 16, int gridL = 8, float tvWeight = 10.0f)
+    {
+        check(gs_set_bilateral_grid(ctx_, grid, grad, gridW, gridH, gridL, tvWeight));
+    }
+    // out = the w x h image in under the grid (device; out may be in): a training view under its learned grid
+    void applyBilateralGrid(int w, int h, const float* grid, int gridW, int gridH, int gridL, const float* in, float* out)
+    {
+        check(gs_apply_bilateral_grid(ctx_, w, h, grid, gridW, gridH, gridL, in, out));
+    }
 
     // The target's windowed SSIM statistics per training view (include/gsplat.h: gs_set_loss_target_cache): cache = device
     // buffer of lossTargetCacheFloats() floats, one per view; filled = false at a view's first loss, true afterwards.

@@ -274,6 +274,37 @@ int gs_set_exposure(gs_ctx* ctx, const float* M /*DEVICE [12] or NULL*/, float* 
  * be in.  Shows or scores a training view under its learned exposure.  Asynchronous on the ctx stream. */
 int gs_apply_exposure(gs_ctx* ctx, long long n_pixels, const float* M /*DEVICE [12]*/, const float* in, float* out);
 
+/* Per-view bilateral grid colour correction (not in the reference; DESIGN.md "Bilateral grid"; Wang et al. 2024, "Bilateral
+ * Guided Radiance Field Processing", gsplat's use_bilateral_grid): exposure compensation whose M varies over the image and with
+ * the render's luminance.  grid DEVICE float32 of grid_h x grid_w x grid_l nodes, G[y][x][z][k] row-major with the node's
+ * 12 coefficients innermost, each an M in gs_set_exposure's convention (m[4c + j] = A[c][j], m[4c + 3] = b[c]); at the
+ * default shape (16, 16, 8) 98,304 bytes.  2 <= grid_w, grid_h <= 64, 2 <= grid_l <= 32.  Pixel (x, y) of the W x H render r:
+ *   u = (float)((2x + 1)(grid_w - 1)) / (float)(2W),  v likewise with y, grid_h, H  (one correctly rounded division),
+ *   gray = fmaf(0.299f, r0, fmaf(0.587f, r1, 0.114f * r2)),  w = min(max(gray, 0), 1) * (grid_l - 1),
+ *   x0 = min((int)u, grid_w - 2), fu = u - x0;  y0, fv and z0, fw likewise,
+ *   a[k] = lerp over z of (lerp over y of (lerp over x)), lerp(a, b, t) = fmaf(t, b - a, a),
+ * and the loss is taken of c[c] = fmaf(a[4c], r0, fmaf(a[4c+1], r1, fmaf(a[4c+2], r2, a[4c+3]))) (no clamp), so a grid whose
+ * nodes all hold M gives gs_set_exposure(M)'s loss and cot_color bit for bit.  With g = dL/dc (the loss's own cotangent),
+ * P_hi / P_lo the bilinear values at layers z0 + 1 / z0 and da[4c + j] = g[c] r[j], da[4c + 3] = g[c]:
+ *   s = sum_k (P_hi[k] - P_lo[k]) da[k],  dgray = s (grid_l - 1) if 0 < gray < 1, else 0,
+ *   dL/dr[j] = fmaf(dgray, lum[j], fmaf(a[j], g0, fmaf(a[4 + j], g1, a[8 + j] * g2))),  lum = (0.299f, 0.587f, 0.114f),
+ * written into cot_color, and grad (the grid's shape) is OVERWRITTEN with dL/dG[node][k] = sum_p wt(p, node) da_p[k] +
+ * tv_weight dTV/dG[node][k], wt the trilinear weight, TV(G) = sum over the axes x, y, z of (1 / n_axis) sum (G_next - G)^2 with
+ * n_axis the number of (pair, k) terms on that axis (n_x = 12 grid_l grid_h (grid_w - 1)).  The sums run in a fixed order
+ * over a launch grid fixed by the image size and the grid shape (the same bits on every run, no atomics).  The corrected image
+ * lives in the ctx's exposure scratch image; the render is not written and cot_color must not alias it.  Everything else is as
+ * for gs_set_exposure: the depth term, the target cache and every render / backward entry point are unchanged, a repeated
+ * loss writes grad again, and gs_adam_step on the grid's floats is gated with the step's other optimizer kernels.  grid and
+ * grad are both set or both NULL; NULL (the default) issues the loss's launches exactly as without it, and ignores the shape
+ * and tv_weight.  tv_weight must be finite and >= 0.  A grid and an exposure are exclusive: while one is set, setting the
+ * other returns GS_ERR_INVALID_ARG and leaves the state as it was.  The partials buffer is allocated or grown here only. */
+int gs_set_bilateral_grid(gs_ctx* ctx, const float* grid /*DEVICE or NULL*/, float* grad /*DEVICE or NULL*/, int grid_w,
+                          int grid_h, int grid_l, float tv_weight);
+/* out = the W x H image in ([H, W, 3] float32, DEVICE) under the grid, in gs_set_bilateral_grid's order of operations; out may
+ * be in.  Shows or scores a training view under its learned grid.  Asynchronous on the ctx stream. */
+int gs_apply_bilateral_grid(gs_ctx* ctx, int W, int H, const float* grid /*DEVICE*/, int grid_w, int grid_h, int grid_l,
+                            const float* in /*[H,W,3]*/, float* out /*[H,W,3], may be in*/);
+
 /* Anti-aliased mode (not in the reference; DESIGN.md "Anti-aliased mode"): Mip-Splatting's 2-D filter, as Inria's rasterizer
  * (antialiasing) and gsplat (rasterize_mode="antialiased") offer it.  With Sigma a splat's projected 2-D covariance BEFORE the
  * reference's blur (J W Sigma3 W^T J^T) and Sigma_b = Sigma + 0.3 I the blurred one, each following gs_render_forward writes
