@@ -11,7 +11,7 @@ using namespace gs;
 
 namespace {
 
-int fail(gs_ctx* c, int code, const char* msg)
+int fail(gs_ctx* c, int code, const std::string& msg)
 {
     if (c) c->err = msg;
     return code;
@@ -270,6 +270,54 @@ int backward_preflight(gs_ctx* c, const char* who, bool wantsDepth)
     return GS_OK;
 }
 
+// the blend backward of the last fused forward: the first stage of every backward entry point
+int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha)
+{
+    GsStageTimer t(c, GS_STAGE_BLEND_BWD);
+    return c->fast16 ? launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
+                                                c->fwd.outAlpha)
+                     : launch_blend_backward(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+}
+
+// the gs_sh_grad_from_views* family's common arguments; own_bad / own_null: what the entry point's own arguments add to the
+// first and to the null-buffer check
+int sh_views_args(gs_ctx* c, const char* who, int N, int K, int R, const float* xyz, const float* color_cot_all,
+                  const float* cam_centers, const float* dc, const float* rest, bool own_bad, bool own_null)
+{
+    if (N < 0 || K < 1 || R < 1 || R > 16 || !cam_centers || own_bad)
+        return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": bad N/K/R");
+    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
+    if (N > 0 && (!xyz || !color_cot_all || !dc || (K > 1 && !rest) || own_null))
+        return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    return GS_OK;
+}
+
+// ... and their last check: the gathered blocks' layout, where gs_set_gathered_gate has described one
+int sh_views_gate_layout(gs_ctx* c, const char* who, int N, int R)
+{
+    if (c->ccBlockFloats > 0 && (R != c->ccBlockCount || c->ccBlockFloats < 3LL * N + 1))
+        return fail(c, GS_ERR_SIZE_MISMATCH, std::string(who) + ": R / N do not match the gs_set_gathered_gate layout");
+    return GS_OK;
+}
+
+// the SH tensors of a fused SH rebuild + Adam lie in [params_base, params_base + n_arena)
+int sh_in_arena(gs_ctx* c, const char* who, int N, int K, const float* dc, const float* rest, const float* params_base,
+                long long n_arena)
+{
+    const float* lo = params_base;
+    const float* hi = params_base + n_arena;
+    if (N > 0 && (dc < lo || dc + 3LL * N > hi || (K > 1 && (rest < lo || rest + 3LL * (K - 1) * N > hi))))
+        return fail(c, GS_ERR_SIZE_MISMATCH, std::string(who) + ": the SH tensors do not lie in the arena");
+    return GS_OK;
+}
+
+// the scratch image the loss reads under a per-view colour correction ([H, W, 3]): allocated once per ctx, by the
+// correction's setter -- a step never allocates
+int ensure_corrected_image(gs_ctx* c)
+{
+    return c->correctedImage ? GS_OK : dev_alloc(c, &c->correctedImage, (size_t)3 * c->H * c->W);
+}
+
 // gs_copy_overflow_flag: a one-thread kernel, not hipMemcpyAsync -- the runtime's device-to-device copy is a blit kernel
 // between two barrier packets (5.6 us + ~7 us of idle in front of the blend backward of every data-parallel step of the
 // torch exchange, tools/trace_gaps.py)
@@ -301,6 +349,28 @@ struct RealGeomScope {
 };
 
 }  // namespace
+
+namespace gs {
+
+int refuse_pose_correction(gs_ctx* c, const char* who)
+{
+    if (!c->poseDelta && !c->fwd.poseDelta) return GS_OK;
+    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a pose correction is set (single-device steps only)");
+}
+
+int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena)
+{
+    const int N = c->fwd.N, K = c->fwd.K;
+    const float* lo = params_base;
+    const float* hi = params_base + n_arena;
+    auto inside = [&](const float* p, long long n) { return n == 0 || (p >= lo && p + n <= hi); };
+    if (inside(c->fwd.xyz, 3LL * N) && inside(c->fwd.fdc, 3LL * N) && inside(c->fwd.frest, 3LL * (K - 1) * N) &&
+        inside(c->fwd.scales, 3LL * N) && inside(c->fwd.rot, 4LL * N) && inside(c->fwd.opacity, N))
+        return GS_OK;
+    return fail(c, GS_ERR_SIZE_MISMATCH, std::string(who) + ": the forward's tensors do not lie in the arena");
+}
+
+}  // namespace gs
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -427,7 +497,7 @@ int gs_ctx_destroy(gs_ctx* c)
     if (c->densifyPlanHost) (void)hipHostFree(c->densifyPlanHost);
     dev_free(c->densifyPlan);
     dev_free(c->poseCam); dev_free(c->posePartials);
-    dev_free(c->expoImage); dev_free(c->expoPartials); dev_free(c->bgPartials);
+    dev_free(c->correctedImage); dev_free(c->expoPartials); dev_free(c->bgPartials);
     dev_free(c->densifyTable);
     mcmc_free(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -930,7 +1000,7 @@ int gs_set_exposure(gs_ctx* c, const float* M, float* grad)
     if (M && c->bgGrid) return fail(c, GS_ERR_INVALID_ARG, "gs_set_exposure: a bilateral grid is set (the two corrections are exclusive)");
     // (once per ctx, here: a step never allocates)
     if (M && !c->expoPartials) { const int arc = dev_alloc(c, &c->expoPartials, (size_t)exposure_partials_doubles()); if (arc) return arc; }
-    if (M && !c->expoImage) { const int arc = dev_alloc(c, &c->expoImage, (size_t)3 * c->H * c->W); if (arc) return arc; }
+    if (M) { const int arc = ensure_corrected_image(c); if (arc) return arc; }
     c->expoM = M;
     c->expoGrad = grad;
     return GS_OK;
@@ -968,7 +1038,7 @@ int gs_set_bilateral_grid(gs_ctx* c, const float* grid, float* grad, int grid_w,
             if (const int arc = dev_alloc(c, &c->bgPartials, (size_t)need)) return arc;
             c->bgPartialsCap = need;
         }
-        if (!c->expoImage) { const int arc = dev_alloc(c, &c->expoImage, (size_t)3 * c->H * c->W); if (arc) return arc; }
+        if (const int arc = ensure_corrected_image(c)) return arc;
     }
     c->bgGrid = grid;
     c->bgGrad = grad;
@@ -1001,14 +1071,7 @@ int gs_render_backward(gs_ctx* c, const float* cot_color, const float* cot_depth
     if (N > 0 && (!grad_xyz || !grad_features_dc || (K > 1 && !grad_features_rest) || !grad_scales || !grad_rotation ||
                   !grad_opacity))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward: null gradient buffer");
-    int rc;
-    {
-        GsStageTimer t(c, GS_STAGE_BLEND_BWD);
-        rc = c->fast16 ? launch_blend_backward_v2(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outColor,
-                                                  c->fwd.outDepth, c->fwd.outAlpha)
-                       : launch_blend_backward(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
-    }
-    if (rc) return rc;
+    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_projection_fused_backward(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
                                             c->fwd.opacity, c->fwd.cam, grad_xyz, grad_features_dc, grad_features_rest,
@@ -1024,20 +1087,8 @@ int gs_render_backward_adam(gs_ctx* c, const float* cot_color, const float* cot_
     const int N = c->fwd.N, K = c->fwd.K;
     if (!cot_color || !lr || n_arena < 0 || (N > 0 && (!params_base || !m_base || !v_base)))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_adam: null buffer");
-    const float* lo = params_base;
-    const float* hi = params_base + n_arena;
-    auto inside = [&](const float* p, long long n) { return n == 0 || (p >= lo && p + n <= hi); };
-    if (!inside(c->fwd.xyz, 3LL * N) || !inside(c->fwd.fdc, 3LL * N) || !inside(c->fwd.frest, 3LL * (K - 1) * N) ||
-        !inside(c->fwd.scales, 3LL * N) || !inside(c->fwd.rot, 4LL * N) || !inside(c->fwd.opacity, N))
-        return fail(c, GS_ERR_SIZE_MISMATCH, "gs_render_backward_adam: the forward's tensors do not lie in the arena");
-    int rc;
-    {
-        GsStageTimer t(c, GS_STAGE_BLEND_BWD);
-        rc = c->fast16 ? launch_blend_backward_v2(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outColor,
-                                                  c->fwd.outDepth, c->fwd.outAlpha)
-                       : launch_blend_backward(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
-    }
-    if (rc) return rc;
+    if (const int rc = forward_in_arena(c, "gs_render_backward_adam", params_base, n_arena)) return rc;
+    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
     c->fwd.consumed = true;     // the parameters the forward saw are gone after this call
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_projection_fused_backward_adam(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
@@ -1049,18 +1100,11 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
                                 float* color_cot)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: a pose correction is set (single-device steps only)");
+    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_begin")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && !color_cot)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: null buffer");
-    int rc;
-    {
-        GsStageTimer t(c, GS_STAGE_BLEND_BWD);
-        rc = c->fast16 ? launch_blend_backward_v2(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outColor,
-                                                  c->fwd.outDepth, c->fwd.outAlpha)
-                       : launch_blend_backward(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
-    }
-    if (rc) return rc;
+    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
     c->fwd.blendBackwardDone = true;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_color_cot(c, N, color_cot);
@@ -1069,7 +1113,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
 int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_finish: a pose correction is set (single-device steps only)");
+    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N, K = c->fwd.K;
@@ -1086,7 +1130,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
                                       float* xyz_own)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_finish_geom: a pose correction is set (single-device steps only)");
+    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish_geom: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N;
@@ -1102,19 +1146,12 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
                                float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity, float* xyz_own)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (c->poseDelta || c->fwd.poseDelta) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_geom: a pose correction is set (single-device steps only)");
+    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_geom")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && (!color_cot || !grad_xyz || !grad_scales || !grad_rotation || !grad_opacity || !xyz_own)))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_geom: null buffer");
-    int rc;
-    {
-        GsStageTimer t(c, GS_STAGE_BLEND_BWD);
-        rc = c->fast16 ? launch_blend_backward_v2(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outColor,
-                                                  c->fwd.outDepth, c->fwd.outAlpha)
-                       : launch_blend_backward(c, N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
-    }
-    if (rc) return rc;
+    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_projection_geom_backward(c, N, c->fwd.xyz, c->fwd.scales, c->fwd.rot, c->fwd.opacity, c->fwd.cam, grad_xyz,
                                            grad_scales, grad_rotation, grad_opacity, xyz_own, color_cot);
@@ -1126,19 +1163,13 @@ int gs_sh_grad_from_views_adam_dir(gs_ctx* c, int N, int K, int R, const float* 
                                    float beta1, float beta2, float eps, float grad_scale, float* xyz_add)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (N < 0 || K < 1 || R < 1 || R > 16 || !cam_centers || n_arena < 0)
-        return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views_adam_dir: bad N/K/R");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
-    if (N > 0 && (!xyz || !color_cot_all || !features_dc || (K > 1 && !features_rest) || !params_base || !m_base || !v_base || !xyz_add))
-        return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views_adam_dir: null buffer");
+    const char* who = "gs_sh_grad_from_views_adam_dir";
+    if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest, n_arena < 0,
+                                     !params_base || !m_base || !v_base || !xyz_add))
+        return rc;
     if ((uintptr_t)xyz_add & 15) return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views_adam_dir: xyz_add must be 16-byte aligned");
-    const float* lo = params_base;
-    const float* hi = params_base + n_arena;
-    if (N > 0 && (features_dc < lo || features_dc + 3LL * N > hi ||
-                  (K > 1 && (features_rest < lo || features_rest + 3LL * (K - 1) * N > hi))))
-        return fail(c, GS_ERR_SIZE_MISMATCH, "gs_sh_grad_from_views_adam_dir: the SH tensors do not lie in the arena");
-    if (c->ccBlockFloats > 0 && (R != c->ccBlockCount || c->ccBlockFloats < 3LL * N + 1))
-        return fail(c, GS_ERR_SIZE_MISMATCH, "gs_sh_grad_from_views_adam_dir: R / N do not match the gs_set_gathered_gate layout");
+    if (const int rc = sh_in_arena(c, who, N, K, features_dc, features_rest, params_base, n_arena)) return rc;
+    if (const int rc = sh_views_gate_layout(c, who, N, R)) return rc;
     GsStageTimer t(c, GS_STAGE_ADAM);
     return launch_sh_views_dir_adam(c, N, K, R, xyz, color_cot_all, cam_centers, own_xyz, features_dc, features_rest, params_base,
                                     m_base, v_base, lr_dc, lr_rest, beta1, beta2, eps, grad_scale, xyz_add);
@@ -1156,12 +1187,11 @@ int gs_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, cons
                           const float* cam_centers, float* grad_features_dc, float* grad_features_rest)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (N < 0 || K < 1 || R < 1 || R > 16 || !cam_centers) return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views: bad N/K/R");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
-    if (N > 0 && (!xyz || !color_cot_all || !grad_features_dc || (K > 1 && !grad_features_rest)))
-        return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views: null buffer");
-    if (c->ccBlockFloats > 0 && (R != c->ccBlockCount || c->ccBlockFloats < 3LL * N + 1))
-        return fail(c, GS_ERR_SIZE_MISMATCH, "gs_sh_grad_from_views: R / N do not match the gs_set_gathered_gate layout");
+    const char* who = "gs_sh_grad_from_views";
+    if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, grad_features_dc, grad_features_rest, false,
+                                     false))
+        return rc;
+    if (const int rc = sh_views_gate_layout(c, who, N, R)) return rc;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_sh_grad_from_views(c, N, K, R, xyz, color_cot_all, cam_centers, grad_features_dc, grad_features_rest);
 }
@@ -1172,18 +1202,12 @@ int gs_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* xyz,
                                float beta2, float eps, float grad_scale)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (N < 0 || K < 1 || R < 1 || R > 16 || !cam_centers || n_arena < 0)
-        return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views_adam: bad N/K/R");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
-    if (N > 0 && (!xyz || !color_cot_all || !features_dc || (K > 1 && !features_rest) || !params_base || !m_base || !v_base))
-        return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views_adam: null buffer");
-    const float* lo = params_base;
-    const float* hi = params_base + n_arena;
-    if (N > 0 && (features_dc < lo || features_dc + 3LL * N > hi ||
-                  (K > 1 && (features_rest < lo || features_rest + 3LL * (K - 1) * N > hi))))
-        return fail(c, GS_ERR_SIZE_MISMATCH, "gs_sh_grad_from_views_adam: the SH tensors do not lie in the arena");
-    if (c->ccBlockFloats > 0 && (R != c->ccBlockCount || c->ccBlockFloats < 3LL * N + 1))
-        return fail(c, GS_ERR_SIZE_MISMATCH, "gs_sh_grad_from_views_adam: R / N do not match the gs_set_gathered_gate layout");
+    const char* who = "gs_sh_grad_from_views_adam";
+    if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest, n_arena < 0,
+                                     !params_base || !m_base || !v_base))
+        return rc;
+    if (const int rc = sh_in_arena(c, who, N, K, features_dc, features_rest, params_base, n_arena)) return rc;
+    if (const int rc = sh_views_gate_layout(c, who, N, R)) return rc;
     GsStageTimer t(c, GS_STAGE_ADAM);
     return launch_sh_grad_from_views_adam(c, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest,
                                           params_base, m_base, v_base, lr_dc, lr_rest, beta1, beta2, eps, grad_scale);
@@ -1200,27 +1224,23 @@ int gs_loss_forward_backward(gs_ctx* c, const float* render, const float* target
         return fail(c, GS_ERR_INVALID_ARG, "gs_loss_forward_backward: depth loss needs depth buffers");
     { const int orc = deferred_overflow(c); if (orc) return orc; }
     GsStageTimer t(c, GS_STAGE_LOSS);
-    if (c->bgGrid) {
-        // bilateral grid: the loss of the sliced transform's image (the ctx's scratch image, as for an exposure), then
-        // cot_color <- dL/dr and grad <- dL/dG
-        if (const int rc = launch_bilateral_apply(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, render, c->expoImage)) return rc;
-        if (const int rc = launch_loss(c, c->expoImage, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth,
-                                       loss_out, cot_color, cot_depth))
-            return rc;
-        return launch_bilateral_backward(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, c->bgChunks, c->bgTv, render, cot_color,
-                                         c->bgPartials, c->bgGrad);
-    }
-    if (!c->expoM)
+    if (!c->bgGrid && !c->expoM)
         return launch_loss(c, render, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth, loss_out,
                            cot_color, cot_depth);
-    // exposure compensation: the loss of A r + b (the ctx's scratch image; the render itself is left alone), then
-    // cot_color <- A^T cot_color and grad <- dL/dM
+    // A per-view colour correction is bound -- a bilateral grid (the sliced transform) or an exposure (A r + b), never both:
+    // the loss of the corrected image (the ctx's scratch image; the render itself is left alone), then the correction's
+    // backward: cot_color <- dL/d render, grad <- dL/dG or dL/dM
+    const bool grid = c->bgGrid != nullptr;
     const long long np = (long long)c->H * c->W;
-    if (const int rc = launch_exposure_apply(c, np, c->expoM, render, c->expoImage)) return rc;
-    if (const int rc = launch_loss(c, c->expoImage, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth,
-                                   loss_out, cot_color, cot_depth))
+    int rc = grid ? launch_bilateral_apply(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, render, c->correctedImage)
+                  : launch_exposure_apply(c, np, c->expoM, render, c->correctedImage);
+    if (rc) return rc;
+    if ((rc = launch_loss(c, c->correctedImage, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth, loss_out,
+                          cot_color, cot_depth)))
         return rc;
-    return launch_exposure_backward(c, np, c->expoM, render, cot_color, c->expoPartials, c->expoGrad);
+    return grid ? launch_bilateral_backward(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, c->bgChunks, c->bgTv, render,
+                                            cot_color, c->bgPartials, c->bgGrad)
+                : launch_exposure_backward(c, np, c->expoM, render, cot_color, c->expoPartials, c->expoGrad);
 }
 
 int gs_loss_target_cache_floats(gs_ctx* c, long long* n)

@@ -376,7 +376,7 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     GsDp* d = c->dp;
-    if (c->poseDelta || c->fwd.poseDelta) { c->err = "gs_dp_step: a pose correction is set (single-device steps only)"; return GS_ERR_INVALID_ARG; }
+    if (const int rc = gs::refuse_pose_correction(c, "gs_dp_step")) return rc;
     if (!d) { c->err = "gs_dp_step: no communicator (gs_dp_init / gs_dp_attach)"; return GS_ERR_INVALID_ARG; }
     if (!a || (mode != GS_DP_ALLREDUCE && mode != GS_DP_SH_COMPRESSED)) { c->err = "gs_dp_step: bad mode / arguments"; return GS_ERR_INVALID_ARG; }
     if (!c->fwd.valid || c->fwd.consumed) { c->err = "gs_dp_step: no gs_render_forward on this context"; return GS_ERR_NO_FORWARD; }
@@ -392,14 +392,8 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
         return GS_ERR_INVALID_ARG;
     }
     // the six tensors of the forward lie in the parameter arena; gradients and moments share its layout
+    if (const int rc = gs::forward_in_arena(c, "gs_dp_step", a->params_base, a->n_arena)) return rc;
     const float* lo = a->params_base;
-    const float* hi = a->params_base + a->n_arena;
-    auto inside = [&](const float* p, long long n) { return n == 0 || (p >= lo && p + n <= hi); };
-    if (!inside(c->fwd.xyz, 3LL * N) || !inside(c->fwd.fdc, 3LL * N) || !inside(c->fwd.frest, 3LL * (K - 1) * N) ||
-        !inside(c->fwd.scales, 3LL * N) || !inside(c->fwd.rot, 4LL * N) || !inside(c->fwd.opacity, N)) {
-        c->err = "gs_dp_step: the forward's tensors do not lie in the arena";
-        return GS_ERR_SIZE_MISMATCH;
-    }
     auto grad_of = [&](const float* p) { return p ? a->grads_base + (p - a->params_base) : nullptr; };
     auto lr_at = [&](const float* p) {
         const long long off = p - a->params_base;

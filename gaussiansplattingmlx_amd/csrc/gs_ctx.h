@@ -198,13 +198,14 @@ struct gs_ctx {
     float* posePartials = nullptr;
     long long posePartialsCap = 0;
     // exposure compensation (gs_set_exposure): caller-owned device M[12] / grad[12], nullptr = off; the corrected image the
-    // loss reads ([H, W, 3]) and the backward's per-workgroup float64 partials, both allocated at the first exposure set
+    // loss reads ([H, W, 3], shared with the bilateral grid) and the backward's per-workgroup float64 partials, both allocated
+    // at the first exposure set
     const float* expoM = nullptr;
     float* expoGrad = nullptr;
-    float* expoImage = nullptr;
+    float* correctedImage = nullptr;
     double* expoPartials = nullptr;
     // bilateral grid (gs_set_bilateral_grid): caller-owned device grid / grad of bgW x bgH x bgL nodes, nullptr = off (never
-    // together with an exposure: the loss reads the corrected image from expoImage); the backward's per-(cell, chunk) partials,
+    // together with an exposure: the loss reads the corrected image from correctedImage); the backward's per-(cell, chunk) partials,
     // grown only by gs_set_bilateral_grid, and the chunk count of the grid shape they were sized for
     const float* bgGrid = nullptr;
     float* bgGrad = nullptr;
@@ -381,6 +382,10 @@ struct GsStageTimer {
 
 // ---- internal launchers (defined in the .hip files) -------------------------
 namespace gs {
+
+// api.hip: refusals that api.hip and dp.hip share (host code; `who` is the entry point's name, in front of the message)
+int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_ARG while a pose correction is bound
+int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
 CamParams make_cam(const gs_camera* cam, int W, int H);
 

@@ -480,15 +480,21 @@ class GaussianRenderer:
                                                 _p(g["rotation"]), _p(g["opacity"])))
         return g
 
+    @staticmethod
+    def _bound_pair(who, names, a, b, n):
+        """The two tensors a setter binds (`names` = what it calls them): both None, or both contiguous float32 device tensors
+        of n elements."""
+        if (a is None) != (b is None):
+            raise ValueError(f"{who}: {names} are both given or both None")
+        for t in (a, b):
+            if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device.type != "cuda"):
+                raise ValueError(f"{who}: {names} are contiguous float32 device tensors of {n} elements")
+
     def setPoseCorrection(self, delta=None, grad=None):
         """gs_set_pose_correction: delta / grad float32 device tensors of 6 elements (w, tau), or both None (off, the default).
         The following renderForward renders the camera c2w [[R(w), tau], [0, 1]] (camera.apply_pose_correction), and its
         renderBackward / renderBackwardAdam overwrite grad with dL/d delta."""
-        if (delta is None) != (grad is None):
-            raise ValueError("setPoseCorrection: delta and grad are both given or both None")
-        for t in (delta, grad):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != 6 or not t.is_contiguous() or t.device.type != "cuda"):
-                raise ValueError("setPoseCorrection: delta and grad are contiguous float32 device tensors of 6 elements")
+        self._bound_pair("setPoseCorrection", "delta and grad", delta, grad, 6)
         self._check(self.lib.gs_set_pose_correction(self.ctx, None if delta is None else _p(delta), None if grad is None else _p(grad)))
         self._pose = (delta, grad)        # (kept alive while the library holds their addresses)
 
@@ -496,11 +502,7 @@ class GaussianRenderer:
         """gs_set_exposure: M / grad float32 device tensors of 12 elements (M = [A | b] row-major 3 x 4), or both None (off, the
         default).  The following lossForwardBackward calls take the loss of A render + b, return dL/d render as the colour
         cotangent and overwrite grad with dL/dM (include/gsplat.h)."""
-        if (M is None) != (grad is None):
-            raise ValueError("setExposure: M and grad are both given or both None")
-        for t in (M, grad):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != 12 or not t.is_contiguous() or t.device.type != "cuda"):
-                raise ValueError("setExposure: M and grad are contiguous float32 device tensors of 12 elements")
+        self._bound_pair("setExposure", "M and grad", M, grad, 12)
         self._check(self.lib.gs_set_exposure(self.ctx, _p(M), _p(grad)))
         self._exposure = (M, grad)        # (kept alive while the library holds their addresses)
 
@@ -531,16 +533,11 @@ class GaussianRenderer:
         following lossForwardBackward calls take the loss of the render under the grid, return dL/d render as the colour
         cotangent and overwrite grad with dL/dG plus tv_weight times the TV term's gradient (include/gsplat.h).  Exclusive with
         setExposure."""
-        if (grid is None) != (grad is None):
-            raise ValueError("setBilateralGrid: grid and grad are both given or both None")
         gw, gh, gl = self._grid_shape(shape, "setBilateralGrid")
         tv = float(tv_weight)
         if not (math.isfinite(tv) and tv >= 0.0):
             raise ValueError("setBilateralGrid: tv_weight must be finite and >= 0")
-        n = gw * gh * gl * 12
-        for t in (grid, grad):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device.type != "cuda"):
-                raise ValueError(f"setBilateralGrid: grid and grad are contiguous float32 device tensors of {n} elements")
+        self._bound_pair("setBilateralGrid", "grid and grad", grid, grad, gw * gh * gl * 12)
         self._check(self.lib.gs_set_bilateral_grid(self.ctx, _p(grid), _p(grad), gw, gh, gl, C.c_float(tv)))
         self._bilateral = (grid, grad)    # (kept alive while the library holds their addresses)
 

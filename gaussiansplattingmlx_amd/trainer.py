@@ -387,6 +387,64 @@ class GaussModel:
         self._layout(int(N), self.capacity, pads=(), stride=self.stride)
 
 
+class _PerViewTable:
+    """The trainable state of one per-view correction (pose_opt, exposure_opt, bilateral_grid): for each of n_views training
+    views a row of `width` floats and its two Adam moments, the gradient the step writes, and how a row is bound to the renderer.
+    Rows lie a multiple of four floats apart: gs_adam_step takes 16-byte aligned arenas.
+
+    feature: the trainer's keyword, in front of every message.  start: a row's first value (None: zero).  segments / rates:
+    gs_adam_step's segment ends within a row and a callable (iteration, iterationCount) -> their learning rates.
+    bind(renderer, row, grad) binds a view's row and its gradient for a step, bind(renderer, None, None) unbinds.  shared_grad:
+    one gradient row serves every view (only the visited view's is ever read) where a row per view would be memory for nothing."""
+
+    def __init__(self, feature, n_views, width, device, segments, rates, bind, start=None, shared_grad=False):
+        self.feature, self.nViews, self.width = feature, int(n_views), int(width)
+        self.segments, self.rates, self.bind = tuple(segments), rates, bind
+        z = lambda n: torch.zeros((n, (self.width + 3) & ~3), dtype=torch.float32, device=device)[:, :self.width]   # noqa: E731
+        self.rows, self.m, self.v = z(self.nViews), z(self.nViews), z(self.nViews)
+        self.grad = z(1 if shared_grad else self.nViews)
+        if start is not None:
+            self.rows.copy_(start)
+
+    def row(self, viewKey) -> int:
+        if viewKey is None or isinstance(viewKey, (list, tuple)):
+            raise ValueError(f"{self.feature}: every trainStep needs the viewKey of its one view")
+        row = int(viewKey)
+        if row != viewKey or not 0 <= row < self.nViews:
+            raise ValueError(f"{self.feature}: viewKey {viewKey!r} is not one of 0 .. {self.nViews - 1}")
+        return row
+
+    def gradRow(self, row: int):
+        return self.grad[row % self.grad.shape[0]]
+
+    def bindRow(self, renderer, row: int):
+        """The view's row, for every forward and loss of this step (repeats included) and their backward."""
+        self.bind(renderer, self.rows[row], self.gradRow(row))
+
+    def unbind(self, renderer):
+        self.bind(renderer, None, None)
+
+    def adam(self, renderer, row: int, iteration: int, iterationCount: int):
+        """Adam on the view's row (gs_adam_step; the project's Adam: beta (0.9, 0.999), eps 1e-15, no bias correction): gated like
+        the step's other optimizer kernels, so a step from a blank render moves no row either.  The other views' rows and moments
+        are left alone."""
+        r, k = renderer, len(self.segments)
+        r._check(r.lib.gs_adam_step(r.ctx, self.width, _p(self.rows[row]), _p(self.gradRow(row)), _p(self.m[row]), _p(self.v[row]),
+                                    k, (C.c_longlong * k)(*self.segments), (C.c_float * k)(*self.rates(iteration, iterationCount)),
+                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0)))
+
+
+def _require_single_device(feature, views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views=1):
+    """What the MCMC strategy and every per-view correction ask of the trainer's arguments: one view per step, on one device --
+    and, of a per-view correction, n_views (strategy='mcmc' has no use for it and leaves the default)."""
+    if views_per_rank != 1:
+        raise ValueError(f"{feature}: one view per step only (views_per_rank > 1 is not supported)")
+    if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
+        raise ValueError(f"{feature}: single-device steps only (no process group, dp_bootstrap or native exchange)")
+    if n_views is None or isinstance(n_views, bool) or int(n_views) != n_views or int(n_views) < 1:
+        raise ValueError(f"{feature} needs n_views >= 1 (view keys 0 .. n_views - 1)")
+
+
 class GaussianTrainer:
     def __init__(self, model: GaussModel, gaussRender: GaussianRenderer, iterationCount: int = 30000,
                  lambda_dssim: float = 0.2, process_group=None, dp_exchange: str = "sh_compressed",
@@ -459,10 +517,7 @@ class GaussianTrainer:
             if not isinstance(cfg, MCMCConfig):
                 raise ValueError("mcmc must be an MCMCConfig")
             cfg.validate()
-            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
-                raise ValueError("strategy='mcmc': single-device steps only (no process group, dp_bootstrap or native exchange)")
-            if views_per_rank != 1:
-                raise ValueError("strategy='mcmc': one view per step only (views_per_rank > 1 is not supported)")
+            _require_single_device("strategy='mcmc'", views_per_rank, process_group, dp_bootstrap, exchange_impl)
             if cfg.cap_max < model.N:
                 raise ValueError(f"strategy='mcmc': cap_max = {cfg.cap_max} is below the model's N = {model.N}")
             self.mcmc = cfg
@@ -471,22 +526,12 @@ class GaussianTrainer:
             raise ValueError("mcmc settings need strategy='mcmc'")
         self.pose_opt = bool(pose_opt)
         if self.pose_opt:
-            if views_per_rank != 1:
-                raise ValueError("pose_opt: one view per step only (views_per_rank > 1 is not supported)")
-            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
-                raise ValueError("pose_opt: single-device steps only (no process group, dp_bootstrap or native exchange)")
-            if n_views is None or int(n_views) < 1:
-                raise ValueError("pose_opt needs n_views >= 1 (view keys 0 .. n_views - 1)")
+            _require_single_device("pose_opt", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
             if len(pose_lr) != 2:
                 raise ValueError("pose_lr = (rotation rate, translation rate)")
         self.exposure_opt = bool(exposure_opt)
         if self.exposure_opt:
-            if views_per_rank != 1:
-                raise ValueError("exposure_opt: one view per step only (views_per_rank > 1 is not supported)")
-            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
-                raise ValueError("exposure_opt: single-device steps only (no process group, dp_bootstrap or native exchange)")
-            if n_views is None or isinstance(n_views, bool) or int(n_views) != n_views or int(n_views) < 1:
-                raise ValueError("exposure_opt needs n_views >= 1 (view keys 0 .. n_views - 1)")
+            _require_single_device("exposure_opt", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
             try:
                 elr = tuple(float(x) for x in exposure_lr)
             except (TypeError, ValueError):
@@ -497,13 +542,7 @@ class GaussianTrainer:
         if self.bilateral_grid:
             if self.exposure_opt:
                 raise ValueError("bilateral_grid and exposure_opt are exclusive (a constant grid is an exposure)")
-            if views_per_rank != 1:
-                raise ValueError("bilateral_grid: one view per step only (views_per_rank > 1 is not supported)")
-            if process_group is not None or dp_bootstrap is not None or exchange_impl == "native":
-                raise ValueError("bilateral_grid: single-device steps only (no process group, dp_bootstrap or native exchange)")
-            if n_views is None or isinstance(n_views, bool) or int(n_views) != n_views or int(n_views) < 1:
-                raise ValueError("bilateral_grid needs n_views >= 1 (view keys 0 .. n_views - 1)")
-            from .renderer import GaussianRenderer
+            _require_single_device("bilateral_grid", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
             bgs = GaussianRenderer._grid_shape(bilateral_grid_shape, "bilateral_grid_shape")
             try:
                 blr, btv = float(bilateral_grid_lr), float(bilateral_grid_tv)
@@ -630,26 +669,32 @@ class GaussianTrainer:
         if self.mcmc is not None:
             model.restride(max(self.mcmc.cap_max, model.capacity))
             self._seg_end = (C.c_longlong * 6)(*[int(x) for x in model.seg_end])
+        # the enabled per-view corrections, in the order a step binds them and runs their Adam: pose, exposure, grid
+        self._perView = {}
+        eye = torch.eye(3, 4, dtype=torch.float32).reshape(12)        # [I | 0]: an exposure, a grid's node
         if self.pose_opt:
             self.nViews, self.poseLr = int(n_views), (float(pose_lr[0]), float(pose_lr[1]))
-            # rows of 8 floats (the first 6 used): gs_adam_step takes 16-byte aligned arenas
-            z = lambda: torch.zeros((self.nViews, 8), dtype=torch.float32, device=r.device)[:, :6]      # noqa: E731
-            self._pose_delta, self._pose_m, self._pose_v, self._pose_grad = z(), z(), z(), z()
+            # delta = (w, tau), zero to start; two segments at constant rates: rotation, translation
+            self._perView["pose_opt"] = _PerViewTable("pose_opt", n_views, 6, r.device, (3, 6), lambda it, total: self.poseLr,
+                                                      GaussianRenderer.setPoseCorrection)
+            self._pose_delta = self._perView["pose_opt"].rows           # (the name the tests know the corrections by)
         if self.exposure_opt:
             self.nViews, self.exposureLr = int(n_views), elr
-            # rows of 12 floats (48 bytes: each row 16-byte aligned, as gs_adam_step wants), the identity [I | 0] to start
-            self._expo = torch.eye(3, 4, dtype=torch.float32, device=r.device).reshape(1, 12).repeat(self.nViews, 1).contiguous()
-            self._expo_grad, self._expo_m, self._expo_v = (torch.zeros_like(self._expo) for _ in range(3))
+            self._perView["exposure_opt"] = _PerViewTable(
+                "exposure_opt", n_views, 12, r.device, (12,), lambda it, total: (exposureLearningRate(it, total, self.exposureLr),),
+                GaussianRenderer.setExposure, start=eye)
+            self._expo_m, self._expo_v = self._perView["exposure_opt"].m, self._perView["exposure_opt"].v      # (likewise)
         if self.bilateral_grid:
             self.nViews, self.bilateralGridShape = int(n_views), bgs
             self.bilateralGridLr, self.bilateralGridTv = blr, btv
-            gw, gh, gl = bgs
-            # rows [grid_h, grid_w, grid_l, 12] (a multiple of 48 bytes: every row 16-byte aligned for gs_adam_step), the
-            # identity [I | 0] at every node to start; one gradient buffer serves every view (only the visited one is set)
-            eye = torch.eye(3, 4, dtype=torch.float32, device=r.device).reshape(12)
-            self._bg = eye.repeat(self.nViews, gh, gw, gl, 1).contiguous()
-            self._bg_m, self._bg_v = torch.zeros_like(self._bg), torch.zeros_like(self._bg)
-            self._bg_grad = torch.zeros_like(self._bg[0])
+            # rows [grid_h, grid_w, grid_l, 12], the identity at every node to start
+            nodes = bgs[0] * bgs[1] * bgs[2]
+            self._perView["bilateral_grid"] = _PerViewTable(
+                "bilateral_grid", n_views, nodes * 12, r.device, (nodes * 12,),
+                lambda it, total: (bilateralGridLearningRate(it, total, self.bilateralGridLr),),
+                lambda rr, G, g: rr.setBilateralGrid(G, g, self.bilateralGridShape, self.bilateralGridTv),
+                start=eye.repeat(nodes), shared_grad=True)
+            self._bg_m, self._bg_v = self._perView["bilateral_grid"].m, self._perView["bilateral_grid"].v      # (likewise)
         if self._exchange:
             # the replicas must START identical too -- and the check's first call pays for the collective's set-up (a first
             # float64 max-reduce cost the torch exchange ~35 ms at the first densify event of a run) here, not there
@@ -1207,19 +1252,14 @@ class GaussianTrainer:
         r = self.gaussRender
         # knobs of the caller's renderer that this step changes, put back whatever happens
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
-        row = self._pose_row(viewKey) if self.pose_opt else None
-        erow = self._view_row(viewKey, "exposure_opt") if self.exposure_opt else None
-        brow = self._view_row(viewKey, "bilateral_grid") if self.bilateral_grid else None
+        tables = list(self._perView.values())
+        row = tables[0].row(viewKey) if tables else None       # (one n_views for all of them)
         try:
             r.setTuning(depth_gradient=0)
             if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
                 r.setMCMC(self._mcmcParams())
-            if self.pose_opt:      # the view's correction, for every forward of this step (repeats included) and its backward
-                r.setPoseCorrection(self._pose_delta[row], self._pose_grad[row])
-            if self.exposure_opt:  # the view's exposure, for every loss of this step (repeats included)
-                r.setExposure(self._expo[erow], self._expo_grad[erow])
-            if self.bilateral_grid:  # the view's grid, likewise
-                r.setBilateralGrid(self._bg[brow], self._bg_grad, self.bilateralGridShape, self.bilateralGridTv)
+            for t in tables:
+                t.bindRow(r, row)
             if self._exchange:
                 r.setTuning(host_overflow_errors=0)
                 if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
@@ -1235,86 +1275,44 @@ class GaussianTrainer:
             r.setTuning(**restore)
             if self.mcmc is not None:
                 r.setMCMC(None)
-            if self.pose_opt:
-                r.setPoseCorrection(None, None)
-            if self.exposure_opt:
-                r.setExposure(None, None)
-            if self.bilateral_grid:
-                r.setBilateralGrid(None, None)
+            for t in tables:
+                t.unbind(r)
 
-    def _view_row(self, viewKey, feature: str) -> int:
-        if viewKey is None or isinstance(viewKey, (list, tuple)):
-            raise ValueError(f"{feature}: every trainStep needs the viewKey of its one view")
-        row = int(viewKey)
-        if row != viewKey or not 0 <= row < self.nViews:
-            raise ValueError(f"{feature}: viewKey {viewKey!r} is not one of 0 .. {self.nViews - 1}")
-        return row
-
-    def _pose_row(self, viewKey) -> int:
-        return self._view_row(viewKey, "pose_opt")
-
-    def _exposureAdam(self, viewKey):
-        """Adam on the view's twelve exposure floats (gs_adam_step, one segment at exposureLearningRate): gated like the step's
-        other optimizer kernels.  The other views' rows and moments are left alone."""
-        r, row = self.gaussRender, int(viewKey)
-        lr = exposureLearningRate(self.iteration, self.iterationCount, self.exposureLr)
-        r._check(r.lib.gs_adam_step(r.ctx, 12, _p(self._expo[row]), _p(self._expo_grad[row]), _p(self._expo_m[row]),
-                                    _p(self._expo_v[row]), 1, (C.c_longlong * 1)(12), (C.c_float * 1)(lr),
-                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0)))
+    def _table(self, who: str, feature: str) -> _PerViewTable:
+        if feature not in self._perView:
+            raise ValueError(f"{who}: the trainer was built without {feature}")
+        return self._perView[feature]
 
     def exposures(self) -> np.ndarray:
         """The views' exposures M = [A | b], host float32 [n_views, 3, 4] (waits for the device)."""
-        if not self.exposure_opt:
-            raise ValueError("exposures: the trainer was built without exposure_opt")
-        return self._expo.cpu().numpy().reshape(self.nViews, 3, 4)
+        t = self._table("exposures", "exposure_opt")
+        return t.rows.cpu().numpy().reshape(t.nViews, 3, 4)
 
     def exposedRender(self, render, viewKey):
         """A render of view `viewKey` under the view's learned exposure (A render + b; gs_apply_exposure), a new tensor."""
-        if not self.exposure_opt:
-            raise ValueError("exposedRender: the trainer was built without exposure_opt")
-        return self.gaussRender.applyExposure(render, self._expo[self._view_row(viewKey, "exposure_opt")])
-
-    def _bilateralGridAdam(self, viewKey):
-        """Adam on the view's grid (gs_adam_step, one segment at bilateralGridLearningRate): gated like the step's other
-        optimizer kernels.  The other views' grids and moments are left alone."""
-        r, row = self.gaussRender, int(viewKey)
-        n = self._bg_grad.numel()
-        lr = bilateralGridLearningRate(self.iteration, self.iterationCount, self.bilateralGridLr)
-        r._check(r.lib.gs_adam_step(r.ctx, n, _p(self._bg[row]), _p(self._bg_grad), _p(self._bg_m[row]), _p(self._bg_v[row]), 1,
-                                    (C.c_longlong * 1)(n), (C.c_float * 1)(lr), C.c_float(0.9), C.c_float(0.999),
-                                    C.c_float(1e-15), C.c_float(1.0)))
+        t = self._table("exposedRender", "exposure_opt")
+        return self.gaussRender.applyExposure(render, t.rows[t.row(viewKey)])
 
     def bilateralGrids(self) -> np.ndarray:
         """The views' grids, host float32 [n_views, grid_h, grid_w, grid_l, 12] (each node an M = [A | b]; waits for the device)."""
-        if not self.bilateral_grid:
-            raise ValueError("bilateralGrids: the trainer was built without bilateral_grid")
-        return self._bg.cpu().numpy()
+        t = self._table("bilateralGrids", "bilateral_grid")
+        gw, gh, gl = self.bilateralGridShape
+        return t.rows.cpu().numpy().reshape(t.nViews, gh, gw, gl, 12)
 
     def bilateralRender(self, render, viewKey):
         """A render of view `viewKey` under the view's learned grid (gs_apply_bilateral_grid), a new tensor."""
-        if not self.bilateral_grid:
-            raise ValueError("bilateralRender: the trainer was built without bilateral_grid")
-        row = self._view_row(viewKey, "bilateral_grid")
-        return self.gaussRender.applyBilateralGrid(render, self._bg[row], self.bilateralGridShape)
-
-    def _poseAdam(self, viewKey):
-        """Adam on the view's six pose floats (gs_adam_step, two segments: rotation, translation): gated like the step's other
-        optimizer kernels, so a step from a blank render moves no pose either."""
-        r, row = self.gaussRender, int(viewKey)
-        r._check(r.lib.gs_adam_step(r.ctx, 6, _p(self._pose_delta[row]), _p(self._pose_grad[row]), _p(self._pose_m[row]),
-                                    _p(self._pose_v[row]), 2, (C.c_longlong * 2)(3, 6), (C.c_float * 2)(*self.poseLr),
-                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0)))
+        t = self._table("bilateralRender", "bilateral_grid")
+        return self.gaussRender.applyBilateralGrid(render, t.rows[t.row(viewKey)], self.bilateralGridShape)
 
     def poseCorrections(self) -> np.ndarray:
         """The views' pose corrections delta = (w, tau), host float32 [n_views, 6] (waits for the device)."""
-        if not self.pose_opt:
-            raise ValueError("poseCorrections: the trainer was built without pose_opt")
-        return self._pose_delta.cpu().numpy()
+        return self._table("poseCorrections", "pose_opt").rows.cpu().numpy()
 
     def refinedCamera(self, viewKey, camera):
         """The view's camera with its learned correction applied (camera.apply_pose_correction, float64)."""
         from .camera import apply_pose_correction
-        return apply_pose_correction(camera, self.poseCorrections()[self._pose_row(viewKey)])
+        t = self._table("poseCorrections", "pose_opt")
+        return apply_pose_correction(camera, self.poseCorrections()[t.row(viewKey)])
 
     def _profiledStep(self, camera, targetRGB, stepCameras, viewKey):
         """One iteration under the reference's IntervalProfiler: host sections by wall clock, device stages by the
@@ -1558,12 +1556,8 @@ class GaussianTrainer:
                 p = m.getParams()
                 r.mcmcInjectNoise(p["xyz"], p["scales"], p["rotation"], p["opacity"],
                                   getLearningRates(self.iteration, self.iterationCount)[0], self._mcmcParams())
-        if self.pose_opt:
-            self._poseAdam(viewKey)
-        if self.exposure_opt:
-            self._exposureAdam(viewKey)
-        if self.bilateral_grid:
-            self._bilateralGridAdam(viewKey)
+        for t in self._perView.values():
+            t.adam(r, int(viewKey), self.iteration, self.iterationCount)
         return self._finishIteration()
 
     def _finishIteration(self):

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Step time of the single-device fused train step with and without exposure compensation (GaussianTrainer(exposure_opt=True)).
+"""Step time of the single-device fused train step without a per-view correction and with each of them: camera pose
+refinement, exposure compensation, the bilateral grid (GaussianTrainer(pose_opt=True) / (exposure_opt=True) /
+(bilateral_grid=True)).
 
-    python tools/exposure_step_time.py [--config c3_300k_800] [--steps 200] [--warmup 2] [--rounds 3] [--modes off,on]
+    python tools/per_view_step_time.py [--config c3_300k_800] [--steps 200] [--warmup 2] [--rounds 3] [--modes off,pose,exposure,grid]
 
-Both modes train the same scene from the same start (a fresh model per run, densify off, every view visited --warmup times
+Every mode trains the same scene from the same start (a fresh model per run, densify off, every view visited --warmup times
 before timing); the modes alternate --rounds times in one process.  One JSON line per run: ms per step over --steps steps
 (device events around the whole loop)."""
 from __future__ import annotations
@@ -24,7 +26,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--modes", default="off,on")
+    ap.add_argument("--modes", default="off,pose,exposure,grid")
     args = ap.parse_args()
     import torch
     from gaussiansplattingmlx_amd.renderer import GaussianRenderer
@@ -38,11 +40,12 @@ def main():
     targets = [r.renderForward(tp, c).render.clone() for c in cams]
     del tp
     V = len(cams)
+    kws = {"off": {}, "pose": dict(pose_opt=True, n_views=V), "exposure": dict(exposure_opt=True, n_views=V),
+           "grid": dict(bilateral_grid=True, n_views=V)}
     for _ in range(args.rounds):
         for mode in args.modes.split(","):
             model = GaussModel(params, r.device)
-            kw = dict(exposure_opt=True, n_views=V) if mode == "on" else {}
-            tr = GaussianTrainer(model, r, iterationCount=30000, densify=False, **kw)
+            tr = GaussianTrainer(model, r, iterationCount=30000, densify=False, **kws[mode])
             tr.iteration = 1
             for i in range(args.warmup * V):
                 tr.trainStep(cams[i % V], targets[i % V], viewKey=i % V)
@@ -54,7 +57,7 @@ def main():
                 tr.trainStep(cams[v], targets[v], viewKey=v)
             b.record()
             torch.cuda.synchronize()
-            print(json.dumps(dict(config=args.config, exposure_opt=mode == "on", steps=args.steps,
+            print(json.dumps(dict(config=args.config, mode=mode, steps=args.steps,
                                   ms_per_step=round(a.elapsed_time(b) / args.steps, 4), loss=float(tr._loss[0]))), flush=True)
             del tr, model
 
