@@ -139,6 +139,10 @@ _SIGS = {
     "gs_set_bilateral_grid": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float]),
     "gs_apply_bilateral_grid": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
+    "gs_set_filter3d_cameras": (C.c_int, [_vp, C.c_int, _vp]),
+    "gs_compute_filter3d": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "gs_set_filter3d": (C.c_int, [_vp, _vp]),
+    "gs_filter3d_bake": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_set_mcmc": (C.c_int, [_vp, _vp]),
     "gs_mcmc_regularizer_grad": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_mcmc_inject_noise": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [C.c_float, _vp]),

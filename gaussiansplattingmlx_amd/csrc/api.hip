@@ -358,6 +358,12 @@ int refuse_pose_correction(gs_ctx* c, const char* who)
     return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a pose correction is set (single-device steps only)");
 }
 
+int refuse_filter3d(gs_ctx* c, const char* who)
+{
+    if (!c->filter3d && !(c->fwd.valid && c->fwd.filter3d)) return GS_OK;
+    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a 3-D filter is set (single-device steps only)");
+}
+
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena)
 {
     const int N = c->fwd.N, K = c->fwd.K;
@@ -497,6 +503,7 @@ int gs_ctx_destroy(gs_ctx* c)
     if (c->densifyPlanHost) (void)hipHostFree(c->densifyPlanHost);
     dev_free(c->densifyPlan);
     dev_free(c->poseCam); dev_free(c->posePartials);
+    dev_free(c->f3dCams); dev_free(c->f3dMax);
     dev_free(c->correctedImage); dev_free(c->expoPartials); dev_free(c->bgPartials);
     dev_free(c->densifyTable);
     mcmc_free(c);
@@ -877,6 +884,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.poseDelta = c->poseDelta;
     c->fwd.poseGrad = c->poseGrad;
     c->fwd.antialias = c->antialias;
+    c->fwd.filter3d = c->filter3d;
     return GS_OK;
 }
 
@@ -886,6 +894,70 @@ int gs_set_antialiasing(gs_ctx* c, int enable)
     if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_antialiasing: enable is 0 or 1");
     c->antialias = enable == 1;
     return GS_OK;
+}
+
+// ---- the 3-D smoothing filter (include/gsplat.h gs_set_filter3d; filter3d.hip, gs_math.h filter3d_activate) -----------------
+int gs_set_filter3d_cameras(gs_ctx* c, int V, const gs_camera* cams)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (V < 0 || (V > 0 && !cams)) return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d_cameras: V >= 0 and V cameras");
+    GS_HIP_CHECK(c, hipSetDevice(c->device));
+    if (V == 0) {
+        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a width kernel may still be reading the table)
+        dev_free(c->f3dCams);
+        c->f3dCamCount = c->f3dCamCap = 0;
+        return GS_OK;
+    }
+    for (int v = 0; v < V; v++)
+        if (!(cams[v].focal_x > 0.0f) || !(cams[v].fov_x > 0.0f) || !(cams[v].fov_y > 0.0f))
+            return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d_cameras: focal_x, fov_x and fov_y are > 0");
+    GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (!c->f3dMax) { if (const int rc = dev_alloc(c, &c->f3dMax, 1)) return rc; }
+    if (V > c->f3dCamCap) {
+        dev_free(c->f3dCams);
+        c->f3dCamCount = c->f3dCamCap = 0;
+        if (const int rc = dev_alloc(c, &c->f3dCams, (size_t)V * GS_F3D_CAM_FLOATS)) return rc;
+        c->f3dCamCap = V;
+    }
+    std::vector<float> rows((size_t)V * GS_F3D_CAM_FLOATS, 0.0f);
+    for (int v = 0; v < V; v++) {
+        float* r = rows.data() + (size_t)v * GS_F3D_CAM_FLOATS;
+        for (int a = 0; a < 3; a++)
+            for (int k = 0; k < 4; k++) r[4 * a + k] = cams[v].view[4 * k + a];      // p_a = [x, 1] . view[:, a]
+        r[12] = tanf(cams[v].fov_x * 0.5f) * 1.3f;      // (make_cam's limX / limY: the EWA clamp's constant)
+        r[13] = tanf(cams[v].fov_y * 0.5f) * 1.3f;
+        r[14] = cams[v].focal_x;
+    }
+    GS_HIP_CHECK(c, hipMemcpy(c->f3dCams, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->f3dCamCount = V;
+    return GS_OK;
+}
+
+int gs_compute_filter3d(gs_ctx* c, int N, const float* xyz, float* filter)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (c->f3dCamCount < 1) return fail(c, GS_ERR_INVALID_ARG, "gs_compute_filter3d: no cameras (gs_set_filter3d_cameras)");
+    if (N < 0 || (N > 0 && (!xyz || !filter))) return fail(c, GS_ERR_INVALID_ARG, "gs_compute_filter3d: N >= 0 and non-null buffers");
+    GS_HIP_CHECK(c, hipSetDevice(c->device));
+    return launch_filter3d_width(c, N, xyz, filter);
+}
+
+int gs_set_filter3d(gs_ctx* c, const float* filter)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (filter && c->mcmcOn) return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d: the MCMC strategy is set (the reference strategy only)");
+    c->filter3d = filter;
+    return GS_OK;
+}
+
+int gs_filter3d_bake(gs_ctx* c, int N, const float* scales_raw, const float* opacity_raw, const float* filter,
+                     float* out_scales_raw, float* out_opacity_raw)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (N < 0 || (N > 0 && (!scales_raw || !opacity_raw || !filter || !out_scales_raw || !out_opacity_raw)))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_filter3d_bake: N >= 0 and non-null buffers");
+    GS_HIP_CHECK(c, hipSetDevice(c->device));
+    return launch_filter3d_bake(c, N, scales_raw, opacity_raw, filter, out_scales_raw, out_opacity_raw);
 }
 
 // ---- the MCMC strategy (include/gsplat.h gs_set_mcmc; mcmc.hip, projection.hip proj_bwd_fused_*mcmc_kernel) ----------------
@@ -907,6 +979,7 @@ int gs_set_mcmc(gs_ctx* c, const gs_mcmc_params* params)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!params) { c->mcmcOn = false; return GS_OK; }
+    if (c->filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_mcmc: a 3-D filter is set (gs_set_filter3d: the reference strategy only)");
     if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
     c->mcmc = *params;
     c->mcmcOn = true;
@@ -1101,6 +1174,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_begin")) return rc;
+    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_begin")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && !color_cot)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: null buffer");
@@ -1114,6 +1188,7 @@ int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales,
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish")) return rc;
+    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N, K = c->fwd.K;
@@ -1131,6 +1206,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish_geom")) return rc;
+    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish_geom: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N;
@@ -1147,6 +1223,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_geom")) return rc;
+    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_geom")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && (!color_cot || !grad_xyz || !grad_scales || !grad_rotation || !grad_opacity || !xyz_own)))

@@ -92,6 +92,7 @@ __device__ __forceinline__ void gs_block_pixels(const GsVirtGeom& g, int bx, int
     X0 = tx * g.tw + ix * 16; Y0 = ty * g.th + iy * 16;
     XL = min(W, min(X0 + 16, (tx + 1) * g.tw)); YL = min(H, min(Y0 + 16, (ty + 1) * g.th));
 }
+constexpr int GS_F3D_CAM_FLOATS = 16;  // floats per camera of the 3-D filter's table (filter3d.hip)
 constexpr int GS_CUT_SUPER = 4;      // tiles per side of a super-tile of the coarse cuts
 // coarse depth cuts handed to the fused projection (binning.hip, cut_super_kernel): null superCut = none
 struct GsCutCoarse {
@@ -215,6 +216,13 @@ struct gs_ctx {
     float* bgPartials = nullptr;
     long long bgPartialsCap = 0;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
+    // 3-D smoothing filter (gs_set_filter3d): the caller-owned device widths [>= N] of the following forwards, nullptr = off; the
+    // training cameras' table for gs_compute_filter3d (GS_F3D_CAM_FLOATS floats per camera) and the max word of its never-seen
+    // rule, both allocated or grown by gs_set_filter3d_cameras only
+    const float* filter3d = nullptr;
+    float* f3dCams = nullptr;
+    int f3dCamCount = 0, f3dCamCap = 0;
+    uint32_t* f3dMax = nullptr;
     bool mcmcOn = false;                 // gs_set_mcmc: the MCMC strategy's step in gs_render_backward_adam, with these parameters
     gs_mcmc_params mcmc = {};
     void* mcmcWs = nullptr;              // mcmc.hip: the event's scratch (grown on demand) and its pinned read-back words
@@ -327,6 +335,7 @@ struct gs_ctx {
         const float* poseDelta = nullptr;  // the correction this forward was composed with (nullptr: none) ...
         float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
         bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
+        const float* filter3d = nullptr;   // the 3-D filter widths this forward ran with (its backward's; nullptr: none)
         uint32_t* cutStore = nullptr;  // the view's cut words at the time of this forward (nullptr: none kept)
         bool cutsActive = false;     // this forward binned under depth cuts
         bool missChecked = true;     // ... and gs_forward_missed has been asked since
@@ -385,6 +394,7 @@ namespace gs {
 
 // api.hip: refusals that api.hip and dp.hip share (host code; `who` is the entry point's name, in front of the message)
 int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_ARG while a pose correction is bound
+int refuse_filter3d(gs_ctx* c, const char* who);             // GS_ERR_INVALID_ARG while a 3-D filter is set (or the forward ran with one)
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
 CamParams make_cam(const gs_camera* cam, int W, int H);
@@ -423,6 +433,10 @@ long long bilateral_partials_floats(int gw, int gh, int gl, int nch);
 int launch_bilateral_apply(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, const float* in, float* out);
 int launch_bilateral_backward(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, int nch, float tvWeight,
                               const float* render, float* cot, float* partials, float* grad);
+// filter3d.hip: the camera table's row is view[0..3][0], view[0..3][1], view[0..3][2], limX, limY, focalX, 0
+int launch_filter3d_width(gs_ctx* c, int N, const float* xyz, float* filter);
+int launch_filter3d_bake(gs_ctx* c, int N, const float* scalesRaw, const float* opacityRaw, const float* filter, float* outScales,
+                         float* outOpacity);
 int launch_colour_rest(gs_ctx* c);      // gs_rider.h: the colour units the binning kernels have not taken along
 int launch_color_cot(gs_ctx* c, int N, float* out);
 int launch_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, const float* mgAll,

@@ -367,6 +367,31 @@ __device__ __forceinline__ float aa_opacity_scale(const float u[4], const float 
     return rho;
 }
 
+// 3-D smoothing filter (gs_set_filter3d; Mip-Splatting's second filter): with f >= 0 the Gaussian's filter
+// width in scene units (filter3d.hip), the fused paths project s_eff_a = sqrt(s_a^2 + f^2) instead of s_a = exp(scales_raw_a) and
+// scale the opacity by kappa = prod_a (s_a / s_eff_a), a product of the three ratios (a ratio of products would overflow for
+// scales whose ratios are harmless).  Returns kappa.  f = 0: sqrtf(s s) = s under correct rounding, every ratio 1, kappa = 1.
+// VJP, with g[a] = dL/ds_eff_a on entry and opCot = dL/d(packed opacity) sigma(o) rho kappa (rho = 1 without the anti-aliased
+// mode): g[a] leaves as dL/dscales_raw_a = g_a s_a^2 / s_eff_a + opCot f^2 / s_eff_a^2 (d s_eff_a / d raw_a = s_a^2 / s_eff_a,
+// d ln kappa / d raw_a = f^2 / s_eff_a^2).  No singularity where the term matters: s_eff >= f > 0.  f is not differentiated.
+// Forward and backward call this one function, so both see the same s_eff and kappa.
+template <bool VJP = false>
+__device__ __forceinline__ float filter3d_activate(const float s[3], float f, float se[3], float* g = nullptr, float opCot = 0.0f)
+{
+    const float f2 = f * f;
+    float ratio[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        se[a] = sqrtf(s[a] * s[a] + f2);
+        ratio[a] = s[a] / se[a];
+    }
+    if constexpr (VJP) {
+#pragma unroll
+        for (int a = 0; a < 3; a++) g[a] = g[a] * (s[a] * ratio[a]) + opCot * (f2 / (se[a] * se[a]));
+    }
+    return ratio[0] * ratio[1] * ratio[2];
+}
+
 struct GeomGrads {
     float dm[3], ds[3], dq[4];
 };

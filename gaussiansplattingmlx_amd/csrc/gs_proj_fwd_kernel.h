@@ -3,7 +3,9 @@
 // refinement, gs_set_pose_correction).  One text, so that the default kernels compile exactly as they did before the pose
 // form existed.  The includer defines GS_FWD_KERNEL, GS_FWD_CAM_PARAM and GS_FWD_CAM_INIT.
 // AA: the anti-aliased mode (gs_set_antialiasing): the packed opacity is sigma(o) rho (aa_opacity_scale, gs_math.h).
-template <bool TWO_PHASE, bool COLOUR, bool SELF = false, bool AA = false>
+// F3D: the 3-D smoothing filter (gs_set_filter3d): the scales are sqrt(s^2 + f^2), f = filter3d[p], and the opacity gains kappa
+// (filter3d_activate, gs_math.h).  The default instantiations never read filter3d, the last kernel argument.
+template <bool TWO_PHASE, bool COLOUR, bool SELF = false, bool AA = false, bool F3D = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void GS_FWD_KERNEL(
     int N, int K, int degree, GS_FWD_CAM_PARAM, int tileW, int tileH, int gridW, int gridH,
     const float* __restrict__ xyz, const float* __restrict__ fdc, const float* __restrict__ frest,
@@ -11,7 +13,7 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void GS_FWD_KERNEL(
     float* __restrict__ packed12, float* __restrict__ radiiOut, ushort4* __restrict__ tileRect,
     uint32_t* __restrict__ tilesTouched, uint32_t* __restrict__ depthKey, uint32_t* __restrict__ depthVal,
     uint32_t* __restrict__ visPerBlock, uint32_t* __restrict__ counters, int flags, ColourRider self,
-    GsVirtGeom vg, GsCutCoarse cc, uint4* __restrict__ tilePieces)
+    GsVirtGeom vg, GsCutCoarse cc, uint4* __restrict__ tilePieces, const float* __restrict__ filter3d)
 {
     GS_FWD_CAM_INIT
     const int noKeyForUntouched = flags & 1;
@@ -57,6 +59,11 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void GS_FWD_KERNEL(
         const float den = sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3) + 1e-8f;
         const float q[4] = {r0 / den, r1 / den, r2 / den, r3 / den};
         opacity = 1.0f / (1.0f + expf(-opacityRaw[p]));
+        if constexpr (F3D) {
+            float se[3];
+            opacity *= filter3d_activate(s, filter3d[p], se);
+            project_geometry(m, se, q, cam, o);
+        } else
         project_geometry(m, s, q, cam, o);
         // A 2-D covariance whose float32 determinant is not positive -- the true one always is (the +0.3 blur), so this is
         // cancellation: a needle tens of thousands of pixels long, cov2d = (4.2e7, -3.8e7; -3.8e7, 3.5e7) -- has a conic that is not

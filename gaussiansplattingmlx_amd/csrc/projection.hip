@@ -439,16 +439,20 @@ __device__ __forceinline__ float wave_sum_xor(float v)
 // MCMC (the MCMC strategy's per-step part, gs_set_mcmc; MODE 2 only): the regularisers' gradients join the opacity and scale
 // gradients in front of adam_step, and the position noise (gs_mcmc.h mcmc_noise) of the updated parameters joins the
 // updated xyz in front of the stores.
-template <int MODE, bool POSE, bool AA = false, bool MCMC = false>
+// F3D (3-D smoothing filter, gs_set_filter3d; MODE 0 and 2, never with MCMC): the forward projected s_eff = sqrt(s^2 + f^2) and
+// blended sigma(o) kappa (rho); the geometry backward runs on s_eff, dop's share of the opacity and of the rho VJP carries kappa,
+// and filter3d_activate (gs_math.h) turns dL/ds_eff into dL/dscales_raw.
+template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false>
 __device__ __forceinline__ void proj_bwd_fused_body(
     int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
     const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
     float* gFdc, float* gFrest, float* gScales, float* gRot,
     float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials,
-    McmcFuse mc = McmcFuse{})
+    McmcFuse mc = McmcFuse{}, const float* __restrict__ filter3d = nullptr)
 {
     static_assert(!MCMC || MODE == 2, "the MCMC step is fused into the Adam form only");
+    static_assert(!F3D || (!MCMC && MODE != 1), "the 3-D filter: single-device steps and the reference strategy only");
     constexpr bool EMIT_MG = MODE == 1, ADAM = MODE == 2;
     extern __shared__ float shLds[];
     // no update from a forward that did not render (gs_ctx.h adamGate).  The word is requested here and looked at only
@@ -500,6 +504,13 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     GeomGrads g;
     float aaRho = 1.0f;
     const float aaSg = AA ? 1.0f / (1.0f + expf(-opacityRaw[p])) : 0.0f;
+    float f3dF = 0.0f, f3dKappa = 1.0f, se[3];
+    if constexpr (F3D) {
+        f3dF = filter3d[p];
+        f3dKappa = filter3d_activate(s, f3dF, se);
+        project_geometry_bwd<POSE, AA>(m, se, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr, cotOpacity * aaSg * f3dKappa,
+                                       &aaRho);
+    } else
     project_geometry_bwd<POSE, AA>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr, cotOpacity * aaSg, &aaRho);
     // A Gaussian no pixel blended (not visible, or off every tile) arrives with an all-zero cotangent row and its
     // gradient is exactly zero.  The reference's arithmetic evaluates J^T 0 term by term, which is 0 * inf = NaN when
@@ -590,9 +601,13 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     if (ADAM) { sg_[0] = gx; sg_[1] = gy; sg_[2] = gz; }
     else { gXyz[3 * p] = gx; gXyz[3 * p + 1] = gy; gXyz[3 * p + 2] = gz; }
     if (gradNormAccum && !gateWord) gradNormAccum[p] += sqrtf(gx * gx + gy * gy + gz * gz);   // accum_grad_norm (densify.hip), fused
+    if constexpr (F3D) {       // dL/dscales_raw through s_eff and through kappa (an all-zero row: g.ds = 0 and cotOpacity = 0)
+        const float sgF = 1.0f / (1.0f + expf(-opr));
+        filter3d_activate<true>(s, f3dF, se, g.ds, cotOpacity * sgF * (AA ? aaRho : 1.0f) * f3dKappa);
+    }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        const float v = g.ds[a] * s[a];          // d exp
+        const float v = F3D ? g.ds[a] : g.ds[a] * s[a];          // d exp
         if (ADAM) sg_[3 + a] = v; else gScales[3 * p + a] = v;
     }
     // rotation normalisation VJP: y = q / (|q| + 1e-8)
@@ -605,7 +620,7 @@ __device__ __forceinline__ void proj_bwd_fused_body(
         if (ADAM) sg_[6 + a] = v; else gRot[4 * p + a] = v;
     }
     const float sg = 1.0f / (1.0f + expf(-opr));
-    const float gop = (AA ? cotOpacity * aaRho : cotOpacity) * sg * (1.0f - sg);
+    const float gop = (F3D ? (AA ? cotOpacity * f3dKappa * aaRho : cotOpacity * f3dKappa) : AA ? cotOpacity * aaRho : cotOpacity) * sg * (1.0f - sg);
     if (ADAM) sg_[10] = gop; else gOpacity[p] = gop;
     if constexpr (MCMC) {      // + the gradients of opacity_reg mean(sigma(o)) and scale_reg mean(exp(s)) (mcmc_reg_kernel's sums)
         sg_[10] = sg_[10] + mc.oCoef * mcmc_sigmoid_slope(opr);
@@ -682,6 +697,35 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_kernel
     const CamParams cam = *dcam;
     proj_bwd_fused_body<MODE, true, AA>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
                                     gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials);
+}
+
+// The 3-D smoothing filter's forms (gs_set_filter3d): MODE 0 and 2, plain and posed, either anti-aliasing mode.  Kernels of their
+// own, so that the ones above keep their arguments and their code.
+template <int MODE, bool AA>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_f3d_kernel(
+    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
+    float* gFdc, float* gFrest, float* gScales, float* gRot,
+    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, const float* __restrict__ filter3d)
+{
+    proj_bwd_fused_body<MODE, false, AA, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
+                                                      gXyz, gFdc, gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, nullptr,
+                                                      McmcFuse{}, filter3d);
+}
+template <int MODE, bool AA>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_f3d_kernel(
+    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
+    float* gFdc, float* gFrest, float* gScales, float* gRot,
+    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials,
+    const float* __restrict__ filter3d)
+{
+    const CamParams cam = *dcam;
+    proj_bwd_fused_body<MODE, true, AA, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
+                                                     gXyz, gFdc, gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials,
+                                                     McmcFuse{}, filter3d);
 }
 
 // The MCMC strategy's step (gs_set_mcmc): MODE 2 with the regularisers and the noise, plain and posed.  Kernels of their own,
@@ -1039,43 +1083,43 @@ int launch_projection_backward(gs_ctx* c, int N, int K, const float* scales, con
 }
 
 // the forward's kernel, in the anti-aliased mode's form (AA: gs_set_antialiasing) or the default one
-template <bool AA>
+template <bool AA, bool F3D = false>
 static void launch_fwd_fused_kernel(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
                                     const float* scales, const float* rot, const float* opacity, const CamParams& cam,
                                     float* radii, bool posed, bool twoPhase, bool selfColour, size_t lds, int pflags,
-                                    const ColourRider& a, const GsCutCoarse& cc, uint4* pieces)
+                                    const ColourRider& a, const GsCutCoarse& cc, uint4* pieces, const float* f3d = nullptr)
 {
     if (c->rider.on)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            0, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
                            scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
     else if (posed && twoPhase)
-        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<true, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<true, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
                            scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
     else if (posed)
-        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<false, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<false, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
                            scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
     else if (selfColour)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, true, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, true, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW, c->stream, N, K, c->degree, cam, c->tileW,
                            c->tileH, c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
                            c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters,
-                           pflags, a, c->virt, cc, pieces);
+                           pflags, a, c->virt, cc, pieces, f3d);
     else if (twoPhase)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
                            scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
     else
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<false, true, false, AA>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
+        hipLaunchKernelGGL((proj_fwd_fused_kernel<false, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
                            lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
                            scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces);
+                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
 }
 
 int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
@@ -1124,7 +1168,14 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
         c->rider.next = 0;
         c->rider.total = gs_div_up(N, 64);
     }
-    if (c->antialias)
+    // (the 3-D smoothing filter's forms, gs_set_filter3d: kernels of their own, the ones below are the ones they were)
+    if (c->filter3d && c->antialias)
+        launch_fwd_fused_kernel<true, true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
+                                            lds, pflags, a, cc, pieces, c->filter3d);
+    else if (c->filter3d)
+        launch_fwd_fused_kernel<false, true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
+                                             lds, pflags, a, cc, pieces, c->filter3d);
+    else if (c->antialias)
         launch_fwd_fused_kernel<true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
                                       lds, pflags, a, cc, pieces);
     else
@@ -1165,6 +1216,22 @@ int launch_projection_fused_backward(gs_ctx* c, int N, int K, const float* xyz, 
     const bool aa = c->fwd.antialias;       // (the mode this backward's forward ran in)
     AdamFuse none = {};
     if (!emitColorCot) { none.ovf = c->counters + GS_CNT_OVERFLOW; none.rider = c->overflowRider; }
+    if (const float* f3d = c->fwd.filter3d) {      // (the filter this backward's forward ran with; no data-parallel form: api.hip refuses)
+        if (c->fwd.poseDelta) {
+            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_f3d_kernel<0, true> : proj_bwd_fused_pose_f3d_kernel<0, false>),
+                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam,
+                               xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz, gFdc, gFrest, gScales, gRot, gOpacity,
+                               c->gradNormAccum, none, c->posePartials, f3d);
+            GS_HIP_CHECK(c, hipGetLastError());
+            return launch_pose_grad(c, N);
+        }
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_f3d_kernel<0, true> : proj_bwd_fused_f3d_kernel<0, false>),
+                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam, xyz, fdc,
+                           frest, scales, rot, opacity, c->gradAcc16, gXyz, gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum,
+                           none, f3d);
+        GS_HIP_CHECK(c, hipGetLastError());
+        return GS_OK;
+    }
     if (c->fwd.poseDelta && !emitColorCot) {
         hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_kernel<0, true> : proj_bwd_fused_pose_kernel<0>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
                            dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity,
@@ -1197,6 +1264,22 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
     a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale;
     a.gate = c->adamGate;
     const bool aa = c->fwd.antialias;
+    if (const float* f3d = c->fwd.filter3d) {      // (never with the MCMC step: gs_set_filter3d and gs_set_mcmc refuse each other)
+        if (c->fwd.poseDelta) {
+            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_f3d_kernel<2, true> : proj_bwd_fused_pose_f3d_kernel<2, false>),
+                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam,
+                               xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               c->gradNormAccum, a, c->posePartials, f3d);
+            GS_HIP_CHECK(c, hipGetLastError());
+            return launch_pose_grad(c, N);
+        }
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_f3d_kernel<2, true> : proj_bwd_fused_f3d_kernel<2, false>),
+                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam, xyz, fdc,
+                           frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           c->gradNormAccum, a, f3d);
+        GS_HIP_CHECK(c, hipGetLastError());
+        return GS_OK;
+    }
     if (c->mcmcOn) {
         const McmcFuse mc = mcmc_fuse(c->mcmc, N, lr[0]);
         if (c->fwd.poseDelta) {

@@ -570,6 +570,56 @@ class GaussianRenderer:
     def antialiased(self, enable: bool):
         self.setAntialiased(enable)
 
+    # -- the 3-D smoothing filter (include/gsplat.h gs_set_filter3d; filter3d.py restates it in float64) ---
+    def setFilterCameras(self, cameras):
+        """gs_set_filter3d_cameras: the training cameras computeFilter3D measures against (Camera objects or gs_camera structs;
+        an empty list frees the table)."""
+        cams = [c if isinstance(c, _lib.gs_camera) else self._camera(c.worldViewTransform, c.projectionMatrix, c.cameraCenter,
+                                                                      c.FoVx, c.FoVy, c.focalX, c.focalY) for c in cameras]
+        arr = (_lib.gs_camera * max(len(cams), 1))(*cams)
+        self._check(self.lib.gs_set_filter3d_cameras(self.ctx, len(cams), C.cast(arr, C.c_void_p) if cams else None))
+        self._filter_cameras = len(cams)
+
+    def computeFilter3D(self, xyz, out=None):
+        """gs_compute_filter3d: the filter widths [N] of the positions xyz [N, 3] (into out[:N] when given: a contiguous float32
+        device tensor of at least N elements; nothing is allocated then).  Asynchronous."""
+        xyz = xyz if isinstance(xyz, torch.Tensor) and xyz.is_cuda and xyz.dtype == torch.float32 and xyz.is_contiguous() else self._t(xyz)
+        N = int(xyz.shape[0])
+        if out is None:
+            out = self._empty(N)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.device.type != "cuda" or out.numel() < N:
+            raise ValueError("computeFilter3D: out is a contiguous float32 device tensor of at least N elements")
+        self._check(self.lib.gs_compute_filter3d(self.ctx, N, _p(xyz), _p(out)))
+        return out
+
+    def setFilter3D(self, t=None):
+        """gs_set_filter3d: the filter widths (a contiguous float32 device tensor of at least N elements) of the following
+        renderForward calls, or None (off, the default).  A backward uses the filter of its forward: keep the tensor unchanged
+        between the two.  Single-device steps and the reference strategy only."""
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda"):
+            raise ValueError("setFilter3D: a contiguous float32 device tensor, or None")
+        self._check(self.lib.gs_set_filter3d(self.ctx, _p(t)))
+        self._filter3d = t                # (kept alive while the library holds its address)
+
+    @property
+    def filter3D(self):
+        return getattr(self, "_filter3d", None)
+
+    def bakeFilter3D(self, params: dict, filter=None):
+        """gs_filter3d_bake: a copy of params with scales = log(s_eff) and opacity = logit(sigma kappa) under `filter` (default:
+        the filter that is set).  Rendered with the filter off, the baked model is the filtered one."""
+        f = self.filter3D if filter is None else filter
+        if f is None:
+            raise ValueError("bakeFilter3D: no filter is set and none was given")
+        sc, op = self._t(params["scales"]), self._t(params["opacity"])
+        N = int(sc.shape[0])
+        if f.numel() < N or op.numel() != N:
+            raise ValueError("bakeFilter3D: the filter holds fewer than N widths")
+        out = dict(params)
+        out["scales"], out["opacity"] = torch.empty_like(sc), torch.empty_like(op)
+        self._check(self.lib.gs_filter3d_bake(self.ctx, N, _p(sc), _p(op), _p(f), _p(out["scales"]), _p(out["opacity"])))
+        return out
+
     # -- the MCMC strategy (include/gsplat.h gs_set_mcmc; mcmc.MCMCConfig.params builds the gs_mcmc_params) -----------------
     def setMCMC(self, params=None):
         """gs_set_mcmc: the MCMC strategy's per-step part (regularisers, noise) in the following renderBackwardAdam calls, or

@@ -452,7 +452,8 @@ class GaussianTrainer:
                  exchange_impl: str = "torch", dp_bootstrap=None, views_per_rank: int = 1, pose_opt: bool = False,
                  pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None,
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
-                 bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0):
+                 bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
+                 filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -505,7 +506,16 @@ class GaussianTrainer:
         Gaussians are relocated onto live ones and the count grows by grow_rate up to cap_max.  The reference strategy is then
         off (densify is ignored).  The model is laid out at stride = capacity >= cap_max on construction, so growth appends in
         place; lastMCMCStats holds the last event's counts.  Single-device steps only (no process group, dp_bootstrap, native
-        exchange or views_per_rank > 1, no referenceParamReload); composes with pose_opt and an anti-aliased renderer."""
+        exchange or views_per_rank > 1, no referenceParamReload); composes with pose_opt and an anti-aliased renderer.
+
+        filter_3d: Mip-Splatting's 3-D smoothing filter (include/gsplat.h gs_set_filter3d).  The trainer
+        owns a [capacity] buffer of filter widths, computed from filter_cameras (the training cameras, as given: a pose_opt
+        run does not move them) at construction, behind every committed densify event, behind every parameter reload and
+        every filter_3d_interval iterations; every step renders and differentiates under it, and save_snapshot writes the
+        BAKED parameters (gs_filter3d_bake), which any viewer renders as the filtered model.  Single-device steps and the
+        reference strategy only; composes with pose_opt, exposure_opt, bilateral_grid, an anti-aliased renderer and
+        referenceParamReload.  filter3D() returns the widths of the current model.  Off (the default): no kernel, buffer or
+        result differs."""
         if strategy not in ("reference", "mcmc"):
             raise ValueError(f"unknown strategy {strategy!r} (\"reference\" or \"mcmc\")")
         self.strategy = strategy
@@ -524,6 +534,17 @@ class GaussianTrainer:
             densify = False
         elif mcmc is not None:
             raise ValueError("mcmc settings need strategy='mcmc'")
+        self.filter_3d = bool(filter_3d)
+        if self.filter_3d:
+            if strategy == "mcmc":
+                raise ValueError("filter_3d: the reference strategy only (not with strategy='mcmc')")
+            _require_single_device("filter_3d", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            if filter_cameras is None or len(filter_cameras) < 1:
+                raise ValueError("filter_3d needs filter_cameras (the training cameras)")
+            if isinstance(filter_3d_interval, bool) or int(filter_3d_interval) != filter_3d_interval or int(filter_3d_interval) < 1:
+                raise ValueError("filter_3d_interval must be an integer >= 1")
+        elif filter_cameras is not None:
+            raise ValueError("filter_cameras need filter_3d=True")
         self.pose_opt = bool(pose_opt)
         if self.pose_opt:
             _require_single_device("pose_opt", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
@@ -695,6 +716,11 @@ class GaussianTrainer:
                 lambda rr, G, g: rr.setBilateralGrid(G, g, self.bilateralGridShape, self.bilateralGridTv),
                 start=eye.repeat(nodes), shared_grad=True)
             self._bg_m, self._bg_v = self._perView["bilateral_grid"].m, self._perView["bilateral_grid"].v      # (likewise)
+        self._filter = None
+        if self.filter_3d:
+            self.filter3dInterval = int(filter_3d_interval)
+            r.setFilterCameras(list(filter_cameras))
+            self._updateFilter3D()
         if self._exchange:
             # the replicas must START identical too -- and the check's first call pays for the collective's set-up (a first
             # float64 max-reduce cost the torch exchange ~35 ms at the first densify event of a run) here, not there
@@ -711,6 +737,21 @@ class GaussianTrainer:
         if value and self.mcmc is not None:
             raise ValueError("referenceParamReload mirrors the reference strategy's commits: not with strategy='mcmc'")
         self._referenceParamReload = value
+
+    def _updateFilter3D(self):
+        """The filter widths of the model as it is now (gs_compute_filter3d), into the trainer's [capacity] buffer -- regrown
+        with the model's capacity, so a steady-state step allocates nothing."""
+        r, m = self.gaussRender, self.model
+        need = max(int(m.capacity), int(m.N), 1)
+        if self._filter is None or self._filter.numel() < need:
+            self._filter = r._empty(need).zero_()
+        r.computeFilter3D(m.getParams()["xyz"], out=self._filter)
+
+    def filter3D(self) -> torch.Tensor:
+        """The filter widths [N] of the current model (a view of the trainer's buffer)."""
+        if not self.filter_3d:
+            raise ValueError("filter3D: the trainer was built without filter_3d")
+        return self._filter[:self.model.N]
 
     def _mcmcParams(self, iteration=None):
         """The gs_mcmc_params of step `iteration` (default: the coming one)."""
@@ -833,6 +874,8 @@ class GaussianTrainer:
         import os
         from .ply import PlyWriter
         p = self.model.getParams()
+        if self.filter_3d:       # the fused export: a viewer without the filter renders the filtered model
+            p = self.gaussRender.bakeFilter3D(p, self._filter)
         PlyWriter(self.gaussRender).writeGaussianBinary(p["xyz"], p["features_dc"], p["features_rest"], p["opacity"],
                                                         p["scales"], p["rotation"],
                                                         to=os.path.join(os.fspath(self.outputDirectory),
@@ -1258,6 +1301,8 @@ class GaussianTrainer:
             r.setTuning(depth_gradient=0)
             if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
                 r.setMCMC(self._mcmcParams())
+            if self.filter_3d:
+                r.setFilter3D(self._filter)
             for t in tables:
                 t.bindRow(r, row)
             if self._exchange:
@@ -1275,6 +1320,8 @@ class GaussianTrainer:
             r.setTuning(**restore)
             if self.mcmc is not None:
                 r.setMCMC(None)
+            if self.filter_3d:
+                r.setFilter3D(None)
             for t in tables:
                 t.unbind(r)
 
@@ -1571,9 +1618,11 @@ class GaussianTrainer:
             # the event has just waited for the device (its count reads): the overflow flag is cheap to look at now
             if self._overflow_reported():
                 self.checkOverflow()
+        moved = False         # (filter_3d: the model's rows or positions changed other than by the step)
         if self.densify and it % self.split_and_prune_per_iteration == 0:
             self._committed = False
             self.split_and_prune(it)
+            moved = self._committed
             # the reference re-creates the optimizer state after every call, changed or not (:1098-1110); a committed
             # event has just done so (GaussModel.commitStaged)
             if not self._committed:
@@ -1581,6 +1630,7 @@ class GaussianTrainer:
                 if self.referenceParamReload and self._committed_params is not None \
                         and self._committed_params.numel() == m.arena.numel():
                     m.arena.copy_(self._committed_params)      # `params = model.getParams()` (:1100): the last COMMITTED tensors
+                    moved = True
             # the event has just waited for the device (its .item()): the overflow flag is cheap to look at now, and in a
             # data-parallel job every rank is here at the same iteration
             if self._exchange and not self._plans_events():
@@ -1589,4 +1639,6 @@ class GaussianTrainer:
                 pass        # a planned event has not drained the queue: the ranks look together at the next cadence (every overflowCheckInterval steps)
             elif self._overflow_reported():
                 self.checkOverflow()
+        if self.filter_3d and (moved or self.iteration % self.filter3dInterval == 0):
+            self._updateFilter3D()        # for the new N, before the next forward
         return self._loss

@@ -125,6 +125,17 @@ public:
         check(gs_apply_bilateral_grid(ctx_, w, h, grid, gridW, gridH, gridL, in, out));
     }
 
+    // Mip-Splatting's 3-D smoothing filter (include/gsplat.h gs_set_filter3d): the training cameras the widths are measured
+    // against (host structs; 0 frees the table), the widths of N positions (device), the filter of the following forwards
+    // (device [>= N]; nullptr = off, the default) and the baked export (outputs may alias scales / opacity).
+    void setFilterCameras(int V, const gs_camera* cams) { check(gs_set_filter3d_cameras(ctx_, V, cams)); }
+    void computeFilter3D(int N, const float* xyz, float* filter) { check(gs_compute_filter3d(ctx_, N, xyz, filter)); }
+    void setFilter3D(const float* filter) { check(gs_set_filter3d(ctx_, filter)); }
+    void bakeFilter3D(int N, const float* scales, const float* opacity, const float* filter, float* outScales, float* outOpacity)
+    {
+        check(gs_filter3d_bake(ctx_, N, scales, opacity, filter, outScales, outOpacity));
+    }
+
     // The target's windowed SSIM statistics per training view (include/gsplat.h: gs_set_loss_target_cache): cache = device
     // buffer of lossTargetCacheFloats() floats, one per view; filled = false at a view's first loss, true afterwards.
     long long lossTargetCacheFloats() { long long n = 0; check(gs_loss_target_cache_floats(ctx_, &n)); return n; }

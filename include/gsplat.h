@@ -325,6 +325,51 @@ int gs_apply_bilateral_grid(gs_ctx* ctx, int W, int H, const float* grid /*DEVIC
  * record it: render a model in the mode it was trained in. */
 int gs_set_antialiasing(gs_ctx* ctx, int enable);
 
+/* 3-D smoothing filter (not in the reference; DESIGN.md "3-D smoothing filter"): Mip-Splatting's other filter.  The anti-aliased
+ * mode above fixes a model viewed from further away than it was trained; this one fixes the other direction: a Gaussian may
+ * not be narrower than the sampling interval of the closest training camera that saw it, or the model shows needle and
+ * erosion artefacts when it is viewed closer, or at a higher resolution, than its training views.
+ *   Filter width f_i >= 0 per Gaussian, in scene units, a float32 DEVICE array the caller owns.  For each training camera n:
+ *     p = [x_i, 1] . view_n (the row-vector convention of gs_camera), z = p.z; the Gaussian is SEEN by n iff z >= 0.2 (the
+ *     projection's visibility rule), |p.x / z| <= 1.3 tan(fov_x / 2) and |p.y / z| <= 1.3 tan(fov_y / 2) (Mip-Splatting's
+ *     15 % screen margin, 0.65 W / focal, the constant of the EWA clamp); its interval there is T_n = z / focal_x,n.
+ *     f_i = sqrt(0.2) min over the seeing cameras of T_n -- the paper's maximal sampling rate max focal / depth, taken per
+ *     camera (Mip-Splatting's code takes one global focal).  A Gaussian no camera sees gets the LARGEST f among the seen ones
+ *     (Mip-Splatting's convention); if none is seen at all, every f_i is 0.
+ *   Activations.  While a filter is set, each gs_render_forward uses, with s_a = exp(scales_raw_a), sigma = sigmoid(opacity_raw):
+ *     s_eff_a = sqrt(s_a^2 + f^2) (a = 0, 1, 2),  kappa = prod_a (s_a / s_eff_a) (a product of the three ratios),
+ *     opacity = sigma kappa (times rho in the anti-aliased mode, rho from the covariance of s_eff).
+ *     Everything downstream is the existing arithmetic on s_eff and that opacity: covariance, conic, radius, rects, trimmed
+ *     rects, block lists, depth cuts, the degenerate-invisible rule.  s_eff >= s, so radii and the pair count M can grow.
+ *     f = 0 gives s_eff = s and kappa = 1 exactly (sqrtf(s s) = s under correct rounding): the filter-less kernels' results.
+ *   Backward, with g_a = dL/ds_eff_a, c = dL/d(packed opacity), rho = 1 outside the anti-aliased mode:
+ *     dL/dscales_raw_a = g_a s_a^2 / s_eff_a + c sigma rho kappa f^2 / s_eff_a^2,   dL/dopacity_raw = c kappa rho sigma (1 - sigma),
+ *     and the anti-aliased mode's covariance cotangent takes c sigma kappa where it takes c sigma without the filter.
+ *     f is not differentiated.  A backward uses the filter pointer its forward ran with; keep the array unchanged between
+ *     the two, as the parameter tensors.
+ *
+ * gs_set_filter3d_cameras: the training cameras gs_compute_filter3d measures against, V >= 0 HOST structs (view, fov_x, fov_y
+ * and focal_x are read), copied into a table the context owns.  The table is allocated or grown here only; V = 0 frees it.
+ * [sync] */
+int gs_set_filter3d_cameras(gs_ctx* ctx, int V, const gs_camera* cams /*HOST [V]*/);
+/* filter[i] = f_i of xyz[i] against the cameras set above (GS_ERR_INVALID_ARG without any).  Asynchronous on the context's
+ * stream, allocates nothing.  The result does not depend on the launch shape: cameras in table order, one fixed float32
+ * expression per (Gaussian, camera), a min and a max. */
+int gs_compute_filter3d(gs_ctx* ctx, int N, const float* xyz /*DEVICE [N,3]*/, float* filter /*DEVICE [N]*/);
+/* The filter of the following forwards: NULL (the default) is the behaviour without the filter, kernel for kernel.  A
+ * per-context setting as gs_set_antialiasing is.  It composes with the anti-aliased mode on and off, pose refinement, depth
+ * cuts and view hints, trimmed rects and block lists, gs_render_backward and gs_render_backward_adam.  Single-device steps and
+ * the reference strategy only: while a filter is set (or the last forward ran with one), gs_render_backward_dp*, gs_dp_step
+ * and gs_set_mcmc with non-NULL params return GS_ERR_INVALID_ARG, and so does this call with a non-NULL filter while the
+ * MCMC strategy is set.  The op-level entry points (gs_projection_*, gs_pack_gaussians, gs_blend_*) ignore it.  PLY snapshots
+ * do not record it: export with gs_filter3d_bake. */
+int gs_set_filter3d(gs_ctx* ctx, const float* filter /*DEVICE [>= N] or NULL*/);
+/* Mip-Splatting's fused export: out_scales_raw = log(s_eff), out_opacity_raw = logit(sigma kappa).  A model baked this way and
+ * rendered with the filter off is the filtered model, for any viewer.  The outputs may alias the inputs they replace (not
+ * `filter`).  Asynchronous on the context's stream. */
+int gs_filter3d_bake(gs_ctx* ctx, int N, const float* scales_raw /*[N,3]*/, const float* opacity_raw /*[N]*/,
+                     const float* filter /*[N]*/, float* out_scales_raw /*[N,3]*/, float* out_opacity_raw /*[N]*/);
+
 /* MCMC densification strategy (not in the reference; DESIGN.md "MCMC strategy"): "3D Gaussian Splatting as Markov Chain Monte
  * Carlo" (Kheradmand et al. 2024), gsplat's MCMCStrategy, with its defaults in brackets.  Notation: o = sigmoid(opacity_raw),
  * s = exp(scales_raw), R the rotation of q / (|q| + 1e-8), Sigma = R diag(s^2) R^T, N the Gaussian count.

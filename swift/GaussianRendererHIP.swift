@@ -154,6 +154,20 @@ public final class GaussianRendererHIP {
         try check(gs_set_loss_target_cache(ctx, cache, filled ? 1 : 0))
     }
 
+    /// Mip-Splatting's 3-D smoothing filter (include/gsplat.h gs_set_filter3d): the training cameras the widths are measured
+    /// against, the widths of a set of positions, the filter of the following forwards (nil = off), and the baked export.
+    public func setFilterCameras(_ cameras: [gs_camera]) throws {
+        try check(gs_set_filter3d_cameras(ctx, Int32(cameras.count), cameras))
+    }
+    public func computeFilter3D(N: Int, xyz: UnsafePointer<Float>, filter: UnsafeMutablePointer<Float>) throws {
+        try check(gs_compute_filter3d(ctx, Int32(N), xyz, filter))
+    }
+    public func setFilter3D(_ filter: UnsafePointer<Float>?) throws { try check(gs_set_filter3d(ctx, filter)) }
+    public func bakeFilter3D(N: Int, scales: UnsafePointer<Float>, opacity: UnsafePointer<Float>, filter: UnsafePointer<Float>,
+                             outScales: UnsafeMutablePointer<Float>, outOpacity: UnsafeMutablePointer<Float>) throws {
+        try check(gs_filter3d_bake(ctx, Int32(N), scales, opacity, filter, outScales, outOpacity))
+    }
+
     // ---- data-parallel step (include/gsplat.h, "row e") -----------------------------------------------------------
     // The reference trains one view per iteration on one device (GaussianTrainer.swift:486-498); on an 8-GPU node every
     // rank is one process with one renderer, renders its own view, and the library exchanges the gradients over RCCL.
