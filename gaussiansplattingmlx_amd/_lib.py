@@ -79,6 +79,9 @@ _SIGS = {
     "gs_pack_gaussians": (C.c_int, [_vp, C.c_int] + [_vp] * 6),
     "gs_blend_forward": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_blend_backward": (C.c_int, [_vp, C.c_int] + [_vp] * 9),
+    "gs_blend_contrib": (C.c_int, [_vp, C.c_int] + [_vp] * 3),
+    "gs_render_contrib": (C.c_int, [_vp, _vp, _vp]),
+    "gs_contrib_actions": (C.c_int, [_vp, C.c_int, _vp, C.c_float, _vp, _vp]),
     "gs_ssim_window": (C.c_int, [C.c_int, C.c_float, _vp]),
     "gs_ssim_forward": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp] * 9),
     "gs_ssim_backward": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp] * 11),

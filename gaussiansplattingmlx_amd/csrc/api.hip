@@ -769,6 +769,20 @@ int gs_blend_backward(gs_ctx* c, int N, const float* packed, const float* cot_co
     return launch_gradacc_to_packed11(c, N, grad_packed);
 }
 
+int gs_blend_contrib(gs_ctx* c, int N, const float* packed, float* max_w, float* sum_w)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!c->binValid) return fail(c, GS_ERR_NO_FORWARD, "gs_blend_contrib: call gs_tile_bin first");
+    if (c->binIsBlockLists) return fail(c, GS_ERR_NO_FORWARD, "gs_blend_contrib: the last binning on this context was a fused forward's block lists (tile size not a multiple of 16); call gs_tile_bin");
+    RealGeomScope real(c);
+    if (N != c->binN) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_blend_contrib: N differs from the binned N");
+    if ((!max_w && !sum_w) || (N > 0 && !packed)) return fail(c, GS_ERR_INVALID_ARG, "gs_blend_contrib: null buffer (one of max_w, sum_w at least)");
+    c->fwd.valid = false; c->fwd.bwdPrepared = false;      // as gs_blend_forward: the ctx's packed records are overwritten
+    int rc = launch_pack11_to_12(c, N, packed);
+    if (rc) return rc;
+    return launch_blend_contrib(c, max_w, sum_w);
+}
+
 // ---- SSIM -----------------------------------------------------------------------------------------
 int gs_ssim_window(int K, float sigma, float* window)
 {
@@ -1149,6 +1163,23 @@ int gs_render_backward(gs_ctx* c, const float* cot_color, const float* cot_depth
     return launch_projection_fused_backward(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
                                             c->fwd.opacity, c->fwd.cam, grad_xyz, grad_features_dc, grad_features_rest,
                                             grad_scales, grad_rotation, grad_opacity);
+}
+
+int gs_render_contrib(gs_ctx* c, float* max_w, float* sum_w)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    { const int prc = backward_preflight(c, "gs_render_contrib", false); if (prc) return prc; }
+    if (!max_w && !sum_w) return fail(c, GS_ERR_INVALID_ARG, "gs_render_contrib: null buffer (one of max_w, sum_w at least)");
+    // reads the forward's records and lists, writes nothing of the context's: a backward may still follow
+    return launch_blend_contrib(c, max_w, sum_w);
+}
+
+int gs_contrib_actions(gs_ctx* c, int N, const float* score, float threshold, int* actions, int* output_counts)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (N < 0 || !(threshold == threshold) || (N > 0 && (!score || !actions || !output_counts)))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_contrib_actions: bad arguments");
+    return launch_contrib_actions(c, N, score, threshold, actions, output_counts);
 }
 
 int gs_render_backward_adam(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha,

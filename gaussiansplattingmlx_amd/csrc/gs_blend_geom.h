@@ -1,0 +1,53 @@
+// gs_blend_geom.h -- what the op-level blend kernels (blend.hip) and the contribution pass (contrib.hip) share: the
+// enumeration of the 16x16 pixel blocks and the forward's exponential
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace gs {
+
+constexpr int TILE = 16;
+
+// Which 16x16 pixel block is work item `blk`, which tile's list does it sweep, and where do its pixels end?
+// Tile sizes that are multiples of 16: the blocks of the image grid, row-major (blocksX per row); every block lies in
+// one tile.  Any other tile size (the reference app's W/4 x H/4 = 200 x 200, Data/ColmapDataLoader.swift:495-498): the
+// blocks are enumerated PER TILE -- bptX x bptY of them, clipped at the tile's right and bottom edge -- so that a
+// block never straddles two tiles and the same LDS-staged kernels serve every tile size (the first builds ran these
+// sizes one thread per pixel from global memory with per-pixel atomics: 425 ms per backward at 800x800 / 200x200).
+struct BlockGeom {
+    int W, H, tileW, tileH, gridW, blocksX, bptX, bptY;      // bptX == 0: image-grid enumeration
+};
+struct BlockRect {
+    int tile, x0, y0, xEnd, yEnd;
+};
+__device__ __forceinline__ BlockRect block_rect(const BlockGeom& g, int blk)
+{
+    BlockRect r;
+    if (g.bptX == 0) {
+        const int by = blk / g.blocksX, bx = blk - by * g.blocksX;
+        r.x0 = bx * TILE; r.y0 = by * TILE; r.xEnd = g.W; r.yEnd = g.H;
+        r.tile = (r.y0 / g.tileH) * g.gridW + r.x0 / g.tileW;
+    } else {
+        const int per = g.bptX * g.bptY;
+        r.tile = blk / per;
+        const int rem = blk - r.tile * per, by = rem / g.bptX, bx = rem - by * g.bptX;
+        const int ty = r.tile / g.gridW, tx = r.tile - ty * g.gridW;
+        r.x0 = tx * g.tileW + bx * TILE; r.y0 = ty * g.tileH + by * TILE;
+        r.xEnd = min(g.W, (tx + 1) * g.tileW); r.yEnd = min(g.H, (ty + 1) * g.tileH);
+    }
+    return r;
+}
+
+// exp(x), x <= 0, for the FORWARD kernels: v_exp_f32 on the rounded product x log2(e) is off by |x log2 e| 2^-24 relative
+// (3.4e-4 on rendered colours of magnitude ~27); carrying the product's rounding error and log2(e)'s tail along brings it
+// to ~1 ulp at four more instructions (blend_v2.hip, gauss_alpha_raw).
+__device__ __forceinline__ float comp_exp(float x)
+{
+    constexpr float L2E = 1.44269502162933349609375f, L2E_TAIL_LN2 = 1.3349758e-08f, LN2 = 0.69314718055994531f;
+    const float hi = x * L2E;
+    const float lo = fmaf(x, L2E, -hi);
+    const float d = fmaf(x, L2E_TAIL_LN2, lo * LN2);
+    const float g = __builtin_amdgcn_exp2f(hi);
+    return fmaf(g, d, g);
+}
+
+}  // namespace gs

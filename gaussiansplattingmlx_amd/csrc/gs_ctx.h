@@ -472,6 +472,11 @@ int launch_blend_backward(gs_ctx* c, int N, const float* cotColor, const float* 
                           const float* outAlpha, const uint32_t* lastContrib);
 int launch_gradacc_to_packed11(gs_ctx* c, int N, float* gradPacked11);
 
+// contrib.hip: per-Gaussian blend weight scores over the lists of the last binning (either output may be null), and the prune
+// decision on a score
+int launch_blend_contrib(gs_ctx* c, float* maxW, float* sumW);
+int launch_contrib_actions(gs_ctx* c, int N, const float* score, float threshold, int* actions, int* outputCounts);
+
 // blend_v2.hip (fused fast path)
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha);
 int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,

@@ -297,6 +297,56 @@ class GaussianRenderer:
             _p(s["depth"]), _p(s["alpha"]), _p(s["last"]), _p(grad))))
         return grad
 
+    # -- per-Gaussian blend weight scores (include/gsplat.h gs_blend_contrib) -------------
+    def _contrib_out(self, who, N, maxW, sumW):
+        if maxW is None and sumW is None:
+            raise ValueError(f"{who}: one of maxW, sumW at least")
+        for name, t in (("maxW", maxW), ("sumW", sumW)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+                                      and t.is_contiguous() and t.numel() == N):
+                raise ValueError(f"{who}: {name} must be a contiguous float32 device tensor of {N} elements")
+
+    def blendContrib(self, packedGaussians, maxW=None, sumW=None):
+        """The blend weight scores of the view whose lists the last buildGlobalTileSliceInfo built: per Gaussian the maximum
+        and the sum over the pixels of w = T alpha.  ACCUMULATES into maxW / sumW (float32 device tensors [N], either may be
+        None): maxW becomes max(old, this view), sumW gets this view added."""
+        packed = self._t(packedGaussians)
+        N = int(packed.shape[0])
+        self._contrib_out("blendContrib", N, maxW, sumW)
+        self._check(self.lib.gs_blend_contrib(self.ctx, N, _p(packed), _p(maxW), _p(sumW)))
+        return maxW, sumW
+
+    def renderContrib(self, maxW=None, sumW=None):
+        """blendContrib for the view of the last renderForward / renderChecked, on that forward's own records and lists (its
+        anti-aliased opacity, 3-D filter and pose correction included).  Consumes nothing: a renderBackward may follow."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "renderContrib: no renderForward on this renderer")
+        N = int(self._fused["params"]["xyz"].shape[0])
+        self._contrib_out("renderContrib", N, maxW, sumW)
+        self._check(self.lib.gs_render_contrib(self.ctx, _p(maxW), _p(sumW)))
+        return maxW, sumW
+
+    def contributionScores(self, params: dict, cameras, viewKeys=None):
+        """(max_w, sum_w) [N] over `cameras`: every camera is rendered with renderChecked (no depth image; a forward that
+        missed under depth cuts is repeated) and scored with renderContrib.  viewKeys: the cameras' view keys, or None."""
+        cameras = list(cameras)
+        if viewKeys is not None and len(viewKeys) != len(cameras):
+            raise ValueError("contributionScores: one view key per camera")
+        N = int(params["xyz"].shape[0])
+        maxW, sumW = self._empty(N).zero_(), self._empty(N).zero_()
+        for i, cam in enumerate(cameras):
+            self.renderChecked(params, cam, viewKey=None if viewKeys is None else viewKeys[i], wantDepth=False)
+            self.renderContrib(maxW, sumW)
+        return maxW, sumW
+
+    def contribActions(self, score, threshold: float):
+        """(actions, counts) of classifyGaussians' kind from a score: prune (3, 0) where score < threshold, else keep (0, 1)."""
+        score = self._t(score)
+        N = int(score.shape[0])
+        actions, counts = self._empty(N, dtype=torch.int32), self._empty(N, dtype=torch.int32)
+        self._check(self.lib.gs_contrib_actions(self.ctx, N, _p(score), C.c_float(threshold), _p(actions), _p(counts)))
+        return actions, counts
+
     # -- render / forward (GaussianRenderer.swift:736-934) ---------------------------------------------------
     def render(self, imageWidth, imageHeight, means2d, cov2d, color, opacity, depths, radii, conic, rect,
                inputIsDepthSorted: bool = False):

@@ -453,7 +453,7 @@ class GaussianTrainer:
                  pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None,
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
-                 filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100):
+                 filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -515,10 +515,33 @@ class GaussianTrainer:
         BAKED parameters (gs_filter3d_bake), which any viewer renders as the filtered model.  Single-device steps and the
         reference strategy only; composes with pose_opt, exposure_opt, bilateral_grid, an anti-aliased renderer and
         referenceParamReload.  filter3D() returns the widths of the current model.  Off (the default): no kernel, buffer or
-        result differs."""
+        result differs.
+
+        contrib_prune: contribution-based pruning (contrib_prune.ContribPruneConfig, include/gsplat.h gs_render_contrib, DESIGN.md
+        section 15).  Behind every iteration listed in contrib_prune.at -- after that iteration's split_and_prune, if it has one --
+        the model is rendered from contrib_prune.cameras (under pose_opt from refinedCamera(i, cameras[i]): view keys 0 .. len - 1),
+        every Gaussian is scored by the largest (score="max", RadSplat) or the summed (score="sum") blend weight T alpha it gets
+        at any pixel of any of them, and those below contrib_prune.threshold are pruned through the densify event's own scan,
+        output map and gather (the planned ones where plannedDensify).  The event commits as a committed densify event does:
+        optimizer state and gradient accumulators reset, filter_3d widths recomputed, depth cuts kept (nothing gets longer).  An
+        event that would prune everything prunes nothing.  lastContribPruneStats holds the last event's N, kept, pruned and
+        threshold; pruneByContribution(cameras, threshold, score) runs the same event on demand (compaction before a snapshot).
+        Single-device steps and the reference strategy only; composes with pose_opt, exposure_opt, bilateral_grid, filter_3d, an
+        anti-aliased renderer and densify on or off.  Off (the default): no kernel, buffer or result differs."""
         if strategy not in ("reference", "mcmc"):
             raise ValueError(f"unknown strategy {strategy!r} (\"reference\" or \"mcmc\")")
         self.strategy = strategy
+        self.contribPrune = None
+        self.lastContribPruneStats = None
+        if contrib_prune is not None:
+            from .contrib_prune import ContribPruneConfig
+            if not isinstance(contrib_prune, ContribPruneConfig):
+                raise ValueError("contrib_prune must be a ContribPruneConfig")
+            contrib_prune.validate()
+            if strategy == "mcmc":
+                raise ValueError("contrib_prune: the reference strategy only (not with strategy='mcmc')")
+            _require_single_device("contrib_prune", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            self.contribPrune = contrib_prune
         self.mcmc = None
         self.lastMCMCStats = None
         if strategy == "mcmc":
@@ -1040,6 +1063,88 @@ class GaussianTrainer:
         self.resetGradientAccumulation()
         if self._exchange:
             self.checkReplicas()       # before the next size-dependent collective
+        return st
+
+    def _contribScores(self, cameras):
+        """(max_w, sum_w) of the current model over `cameras`, rendered as a step renders them: the 3-D filter set, the learned
+        pose of view i applied to cameras[i], no per-view correction bound.  A forward that overflowed the reserved pairs would
+        score its view as blank: the reserve is regrown and the scoring repeated."""
+        r, m = self.gaussRender, self.model
+        cams = list(cameras)
+        if self.pose_opt:
+            cams = [self.refinedCamera(i, c) for i, c in enumerate(cams)]
+        for t in self._perView.values():
+            t.unbind(r)               # (a step binds its view's rows again; the refined cameras above carry the poses)
+        if self.filter_3d:
+            r.setFilter3D(self._filter)
+        try:
+            for attempt in range(4):
+                try:
+                    scores = r.contributionScores(m.getParams(), cams)
+                    r.sync()
+                    return scores
+                except GsplatError as e:
+                    if e.code != GS_ERR_WORKSPACE_OVERFLOW or attempt == 3:
+                        raise
+                    self._recover_overflow()
+        finally:
+            if self.filter_3d:
+                r.setFilter3D(None)
+
+    def _contribPruneEvent(self, cameras, threshold: float, score: str):
+        """Scores the model over `cameras` and prunes what lies below the threshold through the densify event's machinery.
+        Returns the stats; self._committed says whether the model changed."""
+        r, m = self.gaussRender, self.model
+        N = m.N
+        st = dict(N=N, kept=N, pruned=0, threshold=float(threshold))
+        self.lastContribPruneStats = st
+        self._committed = False
+        if N <= 0:
+            return st
+        maxW, sumW = self._contribScores(cameras)
+        actions, counts = r.contribActions(maxW if score == "max" else sumW, float(threshold))
+        p = m.getParams()
+        if self._plans_events():
+            offsets = r.densifyPlan(actions, counts)
+            plan = r.densifyPlanRead(wait=True)
+            if not plan["applies"] or plan["prune"] <= 0:      # nothing below the threshold, or everything: no change
+                return st
+            N_new, cap = plan["N_new"], m.capacity
+            gather, mode = r.buildDensifyOutputMapPlanned(actions, offsets, cap)
+            r.densifyGatherPlanned(p, gather, mode, self.noise_seed, m.stagingViews(cap, stride=cap), cap)
+            m.commitStaged(N_new=N_new)
+        else:
+            offsets, ds = r.densifyOffsets(actions, counts)
+            N_new = ds["total"]
+            if N_new <= 0 or ds["prune"] <= 0:
+                return st
+            gather, mode = r.buildDensifyOutputMap(actions, offsets, N_new)
+            r.densifyGather(p, gather, mode, None, out=m.stagingViews(N_new))
+            m.commitStaged()
+        self._committed = True
+        if self.referenceParamReload:
+            self._committed_params = m.arena.clone()
+        # (the depth cuts stay, as after a densify event that only pruned: see split_and_prune)
+        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in m.seg_end])
+        self._alloc_exchange_buffers()
+        self.resetGradientAccumulation()
+        st.update(kept=int(N_new), pruned=int(N - N_new))
+        return st
+
+    def pruneByContribution(self, cameras, threshold: float = 0.01, score: str = "max"):
+        """The contrib_prune event on demand (e.g. compaction before save_snapshot): scores the model over `cameras`, prunes what
+        lies below the threshold, resets the optimizer state as a committed densify event does.  Returns lastContribPruneStats.
+        Single-device trainers with the reference strategy only."""
+        from .contrib_prune import ContribPruneConfig
+        if self.mcmc is not None:
+            raise ValueError("pruneByContribution: the reference strategy only (not with strategy='mcmc')")
+        if self._dp:
+            raise ValueError("pruneByContribution: single-device steps only (no process group, dp_bootstrap, native exchange or "
+                             "views_per_rank > 1)")
+        cfg = ContribPruneConfig(threshold=threshold, at=(1,), cameras=list(cameras), score=score).validate()
+        st = self._contribPruneEvent(cfg.cameras, cfg.threshold, cfg.score)
+        if self._committed and self.filter_3d:
+            self._updateFilter3D()
         return st
 
     def checkReplicas(self, deferred: bool = False):
@@ -1639,6 +1744,9 @@ class GaussianTrainer:
                 pass        # a planned event has not drained the queue: the ranks look together at the next cadence (every overflowCheckInterval steps)
             elif self._overflow_reported():
                 self.checkOverflow()
+        if self.contribPrune is not None and self.contribPrune.is_event(it):
+            self._contribPruneEvent(self.contribPrune.cameras, self.contribPrune.threshold, self.contribPrune.score)
+            moved = moved or self._committed
         if self.filter_3d and (moved or self.iteration % self.filter3dInterval == 0):
             self._updateFilter3D()        # for the new N, before the next forward
         return self._loss

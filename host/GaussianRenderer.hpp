@@ -136,6 +136,18 @@ public:
         check(gs_filter3d_bake(ctx_, N, scales, opacity, filter, outScales, outOpacity));
     }
 
+    // Contribution-based pruning (include/gsplat.h gs_blend_contrib): per Gaussian the largest and the summed blend weight
+    // T alpha over the pixels of a view, ACCUMULATED into caller-owned device buffers [N] (zero them once, call once per view;
+    // either may be nullptr) -- on the lists of the last binning (blendContrib, packed [N, 11]) or on the last renderForward's
+    // own records and lists (renderContrib: a backward may still follow) -- and the prune decision on a score in the words of
+    // classifyGaussians: action 3 / count 0 where score < threshold, else 0 / 1.
+    void blendContrib(int N, const float* packed, float* maxW, float* sumW) { check(gs_blend_contrib(ctx_, N, packed, maxW, sumW)); }
+    void renderContrib(float* maxW, float* sumW) { check(gs_render_contrib(ctx_, maxW, sumW)); }
+    void contribActions(int N, const float* score, float threshold, int* actions, int* outputCounts)
+    {
+        check(gs_contrib_actions(ctx_, N, score, threshold, actions, outputCounts));
+    }
+
     // The target's windowed SSIM statistics per training view (include/gsplat.h: gs_set_loss_target_cache): cache = device
     // buffer of lossTargetCacheFloats() floats, one per view; filled = false at a view's first loss, true afterwards.
     long long lossTargetCacheFloats() { long long n = 0; check(gs_loss_target_cache_floats(ctx_, &n)); return n; }

@@ -186,6 +186,22 @@ int gs_blend_backward(gs_ctx* ctx, int N, const float* packed, const float* cot_
                       const float* cot_alpha, const float* out_color, const float* out_depth,
                       const float* out_alpha, const uint32_t* last_contrib, float* grad_packed);
 
+/* Per-Gaussian blend weight scores (not in the reference): the quantity contribution-based pruning
+ * (RadSplat's maximum, LightGaussian's / Mini-Splatting's sum) scores a Gaussian by.  For a pixel p and the j-th entry g of its
+ * tile's depth-ordered list the blend computes, with T = 1 in front of the list (gs_blend_forward's arithmetic),
+ *   raw = exp(-1/2 d^T conic d) opacity_g,  alpha = min(raw, 0.99),  w(p, g) = T alpha,  T <- T (1 - alpha),
+ * and the pixel stops after the entry that brings T below 1e-4: later entries have w = 0.  Pixels outside the image do not
+ * exist.  The scores of a view are
+ *   max_w[g] = max over pixels of w(p, g),   sum_w[g] = sum over pixels of w(p, g),
+ * 0 for a Gaussian in no list.  One pass over the tile lists of the last gs_tile_bin / gs_tile_bin_cut.  Both outputs
+ * ACCUMULATE into caller-owned DEVICE buffers [N]: max_w becomes max(old, this view), sum_w gets this view added -- zero them
+ * once, call once per view.  Either may be NULL, not both (GS_ERR_INVALID_ARG).  max_w is exact and the same bits on every
+ * run (an integer maximum on the bit patterns of non-negative floats); sum_w is summed with float atomics.  Every tile size
+ * gs_ctx_create accepts is supported (tiles larger than 16 x 16 sweep their list once per 16 x 16 block).  No sync, no
+ * allocation. */
+int gs_blend_contrib(gs_ctx* ctx, int N, const float* packed /*[N,11]*/, float* max_w /*DEVICE [N] or NULL*/,
+                     float* sum_w /*DEVICE [N] or NULL*/);
+
 /* ---- a10: SSIM -------------------------------------------------------------------------------------- */
 
 /* gaussian(windowSize:sigma:) outer product (LossUtil.swift:47-54, GaussianTrainer.swift:308-314);
@@ -236,6 +252,16 @@ int gs_render_backward(gs_ctx* ctx, const float* cot_color, const float* cot_dep
 int gs_render_backward_adam(gs_ctx* ctx, const float* cot_color, const float* cot_depth, const float* cot_alpha,
                             float* params_base, float* m_base, float* v_base, long long n_arena, const float lr[6],
                             float beta1, float beta2, float eps, float grad_scale);
+
+/* gs_blend_contrib's scores of the last gs_render_forward's view, on that forward's own records and lists: the opacity of
+ * an anti-aliased forward, of a 3-D filter and the camera of a pose correction are what it was composed with.  (The fused
+ * forward bins trimmed rects, and may bin under depth cuts: entries of weight below 2^-29, or behind every pixel's stop, are
+ * not in its lists -- a score moves by less than 1e-8.)  Accumulates into max_w / sum_w DEVICE [N of the forward] like
+ * gs_blend_contrib.  Refuses what gs_render_backward would refuse, with the same codes: no valid forward (or one a
+ * gs_render_backward_adam consumed), a forward reported missed, a forward that overflowed its reserved pairs, checkpoint-arena
+ * overflow.  After a forward under depth cuts ask gs_forward_missed first, as for any other use of its outputs.  Consumes
+ * nothing: a backward may still follow, the render outputs and gs_last_stats are untouched.  No sync, no allocation. */
+int gs_render_contrib(gs_ctx* ctx, float* max_w /*DEVICE [N] or NULL*/, float* sum_w /*DEVICE [N] or NULL*/);
 
 /* Per-view camera pose refinement (not in the reference; DESIGN.md "Pose refinement").  delta DEVICE [6] = (w, tau), float32,
  * a correction of the camera-to-world pose in the camera's own OpenCV frame (x right, y down, z forward):
@@ -642,6 +668,11 @@ int gs_accum_grad_norm(gs_ctx* ctx, int N, const float* xyz_grad, const float* a
 int gs_classify_gaussians(gs_ctx* ctx, int N, const float* grad_accum, float denom, const float* scales,
                           int scale_stride, const float* opacity, float grad_threshold, float max_scale_thresh,
                           float min_opacity_thresh, int allow_densify, int* actions, int* output_counts);
+/* The prune decision on a contribution score (gs_blend_contrib / gs_render_contrib), in gs_classify_gaussians' words:
+ * actions[i] = 3 (prune), output_counts[i] = 0 where score[i] < threshold, else 0 (keep) and 1 -- the scan, the output map and
+ * the gather below then perform the prune unchanged. */
+int gs_contrib_actions(gs_ctx* ctx, int N, const float* score /*DEVICE [N]*/, float threshold, int* actions,
+                       int* output_counts);
 /* offsets = cumsum(output_counts) - output_counts (:813-815) plus the action counts (:838-841).  Synchronises (the
  * reference's .item(), :816): stats HOST [5] = total outputs, keep, split, clone, prune. */
 int gs_densify_offsets(gs_ctx* ctx, int N, const int* actions, const int* output_counts, int* offsets,
