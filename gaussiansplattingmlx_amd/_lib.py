@@ -142,6 +142,8 @@ _SIGS = {
     "gs_set_bilateral_grid": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float]),
     "gs_apply_bilateral_grid": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
+    "gs_set_absgrad": (C.c_int, [_vp, C.c_int]),
+    "gs_get_absgrad": (C.c_int, [_vp, C.c_int, _vp]),
     "gs_set_filter3d_cameras": (C.c_int, [_vp, C.c_int, _vp]),
     "gs_compute_filter3d": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gs_set_filter3d": (C.c_int, [_vp, _vp]),

@@ -271,13 +271,30 @@ int backward_preflight(gs_ctx* c, const char* who, bool wantsDepth)
 }
 
 // the blend backward of the last fused forward: the first stage of every backward entry point
-int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha)
+// absgrad (gs_set_absgrad; gs_render_backward and gs_render_backward_adam only): the ABSGRAD instantiation, which leaves (Ax, Ay)
+// in columns 12 and 13 of gradAcc16, and behind it the AbsGS statistic into the grad-norm accumulator (gate: the overflow word
+// the fused Adam tests, null without it)
+int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha,
+                              bool absgrad = false, const uint32_t* gate = nullptr)
 {
     GsStageTimer t(c, GS_STAGE_BLEND_BWD);
-    return c->fast16 ? launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
-                                                c->fwd.outAlpha)
-                     : launch_blend_backward(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+    c->absgradN = -1;
+    if (!c->fast16) return launch_blend_backward(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+    if (const int rc = launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
+                                                c->fwd.outAlpha, absgrad))
+        return rc;
+    if (!absgrad) return GS_OK;
+    c->absgradN = c->fwd.N;
+    return c->gradNormAccum ? launch_absgrad_accum(c, c->fwd.N, gate, c->gradNormAccum) : GS_OK;
 }
+
+// the projection backward of an absgrad step adds nothing to the grad-norm accumulator: it sees none
+struct AbsgradScope {
+    gs_ctx* c;
+    float* saved;
+    explicit AbsgradScope(gs_ctx* ctx) : c(ctx), saved(ctx->gradNormAccum) { if (c->absgrad) c->gradNormAccum = nullptr; }
+    ~AbsgradScope() { c->gradNormAccum = saved; }
+};
 
 // the gs_sh_grad_from_views* family's common arguments; own_bad / own_null: what the entry point's own arguments add to the
 // first and to the null-buffer check
@@ -356,6 +373,13 @@ int refuse_pose_correction(gs_ctx* c, const char* who)
 {
     if (!c->poseDelta && !c->fwd.poseDelta) return GS_OK;
     return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a pose correction is set (single-device steps only)");
+}
+
+int refuse_absgrad(gs_ctx* c, const char* who)
+{
+    if (!c->absgrad) return GS_OK;
+    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": absgrad is on (gs_set_absgrad): only gs_render_backward and "
+                                       "gs_render_backward_adam accumulate the absolute sums");
 }
 
 int refuse_filter3d(gs_ctx* c, const char* who)
@@ -763,6 +787,7 @@ int gs_blend_backward(gs_ctx* c, int N, const float* packed, const float* cot_co
     if (!cot_color || !out_alpha || !last_contrib || (N > 0 && (!packed || !grad_packed)))
         return fail(c, GS_ERR_INVALID_ARG, "gs_blend_backward: null buffer");
     c->fwd.valid = false; c->fwd.bwdPrepared = false;      // as gs_blend_forward
+    c->absgradN = -1;                                       // (the accumulator's rows are rewritten)
     int rc = launch_pack11_to_12(c, N, packed);
     if (rc) return rc;
     if ((rc = launch_blend_backward(c, N, cot_color, cot_depth, cot_alpha, out_alpha, last_contrib))) return rc;
@@ -887,6 +912,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     }
     if (c->fwd.cutsActive) GS_HIP_CHECK(c, hipEventRecord(c->fwdDone, c->stream));
     c->fwd.valid = true;
+    c->absgradN = -1;                   // (the next loss or backward clears the rows gs_get_absgrad would read)
     c->fwd.blendBackwardDone = false;
     c->fwd.consumed = false;
     c->fwd.blockWork = c->blockWork;
@@ -900,6 +926,29 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.antialias = c->antialias;
     c->fwd.filter3d = c->filter3d;
     return GS_OK;
+}
+
+int gs_set_absgrad(gs_ctx* c, int enable)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_absgrad: enable is 0 or 1");
+    if (enable && !c->fast16)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_set_absgrad: this context's tile size is served by the generic blend kernels, which "
+                                           "have no absolute sums");
+    if ((enable == 1) != c->absgrad) c->absgradN = -1;
+    c->absgrad = enable == 1;
+    return GS_OK;
+}
+
+int gs_get_absgrad(gs_ctx* c, int N, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!c->absgrad || c->absgradN < 0)
+        return fail(c, GS_ERR_NO_FORWARD, "gs_get_absgrad: no gs_render_backward / gs_render_backward_adam with absgrad on since "
+                                          "gs_set_absgrad (or another forward or backward has run since)");
+    if (N != c->absgradN) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_get_absgrad: N differs from the backward's N");
+    if (N > 0 && !out) return fail(c, GS_ERR_INVALID_ARG, "gs_get_absgrad: null buffer");
+    return launch_absgrad_copy(c, N, out);
 }
 
 int gs_set_antialiasing(gs_ctx* c, int enable)
@@ -1158,7 +1207,8 @@ int gs_render_backward(gs_ctx* c, const float* cot_color, const float* cot_depth
     if (N > 0 && (!grad_xyz || !grad_features_dc || (K > 1 && !grad_features_rest) || !grad_scales || !grad_rotation ||
                   !grad_opacity))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward: null gradient buffer");
-    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
+    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha, c->absgrad, nullptr)) return rc;
+    AbsgradScope noNorm(c);
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_projection_fused_backward(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
                                             c->fwd.opacity, c->fwd.cam, grad_xyz, grad_features_dc, grad_features_rest,
@@ -1192,8 +1242,9 @@ int gs_render_backward_adam(gs_ctx* c, const float* cot_color, const float* cot_
     if (!cot_color || !lr || n_arena < 0 || (N > 0 && (!params_base || !m_base || !v_base)))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_adam: null buffer");
     if (const int rc = forward_in_arena(c, "gs_render_backward_adam", params_base, n_arena)) return rc;
-    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
+    if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha, c->absgrad, c->adamGate)) return rc;
     c->fwd.consumed = true;     // the parameters the forward saw are gone after this call
+    AbsgradScope noNorm(c);
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_projection_fused_backward_adam(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
                                                  c->fwd.opacity, c->fwd.cam, params_base, m_base, v_base, lr, beta1, beta2,
@@ -1206,6 +1257,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_begin")) return rc;
+    if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_begin")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && !color_cot)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: null buffer");
@@ -1255,6 +1307,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_geom")) return rc;
+    if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_geom")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && (!color_cot || !grad_xyz || !grad_scales || !grad_rotation || !grad_opacity || !xyz_own)))

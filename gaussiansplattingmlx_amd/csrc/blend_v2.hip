@@ -1103,9 +1103,14 @@ struct PairState {
 //   c_i = (K - R_i) / T_{i+1},   since  cot . (C_final - C_i) = sum_{j>i} T_j a_j S_j,
 // so   dL/d(alpha_i) = sc T_i (S_i - c_i) = Ts_i S_i - Q_i / (1 - alpha_i),   Q_i = Q_{i-1} - sc T_i a_i S_i:
 // the sweep needs neither T nor R themselves, and one reciprocal of 1 - alpha (>= 0.01) per pixel.
-template <bool DEPTH>
-__device__ __forceinline__ void pair_bwd(const RecB& s, uint32_t i, const PairB& e, PairState& p, f2 (&acc)[10])
+// ABSGRAD (gs_set_absgrad): two more sums, of the ABSOLUTE per-pixel terms of the mean gradient,
+//   10 sum |h u|   11 sum |h v|,   u = A dx + (B/2) dy,  v = Dq dy + (B/2) dx   (the conic as the record holds it, times C;
+// 1/|C| at the flush).  |h u| = |h| |u|: both abs are source modifiers of one v_fma_f32 per pixel, which the packed forms
+// do not have -- ten scalar VALU per pixel pair and call (two products, four fma for u and v, four for the sums), B/2 once.
+template <bool DEPTH, bool ABSGRAD, int NACC>
+__device__ __forceinline__ void pair_bwd(const RecB& s, uint32_t i, const PairB& e, PairState& p, f2 (&acc)[NACC])
 {
+    static_assert(NACC == (ABSGRAD ? 12 : 10), "ten sums, twelve with the absolute ones");
     const f2 G = (f2){__builtin_amdgcn_exp2f(e.e2.x), __builtin_amdgcn_exp2f(e.e2.y)};
     const f2 raw = splat2(s.op) * G;
     const bool a0 = i < p.nc0, a1 = i < p.nc1;
@@ -1134,13 +1139,26 @@ __device__ __forceinline__ void pair_bwd(const RecB& s, uint32_t i, const PairB&
     acc[7] = fma2(contrib, p.cCy, acc[7]);
     acc[8] = fma2(contrib, p.cCz, acc[8]);
     if (DEPTH) acc[9] = fma2(contrib, p.cD, acc[9]);
+    if constexpr (ABSGRAD) {
+        const float hB = 0.5f * s.B;
+        const float tx = hB * e.dy, ty = s.Dq * e.dy;
+        const float u0 = fmaf(e.dx.x, s.A, tx), u1 = fmaf(e.dx.y, s.A, tx);
+        const float v0 = fmaf(e.dx.x, hB, ty), v1 = fmaf(e.dx.y, hB, ty);
+        acc[10].x = fmaf(fabsf(hh.x), fabsf(u0), acc[10].x);
+        acc[10].y = fmaf(fabsf(hh.y), fabsf(u1), acc[10].y);
+        acc[11].x = fmaf(fabsf(hh.x), fabsf(v0), acc[11].x);
+        acc[11].y = fmaf(fabsf(hh.y), fabsf(v1), acc[11].y);
+    }
     p.Ts = p.Ts * oma;
 }
 
 // 10 sums per splat: dmx dmy dc00 dc01(=dc10) dc11 dop dr dg db ddepth; flushed into the reference's packed
 // row order (dmx dmy dc00 dc01 dc10 dc11 dr dg db dop ddepth) of gradAcc16
 // DEPTH = false: no depth cotangent (the default training case): nine sums per splat
-template <int SEG, bool DEPTH>
+// ABSGRAD: the two absolute sums of pair_bwd on top, reduced by wave_sum12_transposed into slots 12 and 14 of the splat's row
+// and flushed, times 1/|C|, into columns 12 and 13 of its gradAcc16 row (Ax, Ay in pixel units; bwd_items_kernel clears whole
+// rows, no kernel of the backward reads the row's fourth quarter)
+template <int SEG, bool DEPTH, bool ABSGRAD>
 __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
     int W, int H, int tileW, int tileH, int gridW, int blocksX, int whiteBg, const float4* __restrict__ rec12,
     const uint32_t* __restrict__ sortedIdx, uint32_t idxMask, const uint32_t* __restrict__ tileRanges,
@@ -1296,15 +1314,18 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
             const bool k0 = (tag & 256u) != 0, k1 = (tag & 512u) != 0;     // wave-uniform: half out of reach
             if (!k0) pair_exponent_bwd(s, ps[0].px, ps[0].py, e0);
             if (!k1) pair_exponent_bwd(s, ps[1].px, ps[1].py, e1);
-            f2 acc2[10];
+            constexpr int NACC = ABSGRAD ? 12 : 10;
+            f2 acc2[NACC];
 #pragma unroll
-            for (int q = 0; q < 10; q++) acc2[q] = splat2(0.0f);
-            if (!k0) pair_bwd<DEPTH>(s, i, e0, ps[0], acc2);
-            if (!k1) pair_bwd<DEPTH>(s, i, e1, ps[1], acc2);
-            float acc[10];
+            for (int q = 0; q < NACC; q++) acc2[q] = splat2(0.0f);
+            if (!k0) pair_bwd<DEPTH, ABSGRAD, NACC>(s, i, e0, ps[0], acc2);
+            if (!k1) pair_bwd<DEPTH, ABSGRAD, NACC>(s, i, e1, ps[1], acc2);
+            float acc[NACC];
 #pragma unroll
-            for (int q = 0; q < 10; q++) acc[q] = acc2[q].x + acc2[q].y;
-            float w = wave_sum10_transposed<!DEPTH>(acc);
+            for (int q = 0; q < NACC; q++) acc[q] = acc2[q].x + acc2[q].y;
+            float w;
+            if constexpr (ABSGRAD) w = wave_sum12_transposed<!DEPTH>(acc);     // slots 12 (sum |h u|) and 14 (sum |h v|) on top
+            else w = wave_sum10_transposed<!DEPTH>(acc);
             // slot 4 r + q of the splat's row: 0 a1 (sum h dx), 2 a2 (sum h dy), 1 dc00, 3 dc01, 8 dc11, 10 dop, 9 dr,
             // 11 dg, 4 db, 6 ddepth; idle quads park the conic terms the flush needs for the mean gradient:
             // 5 c00, 7 c11, 13 c01 + c10
@@ -1316,11 +1337,14 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the LDS writes have landed (single wave)
         __builtin_amdgcn_wave_barrier();
-        for (uint32_t e = lane; e < n * 11; e += 64) {
-            const uint32_t j = e / 11, q = e - j * 11;
+        constexpr uint32_t NCOL = ABSGRAD ? 13u : 11u;
+        for (uint32_t e = lane; e < n * NCOL; e += 64) {
+            const uint32_t j = e / NCOL, q = e - j * NCOL;
             // packed column q (dmx dmy dc00 dc01 dc10 dc11 dr dg db dop ddepth) <- slot
             float v;
-            if (q < 2) {
+            if (ABSGRAD && q >= 11) {
+                v = part[j][q == 11 ? 12 : 14] * -EXP_INV_C1;                     // Ax, Ay: columns 12 and 13 (11 is left alone)
+            } else if (q < 2) {
                 // d mean = -(2 c00 A1 + (c01 + c10) A2,  2 c11 A2 + (c01 + c10) A1),  A = -1/2 of the stored sums
                 const float a1 = -0.5f * part[j][0], a2 = -0.5f * part[j][2], cs = part[j][13];
                 v = q == 0 ? -(2.0f * part[j][5] * a1 + cs * a2) : -(2.0f * part[j][7] * a2 + cs * a1);
@@ -1329,7 +1353,7 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
                 v = (DEPTH || q != 10) ? part[j][src] : 0.0f;
                 if (q < 6) v *= -0.5f;                                            // the four conic columns
             }
-            if (v != 0.0f) atomicAdd(&gradAcc16[(size_t)(idx[i0 + j] & idxMask) * 16 + q], v);
+            if (v != 0.0f) atomicAdd(&gradAcc16[(size_t)(idx[i0 + j] & idxMask) * 16 + (ABSGRAD && q >= 11 ? q + 1 : q)], v);
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
@@ -1479,7 +1503,7 @@ int blend_backward_v2_grid(const gs_ctx* c)
 }
 
 int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
-                             const float* outColor, const float* outDepth, const float* outAlpha)
+                             const float* outColor, const float* outDepth, const float* outAlpha, bool absgrad)
 {
     const int blocksX = c->blocksX, nBlocks = c->numPixBlocks;
     const int grid = blend_backward_v2_grid(c);
@@ -1494,7 +1518,8 @@ int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const floa
         const int clearBlocks = (int)((prep.clearCount + 8191) / 8192 < 1024 ? (prep.clearCount + 8191) / 8192 : 1024);
         hipLaunchKernelGGL(bwd_items_kernel<SEGLEN>, dim3(GS_ITEM_PARTS + cutBlocks + clearBlocks), dim3(1024), 0, c->stream, prep, cutBlocks);
     }
-    auto kern = cotDepth ? blend_bwd_v2_kernel<SEGLEN, true> : blend_bwd_v2_kernel<SEGLEN, false>;
+    auto kern = absgrad ? (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, true> : blend_bwd_v2_kernel<SEGLEN, false, true>)
+                        : (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, false> : blend_bwd_v2_kernel<SEGLEN, false, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, c->stream, c->W, c->H, c->tileW, c->tileH,
                        c->gridW, blocksX, c->whiteBg, reinterpret_cast<const float4*>(c->packed12), c->sortedRaw,
                        c->idxMask, c->tileRanges, c->itemRow, reinterpret_cast<const uint4*>(c->segSlot), c->fwd.qslotCap, c->fwd.statePlanes, c->fwd.blockWork, c->itemBlock, c->counters, c->bwdQueue, (uint32_t)c->bwdQueues, cotColor,

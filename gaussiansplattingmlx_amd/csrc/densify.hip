@@ -24,6 +24,28 @@ __global__ __launch_bounds__(DN_THREADS) void accum_grad_norm_kernel(int N, cons
     accumOut[i] = (accumIn ? accumIn[i] : 0.0f) + norm;
 }
 
+// AbsGS densification (gs_set_absgrad): the statistic of accum_grad_norm from the absolute 2-D sums the
+// blend backward left in columns 12 and 13 of the Gaussian's gradAcc16 row, in gsplat's and Inria's NDC scaling.  gate: the
+// overflow word proj_bwd_fused_body tests (null: the backward without the fused Adam, which tests none) -- a step whose
+// forward overflowed its reserved pairs adds nothing.
+__global__ __launch_bounds__(DN_THREADS) void absgrad_accum_kernel(int N, const float* __restrict__ gradAcc16, float halfW,
+                                                                   float halfH, const uint32_t* __restrict__ gate, float* accum)
+{
+    const int i = blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= N) return;
+    if (gate && *gate) return;
+    const float2 a = *reinterpret_cast<const float2*>(gradAcc16 + (size_t)i * 16 + 12);
+    accum[i] += hypotf(halfW * a.x, halfH * a.y);     // (not sqrtf(x x + y y): sums below 1e-19 would square to zero)
+}
+
+// gs_get_absgrad: (Ax, Ay) out of the rows
+__global__ __launch_bounds__(DN_THREADS) void absgrad_copy_kernel(int N, const float* __restrict__ gradAcc16, float2* __restrict__ out)
+{
+    const int i = blockIdx.x * DN_THREADS + threadIdx.x;
+    if (i >= N) return;
+    out[i] = *reinterpret_cast<const float2*>(gradAcc16 + (size_t)i * 16 + 12);
+}
+
 // classify_gaussians, GaussianTrainer.swift:343-393
 __global__ __launch_bounds__(DN_THREADS) void classify_kernel(int N, const float* __restrict__ gradAccum, float denom,
                                                               const float* __restrict__ scales, int scaleStride,
@@ -371,6 +393,24 @@ int launch_accum_grad_norm(gs_ctx* c, int N, const float* xyzGrad, const float* 
     if (N == 0) return GS_OK;
     hipLaunchKernelGGL(accum_grad_norm_kernel, dim3(gs_div_up(N, DN_THREADS)), dim3(DN_THREADS), 0, c->stream, N,
                        xyzGrad, accumIn, accumOut);
+    GS_HIP_CHECK(c, hipGetLastError());
+    return GS_OK;
+}
+
+int launch_absgrad_accum(gs_ctx* c, int N, const uint32_t* gate, float* accum)
+{
+    if (N == 0) return GS_OK;
+    hipLaunchKernelGGL(absgrad_accum_kernel, dim3(gs_div_up(N, DN_THREADS)), dim3(DN_THREADS), 0, c->stream, N, c->gradAcc16,
+                       0.5f * (float)c->W, 0.5f * (float)c->H, gate, accum);
+    GS_HIP_CHECK(c, hipGetLastError());
+    return GS_OK;
+}
+
+int launch_absgrad_copy(gs_ctx* c, int N, float* out)
+{
+    if (N == 0) return GS_OK;
+    hipLaunchKernelGGL(absgrad_copy_kernel, dim3(gs_div_up(N, DN_THREADS)), dim3(DN_THREADS), 0, c->stream, N, c->gradAcc16,
+                       reinterpret_cast<float2*>(out));
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }

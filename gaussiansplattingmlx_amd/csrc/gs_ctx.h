@@ -216,6 +216,8 @@ struct gs_ctx {
     float* bgPartials = nullptr;
     long long bgPartialsCap = 0;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
+    bool absgrad = false;                // gs_set_absgrad: the fused backward also sums |g_x|, |g_y| per Gaussian
+    int absgradN = -1;                   // N of the last backward that left (Ax, Ay) in gradAcc16's columns 12, 13; -1: none to read
     // 3-D smoothing filter (gs_set_filter3d): the caller-owned device widths [>= N] of the following forwards, nullptr = off; the
     // training cameras' table for gs_compute_filter3d (GS_F3D_CAM_FLOATS floats per camera) and the max word of its never-seen
     // rule, both allocated or grown by gs_set_filter3d_cameras only
@@ -395,6 +397,7 @@ namespace gs {
 // api.hip: refusals that api.hip and dp.hip share (host code; `who` is the entry point's name, in front of the message)
 int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_ARG while a pose correction is bound
 int refuse_filter3d(gs_ctx* c, const char* who);             // GS_ERR_INVALID_ARG while a 3-D filter is set (or the forward ran with one)
+int refuse_absgrad(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while absgrad is on (gs_set_absgrad)
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
 CamParams make_cam(const gs_camera* cam, int W, int H);
@@ -480,7 +483,7 @@ int launch_contrib_actions(gs_ctx* c, int N, const float* score, float threshold
 // blend_v2.hip (fused fast path)
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha);
 int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
-                             const float* outColor, const float* outDepth, const float* outAlpha);
+                             const float* outColor, const float* outDepth, const float* outAlpha, bool absgrad = false);
 int blend_backward_v2_grid(const gs_ctx* c);
 int blend_forward_v2_grid(const gs_ctx* c);
 bool blend_forward_v2_pair_decide(const gs_ctx* c);
@@ -499,6 +502,10 @@ int launch_loss(gs_ctx* c, const float* render, const float* target, const float
 // optim.hip
 // densify.hip
 int launch_accum_grad_norm(gs_ctx* c, int N, const float* xyzGrad, const float* accumIn, float* accumOut);
+// AbsGS (gs_set_absgrad): accum += hypot(W/2 Ax, H/2 Ay) from the rows the blend backward left (gate: null or the overflow
+// word), and (Ax, Ay) copied out
+int launch_absgrad_accum(gs_ctx* c, int N, const uint32_t* gate, float* accum);
+int launch_absgrad_copy(gs_ctx* c, int N, float* out);
 int launch_classify(gs_ctx* c, int N, const float* gradAccum, float denom, const float* scales, int scaleStride,
                     const float* opacity, float gradThreshold, float maxScale, float minOpacity, int allowDensify,
                     int* actions, int* outputCounts);

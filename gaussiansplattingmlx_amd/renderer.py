@@ -109,6 +109,7 @@ class GaussianRenderer:
         self._target_cache = OrderedDict()
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
         self._antialiased = False
+        self._absgrad = False
         self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
         self._bilateral = (None, None)  # setBilateralGrid's, likewise
         if antialiased:
@@ -619,6 +620,24 @@ class GaussianRenderer:
     @antialiased.setter
     def antialiased(self, enable: bool):
         self.setAntialiased(enable)
+
+    # -- AbsGS densification statistic (include/gsplat.h gs_set_absgrad; absgrad.py restates it) --------
+    def setAbsgrad(self, enable: bool = True):
+        """gs_set_absgrad: the following renderBackward / fused train steps also sum, per Gaussian, the per-pixel absolute values
+        of the 2-D mean gradient (absgrad()), and a grad-norm accumulator gets hypot(W/2 Ax, H/2 Ay) in place of |grad xyz|.
+        Single-device steps; refused on a renderer whose tile size is served by the generic blend kernels.  Off (the
+        default): no kernel, buffer or result differs."""
+        self._check(self.lib.gs_set_absgrad(self.ctx, 1 if enable else 0))
+        self._absgrad = bool(enable)
+
+    def absgrad(self):
+        """gs_get_absgrad: (Ax, Ay) [N, 2] of the last backward, in pixel units; valid until the next forward or backward."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "absgrad: no renderForward on this renderer")
+        N = int(self._fused["params"]["xyz"].shape[0])
+        out = self._empty(N, 2)
+        self._check(self.lib.gs_get_absgrad(self.ctx, N, _p(out)))
+        return out
 
     # -- the 3-D smoothing filter (include/gsplat.h gs_set_filter3d, DESIGN.md section 14; filter3d.py restates it in float64) ---
     def setFilterCameras(self, cameras):

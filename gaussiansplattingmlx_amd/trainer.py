@@ -453,7 +453,8 @@ class GaussianTrainer:
                  pose_lr=(1e-4, 1e-4), n_views: int | None = None, strategy: str = "reference", mcmc=None,
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
-                 filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None):
+                 filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
+                 absgrad=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -527,7 +528,18 @@ class GaussianTrainer:
         event that would prune everything prunes nothing.  lastContribPruneStats holds the last event's N, kept, pruned and
         threshold; pruneByContribution(cameras, threshold, score) runs the same event on demand (compaction before a snapshot).
         Single-device steps and the reference strategy only; composes with pose_opt, exposure_opt, bilateral_grid, filter_3d, an
-        anti-aliased renderer and densify on or off.  Off (the default): no kernel, buffer or result differs."""
+        anti-aliased renderer and densify on or off.  Off (the default): no kernel, buffer or result differs.
+
+        absgrad: AbsGS densification (absgrad.AbsGradConfig, include/gsplat.h gs_set_absgrad; Ye et al.
+        2024, gsplat's absgrad=True).  The trainer turns the renderer's absgrad setting on: every step's blend backward also sums,
+        per Gaussian, the per-pixel absolute values of the 2-D mean gradient, and xyzGradAccumulation gets hypot(W/2 Ax, H/2 Ay)
+        in place of |grad xyz| -- a large Gaussian over fine detail, whose per-pixel gradients cancel in the signed sum, is then
+        split.  gradientThreshold becomes absgrad.threshold; the global step denominator, classifyGaussians and the event code
+        stay as they are: only what is summed changes.  The default threshold, 0.0008, is gsplat's documented value for absgrad,
+        where the sum is divided by a per-Gaussian visibility count; this trainer keeps the reference's global step count, and
+        nobody has tuned the value here.  Single-device steps and the reference strategy with densify on only; composes with
+        pose_opt, exposure_opt, bilateral_grid, filter_3d, contrib_prune, an anti-aliased renderer and referenceParamReload.
+        Off (the default): no kernel, buffer or result differs."""
         if strategy not in ("reference", "mcmc"):
             raise ValueError(f"unknown strategy {strategy!r} (\"reference\" or \"mcmc\")")
         self.strategy = strategy
@@ -542,6 +554,18 @@ class GaussianTrainer:
                 raise ValueError("contrib_prune: the reference strategy only (not with strategy='mcmc')")
             _require_single_device("contrib_prune", views_per_rank, process_group, dp_bootstrap, exchange_impl)
             self.contribPrune = contrib_prune
+        self.absgrad = None
+        if absgrad is not None:
+            from .absgrad import AbsGradConfig
+            if not isinstance(absgrad, AbsGradConfig):
+                raise ValueError("absgrad must be an AbsGradConfig")
+            absgrad.validate()
+            if strategy == "mcmc":
+                raise ValueError("absgrad: the reference strategy only (not with strategy='mcmc')")
+            if not densify:
+                raise ValueError("absgrad changes the densification criterion: not with densify=False")
+            _require_single_device("absgrad", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            self.absgrad = absgrad
         self.mcmc = None
         self.lastMCMCStats = None
         if strategy == "mcmc":
@@ -633,6 +657,8 @@ class GaussianTrainer:
         self.iteration = 0
         # densification (GaussianTrainer.swift:293-300, 304)
         self.gradientThreshold, self.minOpacity, self.maxScale = 0.0002, 0.005, 0.01
+        if self.absgrad is not None:
+            self.gradientThreshold = float(self.absgrad.threshold)
         self.densifyFromIter, self.densifyUntilIter, self.maxGaussians = 500, 15000, 1_000_000
         self.split_and_prune_per_iteration = 100
         self.densify = densify
@@ -1524,6 +1550,8 @@ class GaussianTrainer:
                 r.setGradNormAccum(self.xyzGradAccumulation)      # the backward below adds this view's |grad xyz|
         elif getattr(r, "_grad_norm_accum", None) is not None:
             r.setGradNormAccum(None)
+        if self.absgrad is not None and not getattr(r, "_absgrad", False):
+            r.setAbsgrad(True)          # the backward below adds hypot(W/2 Ax, H/2 Ay) instead (absgrad.py)
 
     def _forwardAndLoss(self, camera, targetRGB, viewKey, lossOut):
         """lossFn of one view (GaussianTrainer.swift:627-723): forward, L1 + DSSIM loss -> lossOut[4] and the colour cotangent

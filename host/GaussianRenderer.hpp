@@ -131,6 +131,11 @@ public:
     void setFilterCameras(int V, const gs_camera* cams) { check(gs_set_filter3d_cameras(ctx_, V, cams)); }
     void computeFilter3D(int N, const float* xyz, float* filter) { check(gs_compute_filter3d(ctx_, N, xyz, filter)); }
     void setFilter3D(const float* filter) { check(gs_set_filter3d(ctx_, filter)); }
+    // AbsGS densification statistic (include/gsplat.h gs_set_absgrad): while on, the fused backward also sums the per-pixel
+    // absolute values of the 2-D mean gradient per Gaussian -- absgrad(N, out): (Ax, Ay) DEVICE [N,2] of the last backward -- and
+    // the grad-norm accumulator gets hypot(W/2 Ax, H/2 Ay) in place of |grad xyz|.  Single-device steps.
+    void setAbsgrad(bool enable) { check(gs_set_absgrad(ctx_, enable ? 1 : 0)); }
+    void absgrad(int N, float* out) { check(gs_get_absgrad(ctx_, N, out)); }
     void bakeFilter3D(int N, const float* scales, const float* opacity, const float* filter, float* outScales, float* outOpacity)
     {
         check(gs_filter3d_bake(ctx_, N, scales, opacity, filter, outScales, outOpacity));

@@ -351,6 +351,30 @@ int gs_apply_bilateral_grid(gs_ctx* ctx, int W, int H, const float* grid /*DEVIC
  * record it: render a model in the mode it was trained in. */
 int gs_set_antialiasing(gs_ctx* ctx, int enable);
 
+/* AbsGS densification statistic (not in the reference; Ye et al. 2024, gsplat's absgrad=True).  The
+ * gradient of the loss with respect to a splat's 2-D mean is a sum over the pixels it covers; on a large splat over fine detail
+ * the pixels pull in opposite directions and the sum cancels ("gradient collision").  With absgrad on, the blend backward of
+ * gs_render_backward and gs_render_backward_adam also sums the per-pixel ABSOLUTE values, per Gaussian and in pixel units:
+ *   Ax = sum over pixels |g_x|,   g_x = h (c00 dx + 1/2 (c01 + c10) dy),
+ *   Ay = sum over pixels |g_y|,   g_y = h (c11 dy + 1/2 (c01 + c10) dx),
+ * d = pixel - mean, c the conic, h = dL/d(alpha) raw, 0 for an entry at or past the pixel's stop and for raw > 0.99 (the signed
+ * sums of the same terms are the mean's gradient the backward has always produced).  While a grad-norm accumulator is set
+ * (gs_set_grad_norm_accum) such a backward adds
+ *   accum[p] += hypot(W/2 Ax, H/2 Ay)
+ * (gsplat's and Inria's NDC scaling of the screen-space gradient) in place of |grad xyz|; a step whose forward overflowed its
+ * reserved pairs adds nothing, as before.  Every gradient, render and parameter update is what it is with absgrad off.
+ * enable: 0 (the default: no kernel, buffer or result differs) or 1; any other value returns GS_ERR_INVALID_ARG.  A
+ * per-context setting as gs_set_antialiasing is.  GS_ERR_INVALID_ARG with enable = 1 on a context whose tile size is served by
+ * the generic blend kernels (not a multiple of 16 and block lists off).  Composes with the anti-aliased mode, the 3-D filter,
+ * pose refinement, depth cuts, view hints and block lists.  Single-device steps only: while it is on, gs_render_backward_dp*
+ * and gs_dp_step return GS_ERR_INVALID_ARG.  The op-level gs_blend_backward ignores it. */
+int gs_set_absgrad(gs_ctx* ctx, int enable);
+/* (Ax, Ay) of the last gs_render_backward / gs_render_backward_adam, as defined above, 0 for a Gaussian in no list.  Valid
+ * until the next forward or backward on the context.  GS_ERR_NO_FORWARD if no backward has run with absgrad on since it was
+ * enabled (or a forward has run since); GS_ERR_SIZE_MISMATCH if N is not that backward's N.  Asynchronous on the context's
+ * stream, no allocation. */
+int gs_get_absgrad(gs_ctx* ctx, int N, float* out /* DEVICE [N,2] */);
+
 /* 3-D smoothing filter (not in the reference; DESIGN.md "3-D smoothing filter"): Mip-Splatting's other filter.  The anti-aliased
  * mode above fixes a model viewed from further away than it was trained; this one fixes the other direction: a Gaussian may
  * not be narrower than the sampling interval of the closest training camera that saw it, or the model shows needle and
