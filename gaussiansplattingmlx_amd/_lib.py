@@ -144,6 +144,9 @@ _SIGS = {
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
     "gs_set_absgrad": (C.c_int, [_vp, C.c_int]),
     "gs_get_absgrad": (C.c_int, [_vp, C.c_int, _vp]),
+    "gs_set_sparse_adam": (C.c_int, [_vp, C.c_int]),
+    "gs_get_visibility": (C.c_int, [_vp, C.c_int, _vp]),
+    "gs_adam_step_visible": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4 + [C.c_int, _vp, _vp, _vp] + [C.c_float] * 4 + [C.c_int, _vp]),
     "gs_set_filter3d_cameras": (C.c_int, [_vp, C.c_int, _vp]),
     "gs_compute_filter3d": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gs_set_filter3d": (C.c_int, [_vp, _vp]),

@@ -382,6 +382,13 @@ int refuse_absgrad(gs_ctx* c, const char* who)
                                        "gs_render_backward_adam accumulate the absolute sums");
 }
 
+int refuse_sparse_adam(gs_ctx* c, const char* who)
+{
+    if (!c->sparseAdam) return GS_OK;
+    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": sparse Adam is on (gs_set_sparse_adam): single-device steps through "
+                                       "gs_render_backward_adam or gs_adam_step_visible only");
+}
+
 int refuse_filter3d(gs_ctx* c, const char* who)
 {
     if (!c->filter3d && !(c->fwd.valid && c->fwd.filter3d)) return GS_OK;
@@ -528,6 +535,7 @@ int gs_ctx_destroy(gs_ctx* c)
     dev_free(c->densifyPlan);
     dev_free(c->poseCam); dev_free(c->posePartials);
     dev_free(c->f3dCams); dev_free(c->f3dMax);
+    dev_free(c->visMask); dev_free(c->visRadii);
     dev_free(c->correctedImage); dev_free(c->expoPartials); dev_free(c->bgPartials);
     dev_free(c->densifyTable);
     mcmc_free(c);
@@ -866,6 +874,22 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     if (N > 0 && (!xyz || !features_dc || (K > 1 && !features_rest) || !scales || !rotation || !opacity))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: null parameter tensor");
     c->fwd.valid = false;
+    c->visN = -1;
+    if (c->sparseAdam && N > c->visCap) {       // sparse Adam's mask and radii: grown by the first forward that needs more rows
+        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+        if (c->visMask) c->ws_bytes -= (size_t)c->visCap * (sizeof(unsigned char) + sizeof(float));
+        dev_free(c->visMask); dev_free(c->visRadii);
+        c->visCap = 0;
+        const int cap = N > c->capN ? N : c->capN;
+        if (const int arc = dev_alloc(c, &c->visMask, (size_t)cap)) return arc;
+        if (const int arc = dev_alloc(c, &c->visRadii, (size_t)cap)) {      // (both or neither: visCap describes the pair)
+            c->ws_bytes -= (size_t)cap * sizeof(unsigned char);
+            dev_free(c->visMask);
+            return arc;
+        }
+        c->visCap = cap;
+    }
+    if (c->sparseAdam && !radii) radii = c->visRadii;      // (the mask is taken from the radii the projection writes)
     c->binIsBlockLists = c->virt.nbx != 0;
     const bool reserved = c->pairsReserved && c->capN >= N;
     if (reserved) { const int orc = deferred_overflow(c); if (orc) return orc; }
@@ -925,6 +949,31 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.poseGrad = c->poseGrad;
     c->fwd.antialias = c->antialias;
     c->fwd.filter3d = c->filter3d;
+    if (c->sparseAdam) c->visN = N;
+    return GS_OK;
+}
+
+// ---- sparse Adam (include/gsplat.h gs_set_sparse_adam; projection.hip proj_bwd_fused_*sparse_kernel, optim.hip) -------------
+int gs_set_sparse_adam(gs_ctx* c, int enable)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: enable is 0 or 1");
+    if (enable && c->mcmcOn)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: the MCMC strategy is set (its noise and regularisers act on every Gaussian)");
+    if (enable && c->filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: a 3-D filter is set (gs_set_filter3d)");
+    // (the mask of the last forward made under the setting stays readable when the setting goes off: every forward drops it first)
+    c->sparseAdam = enable == 1;
+    return GS_OK;
+}
+
+int gs_get_visibility(gs_ctx* c, int N, unsigned char* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (c->visN < 0)
+        return fail(c, GS_ERR_NO_FORWARD, "gs_get_visibility: the last gs_render_forward was not made with sparse Adam on (gs_set_sparse_adam)");
+    if (N != c->visN) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_get_visibility: N differs from the forward's N");
+    if (N > 0 && !out) return fail(c, GS_ERR_INVALID_ARG, "gs_get_visibility: null buffer");
+    if (N > 0) GS_HIP_CHECK(c, hipMemcpyAsync(out, c->visMask, (size_t)N, hipMemcpyDeviceToDevice, c->stream));
     return GS_OK;
 }
 
@@ -1009,6 +1058,7 @@ int gs_set_filter3d(gs_ctx* c, const float* filter)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (filter && c->mcmcOn) return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d: the MCMC strategy is set (the reference strategy only)");
+    if (filter) { if (const int rc = refuse_sparse_adam(c, "gs_set_filter3d")) return rc; }
     c->filter3d = filter;
     return GS_OK;
 }
@@ -1043,6 +1093,7 @@ int gs_set_mcmc(gs_ctx* c, const gs_mcmc_params* params)
     if (!c) return GS_ERR_INVALID_ARG;
     if (!params) { c->mcmcOn = false; return GS_OK; }
     if (c->filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_mcmc: a 3-D filter is set (gs_set_filter3d: the reference strategy only)");
+    if (const int rc = refuse_sparse_adam(c, "gs_set_mcmc")) return rc;
     if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
     c->mcmc = *params;
     c->mcmcOn = true;
@@ -1242,6 +1293,9 @@ int gs_render_backward_adam(gs_ctx* c, const float* cot_color, const float* cot_
     if (!cot_color || !lr || n_arena < 0 || (N > 0 && (!params_base || !m_base || !v_base)))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_adam: null buffer");
     if (const int rc = forward_in_arena(c, "gs_render_backward_adam", params_base, n_arena)) return rc;
+    if (c->sparseAdam && (c->visN != N || c->fwd.filter3d))
+        return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_adam: sparse Adam is on, but the forward was not made under it "
+                                          "(gs_set_sparse_adam comes before gs_render_forward)");
     if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha, c->absgrad, c->adamGate)) return rc;
     c->fwd.consumed = true;     // the parameters the forward saw are gone after this call
     AbsgradScope noNorm(c);
@@ -1257,6 +1311,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_begin")) return rc;
+    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_begin")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
@@ -1272,6 +1327,7 @@ int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales,
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish")) return rc;
+    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_finish")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N, K = c->fwd.K;
@@ -1290,6 +1346,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish_geom")) return rc;
+    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish_geom: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N;
@@ -1307,6 +1364,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_geom")) return rc;
+    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_geom")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
@@ -1325,6 +1383,7 @@ int gs_sh_grad_from_views_adam_dir(gs_ctx* c, int N, int K, int R, const float* 
 {
     if (!c) return GS_ERR_INVALID_ARG;
     const char* who = "gs_sh_grad_from_views_adam_dir";
+    if (const int rc = refuse_sparse_adam(c, who)) return rc;
     if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest, n_arena < 0,
                                      !params_base || !m_base || !v_base || !xyz_add))
         return rc;
@@ -1364,6 +1423,7 @@ int gs_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* xyz,
 {
     if (!c) return GS_ERR_INVALID_ARG;
     const char* who = "gs_sh_grad_from_views_adam";
+    if (const int rc = refuse_sparse_adam(c, who)) return rc;
     if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest, n_arena < 0,
                                      !params_base || !m_base || !v_base))
         return rc;
@@ -1627,6 +1687,36 @@ int gs_adam_step(gs_ctx* c, long long n, float* params, const float* grads, floa
     if (prev != n) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_adam_step: segments do not cover the arena");
     { const int orc = deferred_overflow(c); if (orc) return orc; }
     return launch_adam(c, n, params, grads, m, v, nseg, seg_end, seg_lr, beta1, beta2, eps, grad_scale);
+}
+
+int gs_adam_step_visible(gs_ctx* c, long long n, float* params, const float* grads, float* m, float* v, int nseg,
+                         const long long* seg_end, const float* seg_lr, const int* seg_row_floats, float beta1, float beta2,
+                         float eps, float grad_scale, int N, const unsigned char* visible)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n < 0 || nseg < 1 || nseg > 8 || !seg_end || !seg_lr || !seg_row_floats || N < 0)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adam_step_visible: bad segments");
+    if (n > 0 && (!params || !grads || !m || !v)) return fail(c, GS_ERR_INVALID_ARG, "gs_adam_step_visible: null buffer");
+    if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v) & 15)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adam_step_visible: arenas must be 16-byte aligned");
+    long long prev = 0;
+    for (int i = 0; i < nseg; i++) {
+        if (seg_end[i] < prev || seg_end[i] > n) return fail(c, GS_ERR_INVALID_ARG, "gs_adam_step_visible: segments not ascending");
+        if (seg_row_floats[i] < 1) return fail(c, GS_ERR_INVALID_ARG, "gs_adam_step_visible: seg_row_floats are >= 1");
+        prev = seg_end[i];
+    }
+    if (prev != n) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_adam_step_visible: segments do not cover the arena");
+    if (!visible) {
+        if (c->visN < 0)
+            return fail(c, GS_ERR_NO_FORWARD, "gs_adam_step_visible: visible is NULL and the last gs_render_forward was not made with "
+                                              "sparse Adam on (gs_set_sparse_adam)");
+        if (N != c->visN) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_adam_step_visible: N differs from the forward's N");
+        visible = c->visMask;
+    }
+    { const int orc = deferred_overflow(c); if (orc) return orc; }
+    if (N == 0) return GS_OK;      // (no row below N: nothing moves)
+    return launch_adam_visible(c, n, params, grads, m, v, nseg, seg_end, seg_lr, seg_row_floats, beta1, beta2, eps, grad_scale, N,
+                               visible);
 }
 
 int gs_adam_step_add(gs_ctx* c, long long n, float* params, const float* grads, float* m, float* v, int nseg,

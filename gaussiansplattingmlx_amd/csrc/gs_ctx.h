@@ -218,6 +218,14 @@ struct gs_ctx {
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
     bool absgrad = false;                // gs_set_absgrad: the fused backward also sums |g_x|, |g_y| per Gaussian
     int absgradN = -1;                   // N of the last backward that left (Ax, Ay) in gradAcc16's columns 12, 13; -1: none to read
+    // sparse Adam (gs_set_sparse_adam): while on, every fused forward leaves radius > 0 of its N Gaussians
+    // as bytes in visMask (vis_mask_kernel behind the projection, from the radii the projection wrote: the caller's buffer, or
+    // visRadii where the caller takes none); both [visCap], grown by the first forward that needs more, never by a backward
+    bool sparseAdam = false;
+    unsigned char* visMask = nullptr;
+    float* visRadii = nullptr;
+    int visCap = 0;
+    int visN = -1;                       // N of the last fused forward made under the setting (its mask is in visMask); -1: none
     // 3-D smoothing filter (gs_set_filter3d): the caller-owned device widths [>= N] of the following forwards, nullptr = off; the
     // training cameras' table for gs_compute_filter3d (GS_F3D_CAM_FLOATS floats per camera) and the max word of its never-seen
     // rule, both allocated or grown by gs_set_filter3d_cameras only
@@ -398,6 +406,7 @@ namespace gs {
 int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_ARG while a pose correction is bound
 int refuse_filter3d(gs_ctx* c, const char* who);             // GS_ERR_INVALID_ARG while a 3-D filter is set (or the forward ran with one)
 int refuse_absgrad(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while absgrad is on (gs_set_absgrad)
+int refuse_sparse_adam(gs_ctx* c, const char* who);          // GS_ERR_INVALID_ARG while sparse Adam is on (gs_set_sparse_adam)
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
 CamParams make_cam(const gs_camera* cam, int W, int H);
@@ -422,6 +431,7 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
                                           const float* frest, const float* scales, const float* rot,
                                           const float* opacity, const CamParams& cam, const float* pBase, float* mBase,
                                           float* vBase, const float lr[6], float b1, float b2, float eps, float gscale);
+int launch_vis_mask(gs_ctx* c, int N, const float* radii);      // sparse Adam: radii > 0 -> c->visMask
 bool depth_sort_takes_splitters(const gs_ctx* c, int N);      // binning.hip
 int launch_pose_camera(gs_ctx* c, const gs::CamParams& host, const float* delta);   // projection.hip, pose refinement
 int launch_pose_grad(gs_ctx* c, int N);
@@ -557,5 +567,9 @@ int ply_load_file(gs_ctx* c, const char* path, int N, int K, float* xyz, float* 
 int launch_adam(gs_ctx* c, long long n, float* params, const float* grads, float* m, float* v, int nseg,
                 const long long* segEnd, const float* segLr, float b1, float b2, float eps, float gradScale,
                 const float* add = nullptr, long long addN = 0);
+// gs_adam_step_visible: the same update on the rows below N whose mask byte is set (segment s holds rows of rowFloats[s] floats)
+int launch_adam_visible(gs_ctx* c, long long n, float* params, const float* grads, float* m, float* v, int nseg,
+                        const long long* segEnd, const float* segLr, const int* rowFloats, float b1, float b2, float eps,
+                        float gradScale, int N, const unsigned char* visible);
 
 }  // namespace gs

@@ -308,8 +308,12 @@ __device__ __forceinline__ void adam_step(const AdamFuse& A, float g, float lr, 
 // against p, m, v, four consecutive elements per lane, the loads of a whole batch in flight before the first update
 // (nothing may wait on a store).  16-B accesses need 16-B aligned addresses: scalar head up to the first aligned
 // element, float4 body, scalar tail.
+// SPARSE (sparse Adam, gs_set_sparse_adam): bit r of visBits = row r of the wave is visible.  Only the elements of visible rows
+// move; a float4 none of whose rows is visible is neither loaded nor stored, one that straddles a visible and an invisible
+// row (L % 4 != 0) is loaded and written back whole with the invisible row's elements as they came.
+template <bool SPARSE = false>
 __device__ __forceinline__ void adam_rows(const AdamFuse& adam, const float* frest, int row0, int rows, int L,
-                                          const float* myRows, int lane, float lr)
+                                          const float* myRows, int lane, float lr, unsigned long long visBits = ~0ull)
 {
     const size_t off0 = (size_t)(frest - adam.pBase) + (size_t)row0 * L;
     float* P = const_cast<float*>(adam.pBase) + off0;
@@ -317,18 +321,39 @@ __device__ __forceinline__ void adam_rows(const AdamFuse& adam, const float* fre
     float* V = adam.vBase + off0;
     const int total = rows * L;
     auto grad_at = [&](int e) { const int r = e / L; return myRows[r * (L + 1) + (e - r * L)]; };
+    auto vis_at = [&](int e) { return ((visBits >> (e / L)) & 1ull) != 0ull; };      // (SPARSE only)
     const int head = min(total, (int)((4 - (off0 & 3)) & 3));
     const int n4 = (total - head) >> 2;
     const int tail0 = head + 4 * n4;
     if (lane < head + (total - tail0)) {
         const int e = lane < head ? lane : tail0 + (lane - head);
-        float pv = P[e], mv = M[e], vv = V[e];
-        adam_step(adam, grad_at(e), lr, pv, mv, vv);
-        P[e] = pv; M[e] = mv; V[e] = vv;
+        bool on = true;
+        if constexpr (SPARSE) on = vis_at(e);
+        if (on) {
+            float pv = P[e], mv = M[e], vv = V[e];
+            adam_step(adam, grad_at(e), lr, pv, mv, vv);
+            P[e] = pv; M[e] = mv; V[e] = vv;
+        }
     }
     float4* P4 = reinterpret_cast<float4*>(P + head);
     float4* M4 = reinterpret_cast<float4*>(M + head);
     float4* V4 = reinterpret_cast<float4*>(V + head);
+    if constexpr (SPARSE) {
+        // one float4 at a time (this form serves the spans the kept registers do not: K != 25, or an unaligned span).  A float4
+        // spans at most two rows (L >= 3), and f, f + 3 name them.
+        for (int e = lane; e < n4; e += 64) {
+            const int f = head + 4 * e;
+            const bool v0 = vis_at(f), v1 = vis_at(f + 1), v2 = vis_at(f + 2), v3 = vis_at(f + 3);
+            if (!(v0 || v3)) continue;
+            float4 p4 = P4[e], m4 = M4[e], w4 = V4[e];
+            if (v0) adam_step(adam, grad_at(f), lr, p4.x, m4.x, w4.x);
+            if (v1) adam_step(adam, grad_at(f + 1), lr, p4.y, m4.y, w4.y);
+            if (v2) adam_step(adam, grad_at(f + 2), lr, p4.z, m4.z, w4.z);
+            if (v3) adam_step(adam, grad_at(f + 3), lr, p4.w, m4.w, w4.w);
+            P4[e] = p4; M4[e] = m4; V4[e] = w4;
+        }
+        return;
+    }
     constexpr int B = 6;
     for (int e0 = lane; e0 < n4; e0 += 64 * B) {
         float4 pp[B], mm[B], vv[B];
@@ -357,9 +382,12 @@ __device__ __forceinline__ void adam_rows(const AdamFuse& adam, const float* fre
 // with the gradients by now, and a second read of the 18 KB span came from HBM again (the PMC fetch bytes of the
 // kernel were 1.25x its algorithmic bytes, the excess = N x 288 B).  Moments in batches of 3 float4, one batch ahead
 // (the 18 kept float4 leave room for no more under the 256 registers of two waves per SIMD).
+// SPARSE: as adam_rows; L % 4 == 0 here, so a float4 lies in one row and is either updated whole or left alone (its moments
+// not loaded, nothing stored).
+template <bool SPARSE = false>
 __device__ __forceinline__ void adam_rows_kept(const AdamFuse& adam, const float* frest, int row0, int total4, int L,
                                                const float* myRows, int lane, float lr,
-                                               float4 (&pp)[SH_ROWS_MAX4])
+                                               float4 (&pp)[SH_ROWS_MAX4], unsigned long long visBits = ~0ull)
 {
     const size_t off0 = (size_t)(frest - adam.pBase) + (size_t)row0 * L;
     float4* P4 = reinterpret_cast<float4*>(const_cast<float*>(adam.pBase) + off0);
@@ -373,18 +401,27 @@ __device__ __forceinline__ void adam_rows_kept(const AdamFuse& adam, const float
 #endif
     constexpr int D = GS_ADAM_ROWS_DEPTH;      // batches of moments in flight ahead of the update
     float4 mm[D][B], vv[D][B];
+    auto vis4 = [&](int e) { return ((visBits >> ((4 * e) / L)) & 1ull) != 0ull; };      // (SPARSE only)
     auto load = [&](int k, float4 (&m)[B], float4 (&v)[B]) {
 #pragma unroll
         for (int b = 0; b < B; b++) {
             const int e = min(lane + 64 * (k * B + b), total4 - 1);
-            m[b] = M4[e]; v[b] = V4[e];
+            if constexpr (SPARSE) {
+                float4 mz = make_float4(0.f, 0.f, 0.f, 0.f), vz = mz;
+                if (vis4(e)) { mz = M4[e]; vz = V4[e]; }
+                m[b] = mz; v[b] = vz;
+            } else {
+                m[b] = M4[e]; v[b] = V4[e];
+            }
         }
     };
     auto update = [&](int k, float4 (&m)[B], float4 (&v)[B]) {
 #pragma unroll
         for (int b = 0; b < B; b++) {
             const int e = lane + 64 * (k * B + b);
-            if (e < total4) {
+            bool on = e < total4;
+            if constexpr (SPARSE) on = on && vis4(e);
+            if (on) {
                 float4& p = pp[k * B + b];
                 adam_step(adam, grad_at(4 * e), lr, p.x, m[b].x, v[b].x);
                 adam_step(adam, grad_at(4 * e + 1), lr, p.y, m[b].y, v[b].y);
@@ -442,16 +479,21 @@ __device__ __forceinline__ float wave_sum_xor(float v)
 // F3D (3-D smoothing filter, gs_set_filter3d; MODE 0 and 2, never with MCMC): the forward projected s_eff = sqrt(s^2 + f^2) and
 // blended sigma(o) kappa (rho); the geometry backward runs on s_eff, dop's share of the opacity and of the rho VJP carries kappa,
 // and filter3d_activate (gs_math.h) turns dL/ds_eff into dL/dscales_raw.
-template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false>
+// SPARSE (sparse Adam, gs_set_sparse_adam; MODE 2 only, never with MCMC or F3D): visMask[p] = the forward gave Gaussian p a radius
+// > 0.  A wave whose 64 rows are all invisible returns before it has staged, loaded or stored anything (under POSE it writes
+// its zero partials); in a mixed wave the invisible lanes store none of their 14 small elements and adam_rows / adam_rows_kept
+// skip their rows.  An invisible row's cotangent is all zero, so it adds nothing to gradNormAccum or to the pose sums either way.
+template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false, bool SPARSE = false>
 __device__ __forceinline__ void proj_bwd_fused_body(
     int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
     const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
     float* gFdc, float* gFrest, float* gScales, float* gRot,
     float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials,
-    McmcFuse mc = McmcFuse{}, const float* __restrict__ filter3d = nullptr)
+    McmcFuse mc = McmcFuse{}, const float* __restrict__ filter3d = nullptr, const unsigned char* __restrict__ visMask = nullptr)
 {
     static_assert(!MCMC || MODE == 2, "the MCMC step is fused into the Adam form only");
+    static_assert(!SPARSE || (MODE == 2 && !MCMC && !F3D), "sparse Adam: the plain fused Adam form only");
     static_assert(!F3D || (!MCMC && MODE != 1), "the 3-D filter: single-device steps and the reference strategy only");
     constexpr bool EMIT_MG = MODE == 1, ADAM = MODE == 2;
     extern __shared__ float shLds[];
@@ -462,6 +504,18 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     const int p = blockIdx.x * PROJ_FUSED_THREADS + threadIdx.x;
     if (MODE == 0 && adam.rider && p == 0) *adam.rider = *adam.ovf ? 1.0f : 0.0f;      // (data-parallel all-reduce: the gate rides behind the gradients)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    bool myVis = true;
+    unsigned long long visBits = ~0ull;
+    if constexpr (SPARSE) {
+        myVis = p < N && visMask[p] != 0;
+        visBits = __ballot(myVis);
+        if (visBits == 0ull) {       // (wave-uniform; the kernel has no workgroup barrier)
+            if constexpr (POSE) {
+                if (lane < 16) posePartials[16 * ((size_t)blockIdx.x * (PROJ_FUSED_THREADS / 64) + wv) + lane] = 0.f;
+            }
+            return;
+        }
+    }
     const int L = (K - 1) * 3;
     float* myRows = shLds + wv * 64 * (L + 1);
     const int row0 = blockIdx.x * PROJ_FUSED_THREADS + wv * 64;
@@ -580,7 +634,7 @@ __device__ __forceinline__ void proj_bwd_fused_body(
                        }, d);
         if (ADAM) { sg_[11] = gdc[0]; sg_[12] = gdc[1]; sg_[13] = gdc[2]; }
     }
-    if (ADAM && GS_PROJ_LATE_MOMENTS) small_moments();
+    if (ADAM && GS_PROJ_LATE_MOMENTS) small_moments();      // (SPARSE: an invisible lane of a mixed wave loads them too and stores nothing)
     if constexpr (POSE) {
         // xyz - cam' is the SH view direction's argument: dL/dcam' = -d (a zero row has d = 0 up to 0 x inf: selected away)
         const bool live = (g0.x != 0.f || g0.y != 0.f || g0.z != 0.f || g0.w != 0.f || g1.x != 0.f ||
@@ -627,7 +681,9 @@ __device__ __forceinline__ void proj_bwd_fused_body(
 #pragma unroll
         for (int a = 0; a < 3; a++) sg_[3 + a] = sg_[3 + a] + mc.sCoef * s[a];
     }
-    if (ADAM && !gateWord) {
+    bool smallOn = ADAM && !gateWord;
+    if constexpr (SPARSE) smallOn = smallOn && myVis;
+    if (smallOn) {
         // the 14 small elements: values and moments were loaded at the top; one burst of stores here
         float sp[14] = {m[0], m[1], m[2], sr[0], sr[1], sr[2], rr[0], rr[1], rr[2], rr[3], opr, d0v[0], d0v[1], d0v[2]};
         const float slr[14] = {adam.lr[0], adam.lr[0], adam.lr[0], adam.lr[3], adam.lr[3], adam.lr[3], adam.lr[4],
@@ -658,8 +714,8 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     }
     if (MODE == 0 && rows > 0 && L > 0) sh_rows_out(myRows, gFrest + (size_t)row0 * L, rows, L, lane);
     if (ADAM && !gateWord && rows > 0 && L > 0) {
-        if (kept) adam_rows_kept(adam, frest, row0, total4, L, myRows, lane, adam.lr[2], keptRows);
-        else adam_rows(adam, frest, row0, rows, L, myRows, lane, adam.lr[2]);
+        if (kept) adam_rows_kept<SPARSE>(adam, frest, row0, total4, L, myRows, lane, adam.lr[2], keptRows, visBits);
+        else adam_rows<SPARSE>(adam, frest, row0, rows, L, myRows, lane, adam.lr[2], visBits);
     }
     if constexpr (POSE) {
         float* out = posePartials + 16 * ((size_t)blockIdx.x * (PROJ_FUSED_THREADS / 64) + wv);
@@ -726,6 +782,39 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_f3d_ke
     proj_bwd_fused_body<MODE, true, AA, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
                                                      gXyz, gFdc, gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials,
                                                      McmcFuse{}, filter3d);
+}
+
+// Sparse Adam (gs_set_sparse_adam): MODE 2 with the forward's visibility mask, plain and posed.  Kernels of their own, so that
+// the default ones above keep their arguments and their code.
+template <bool AA>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_sparse_kernel(
+    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
+    const unsigned char* __restrict__ visMask)
+{
+    proj_bwd_fused_body<2, false, AA, false, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam,
+                                                          nullptr, McmcFuse{}, nullptr, visMask);
+}
+template <bool AA>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_sparse_kernel(
+    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
+    const float* frest, const float* scalesRaw, const float* rotRaw,
+    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
+    float* __restrict__ posePartials, const unsigned char* __restrict__ visMask)
+{
+    const CamParams cam = *dcam;
+    proj_bwd_fused_body<2, true, AA, false, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
+                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam,
+                                                         posePartials, McmcFuse{}, nullptr, visMask);
+}
+
+// ... and what the fused forward leaves for them: radius > 0 of every Gaussian, as a byte (gs_get_visibility reads the same)
+__global__ __launch_bounds__(256) void vis_mask_kernel(int N, const float* __restrict__ radii, unsigned char* __restrict__ mask)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < N) mask[p] = radii[p] > 0.0f ? 1 : 0;
 }
 
 // The MCMC strategy's step (gs_set_mcmc): MODE 2 with the regularisers and the noise, plain and posed.  Kernels of their own,
@@ -1183,6 +1272,16 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
                                        lds, pflags, a, cc, pieces);
     c->visBlocks = gs_div_up(N, PROJ_FUSED_THREADS);
     GS_HIP_CHECK(c, hipGetLastError());
+    if (c->sparseAdam) return launch_vis_mask(c, N, radii);      // (gs_render_forward hands a radii buffer of the context's in then)
+    return GS_OK;
+}
+
+int launch_vis_mask(gs_ctx* c, int N, const float* radii)
+{
+    if (N == 0) return GS_OK;
+    if (!radii || !c->visMask || N > c->visCap) { c->err = "sparse Adam: no visibility buffers for this forward"; return GS_ERR_INVALID_ARG; }
+    hipLaunchKernelGGL(vis_mask_kernel, dim3(gs_div_up(N, 256)), dim3(256), 0, c->stream, N, radii, c->visMask);
+    GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }
 
@@ -1293,6 +1392,21 @@ int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* 
         hipLaunchKernelGGL((aa ? proj_bwd_fused_mcmc_kernel<true> : proj_bwd_fused_mcmc_kernel<false>),
                            dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam,
                            xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a, mc);
+        GS_HIP_CHECK(c, hipGetLastError());
+        return GS_OK;
+    }
+    if (c->sparseAdam) {       // (api.hip has checked that the forward left its mask; never with a filter or the MCMC step: refused)
+        if (c->fwd.poseDelta) {
+            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_sparse_kernel<true> : proj_bwd_fused_pose_sparse_kernel<false>),
+                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree,
+                               c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a,
+                               c->posePartials, c->visMask);
+            GS_HIP_CHECK(c, hipGetLastError());
+            return launch_pose_grad(c, N);
+        }
+        hipLaunchKernelGGL((aa ? proj_bwd_fused_sparse_kernel<true> : proj_bwd_fused_sparse_kernel<false>),
+                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam,
+                           xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a, c->visMask);
         GS_HIP_CHECK(c, hipGetLastError());
         return GS_OK;
     }

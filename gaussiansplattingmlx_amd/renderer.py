@@ -110,6 +110,7 @@ class GaussianRenderer:
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
         self._antialiased = False
         self._absgrad = False
+        self._sparse_adam = False
         self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
         self._bilateral = (None, None)  # setBilateralGrid's, likewise
         if antialiased:
@@ -638,6 +639,46 @@ class GaussianRenderer:
         out = self._empty(N, 2)
         self._check(self.lib.gs_get_absgrad(self.ctx, N, _p(out)))
         return out
+
+    # -- sparse Adam (include/gsplat.h gs_set_sparse_adam; sparse_adam.py restates the rule) ---------------
+    def setSparseAdam(self, enable: bool = True):
+        """gs_set_sparse_adam: the following renderForward calls keep which Gaussians they gave a radius > 0 (visibility()), and
+        renderBackwardAdam / adamStepVisible update those rows alone: every element of an invisible row -- parameter and both
+        moments -- keeps its bits.  Single-device steps; not with the MCMC strategy or a 3-D filter.  Off (the default): no
+        kernel, buffer or result differs."""
+        self._check(self.lib.gs_set_sparse_adam(self.ctx, 1 if enable else 0))
+        self._sparse_adam = bool(enable)
+
+    @property
+    def sparseAdam(self) -> bool:
+        return self._sparse_adam
+
+    def visibility(self):
+        """gs_get_visibility: torch.bool [N], the Gaussians the last renderForward made under setSparseAdam saw (radius > 0)."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "visibility: no renderForward on this renderer")
+        N = int(self._fused["params"]["xyz"].shape[0])
+        out = self._empty(max(N, 1), dtype=torch.uint8)[:N]
+        self._check(self.lib.gs_get_visibility(self.ctx, N, _p(out)))
+        return out.bool()
+
+    def adamStepVisible(self, arena, grad, m, v, seg_end, lrs, seg_row_floats, N: int, visible=None, beta1=0.9, beta2=0.999,
+                        eps=1e-15, grad_scale=1.0):
+        """gs_adam_step_visible: gs_adam_step on the rows < N whose mask byte is set (visible: torch.bool / uint8 [N] on the
+        device, or None for the mask of the last renderForward made under setSparseAdam).  seg_end / lrs / seg_row_floats: one
+        entry per segment (a GaussModel's seg_end, arenaLearningRates and sparse_adam.model_row_floats)."""
+        k = len(seg_end)
+        if len(lrs) != k or len(seg_row_floats) != k:
+            raise ValueError("adamStepVisible: one learning rate and one row width per segment")
+        vis = None
+        if visible is not None:
+            vis = visible.to(device=self.device, dtype=torch.uint8).contiguous()
+            if vis.numel() != int(N):
+                raise ValueError("adamStepVisible: visible holds N entries")
+        self._check(self.lib.gs_adam_step_visible(
+            self.ctx, int(arena.numel()), _p(arena), _p(grad), _p(m), _p(v), k, (C.c_longlong * k)(*[int(x) for x in seg_end]),
+            (C.c_float * k)(*[float(x) for x in lrs]), (C.c_int * k)(*[int(x) for x in seg_row_floats]), C.c_float(beta1),
+            C.c_float(beta2), C.c_float(eps), C.c_float(grad_scale), int(N), _p(vis)))
 
     # -- the 3-D smoothing filter (include/gsplat.h gs_set_filter3d, DESIGN.md section 14; filter3d.py restates it in float64) ---
     def setFilterCameras(self, cameras):

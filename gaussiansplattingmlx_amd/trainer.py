@@ -454,7 +454,7 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None):
+                 absgrad=None, sparse_adam: bool = False):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -539,7 +539,28 @@ class GaussianTrainer:
         where the sum is divided by a per-Gaussian visibility count; this trainer keeps the reference's global step count, and
         nobody has tuned the value here.  Single-device steps and the reference strategy with densify on only; composes with
         pose_opt, exposure_opt, bilateral_grid, filter_3d, contrib_prune, an anti-aliased renderer and referenceParamReload.
-        Off (the default): no kernel, buffer or result differs."""
+        Off (the default): no kernel, buffer or result differs.
+
+        sparse_adam: the step updates only the Gaussians its view saw (include/gsplat.h gs_set_sparse_adam, DESIGN.md section 17;
+        Taming 3DGS, Mallick et al. 2024: Inria's --optimizer_type sparse_adam, gsplat's visible_adam).  A Gaussian is visible in
+        a step iff the step's forward gave it a radius > 0 (the renderer's N_visible).  A visible row gets the update it gets
+        today -- on a zero gradient too, if no pixel blended it --; every element of an invisible row, parameter and both
+        moments, keeps its bits, where dense Adam lets it drift on its momentum and lets its second moment decay.  The trainer
+        turns the renderer's setting on around its own steps and puts it back.  fuse_adam=True: the fused backward + Adam skips
+        the invisible rows (a wave of 64 invisible rows loads and stores nothing); fuse_adam=False: the step ends with
+        gs_adam_step_visible on the forward's mask.  The densify statistic is what it is without the setting.  Composes with
+        pose_opt, exposure_opt, bilateral_grid, absgrad, contrib_prune, an anti-aliased renderer, densify on or off and
+        referenceParamReload; single-device steps with one view only, not with strategy='mcmc' (its noise and regularisers act
+        on every Gaussian every step) and not with filter_3d.  Off (the default): no kernel, buffer or result differs."""
+        if not isinstance(sparse_adam, bool):
+            raise ValueError("sparse_adam is True or False")
+        self.sparse_adam = sparse_adam
+        if sparse_adam:
+            if strategy == "mcmc":
+                raise ValueError("sparse_adam: the reference strategy only (strategy='mcmc' moves every Gaussian every step)")
+            if filter_3d:
+                raise ValueError("sparse_adam: not with filter_3d=True")
+            _require_single_device("sparse_adam", views_per_rank, process_group, dp_bootstrap, exchange_impl)
         if strategy not in ("reference", "mcmc"):
             raise ValueError(f"unknown strategy {strategy!r} (\"reference\" or \"mcmc\")")
         self.strategy = strategy
@@ -1426,6 +1447,7 @@ class GaussianTrainer:
         r = self.gaussRender
         # knobs of the caller's renderer that this step changes, put back whatever happens
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
+        sparse_was = getattr(r, "_sparse_adam", False)
         tables = list(self._perView.values())
         row = tables[0].row(viewKey) if tables else None       # (one n_views for all of them)
         try:
@@ -1434,6 +1456,8 @@ class GaussianTrainer:
                 r.setMCMC(self._mcmcParams())
             if self.filter_3d:
                 r.setFilter3D(self._filter)
+            if self.sparse_adam and not sparse_was:
+                r.setSparseAdam(True)
             for t in tables:
                 t.bindRow(r, row)
             if self._exchange:
@@ -1453,6 +1477,8 @@ class GaussianTrainer:
                 r.setMCMC(None)
             if self.filter_3d:
                 r.setFilter3D(None)
+            if self.sparse_adam and not sparse_was:
+                r.setSparseAdam(False)
             for t in tables:
                 t.unbind(r)
 
@@ -1728,7 +1754,14 @@ class GaussianTrainer:
                 self._xt_mark(xt, "wr0")
                 reduce.wait()
                 self._xt_mark(xt, "wr1")
-        if not fused:
+        if not fused and self.sparse_adam:
+            # the rows the step's forward saw, and only those (rows >= N of a strided layout and the pads are left alone too)
+            lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
+            widths = (C.c_int * 6)(*[max(int(m._per[k]), 1) for k in ARENA_ORDER])      # (K = 1: an empty segment, any width)
+            r._check(r.lib.gs_adam_step_visible(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
+                                                widths, C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0),
+                                                m.N, None))
+        elif not fused:
             lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
             r._check(r.lib.gs_adam_step(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
                                         C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0 / self.world)))

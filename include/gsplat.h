@@ -375,6 +375,30 @@ int gs_set_absgrad(gs_ctx* ctx, int enable);
  * stream, no allocation. */
 int gs_get_absgrad(gs_ctx* ctx, int N, float* out /* DEVICE [N,2] */);
 
+/* Sparse Adam (not in the reference; Taming 3DGS, Mallick et al. 2024: Inria's --optimizer_type sparse_adam,
+ * gsplat's visible_adam / SelectiveAdam): the step updates only the Gaussians its view saw.  A Gaussian is VISIBLE in a step iff
+ * the step's fused forward gave it a radius > 0 -- the N_visible of gs_last_stats; a Gaussian the forward treats as degenerate has
+ * radius 0; under a pose correction or the anti-aliased mode it is whatever that forward computed; depth cuts, view hints, trimmed
+ * rects, the tile size and block lists do not enter.  A visible Gaussian no pixel blended (occluded, cut) is still visible: it takes
+ * the ordinary update on a zero gradient, so its moments decay.
+ * While on, every gs_render_forward keeps the visibility of its N Gaussians in memory of the context's (allocated by the first
+ * forward that needs it, regrown only when N outgrows it: no step allocates), and gs_render_backward_adam gives a visible row
+ * exactly the update it gets with the setting off, and leaves every element of an invisible row -- parameter, first and second
+ * moment, in all six tensors -- bit for bit as it was.  The overflow gate keeps its meaning (raised: no row moves), and the
+ * grad-norm accumulator gets what it gets with the setting off (an invisible row adds 0 to it either way).
+ * enable: 0 (the default: no kernel, buffer or result differs) or 1; any other value returns GS_ERR_INVALID_ARG.  A per-context
+ * setting as gs_set_antialiasing is.  Composes with the anti-aliased mode, pose refinement, the per-view colour corrections,
+ * absgrad, depth cuts, view hints and block lists.  Refused with GS_ERR_INVALID_ARG while it is on: gs_render_backward_dp*,
+ * gs_dp_step, gs_sh_grad_from_views_adam*, gs_set_mcmc and gs_set_filter3d with a non-NULL argument; turning it on while the MCMC
+ * strategy or a 3-D filter is set is refused likewise.  gs_render_backward_adam returns GS_ERR_NO_FORWARD when the setting is on
+ * and the forward was made before it was turned on. */
+int gs_set_sparse_adam(gs_ctx* ctx, int enable);
+/* The visibility mask of the context's last gs_render_forward, which must have been made with sparse Adam on: 1 or 0 per
+ * Gaussian.  It stays readable after the setting has been turned off, until the next forward.  GS_ERR_NO_FORWARD if the last
+ * forward was not made under the setting (or there is none); GS_ERR_SIZE_MISMATCH if N is not that forward's N.  Asynchronous on
+ * the context's stream, no allocation. */
+int gs_get_visibility(gs_ctx* ctx, int N, unsigned char* out /* DEVICE [N] */);
+
 /* 3-D smoothing filter (not in the reference; DESIGN.md "3-D smoothing filter"): Mip-Splatting's other filter.  The anti-aliased
  * mode above fixes a model viewed from further away than it was trained; this one fixes the other direction: a Gaussian may
  * not be narrower than the sampling interval of the closest training camera that saw it, or the model shows needle and
@@ -677,6 +701,16 @@ int gs_set_loss_target_cache(gs_ctx* ctx, float* cache /*DEVICE or NULL*/, int f
 int gs_adam_step(gs_ctx* ctx, long long n, float* params, const float* grads, float* m, float* v, int nseg,
                  const long long* seg_end /*HOST*/, const float* seg_lr /*HOST*/, float beta1, float beta2,
                  float eps, float grad_scale);
+/* gs_adam_step on the visible rows only (sparse Adam, above; what the unfused single-device step ends with).  Segment s holds
+ * rows of seg_row_floats[s] >= 1 floats: element e of segment s belongs to row (e - start_s) / seg_row_floats[s].  Rows >= N -- the
+ * tail of a capacity-strided segment and the pads that align the segments to 16 bytes -- are left alone, and so are the rows whose
+ * mask byte is 0: every element of theirs in params, m and v keeps its bits.  Every other element gets gs_adam_step's update.
+ * visible == NULL: the mask gs_get_visibility would return (GS_ERR_NO_FORWARD without one,
+ * GS_ERR_SIZE_MISMATCH if N is not that forward's N).  Arguments are checked as gs_adam_step checks its own; gated like it. */
+int gs_adam_step_visible(gs_ctx* ctx, long long n, float* params, const float* grads, float* m, float* v, int nseg,
+                         const long long* seg_end /*HOST*/, const float* seg_lr /*HOST*/, const int* seg_row_floats /*HOST [nseg]*/,
+                         float beta1, float beta2, float eps, float grad_scale, int N,
+                         const unsigned char* visible /*DEVICE [N] or NULL*/);
 
 /* ---- next row: densify / prune -------------------------------------------------------------
  * The three kernels of GaussianTrainer.swift:317-427 one to one, the scan between them, and the gather + per-slot
