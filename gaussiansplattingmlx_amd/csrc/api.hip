@@ -317,6 +317,19 @@ int sh_views_gate_layout(gs_ctx* c, const char* who, int N, int R)
     return GS_OK;
 }
 
+// the kernels move a wave's f_rest span as float4 when its row length L = 3 (K - 1) is a multiple of four (sh_rows_in /
+// sh_rows_out / the kept registers): the tensor must then start on a 16-byte boundary.  Other row lengths go element by element
+// (or through adam_rows' scalar head and tail) and may lie anywhere.  bases: the arenas the Adam forms address by one offset
+int sh_rest_alignment(gs_ctx* c, const char* who, int N, int K, const float* rest, const float* params_base = nullptr,
+                      const float* m_base = nullptr, const float* v_base = nullptr)
+{
+    if (((uintptr_t)params_base | (uintptr_t)m_base | (uintptr_t)v_base) & 15)
+        return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": the parameter and moment arenas must be 16-byte aligned");
+    if (N > 0 && K > 1 && ((3 * (K - 1)) & 3) == 0 && ((uintptr_t)rest & 15))
+        return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": with 3 (K - 1) a multiple of four the f_rest tensor must be 16-byte aligned");
+    return GS_OK;
+}
+
 // the SH tensors of a fused SH rebuild + Adam lie in [params_base, params_base + n_arena)
 int sh_in_arena(gs_ctx* c, const char* who, int N, int K, const float* dc, const float* rest, const float* params_base,
                 long long n_arena)
@@ -1389,6 +1402,7 @@ int gs_sh_grad_from_views_adam_dir(gs_ctx* c, int N, int K, int R, const float* 
         return rc;
     if ((uintptr_t)xyz_add & 15) return fail(c, GS_ERR_INVALID_ARG, "gs_sh_grad_from_views_adam_dir: xyz_add must be 16-byte aligned");
     if (const int rc = sh_in_arena(c, who, N, K, features_dc, features_rest, params_base, n_arena)) return rc;
+    if (const int rc = sh_rest_alignment(c, who, N, K, features_rest, params_base, m_base, v_base)) return rc;
     if (const int rc = sh_views_gate_layout(c, who, N, R)) return rc;
     GsStageTimer t(c, GS_STAGE_ADAM);
     return launch_sh_views_dir_adam(c, N, K, R, xyz, color_cot_all, cam_centers, own_xyz, features_dc, features_rest, params_base,
@@ -1411,6 +1425,7 @@ int gs_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, cons
     if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, grad_features_dc, grad_features_rest, false,
                                      false))
         return rc;
+    if (const int rc = sh_rest_alignment(c, who, N, K, grad_features_rest)) return rc;
     if (const int rc = sh_views_gate_layout(c, who, N, R)) return rc;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
     return launch_sh_grad_from_views(c, N, K, R, xyz, color_cot_all, cam_centers, grad_features_dc, grad_features_rest);
@@ -1428,6 +1443,7 @@ int gs_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* xyz,
                                      !params_base || !m_base || !v_base))
         return rc;
     if (const int rc = sh_in_arena(c, who, N, K, features_dc, features_rest, params_base, n_arena)) return rc;
+    if (const int rc = sh_rest_alignment(c, who, N, K, features_rest, params_base, m_base, v_base)) return rc;
     if (const int rc = sh_views_gate_layout(c, who, N, R)) return rc;
     GsStageTimer t(c, GS_STAGE_ADAM);
     return launch_sh_grad_from_views_adam(c, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest,

@@ -526,7 +526,11 @@ int gs_render_backward_dp_begin(gs_ctx* ctx, const float* cot_color, const float
 int gs_render_backward_dp_finish(gs_ctx* ctx, float* grad_xyz, float* grad_scales, float* grad_rotation,
                                  float* grad_opacity);
 /* grad_features_dc[N,1,3] / grad_features_rest[N,K-1,3] = sum over the R views (R <= 16) of
- * basis_k(xyz - cam_centers[r]) * color_cot_all[r][N][3]. */
+ * basis_k(xyz - cam_centers[r]) * color_cot_all[r][N][3].
+ * Alignment, here and in the two _adam forms below: when a row of the rest tensor, 3 (K - 1) floats, is a multiple of four floats
+ * (K = 9, 25) the kernels move it as 16-byte words and the tensor (grad_features_rest / features_rest) must be 16-byte aligned;
+ * the _adam forms also need params_base, m_base and v_base 16-byte aligned.  GS_ERR_INVALID_ARG otherwise.  Other K may place the
+ * tensor on any float. */
 int gs_sh_grad_from_views(gs_ctx* ctx, int N, int K, int R, const float* xyz, const float* color_cot_all,
                           const float* cam_centers /*HOST [R,3]*/, float* grad_features_dc, float* grad_features_rest);
 
