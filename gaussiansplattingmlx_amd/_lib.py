@@ -142,6 +142,9 @@ _SIGS = {
     "gs_set_bilateral_grid": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float]),
     "gs_apply_bilateral_grid": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
+    "gs_set_background": (C.c_int, [_vp, _vp]),
+    "gs_get_background": (C.c_int, [_vp, _vp]),
+    "gs_composite_target": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp, _vp]),
     "gs_set_absgrad": (C.c_int, [_vp, C.c_int]),
     "gs_get_absgrad": (C.c_int, [_vp, C.c_int, _vp]),
     "gs_set_sparse_adam": (C.c_int, [_vp, C.c_int]),

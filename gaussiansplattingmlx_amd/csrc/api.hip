@@ -279,7 +279,7 @@ int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* co
 {
     GsStageTimer t(c, GS_STAGE_BLEND_BWD);
     c->absgradN = -1;
-    if (!c->fast16) return launch_blend_backward(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+    if (!c->fast16) return launch_blend_backward(c, c->fwd.bg, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
     if (const int rc = launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
                                                 c->fwd.outAlpha, absgrad))
         return rc;
@@ -440,6 +440,7 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     c->gridW = (W + tile_w - 1) / tile_w; c->gridH = (H + tile_h - 1) / tile_h;
     c->T = c->gridW * c->gridH;
     c->degree = sh_degree; c->whiteBg = white_bg ? 1 : 0;
+    c->bg.mode = c->whiteBg ? GS_BG_WHITE : GS_BG_BLACK;
     c->fast16 = (tile_w % 16 == 0) && (tile_h % 16 == 0);
     c->blocksX = gs_div_up(W, 16); c->blocksY = gs_div_up(H, 16);
     c->real.tileW = tile_w; c->real.tileH = tile_h; c->real.gridW = c->gridW; c->real.gridH = c->gridH; c->real.T = c->T;
@@ -792,7 +793,7 @@ int gs_blend_forward(gs_ctx* c, int N, const float* packed, float* out_color, fl
     c->fwd.valid = false; c->fwd.bwdPrepared = false;
     int rc = launch_pack11_to_12(c, N, packed);
     if (rc) return rc;
-    return launch_blend_forward(c, out_color, out_depth, out_alpha, last_contrib);
+    return launch_blend_forward(c, c->bg, out_color, out_depth, out_alpha, last_contrib);
 }
 
 int gs_blend_backward(gs_ctx* c, int N, const float* packed, const float* cot_color, const float* cot_depth,
@@ -811,7 +812,7 @@ int gs_blend_backward(gs_ctx* c, int N, const float* packed, const float* cot_co
     c->absgradN = -1;                                       // (the accumulator's rows are rewritten)
     int rc = launch_pack11_to_12(c, N, packed);
     if (rc) return rc;
-    if ((rc = launch_blend_backward(c, N, cot_color, cot_depth, cot_alpha, out_alpha, last_contrib))) return rc;
+    if ((rc = launch_blend_backward(c, c->bg, N, cot_color, cot_depth, cot_alpha, out_alpha, last_contrib))) return rc;
     return launch_gradacc_to_packed11(c, N, grad_packed);
 }
 
@@ -944,7 +945,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     {
         GsStageTimer t(c, GS_STAGE_BLEND_FWD);
         rc = c->fast16 ? launch_blend_forward_v2(c, out_color, out_depth, out_alpha)
-                       : launch_blend_forward(c, out_color, out_depth, out_alpha, c->lastContrib);
+                       : launch_blend_forward(c, c->bg, out_color, out_depth, out_alpha, c->lastContrib);
         if (rc) return rc;
     }
     if (c->fwd.cutsActive) GS_HIP_CHECK(c, hipEventRecord(c->fwdDone, c->stream));
@@ -961,6 +962,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.poseDelta = c->poseDelta;
     c->fwd.poseGrad = c->poseGrad;
     c->fwd.antialias = c->antialias;
+    c->fwd.bg = c->bg;
     c->fwd.filter3d = c->filter3d;
     if (c->sparseAdam) c->visN = N;
     return GS_OK;
@@ -1019,6 +1021,38 @@ int gs_set_antialiasing(gs_ctx* c, int enable)
     if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_antialiasing: enable is 0 or 1");
     c->antialias = enable == 1;
     return GS_OK;
+}
+
+// ---- background colour (include/gsplat.h gs_set_background; gs_ctx.h GsBackground, background.hip) -------------------------
+int gs_set_background(gs_ctx* c, const float* rgb)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    GsBackground bg;
+    bg.mode = c->whiteBg ? GS_BG_WHITE : GS_BG_BLACK;
+    if (rgb) {
+        if (!isfinite(rgb[0]) || !isfinite(rgb[1]) || !isfinite(rgb[2]))
+            return fail(c, GS_ERR_INVALID_ARG, "gs_set_background: the three values must be finite");
+        bg.mode = GS_BG_COLOUR; bg.r = rgb[0]; bg.g = rgb[1]; bg.b = rgb[2];
+    }
+    c->bg = bg;
+    return GS_OK;
+}
+
+int gs_get_background(gs_ctx* c, float rgb[3])
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!rgb) return fail(c, GS_ERR_INVALID_ARG, "gs_get_background: null buffer");
+    if (c->bg.mode == GS_BG_COLOUR) { rgb[0] = c->bg.r; rgb[1] = c->bg.g; rgb[2] = c->bg.b; }
+    else rgb[0] = rgb[1] = rgb[2] = c->bg.mode == GS_BG_WHITE ? 1.0f : 0.0f;
+    return GS_OK;
+}
+
+int gs_composite_target(gs_ctx* c, long long n_pixels, const float* rgb, const float* alpha, const float* bg, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_composite_target: negative n_pixels");
+    if (!rgb || !alpha || !bg || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_composite_target: null pointer");
+    return launch_composite_target(c, n_pixels, rgb, alpha, bg, out);
 }
 
 // ---- the 3-D smoothing filter (include/gsplat.h gs_set_filter3d; filter3d.hip, gs_math.h filter3d_activate) -----------------

@@ -62,7 +62,7 @@ __device__ __forceinline__ void wave_sum11(float (&v)[11])
 // -----------------------------------------------------------------------------------------------
 template <int PPL>
 __global__ __launch_bounds__(256 / PPL) void blend_fwd_kernel(
-    BlockGeom geom, int whiteBg, const float4* __restrict__ packed12,
+    BlockGeom geom, GsBackground bgc, const float4* __restrict__ packed12,
     const uint32_t* __restrict__ sortedIdx, const uint32_t* __restrict__ tileRanges, float* __restrict__ outColor,
     float* __restrict__ outDepth, float* __restrict__ outAlpha, uint32_t* __restrict__ lastContrib,
     const uint32_t* __restrict__ blockOrder)
@@ -140,8 +140,9 @@ __global__ __launch_bounds__(256 / PPL) void blend_fwd_kernel(
             const int p = tid + k * NT;
             const int x = br.x0 + (p & 15), y = br.y0 + (p >> 4);
             const size_t pix = (size_t)y * W + x;
-            const float bg = whiteBg ? T[k] : 0.0f;
-            outColor[3 * pix] = cr[k] + bg; outColor[3 * pix + 1] = cg[k] + bg; outColor[3 * pix + 2] = cb[k] + bg;
+            float bg0, bg1, bg2;
+            gs_bg_terms(bgc, T[k], bg0, bg1, bg2);
+            outColor[3 * pix] = cr[k] + bg0; outColor[3 * pix + 1] = cg[k] + bg1; outColor[3 * pix + 2] = cb[k] + bg2;
             if (outDepth) outDepth[pix] = dd[k];
             outAlpha[pix] = 1.0f - T[k];
             lastContrib[pix] = nc[k];
@@ -191,7 +192,7 @@ __device__ __forceinline__ uint32_t kept_rank(bool keep, uint32_t* waveCnt, uint
 
 template <int PPL>
 __global__ __launch_bounds__(256 / PPL) void blend_fwd_cull_kernel(
-    BlockGeom geom, int whiteBg, const float4* __restrict__ packed12,
+    BlockGeom geom, GsBackground bgc, const float4* __restrict__ packed12,
     const uint32_t* __restrict__ sortedIdx, const uint32_t* __restrict__ tileRanges, float* __restrict__ outColor,
     float* __restrict__ outDepth, float* __restrict__ outAlpha, uint32_t* __restrict__ lastContrib,
     const uint32_t* __restrict__ blockOrder)
@@ -282,8 +283,9 @@ __global__ __launch_bounds__(256 / PPL) void blend_fwd_cull_kernel(
             const int p = tid + k * NT;
             const int x = br.x0 + (p & 15), y = br.y0 + (p >> 4);
             const size_t pix = (size_t)y * W + x;
-            const float bg = whiteBg ? T[k] : 0.0f;
-            outColor[3 * pix] = cr[k] + bg; outColor[3 * pix + 1] = cg[k] + bg; outColor[3 * pix + 2] = cb[k] + bg;
+            float bg0, bg1, bg2;
+            gs_bg_terms(bgc, T[k], bg0, bg1, bg2);
+            outColor[3 * pix] = cr[k] + bg0; outColor[3 * pix + 1] = cg[k] + bg1; outColor[3 * pix + 2] = cb[k] + bg2;
             if (outDepth) outDepth[pix] = dd[k];
             outAlpha[pix] = 1.0f - T[k];
             lastContrib[pix] = nc[k];
@@ -341,7 +343,7 @@ __device__ __forceinline__ void bwd_step(const float4& a, const float4& b, const
 
 template <int PPL>
 __global__ __launch_bounds__(256 / PPL) void blend_bwd_kernel(
-    BlockGeom geom, int whiteBg, const float4* __restrict__ packed12,
+    BlockGeom geom, GsBackground bgc, const float4* __restrict__ packed12,
     const uint32_t* __restrict__ sortedIdx, const uint32_t* __restrict__ tileRanges,
     const float* __restrict__ cotColor, const float* __restrict__ cotDepth, const float* __restrict__ cotAlpha,
     const float* __restrict__ outAlpha, const uint32_t* __restrict__ lastContrib, float* __restrict__ gradAcc16,
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(256 / PPL) void blend_bwd_kernel(
             cD[k] = cotDepth ? cotDepth[pix] : 0.0f;
             const float cA = cotAlpha ? cotAlpha[pix] : 0.0f;
             T[k] = 1.0f - outAlpha[pix];
-            cT[k] = -cA + (whiteBg ? (cCx[k] + cCy[k] + cCz[k]) : 0.0f);
+            cT[k] = -cA + gs_bg_cot(bgc, cCx[k], cCy[k], cCz[k]);
             nc[k] = min(lastContrib[pix], count);
         }
         myMax = max(myMax, nc[k]);
@@ -445,7 +447,7 @@ __global__ __launch_bounds__(256 / PPL) void blend_bwd_kernel(
 // kept entries compacted in sweep order; per batch of 64 kept entries one reduction + flush round as in blend_bwd_kernel
 template <int PPL>
 __global__ __launch_bounds__(256 / PPL) void blend_bwd_cull_kernel(
-    BlockGeom geom, int whiteBg, const float4* __restrict__ packed12,
+    BlockGeom geom, GsBackground bgc, const float4* __restrict__ packed12,
     const uint32_t* __restrict__ sortedIdx, const uint32_t* __restrict__ tileRanges,
     const float* __restrict__ cotColor, const float* __restrict__ cotDepth, const float* __restrict__ cotAlpha,
     const float* __restrict__ outAlpha, const uint32_t* __restrict__ lastContrib, float* __restrict__ gradAcc16,
@@ -485,7 +487,7 @@ __global__ __launch_bounds__(256 / PPL) void blend_bwd_cull_kernel(
             cD[k] = cotDepth ? cotDepth[pix] : 0.0f;
             const float cA = cotAlpha ? cotAlpha[pix] : 0.0f;
             T[k] = 1.0f - outAlpha[pix];
-            cT[k] = -cA + (whiteBg ? (cCx[k] + cCy[k] + cCz[k]) : 0.0f);
+            cT[k] = -cA + gs_bg_cot(bgc, cCx[k], cCy[k], cCz[k]);
             nc[k] = min(lastContrib[pix], count);
         }
         myMax = max(myMax, nc[k]);
@@ -685,7 +687,7 @@ static int launch_block_order(gs_ctx* c, const uint32_t* work)
 // -----------------------------------------------------------------------------------------------
 // launchers
 // -----------------------------------------------------------------------------------------------
-int launch_blend_forward(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha, uint32_t* lastContrib)
+int launch_blend_forward(gs_ctx* c, const GsBackground& bg, float* outColor, float* outDepth, float* outAlpha, uint32_t* lastContrib)
 {
     const float4* p12 = reinterpret_cast<const float4*>(c->packed12);
     const BlockGeom geom = op_geom(c);
@@ -696,10 +698,10 @@ int launch_blend_forward(gs_ctx* c, float* outColor, float* outDepth, float* out
                        c->blockOrder);
     const dim3 grid(nBlocks);
 #define GS_FWD(P)                                                                                                  \
-    hipLaunchKernelGGL(blend_fwd_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, c->whiteBg, p12, c->sortedIdx, \
+    hipLaunchKernelGGL(blend_fwd_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, bg, p12, c->sortedIdx, \
                        c->tileRanges, outColor, outDepth, outAlpha, lastContrib, c->blockOrder)
 #define GS_FWDC(P)                                                                                                      \
-    hipLaunchKernelGGL(blend_fwd_cull_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, c->whiteBg, p12, c->sortedIdx, \
+    hipLaunchKernelGGL(blend_fwd_cull_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, bg, p12, c->sortedIdx, \
                        c->tileRanges, outColor, outDepth, outAlpha, lastContrib, c->blockOrder)
     if (c->tileW > TILE || c->tileH > TILE) {       // a tile is more than one block: scan, cull, sweep the rest
         if (c->opFwdPpl == 4) GS_FWDC(4);
@@ -715,7 +717,7 @@ int launch_blend_forward(gs_ctx* c, float* outColor, float* outDepth, float* out
 }
 
 // accumulates d(packed) into ctx->gradAcc16 (zeroed here)
-int launch_blend_backward(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
+int launch_blend_backward(gs_ctx* c, const GsBackground& bg, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
                           const float* outAlpha, const uint32_t* lastContrib)
 {
     GS_HIP_CHECK(c, hipMemsetAsync(c->gradAcc16, 0, sizeof(float) * 16 * (size_t)N, c->stream));
@@ -730,10 +732,10 @@ int launch_blend_backward(gs_ctx* c, int N, const float* cotColor, const float* 
     if (rc) return rc;
     const dim3 grid(nBlocks);
 #define GS_BWD(P)                                                                                                  \
-    hipLaunchKernelGGL(blend_bwd_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, c->whiteBg, p12, c->sortedIdx, \
+    hipLaunchKernelGGL(blend_bwd_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, bg, p12, c->sortedIdx, \
                        c->tileRanges, cotColor, cotDepth, cotAlpha, outAlpha, lastContrib, c->gradAcc16, c->blockOrder)
 #define GS_BWDC(P)                                                                                                      \
-    hipLaunchKernelGGL(blend_bwd_cull_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, c->whiteBg, p12, c->sortedIdx, \
+    hipLaunchKernelGGL(blend_bwd_cull_kernel<P>, grid, dim3(256 / P), 0, c->stream, geom, bg, p12, c->sortedIdx, \
                        c->tileRanges, cotColor, cotDepth, cotAlpha, outAlpha, lastContrib, c->gradAcc16, c->blockOrder)
     if (c->tileW > TILE || c->tileH > TILE) {       // (two pixels per lane unless the knob says four: 1.54 -> 1.44 ms at 200x200)
         if (c->opBwdPpl == 4) GS_BWDC(4);

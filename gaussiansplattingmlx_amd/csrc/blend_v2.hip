@@ -220,7 +220,7 @@ __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementw
 // its ~30 vector instructions per splat), none in the checkpoints, nothing stored.
 template <int SEG, bool DEPTH>
 __global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, int whiteBg,
+    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, GsBackground bgc,
     const float4* __restrict__ rec12, const uint32_t* __restrict__ sortedIdx, uint32_t idxMask,
     const uint32_t* __restrict__ tileRanges, const uint32_t* __restrict__ segBase, uint32_t segCap, int statePlanes,
     float* __restrict__ outColor, float* __restrict__ outDepth,
@@ -481,8 +481,9 @@ __global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
         if (cutStore && any_live() && lane == 0 && cutStore[tile] != 0u) hostWords[0] = 1u;
         if (in) {
             const size_t pix = (size_t)y * W + x;
-            const float bg = whiteBg ? T : 0.0f;
-            outColor[3 * pix] = (br + cr) + bg; outColor[3 * pix + 1] = (bgr + cg) + bg; outColor[3 * pix + 2] = (bb + cb) + bg;
+            float bg0, bg1, bg2;
+            gs_bg_terms(bgc, T, bg0, bg1, bg2);
+            outColor[3 * pix] = (br + cr) + bg0; outColor[3 * pix + 1] = (bgr + cg) + bg1; outColor[3 * pix + 2] = (bb + cb) + bg2;
             if (DEPTH) outDepth[pix] = bd + dd;
             outAlpha[pix] = 1.0f - T; lastContrib[pix] = nc; finalT[pix] = T;
         }
@@ -515,7 +516,7 @@ __global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
 #define GS_V2P_WGS (2 * GS_V2P_WAVES)      // workgroups (pairs) per CU at that occupancy
 template <int SEG, bool DEPTH>
 __global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, int whiteBg,
+    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, GsBackground bgc,
     const float4* __restrict__ rec12, const uint32_t* __restrict__ sortedIdx, uint32_t idxMask,
     const uint32_t* __restrict__ tileRanges, const uint32_t* __restrict__ segBase, uint32_t segCap, int statePlanes,
     float* __restrict__ outColor, float* __restrict__ outDepth,
@@ -723,8 +724,9 @@ __global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
             if (cutStore && any_live() && lane == 0 && cutStore[tile] != 0u) hostWords[0] = 1u;
             if (in) {
                 const size_t pix = (size_t)y * W + x;
-                const float bg = whiteBg ? T : 0.0f;
-                outColor[3 * pix] = (br + cr) + bg; outColor[3 * pix + 1] = (bgr + cg) + bg; outColor[3 * pix + 2] = (bb + cb) + bg;
+                float bg0, bg1, bg2;
+                gs_bg_terms(bgc, T, bg0, bg1, bg2);
+                outColor[3 * pix] = (br + cr) + bg0; outColor[3 * pix + 1] = (bgr + cg) + bg1; outColor[3 * pix + 2] = (bb + cb) + bg2;
                 if (DEPTH) outDepth[pix] = bd + dd;
                 outAlpha[pix] = 1.0f - T; lastContrib[pix] = nc; finalT[pix] = T;
             }
@@ -762,7 +764,7 @@ __global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
 #define GS_V2W_WGS 5
 template <int SEG, bool DEPTH>
 __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, int whiteBg,
+    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, GsBackground bgc,
     const float4* __restrict__ rec12, const uint32_t* __restrict__ sortedIdx, uint32_t idxMask,
     const uint32_t* __restrict__ tileRanges, const uint32_t* __restrict__ segBase, uint32_t segCap, int statePlanes,
     float* __restrict__ outColor, float* __restrict__ outDepth,
@@ -1034,8 +1036,9 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
             const int xe = X0 + k * 8 + (lane & 7), ye = Y0 + h * 8 + (lane >> 3);
             if (xe < XL && ye < YL) {
                 const size_t pix = (size_t)ye * W + xe;
-                const float bg = whiteBg ? T : 0.0f;
-                outColor[3 * pix] = cr + bg; outColor[3 * pix + 1] = cg + bg; outColor[3 * pix + 2] = cb + bg;
+                float bg0, bg1, bg2;
+                gs_bg_terms(bgc, T, bg0, bg1, bg2);
+                outColor[3 * pix] = cr + bg0; outColor[3 * pix + 1] = cg + bg1; outColor[3 * pix + 2] = cb + bg2;
                 if (DEPTH) outDepth[pix] = dd;
                 outAlpha[pix] = 1.0f - T; lastContrib[pix] = nc; finalT[pix] = T;
             }
@@ -1160,7 +1163,7 @@ __device__ __forceinline__ void pair_bwd(const RecB& s, uint32_t i, const PairB&
 // rows, no kernel of the backward reads the row's fourth quarter)
 template <int SEG, bool DEPTH, bool ABSGRAD>
 __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int whiteBg, const float4* __restrict__ rec12,
+    int W, int H, int tileW, int tileH, int gridW, int blocksX, GsBackground bgc, const float4* __restrict__ rec12,
     const uint32_t* __restrict__ sortedIdx, uint32_t idxMask, const uint32_t* __restrict__ tileRanges,
     const uint32_t* __restrict__ itemRow, const uint4* __restrict__ segSlot, uint32_t qslotCap, int statePlanes,
     const uint32_t* __restrict__ blockWork,
@@ -1245,8 +1248,9 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
                         p.cCx[k] = gx; p.cCy[k] = gy; p.cCz[k] = gz; p.cD[k] = gd;
                         const float cA = cotAlpha ? cotAlpha[pix] : 0.0f;
                         const float Tn = finalT[pix];
-                        const float bg = whiteBg ? Tn : 0.0f;
-                        const float cTn = -cA + (whiteBg ? (gx + gy + gz) : 0.0f);
+                        float bg0, bg1, bg2;      // T_n b_c: the products the forward added (gs_bg_terms)
+                        gs_bg_terms(bgc, Tn, bg0, bg1, bg2);
+                        const float cTn = -cA + gs_bg_cot(bgc, gx, gy, gz);
                         // What the rest of the list still owes: cot . (final sums - the sums in front of the segment).  Round 6:
                         // the DIFFERENCE per channel first, then the dot product -- deep in a list both are of the size of the
                         // total and their difference small, and cot . final - cot . checkpoint (rounds 2-5) carried two dot
@@ -1260,7 +1264,7 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
                             T0 = st[0]; s0 = st[64]; s1 = st[128]; s2 = st[192];
                             if (DEPTH) s3 = st[256];
                         }
-                        const float d0 = (outColor[3 * pix] - bg) - s0, d1 = (outColor[3 * pix + 1] - bg) - s1, d2 = (outColor[3 * pix + 2] - bg) - s2;
+                        const float d0 = (outColor[3 * pix] - bg0) - s0, d1 = (outColor[3 * pix + 1] - bg1) - s1, d2 = (outColor[3 * pix + 2] - bg2) - s2;
                         const float owedC = fmaf(gx, d0, fmaf(gy, d1, fmaf(gz, d2, DEPTH ? gd * (outDepth[pix] - s3) : 0.0f)));
                         p.Ts[k] = sc * T0;
                         p.Q[k] = sc * (owedC + Tn * cTn);
@@ -1442,7 +1446,7 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
         const uint32_t partW = (qcap - c->fwd.qslotStatic) / 8u;
         auto kw = outDepth ? blend_fwd_v2w_kernel<SEGLEN, true> : blend_fwd_v2w_kernel<SEGLEN, false>;
         hipLaunchKernelGGL(kw, dim3(grid), dim3(256), 0, c->stream, c->W, c->H, c->tileW,
-                           c->tileH, c->gridW, blocksX, nItems, c->whiteBg, reinterpret_cast<const float4*>(c->packed12),
+                           c->tileH, c->gridW, blocksX, nItems, c->bg, reinterpret_cast<const float4*>(c->packed12),
                            c->sortedRaw, c->idxMask, c->tileRanges, c->segBase, (uint32_t)c->segCap, c->renderOnly ? 0 : c->fwd.statePlanes, outColor, outDepth,
                            outAlpha, c->lastContrib, c->finalT, c->segState, c->segSlot, qcap, ownW, partW, ckpt_pool(partW, (uint32_t)grid * 4u), c->blockWork, c->counters, c->fwdQueue,
                            (uint32_t)c->fwdQueues, c->blockOrder, cuts, c->missDev, c->fwdFoldScale, c->virt);
@@ -1453,7 +1457,7 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
     if (blend_forward_v2_pair(c)) {
         auto kp = outDepth ? blend_fwd_v2p_kernel<SEGLEN, true> : blend_fwd_v2p_kernel<SEGLEN, false>;
         hipLaunchKernelGGL(kp, dim3(grid), dim3(128), 0, c->stream, c->W, c->H, c->tileW,
-                           c->tileH, c->gridW, blocksX, nItems, c->whiteBg, reinterpret_cast<const float4*>(c->packed12),
+                           c->tileH, c->gridW, blocksX, nItems, c->bg, reinterpret_cast<const float4*>(c->packed12),
                            c->sortedRaw, c->idxMask, c->tileRanges, c->segBase, (uint32_t)c->segCap, c->renderOnly ? 0 : c->fwd.statePlanes, outColor, outDepth,
                            outAlpha, c->lastContrib, c->finalT, c->segState, c->segSlot, qcap, own, partSlots, ckpt_pool(partSlots, (uint32_t)grid), c->blockWork, c->counters, c->fwdQueue, (uint32_t)c->fwdQueues, c->blockOrder,
                            cuts, c->missDev, c->virt);
@@ -1463,7 +1467,7 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
     }
     auto kern = outDepth ? blend_fwd_v2q_kernel<SEGLEN, true> : blend_fwd_v2q_kernel<SEGLEN, false>;
     hipLaunchKernelGGL(kern, dim3(grid / 4), dim3(256), 0, c->stream, c->W, c->H, c->tileW,      // (grid = waves, a multiple of four)
-                       c->tileH, c->gridW, blocksX, nItems, c->whiteBg, reinterpret_cast<const float4*>(c->packed12),
+                       c->tileH, c->gridW, blocksX, nItems, c->bg, reinterpret_cast<const float4*>(c->packed12),
                        c->sortedRaw, c->idxMask, c->tileRanges, c->segBase, (uint32_t)c->segCap, c->renderOnly ? 0 : c->fwd.statePlanes, outColor, outDepth,
                        outAlpha, c->lastContrib, c->finalT, c->segState, c->segSlot, qcap, own, partSlots, ckpt_pool(partSlots, (uint32_t)grid), c->blockWork, c->counters, c->fwdQueue, (uint32_t)c->fwdQueues, c->blockOrder,
                        c->fwdTrace, cuts, c->missDev, (uint32_t)c->fwdSlowSlot, c->virt);
@@ -1521,7 +1525,7 @@ int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const floa
     auto kern = absgrad ? (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, true> : blend_bwd_v2_kernel<SEGLEN, false, true>)
                         : (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, false> : blend_bwd_v2_kernel<SEGLEN, false, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, c->stream, c->W, c->H, c->tileW, c->tileH,
-                       c->gridW, blocksX, c->whiteBg, reinterpret_cast<const float4*>(c->packed12), c->sortedRaw,
+                       c->gridW, blocksX, c->fwd.bg, reinterpret_cast<const float4*>(c->packed12), c->sortedRaw,
                        c->idxMask, c->tileRanges, c->itemRow, reinterpret_cast<const uint4*>(c->segSlot), c->fwd.qslotCap, c->fwd.statePlanes, c->fwd.blockWork, c->itemBlock, c->counters, c->bwdQueue, (uint32_t)c->bwdQueues, cotColor,
                        cotDepth, cotAlpha, outColor, outDepth, outAlpha, c->lastContrib, c->finalT, c->segState,
                        c->gradAcc16, c->virt);

@@ -54,6 +54,30 @@ __device__ __forceinline__ float gs_adam_delta(float lr, float m, float v, float
 }
 #endif
 
+// The colour the blend composites over (gs_set_background), a by-value argument of every blend kernel.
+// BLACK and WHITE are the creation backgrounds and keep the expressions they always had (0 and T; 0 and gx + gy + gz), so an
+// unset context computes bit for bit what it did before the colour existed; COLOUR adds T b_c per channel.
+enum { GS_BG_BLACK = 0, GS_BG_WHITE = 1, GS_BG_COLOUR = 2 };
+struct GsBackground {
+    int mode = GS_BG_BLACK;
+    float r = 0.0f, g = 0.0f, b = 0.0f;
+};
+#if defined(__HIPCC__)
+// the three background terms T b_c of a pixel.  Each is ONE rounded product (__fmul_rn: never contracted into the sum it joins,
+// whatever -ffp-contract says), so the fused backward takes off the stored image exactly what the forward put on
+__device__ __forceinline__ void gs_bg_terms(const GsBackground& bg, float T, float& t0, float& t1, float& t2)
+{
+    if (bg.mode == GS_BG_COLOUR) { t0 = __fmul_rn(T, bg.r); t1 = __fmul_rn(T, bg.g); t2 = __fmul_rn(T, bg.b); }
+    else t0 = t1 = t2 = bg.mode ? T : 0.0f;
+}
+// d(colour . cot) / dT through the background: g . b
+__device__ __forceinline__ float gs_bg_cot(const GsBackground& bg, float gx, float gy, float gz)
+{
+    if (bg.mode == GS_BG_COLOUR) return fmaf(gx, bg.r, fmaf(gy, bg.g, __fmul_rn(gz, bg.b)));
+    return bg.mode ? (gx + gy + gz) : 0.0f;
+}
+#endif
+
 struct GsDp;      // dp.hip: communicator, side stream and events of the data-parallel step
 
 // the fused forward's SH colours as rider workgroups of the binning kernels (gs_rider.h): what a rider needs, by value
@@ -112,6 +136,7 @@ struct gs_ctx {
     hipStream_t own_stream = nullptr;
     int W = 0, H = 0, tileW = 16, tileH = 16, gridW = 0, gridH = 0, T = 0, degree = 0, whiteBg = 0;
     int tileBits = 1;
+    GsBackground bg;             // gs_set_background: what the following forwards composite over (unset: whiteBg's black or white)
     bool fast16 = false;
     GsVirtGeom virt;             // block lists (above); virt.nbx != 0 <=> tileW .. T describe the block grid, `real` the caller's
     GsRealGeom real;
@@ -345,6 +370,7 @@ struct gs_ctx {
         const float* poseDelta = nullptr;  // the correction this forward was composed with (nullptr: none) ...
         float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
         bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
+        GsBackground bg;                   // the background this forward composited over (its backward's)
         const float* filter3d = nullptr;   // the 3-D filter widths this forward ran with (its backward's; nullptr: none)
         uint32_t* cutStore = nullptr;  // the view's cut words at the time of this forward (nullptr: none kept)
         bool cutsActive = false;     // this forward binned under depth cuts
@@ -446,6 +472,7 @@ long long bilateral_partials_floats(int gw, int gh, int gl, int nch);
 int launch_bilateral_apply(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, const float* in, float* out);
 int launch_bilateral_backward(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, int nch, float tvWeight,
                               const float* render, float* cot, float* partials, float* grad);
+int launch_composite_target(gs_ctx* c, long long n, const float* rgb, const float* alpha, const float bg[3], float* out);   // background.hip
 // filter3d.hip: the camera table's row is view[0..3][0], view[0..3][1], view[0..3][2], limX, limY, focalX, 0
 int launch_filter3d_width(gs_ctx* c, int N, const float* xyz, float* filter);
 int launch_filter3d_bake(gs_ctx* c, int N, const float* scalesRaw, const float* opacityRaw, const float* filter, float* outScales,
@@ -480,8 +507,8 @@ int cut_super_width(const gs_ctx* c);
 int launch_build_packed_tile_indices(gs_ctx* c, uint32_t B, int32_t* out);
 
 // blend.hip
-int launch_blend_forward(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha, uint32_t* lastContrib);
-int launch_blend_backward(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
+int launch_blend_forward(gs_ctx* c, const GsBackground& bg, float* outColor, float* outDepth, float* outAlpha, uint32_t* lastContrib);
+int launch_blend_backward(gs_ctx* c, const GsBackground& bg, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
                           const float* outAlpha, const uint32_t* lastContrib);
 int launch_gradacc_to_packed11(gs_ctx* c, int N, float* gradPacked11);
 

@@ -111,6 +111,7 @@ class GaussianRenderer:
         self._antialiased = False
         self._absgrad = False
         self._sparse_adam = False
+        self._background = None
         self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
         self._bilateral = (None, None)  # setBilateralGrid's, likewise
         if antialiased:
@@ -621,6 +622,42 @@ class GaussianRenderer:
     @antialiased.setter
     def antialiased(self, enable: bool):
         self.setAntialiased(enable)
+
+    # -- background colour (include/gsplat.h gs_set_background; background.py restates it) -------------
+    def setBackground(self, rgb=None):
+        """gs_set_background: the colour the following renderForward / blendForward calls composite over (three finite floats,
+        not confined to [0, 1]), or None (the default): the renderer's own black or white, bit for bit as without the call.
+        Every fused backward uses the background of its forward.  A by-value kernel argument: free to change every step."""
+        if rgb is None:
+            self._check(self.lib.gs_set_background(self.ctx, None))
+            self._background = None
+            return
+        b = np.ascontiguousarray(np.asarray(rgb.detach().cpu() if torch.is_tensor(rgb) else rgb, dtype=np.float32).reshape(-1))
+        if b.size != 3:
+            raise ValueError("setBackground: three floats (r, g, b), or None")
+        self._check(self.lib.gs_set_background(self.ctx, b.ctypes.data_as(C.c_void_p)))
+        self._background = b          # (what setBackground last set, as _sparse_adam is kept: a trainer puts it back behind its step)
+
+    @property
+    def background(self):
+        """The colour in effect (gs_get_background), float32 [3]: the one set, or the renderer's black or white."""
+        b = np.zeros(3, np.float32)
+        self._check(self.lib.gs_get_background(self.ctx, b.ctypes.data_as(C.c_void_p)))
+        return b
+
+    def compositeTarget(self, rgb, alpha, bg, out=None):
+        """gs_composite_target: the target of an RGBA view over bg, fma(a, rgb, (1 - a) bg) per pixel of an [..., 3] straight
+        (un-premultiplied) image and its [...] alpha (a new tensor; out=rgb works in place)."""
+        rgb, alpha = self._t(rgb), self._t(alpha)
+        b = np.ascontiguousarray(np.asarray(bg.detach().cpu() if torch.is_tensor(bg) else bg, dtype=np.float32).reshape(-1))
+        if rgb.shape[-1] != 3 or alpha.numel() * 3 != rgb.numel() or b.size != 3:
+            raise ValueError("compositeTarget: an [..., 3] image, its [...] alpha and three background floats")
+        out = torch.empty_like(rgb) if out is None else out
+        if out.shape != rgb.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != rgb.device:
+            raise ValueError("compositeTarget: out is a contiguous float32 device tensor of the image's shape")
+        self._check(self.lib.gs_composite_target(self.ctx, alpha.numel(), _p(rgb), _p(alpha), b.ctypes.data_as(C.c_void_p),
+                                                 _p(out)))
+        return out
 
     # -- AbsGS densification statistic (include/gsplat.h gs_set_absgrad, DESIGN.md section 16; absgrad.py restates it) --------
     def setAbsgrad(self, enable: bool = True):

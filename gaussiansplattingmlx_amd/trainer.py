@@ -454,7 +454,7 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None, sparse_adam: bool = False):
+                 absgrad=None, sparse_adam: bool = False, background=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -551,7 +551,31 @@ class GaussianTrainer:
         gs_adam_step_visible on the forward's mask.  The densify statistic is what it is without the setting.  Composes with
         pose_opt, exposure_opt, bilateral_grid, absgrad, contrib_prune, an anti-aliased renderer, densify on or off and
         referenceParamReload; single-device steps with one view only, not with strategy='mcmc' (its noise and regularisers act
-        on every Gaussian every step) and not with filter_3d.  Off (the default): no kernel, buffer or result differs."""
+        on every Gaussian every step) and not with filter_3d.  Off (the default): no kernel, buffer or result differs.
+
+        background: training on RGBA views over a background colour (background.BackgroundConfig, include/gsplat.h
+        gs_set_background; Inria's --random_background, gsplat's backgrounds= / random_bkgd).  Every step
+        takes trainStep's targetAlpha beside targetRGB (straight, un-premultiplied, as the loaders return them), picks the step's
+        colour b -- background_for(seed, t) in mode "random", the configured colour in mode "fixed" --, sets it as the renderer's
+        background, composites the target over it into a buffer the trainer owns (gs_composite_target) and runs the step on
+        that target; a forward repeated for an overflow or a depth-cut miss runs under the same b.  Only a truly empty pixel
+        then matches its target at every step, where a fixed black or white lets floaters of the background's colour go
+        free.  The renderer's own background is put back behind the step; lastBackground holds b.  Mode "random" calls the
+        loss without a target key (the target statistics cache cannot serve an image that changes every step); mode "fixed"
+        keeps it.  The feature only sets a blend-level colour and swaps the target: it composes with pose_opt, exposure_opt,
+        bilateral_grid, absgrad, sparse_adam, filter_3d, contrib_prune, strategy='mcmc', an anti-aliased renderer and fuse_adam
+        on or off; single-device steps with one view only.  Off (the default): no kernel, buffer or result differs."""
+        self.background = None
+        self.lastBackground = None
+        self._bgTarget = None
+        self._bgSource = None
+        if background is not None:
+            from .background import BackgroundConfig
+            if not isinstance(background, BackgroundConfig):
+                raise ValueError("background must be a BackgroundConfig")
+            background.validate()
+            _require_single_device("background", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            self.background = background
         if not isinstance(sparse_adam, bool):
             raise ValueError("sparse_adam is True or False")
         self.sparse_adam = sparse_adam
@@ -1431,7 +1455,7 @@ class GaussianTrainer:
         return exchange_summary(self.exchange_impl, self.dp_exchange, self.world, m.N, int(m.geom_numel), int(m.numel), n, sums,
                                 counts, version, source, self.viewsPerRank)
 
-    def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None):
+    def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None, targetAlpha=None):
         """One iteration: forward, loss, backward, (gradient exchange), Adam.  Asynchronous; returns the device
         loss[4].  stepCameras: the cameras of ALL ranks for this step in rank order (every rank derives them from the
         shared view permutation, see view_for), or just their centres [R,3]; required by the sh_compressed exchange.
@@ -1440,7 +1464,14 @@ class GaussianTrainer:
         Reserved-capacity overflow: the step's calls raise GS_ERR_WORKSPACE_OVERFLOW as soon as the host sees the
         device's flag (at the latest at the checks below: the first visit of every view, every densify cadence); the
         reserve is regrown and the step repeated once.  Steps queued in between were skipped on the device (no
-        optimizer update from a blank render), never applied."""
+        optimizer update from a blank render), never applied.
+
+        targetAlpha: the view's alpha, [H, W], with a trainer built with background= (and only then): targetRGB is then the
+        view's straight colour, and the step's target their composite over the step's background."""
+        if (targetAlpha is None) != (self.background is None):
+            raise ValueError("trainStep: targetAlpha goes with a trainer built with background=BackgroundConfig(...)"
+                             if self.background is None else
+                             "trainStep: a trainer built with background= needs targetAlpha (the view's alpha, [H, W])")
         profiled = self.enableIntervalProfiling and (self.iteration % self.profilingLogInterval == 0
                                                      or self.iteration == self.iterationCount - 1)
         step = self._profiledStep if profiled else (self._trainStepMulti if self.viewsPerRank > 1 else self._trainStep)
@@ -1448,6 +1479,12 @@ class GaussianTrainer:
         # knobs of the caller's renderer that this step changes, put back whatever happens
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
         sparse_was = getattr(r, "_sparse_adam", False)
+        bg_was = None
+        if self.background is not None:
+            # the step's colour: the renderer's background for every forward of the step, and the target over it
+            b = self.background.color_at(self.iteration)
+            bg_was = (getattr(r, "_background", None),)
+            targetRGB = self._compositeTarget(targetRGB, targetAlpha, b)
         tables = list(self._perView.values())
         row = tables[0].row(viewKey) if tables else None       # (one n_views for all of them)
         try:
@@ -1458,6 +1495,9 @@ class GaussianTrainer:
                 r.setFilter3D(self._filter)
             if self.sparse_adam and not sparse_was:
                 r.setSparseAdam(True)
+            if self.background is not None:
+                r.setBackground(b)
+                self.lastBackground = b
             for t in tables:
                 t.bindRow(r, row)
             if self._exchange:
@@ -1479,8 +1519,34 @@ class GaussianTrainer:
                 r.setFilter3D(None)
             if self.sparse_adam and not sparse_was:
                 r.setSparseAdam(False)
+            if bg_was is not None:
+                r.setBackground(bg_was[0])
             for t in tables:
                 t.unbind(r)
+
+    def _compositeTarget(self, targetRGB, targetAlpha, b):
+        """The step's target: targetRGB over b by targetAlpha, in the trainer's own buffer (allocated once)."""
+        r = self.gaussRender
+        rgb, alpha = r._t(targetRGB), r._t(targetAlpha)
+        if rgb.dim() != 3 or rgb.shape[-1] != 3 or tuple(alpha.shape) != tuple(rgb.shape[:2]):
+            raise ValueError("trainStep: targetRGB is [H, W, 3] and targetAlpha [H, W]")
+        if self._bgTarget is None or self._bgTarget.shape != rgb.shape:
+            self._bgTarget = torch.empty_like(rgb)
+        # what the composite was made of: the buffer is one for all views and is written behind torch's back, so its own identity
+        # (which the renderer's target statistics cache checks) says nothing about the image it holds
+        self._bgSource = (rgb.data_ptr(), rgb._version, alpha.data_ptr(), alpha._version, tuple(rgb.shape)) + tuple(float(x) for x in b)
+        return r.compositeTarget(rgb, alpha, b, out=self._bgTarget)
+
+    def _lossTargetKey(self, viewKey):
+        """The key the loss caches the target's statistics under: none where the target changes every step (mode "random"); in
+        mode "fixed" the view key together with the identity of the RGBA tensors and the colour the composite was made of, so that
+        another image behind the key, an in-place write to it or another colour is a cache miss, as a rewritten target is without
+        the feature (device tensors that stay where they are hit; a host array is uploaded anew every step and never does)."""
+        if self.background is None or viewKey is None:
+            return viewKey
+        if self.background.mode == "random":
+            return None
+        return ("background", viewKey) + self._bgSource
 
     def _table(self, who: str, feature: str) -> _PerViewTable:
         if feature not in self._perView:
@@ -1593,14 +1659,14 @@ class GaussianTrainer:
                 res = r.renderForward(m.getParams(), camera, viewKey=viewKey, wantDepth=False)
         r._measure("train.loss.total", lambda: r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim,
                                                                       out=dict(loss=lossOut, cotColor=self._cot),
-                                                                      targetKey=viewKey))
+                                                                      targetKey=self._lossTargetKey(viewKey)))
         # depth cuts (renderer.renderForward): nothing that changes state has been queued yet; the loss kernel above
         # keeps the GPU busy while the host learns whether the forward has to be repeated in full
         if viewKey is not None and r.forwardMissed():
             self.forwardMisses += 1
             res = r.renderForward(m.getParams(), camera, viewKey=viewKey, depthCuts=False, wantDepth=False)
             r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim, out=dict(loss=lossOut, cotColor=self._cot),
-                                  targetKey=viewKey)
+                                  targetKey=self._lossTargetKey(viewKey))
 
     def _geometryAdam(self, lr: dict, scale: float):
         """Adam on the geometry slice after the all-reduce; the xyz segment's gradient = reduced + the view-direction terms the

@@ -351,6 +351,28 @@ int gs_apply_bilateral_grid(gs_ctx* ctx, int W, int H, const float* grid /*DEVIC
  * record it: render a model in the mode it was trained in. */
 int gs_set_antialiasing(gs_ctx* ctx, int enable);
 
+/* Background colour (not in the reference, which composites over black or white; Inria's
+ * --random_background, gsplat's backgrounds=).  With a colour b set, every following blend forward writes, per pixel and channel,
+ *   out_c = sums_c + T b_c        (T the final transmittance; alpha, depth and nContrib do not change),
+ * and its backward takes cT = -cot_alpha + g . b as the transmittance's cotangent.  T b_c is one rounded float32 product.
+ * rgb == NULL (the default) is the creation background (white_bg): images and gradients are then bit for bit what they are on a
+ * context that never had a colour.  The three values must be finite and are not confined to [0, 1]; otherwise
+ * GS_ERR_INVALID_ARG, and the previous setting stays.  The colour is a by-value kernel argument: the call allocates nothing,
+ * waits for nothing and may be made before every step.  A per-context setting as gs_set_antialiasing is: it holds for the
+ * forwards that follow, and a fused backward (gs_render_backward, gs_render_backward_adam, gs_render_backward_dp*) uses the
+ * background of its gs_render_forward, whatever has been set since.  The op-level gs_blend_forward / gs_blend_backward keep no
+ * forward of their own and read the setting in effect at the call.  gs_render_contrib / gs_blend_contrib do not see it: blend
+ * weights carry no background.  Honoured on every path a forward can take (one-wave, pair and four-wave forwards, block lists,
+ * the generic and cull kernels at every GS_TUNE_OP_*_PPL). */
+int gs_set_background(gs_ctx* ctx, const float* rgb /*HOST [3] or NULL*/);
+/* The colour in effect: the one set, or (1,1,1) / (0,0,0) for an unset context by its white_bg. */
+int gs_get_background(gs_ctx* ctx, float rgb[3] /*HOST*/);
+/* The training target of an RGBA view over bg: out_c = fmaf(a, rgb_c, (1 - a) bg_c) for n_pixels pixels, rgb straight
+ * (un-premultiplied).  out may be rgb itself.  Asynchronous on the ctx stream, allocates nothing.  n_pixels < 0 or a NULL
+ * pointer: GS_ERR_INVALID_ARG; n_pixels == 0: nothing is launched. */
+int gs_composite_target(gs_ctx* ctx, long long n_pixels, const float* rgb /*DEVICE [n,3]*/, const float* alpha /*DEVICE [n]*/,
+                        const float* bg /*HOST [3]*/, float* out /*DEVICE [n,3]*/);
+
 /* AbsGS densification statistic (not in the reference; Ye et al. 2024, gsplat's absgrad=True).  The
  * gradient of the loss with respect to a splat's 2-D mean is a sum over the pixels it covers; on a large splat over fine detail
  * the pixels pull in opposite directions and the sum cancels ("gradient collision").  With absgrad on, the blend backward of
