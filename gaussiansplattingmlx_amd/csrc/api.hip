@@ -1498,6 +1498,7 @@ int gs_loss_forward_backward(gs_ctx* c, const float* render, const float* target
     if (!c->bgGrid && !c->expoM)
         return launch_loss(c, render, target, render_depth, target_depth, depth_mask, lambda_dssim, lambda_depth, loss_out,
                            cot_color, cot_depth);
+    // (a loss mask, gs_set_loss_mask, is launch_loss's business: the correction's backward below gets the weighted cotangent)
     // A per-view colour correction is bound -- a bilateral grid (the sliced transform) or an exposure (A r + b), never both:
     // the loss of the corrected image (the ctx's scratch image; the render itself is left alone), then the correction's
     // backward: cot_color <- dL/d render, grad <- dL/dG or dL/dM
@@ -1526,6 +1527,13 @@ int gs_set_loss_target_cache(gs_ctx* c, float* cache, int filled)
     if (!c) return GS_ERR_INVALID_ARG;
     c->lossTargetCache = cache;
     c->lossTargetCacheFilled = cache != nullptr && filled != 0;
+    return GS_OK;
+}
+
+int gs_set_loss_mask(gs_ctx* c, const unsigned char* mask)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    c->lossMask = mask;      // read by launch_loss (ssim.hip) only
     return GS_OK;
 }
 

@@ -325,6 +325,7 @@ struct gs_ctx {
     float* lossPartials = nullptr;    // [lossPartialBlocks*4 + 16]
     float* lossTargetCache = nullptr; // caller-owned [2][3][H][W]: the target's windowed mean and mean of squares (ssim.hip)
     bool lossTargetCacheFilled = false;
+    const unsigned char* lossMask = nullptr;   // gs_set_loss_mask: caller-owned [H][W] per-pixel loss weights v / 255, nullptr = off
     int lossPartialBlocks = 0;
     float* windowDev = nullptr;       // [121] default SSIM window
     // densify scan scratch: [densifyTileCap] tile sums + 8 counters, grown on demand

@@ -173,14 +173,28 @@ constexpr int loss_strip(int lines, int outputs, int threads, int lo, int hi)
 // them as always and keep them (tcache: [2][3][H][W], caller-owned, one per view: gs_set_loss_target_cache); 2: read them
 // -- three planes instead of five in both passes and in LDS (48 KB instead of 65: three blocks per CU).  The values are
 // the very floats mode 1 computed, so the loss and its cotangent are bit-identical with and without the cache.
-template <int TX, int TY, int NT, int TCACHE>
+//
+// MASK: a per-pixel loss mask is bound (gs_set_loss_mask: uint8 [H][W], weight w = v / 255).  The loss is then the very loss
+// of the weighted images w R and w G: the patches are weighted on their way into LDS, so the four passes, the partial sums
+// and the target cache (mode 1 keeps the statistics of the MASKED target, mode 2 reads them) see nothing but other inputs,
+// and the chain rule's dL/dR = w dL/d(wR) is one multiply by the pixel's own w at the final store.  The quotient is the
+// correctly rounded one (255 -> 1.0f, 0 -> 0.0f) and that multiply is the last operation, so the results are, bit for bit,
+// those of the unmasked kernel on images weighted beforehand, the cotangent times w.  The pointer is a trailing argument
+// that only the MASK instantiations have (a pack of one or none: even an empty struct would lengthen the kernel's argument
+// block): MASK = false is the kernel as it was, arguments included.
+__device__ __forceinline__ const unsigned char* loss_mask_of() { return nullptr; }
+__device__ __forceinline__ const unsigned char* loss_mask_of(const unsigned char* m) { return m; }
+
+template <int TX, int TY, int NT, int TCACHE, bool MASK, typename... MaskPtr>
 __global__ __launch_bounds__(NT) void loss_fused_kernel(int H, int W, int ntx, int nty,
                                                         const float* __restrict__ img1,
                                                         const float* __restrict__ img2, float upstream,
                                                         float l1Weight, float* __restrict__ cot,
                                                         float* __restrict__ partials, BwdPrepArgs prep, int prepBlocks, int cutBlocks, SsimTaps taps,
-                                                        float* __restrict__ tcache)
+                                                        float* __restrict__ tcache, MaskPtr... maskArg)
 {
+    static_assert(sizeof...(MaskPtr) == (MASK ? 1 : 0), "the mask argument exists with MASK only");
+    const unsigned char* const mask = loss_mask_of(maskArg...);
     constexpr int LCX = TX + LK - 1, LCY = TY + LK - 1;        // window centres that reach the tile
     constexpr int LIX = LCX + LK - 1, LIY = LCY + LK - 1;      // input patch
     constexpr int NPL = TCACHE == 2 ? 3 : 5;                   // statistic planes computed here: (mu1, E11, E12) or (mu1, mu2, E11, E22, E12)
@@ -220,11 +234,23 @@ __global__ __launch_bounds__(NT) void loss_fused_kernel(int H, int W, int ntx, i
     if (tileId >= nTiles) return;          // whole block: the grid is 8 * 3 * perXcd
     const int ty = tileId / ntx, tx = tileId - ty * ntx;
     const int h0 = ty * TY, w0 = tx * TX;
+    constexpr int PPT = TX * TY / NT;
+    float ownW[MASK ? PPT : 1];         // MASK: the weights of this thread's own pixels, for the final store
     {   // the two input patches.  All of a thread's loads are issued before the first is used (unconditional, from
         // clamped addresses): as a loop with the loads under `if (inside the image)` every iteration waited for its
         // own pair -- six memory latencies in a row at the head of every block of a latency-bound kernel
         constexpr int NLD = (LIY * LIX + NT - 1) / NT;
         float va[NLD], vb[NLD];
+        // MASK: the mask bytes join the same round of loads, from the same clamped pixel (and this thread's own pixels',
+        // clamped alike: a partial tile's pixels beyond the image are never stored)
+        unsigned char vm[MASK ? NLD : 1], om[MASK ? PPT : 1];
+        if constexpr (MASK) {
+#pragma unroll
+            for (int k = 0; k < PPT; k++) {
+                const int p = tid + k * NT, ly = p / TX, lx = p - ly * TX;
+                om[k] = mask[(size_t)min(h0 + ly, H - 1) * W + min(w0 + lx, W - 1)];
+            }
+        }
 #pragma unroll
         for (int k = 0; k < NLD; k++) {
             const int i = tid + k * NT;
@@ -234,8 +260,18 @@ __global__ __launch_bounds__(NT) void loss_fused_kernel(int H, int W, int ntx, i
             const int shc = min(max(sh, 0), H - 1), swc = min(max(sw, 0), W - 1);
             const size_t si = ((size_t)shc * W + swc) * 3 + c;
             const float a = img1[si], b = img2[si];
+            if constexpr (MASK) vm[k] = mask[(size_t)shc * W + swc];
             va[k] = ok ? a : 0.0f;
             vb[k] = ok ? b : 0.0f;
+        }
+        if constexpr (MASK) {
+#pragma unroll
+            for (int k = 0; k < NLD; k++) {
+                const float w = (float)vm[k] / 255.0f;
+                va[k] = w * va[k]; vb[k] = w * vb[k];
+            }
+#pragma unroll
+            for (int k = 0; k < PPT; k++) ownW[k] = (float)om[k] / 255.0f;
         }
 #pragma unroll
         for (int k = 0; k < NLD; k++) {
@@ -245,7 +281,6 @@ __global__ __launch_bounds__(NT) void loss_fused_kernel(int H, int W, int ntx, i
     }
     __syncthreads();
     // this thread's own pixels (pixel p = tid + k NT of the tile, row-major), before the patches are reused
-    constexpr int PPT = TX * TY / NT;
     float own1[PPT], own2[PPT];
 #pragma unroll
     for (int k = 0; k < PPT; k++) {
@@ -384,7 +419,9 @@ __global__ __launch_bounds__(NT) void loss_fused_kernel(int H, int W, int ntx, i
             const float v1 = own1[kk], v2 = own2[kk];
             const float d = v1 - v2;
             l1 += fabsf(d);
-            cot[((size_t)h * W + w) * 3 + c] = A + 2.0f * v1 * B + v2 * Cc + l1Weight * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.0f));
+            const float cv = A + 2.0f * v1 * B + v2 * Cc + l1Weight * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.0f));
+            if constexpr (MASK) cot[((size_t)h * W + w) * 3 + c] = ownW[kk] * cv;     // v1, v2 are w R, w G here
+            else cot[((size_t)h * W + w) * 3 + c] = cv;
         }
     }
     // block partial sums: |R-G| and ssim
@@ -545,11 +582,17 @@ int launch_loss(gs_ctx* c, const float* render, const float* target, const float
     constexpr size_t lds3 = sizeof(float) * ((size_t)2 * (LTY + 20) * (LTX + 20) + (size_t)3 * (LTY + 20) * (LTX + 10));
     static bool ldsAllowed = false;
     if (!ldsAllowed) {
-        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 0>),
+        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 0, false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5));
-        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 1>),
+        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 1, false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5));
-        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 2>),
+        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 2, false>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
+        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 0, true, const unsigned char*>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5));
+        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 1, true, const unsigned char*>),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds5));
+        GS_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<LTX, LTY, LNT, 2, true, const unsigned char*>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
         ldsAllowed = true;
     }
@@ -557,15 +600,20 @@ int launch_loss(gs_ctx* c, const float* render, const float* target, const float
     const int tmode = c->lossTargetCache ? (c->lossTargetCacheFilled ? 2 : 1) : 0;
     const dim3 lgrid(prepBlocks + 8 * 3 * perXcd), lblock(LNT);
     const float up = -lambdaDssim / (float)n3, l1w = (1.0f - lambdaDssim) / (float)n3;
-    if (tmode == 2)
-        hipLaunchKernelGGL((loss_fused_kernel<LTX, LTY, LNT, 2>), lgrid, lblock, lds3, c->stream, H, W, (int)grid.x, (int)grid.y, render, target,
-                           up, l1w, cotColor, c->lossPartials, prep, prepBlocks, cutBlocks, taps, c->lossTargetCache);
-    else if (tmode == 1)
-        hipLaunchKernelGGL((loss_fused_kernel<LTX, LTY, LNT, 1>), lgrid, lblock, lds5, c->stream, H, W, (int)grid.x, (int)grid.y, render, target,
-                           up, l1w, cotColor, c->lossPartials, prep, prepBlocks, cutBlocks, taps, c->lossTargetCache);
-    else
-        hipLaunchKernelGGL((loss_fused_kernel<LTX, LTY, LNT, 0>), lgrid, lblock, lds5, c->stream, H, W, (int)grid.x, (int)grid.y, render, target,
-                           up, l1w, cotColor, c->lossPartials, prep, prepBlocks, cutBlocks, taps, nullptr);
+    // (a macro, not a lambda: the template arguments are the instantiation; without a mask, today's three with today's arguments)
+#define GS_LAUNCH_LOSS(KERNEL, LDS, ...)                                                                                       \
+    hipLaunchKernelGGL(KERNEL, lgrid, lblock, LDS, c->stream, H, W, (int)grid.x, (int)grid.y, render, target, up, l1w, cotColor, \
+                       c->lossPartials, prep, prepBlocks, cutBlocks, taps, __VA_ARGS__)
+    if (const unsigned char* const lm = c->lossMask) {
+        if (tmode == 2) GS_LAUNCH_LOSS((loss_fused_kernel<LTX, LTY, LNT, 2, true, const unsigned char*>), lds3, c->lossTargetCache, lm);
+        else if (tmode == 1) GS_LAUNCH_LOSS((loss_fused_kernel<LTX, LTY, LNT, 1, true, const unsigned char*>), lds5, c->lossTargetCache, lm);
+        else GS_LAUNCH_LOSS((loss_fused_kernel<LTX, LTY, LNT, 0, true, const unsigned char*>), lds5, nullptr, lm);
+    } else {
+        if (tmode == 2) GS_LAUNCH_LOSS((loss_fused_kernel<LTX, LTY, LNT, 2, false>), lds3, c->lossTargetCache);
+        else if (tmode == 1) GS_LAUNCH_LOSS((loss_fused_kernel<LTX, LTY, LNT, 1, false>), lds5, c->lossTargetCache);
+        else GS_LAUNCH_LOSS((loss_fused_kernel<LTX, LTY, LNT, 0, false>), lds5, nullptr);
+    }
+#undef GS_LAUNCH_LOSS
     if (tmode == 1) c->lossTargetCacheFilled = true;
     if (depthOn)
         hipLaunchKernelGGL(depth_reduce_kernel, dim3(nb < 512 ? nb : 512), dim3(256), 0, c->stream, np, renderDepth,

@@ -3,7 +3,8 @@ Data/BlenderDataLoader.swift): file formats, pose / intrinsics conventions, the 
 
 What is mirrored exactly: the binary / JSON / PLY parsing, quaternion -> rotation, world-to-camera inversion, the
 OpenGL -> OpenCV flip (rows 1-2 of w2c negated), intrinsics scaling by resizeFactor, white-background compositing,
-the tile size rule (W/4, H/4).  What is not: image decoding and resampling (the reference goes through UIKit /
+the tile size rule (W/4, H/4).  Not in the reference: per-view loss masks (readMask, TrainData.maskArray).
+What is not mirrored: image decoding and resampling (the reference goes through UIKit /
 CoreGraphics; here PIL, bilinear) and the downloads / unzipping of the demo sets (no network: loaders take paths)."""
 from __future__ import annotations
 
@@ -29,6 +30,7 @@ class TrainData:
     rgbArray: np.ndarray
     alphaArray: np.ndarray
     depthArray: np.ndarray | None = None
+    maskArray: np.ndarray | None = None       # uint8 [n, H, W] loss masks (255 keeps a pixel), None when no view has one
 
     def getCameraParams(self):
         return self.Hs, self.Ws, self.intrinsicArray, self.c2wArray
@@ -47,6 +49,30 @@ def readImageRGBA(path, resizeFactor: float = 1.0):
     """ColmapDataLoader.readImage / NerfStudio readImage: rgb [H,W,3], alpha [H,W], H, W (floats in [0,1])."""
     rgba = _load_image(path, resizeFactor, "RGBA")
     return rgba[..., :3], rgba[..., 3], float(rgba.shape[0]), float(rgba.shape[1])
+
+
+def readMask(path, resizeFactor: float = 1.0):
+    """A view's loss mask (trainStep's lossMask): uint8 [H, W], the file's grey levels (PIL mode "L") under the images' own
+    bilinear resize.  White keeps a pixel; nothing is inverted or thresholded."""
+    from PIL import Image
+    img = Image.open(path).convert("L")
+    if resizeFactor != 1.0:
+        img = img.resize((int(img.size[0] * resizeFactor), int(img.size[1] * resizeFactor)), Image.BILINEAR)
+    return np.array(img, np.uint8)
+
+
+def _stack_masks(paths, Hs, Ws, resizeFactor: float):
+    """maskArray of the views whose mask files are `paths` (None: the view has none): None when no view has a mask, else
+    uint8 [n, H, W] with all 255 (keep everything) for a view without one."""
+    if all(p is None for p in paths):
+        return None
+    masks = []
+    for p, H, W in zip(paths, Hs, Ws):
+        m = np.full((int(H), int(W)), 255, np.uint8) if p is None else readMask(p, resizeFactor)
+        if m.shape != (int(H), int(W)):
+            raise ValueError(f"mask {p}: {m.shape[1]} x {m.shape[0]} after the resize, its image is {int(W)} x {int(H)}")
+        masks.append(m)
+    return np.stack(masks)
 
 
 def _stack_frames(frames, whiteBackground: bool):
@@ -136,8 +162,18 @@ def colmapReadPointSet(points3DPath):
 
 
 class ColmapDataLoader:
-    def __init__(self, binRoot, imageRoot):
-        self.binRoot, self.imageRoot = binRoot, imageRoot
+    def __init__(self, binRoot, imageRoot, maskRoot=None):
+        """maskRoot: a directory of per-view loss masks (TrainData.maskArray).  A view's mask is <maskRoot>/<image file
+        name>.png (COLMAP's own convention: "frame.jpg.png") or, failing that, <maskRoot>/<image file name without its
+        extension>.png; a view with neither keeps every pixel."""
+        self.binRoot, self.imageRoot, self.maskRoot = binRoot, imageRoot, maskRoot
+
+    def _maskPath(self, imagePath):
+        name = os.path.relpath(imagePath, self.imageRoot)
+        for cand in (name + ".png", os.path.splitext(name)[0] + ".png"):
+            if os.path.exists(os.path.join(self.maskRoot, cand)):
+                return os.path.join(self.maskRoot, cand)
+        return None
 
     def getOriginalImageSize(self):
         camMap, poses = colmapReadCamerasAndPoses(self.binRoot, self.imageRoot)
@@ -155,7 +191,8 @@ class ColmapDataLoader:
         pts, cols = colmapReadPointSet(os.path.join(self.binRoot, "points3D.bin"))
         ch = cols.astype(np.float32) / np.float32(255.0)
         pcd = PointCloud(pts.astype(np.float32), dict(R=ch[:, 0], G=ch[:, 1], B=ch[:, 2]))
-        return (TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, None), pcd,
+        masks = None if self.maskRoot is None else _stack_masks([self._maskPath(p.filePath) for p in poses], Hs, Ws, resizeFactor)
+        return (TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, None, masks), pcd,
                 TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
 
 
@@ -200,7 +237,8 @@ class NerfStudioDataLoader:
         self.directory = directory
 
     def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA):
-        """loadTrainDataAndPointCloud (:385-416): transforms.json + its ply_file_path."""
+        """loadTrainDataAndPointCloud (:385-416): transforms.json + its ply_file_path.  A frame's "mask_path" (relative to the
+        dataset directory, as nerfstudio writes it) is its loss mask (TrainData.maskArray)."""
         meta = json.load(open(os.path.join(self.directory, "transforms.json")))
         xyz, rgb = parsePLY(os.path.join(self.directory, meta["ply_file_path"]))
         ch = rgb.astype(np.float32) / np.float32(255.0)
@@ -208,8 +246,9 @@ class NerfStudioDataLoader:
 
         def intrinsic(d):
             return _intrinsics3(d["fl_x"], d["fl_y"], d["cx"], d["cy"]) if all(k in d for k in ("fl_x", "fl_y", "cx", "cy")) else None
-        intr, c2ws, frames = [], [], []
+        intr, c2ws, frames, maskPaths = [], [], [], []
         for fr in meta["frames"]:
+            maskPaths.append(os.path.join(self.directory, fr["mask_path"]) if fr.get("mask_path") else None)
             K = intrinsic(fr)
             K = intrinsic(meta) if K is None else K
             if K is None:
@@ -221,7 +260,8 @@ class NerfStudioDataLoader:
             # the reference reads transform_matrix as Float before widening (:359)
             c2ws.append(opengl_c2w_to_opencv(np.asarray(fr["transform_matrix"], np.float32).astype(np.float64)).astype(np.float32))
         Hs, Ws, rgbs, alphas = _stack_frames(frames, whiteBackground)
-        return (TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None), pcd,
+        return (TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None,
+                          _stack_masks(maskPaths, Hs, Ws, resizeFactor)), pcd,
                 TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
 
 

@@ -15,7 +15,7 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, loss_mask
 from ._lib import GsplatError
 
 TILE_SIZE_H_W = namedtuple("TILE_SIZE_H_W", ["w", "h"])
@@ -114,6 +114,7 @@ class GaussianRenderer:
         self._background = None
         self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
         self._bilateral = (None, None)  # setBilateralGrid's, likewise
+        self._loss_mask = None         # setLossMask's uint8 device tensor, likewise
         if antialiased:
             self.setAntialiased(True)
 
@@ -121,6 +122,7 @@ class GaussianRenderer:
         if getattr(self, "ctx", None):
             self.lib.gs_set_block_work_buffer(self.ctx, None)
             self.lib.gs_set_loss_target_cache(self.ctx, None, 0)
+            self.lib.gs_set_loss_mask(self.ctx, None)
             self.lib.gs_set_grad_norm_accum(self.ctx, None)
             self.lib.gs_ctx_destroy(self.ctx)
             self.ctx = None
@@ -607,6 +609,36 @@ class GaussianRenderer:
         self._check(self.lib.gs_apply_bilateral_grid(self.ctx, W, H, _p(grid), gw, gh, gl, _p(img), _p(out)))
         return out
 
+    # -- per-pixel loss mask (include/gsplat.h gs_set_loss_mask; loss_mask.py restates it) --------------
+    def setLossMask(self, mask=None):
+        """gs_set_loss_mask: a uint8 (weight v / 255; 255 keeps a pixel, 0 ignores it) or bool (0 / 255) image of shape (H, W),
+        tensor or array, or None (off, the default).  The following lossForwardBackward calls take the loss of the weighted
+        render and target -- after a bound exposure or bilateral grid -- normalised over all pixels as without a mask (no
+        division by the mask's coverage), and return w * dL/d(w render) as the colour cotangent: exactly zero where the mask is.
+        A contiguous uint8 device tensor is bound as it is (write it in place and the next loss sees it); anything else is
+        converted and uploaded once, here."""
+        if mask is None:
+            self._check(self.lib.gs_set_loss_mask(self.ctx, None))
+            self._loss_mask = None
+            return
+        loss_mask.validate(mask, self.H, self.W, "setLossMask")
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(loss_mask.as_uint8(mask)))
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8) * 255
+        mask = mask.to(self.device).contiguous()
+        self._check(self.lib.gs_set_loss_mask(self.ctx, _p(mask)))
+        self._loss_mask = mask            # (kept alive while the library holds its address)
+
+    @property
+    def lossMask(self):
+        """The bound mask as the uint8 device tensor the library reads, or None."""
+        return self._loss_mask
+
+    @lossMask.setter
+    def lossMask(self, mask):
+        self.setLossMask(mask)
+
     def setAntialiased(self, enable: bool = True):
         """gs_set_antialiasing: the anti-aliased mode (Mip-Splatting's 2-D filter; include/gsplat.h) for the
         following renderForward calls, off by default.  Every backward uses the mode of its forward, so a GaussianTrainer
@@ -1052,14 +1084,17 @@ class GaussianRenderer:
         """targetKey: any hashable naming the target image (e.g. the training view index).  When given, the target's
         windowed statistics are kept in a per-key device buffer at the first call (15 MB at 800x800) and read back at the
         later ones (gs_set_loss_target_cache); the results are bit-identical either way.  A key whose target tensor has
-        changed (another storage, or written in place since) is refilled; the caches together are capped at
+        changed (another storage, or written in place since), or that was filled under another loss mask (setLossMask: another
+        tensor, none, or the same written in place since), is refilled; the caches together are capped at
         targetStatsCacheBytes, least recently used keys first."""
         render, target = self._t(render), self._t(target)
         ent = None
         if targetKey is not None and self.targetStatsCache:
             # an entry is valid for ONE image: same storage and no in-place write since it was filled (a target rewritten in
             # place, or another image in a reused allocator block, refills it); invalidateTarget(key) drops it explicitly
-            ident = (target.data_ptr(), target._version, tuple(target.shape))
+            # ... under ONE mask: the statistics are those of the weighted target (gs_set_loss_mask)
+            lm = self._loss_mask
+            ident = (target.data_ptr(), target._version, tuple(target.shape), None if lm is None else (lm.data_ptr(), lm._version))
             ent = self._target_cache.get(targetKey)
             if ent is None or ent[1] != ident:
                 n = C.c_longlong()

@@ -1455,7 +1455,7 @@ class GaussianTrainer:
         return exchange_summary(self.exchange_impl, self.dp_exchange, self.world, m.N, int(m.geom_numel), int(m.numel), n, sums,
                                 counts, version, source, self.viewsPerRank)
 
-    def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None, targetAlpha=None):
+    def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None, targetAlpha=None, lossMask=None):
         """One iteration: forward, loss, backward, (gradient exchange), Adam.  Asynchronous; returns the device
         loss[4].  stepCameras: the cameras of ALL ranks for this step in rank order (every rank derives them from the
         shared view permutation, see view_for), or just their centres [R,3]; required by the sh_compressed exchange.
@@ -1467,7 +1467,24 @@ class GaussianTrainer:
         optimizer update from a blank render), never applied.
 
         targetAlpha: the view's alpha, [H, W], with a trainer built with background= (and only then): targetRGB is then the
-        view's straight colour, and the step's target their composite over the step's background."""
+        view's straight colour, and the step's target their composite over the step's background.
+
+        lossMask: regions of this view to ignore (include/gsplat.h gs_set_loss_mask; gsplat's masks=,
+        Inria's alpha_mask): a uint8 (weight v / 255: 255 keeps a pixel, 0 ignores it, between is a soft edge) or bool (0 / 255)
+        image [H, W], tensor or array.  It is bound to the renderer for the step's forwards and losses -- a forward repeated for
+        an overflow or a depth-cut miss included -- and the renderer's previous mask is put back behind the step.  The step's
+        colour loss is that of the weighted render and target, still divided by all 3 H W elements (no re-normalisation by the
+        mask's coverage: a kept pixel's gradient has the scale it has without a mask), and its cotangent is exactly zero where
+        the mask is: an ignored region moves no Gaussian, trains no exposure or grid and adds nothing to a densify statistic.
+        A uint8 device tensor that stays where it is keeps the view's target statistics cached; a host array is uploaded anew
+        every step and refills them.  Needs no constructor argument; composes with pose_opt, exposure_opt, bilateral_grid,
+        absgrad, sparse_adam, filter_3d, contrib_prune, background, strategy='mcmc', an anti-aliased renderer and fuse_adam on
+        or off; single-device steps with one view only.  None (the default): no kernel, buffer or result differs."""
+        if lossMask is not None:
+            if self.viewsPerRank != 1:
+                raise ValueError("trainStep: lossMask takes one view per step only (views_per_rank > 1 is not supported)")
+            if self.pg is not None or self.exchange_impl == "native":
+                raise ValueError("trainStep: lossMask takes single-device steps only (no process group, dp_bootstrap or native exchange)")
         if (targetAlpha is None) != (self.background is None):
             raise ValueError("trainStep: targetAlpha goes with a trainer built with background=BackgroundConfig(...)"
                              if self.background is None else
@@ -1479,7 +1496,7 @@ class GaussianTrainer:
         # knobs of the caller's renderer that this step changes, put back whatever happens
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
         sparse_was = getattr(r, "_sparse_adam", False)
-        bg_was = None
+        bg_was = mask_was = None
         if self.background is not None:
             # the step's colour: the renderer's background for every forward of the step, and the target over it
             b = self.background.color_at(self.iteration)
@@ -1500,6 +1517,10 @@ class GaussianTrainer:
                 self.lastBackground = b
             for t in tables:
                 t.bindRow(r, row)
+            if lossMask is not None:
+                was = r.lossMask
+                r.setLossMask(lossMask)
+                mask_was = (was,)
             if self._exchange:
                 r.setTuning(host_overflow_errors=0)
                 if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
@@ -1521,6 +1542,8 @@ class GaussianTrainer:
                 r.setSparseAdam(False)
             if bg_was is not None:
                 r.setBackground(bg_was[0])
+            if mask_was is not None:
+                r.setLossMask(mask_was[0])
             for t in tables:
                 t.unbind(r)
 

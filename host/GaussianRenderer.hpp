@@ -157,6 +157,9 @@ public:
     // buffer of lossTargetCacheFloats() floats, one per view; filled = false at a view's first loss, true afterwards.
     long long lossTargetCacheFloats() { long long n = 0; check(gs_loss_target_cache_floats(ctx_, &n)); return n; }
     void setLossTargetCache(float* cache, bool filled) { check(gs_set_loss_target_cache(ctx_, cache, filled ? 1 : 0)); }
+    // Per-pixel loss mask (include/gsplat.h gs_set_loss_mask): while mask (device uint8 [H, W], weight v / 255) is set, loss()
+    // is the loss of the weighted render and target; nullptr (the default) turns it off.
+    void setLossMask(const unsigned char* mask) { check(gs_set_loss_mask(ctx_, mask)); }
 
     // ---- data-parallel step (include/gsplat.h, "row e"): one process per GPU, one renderer per process --------------
     // The densify event without a drain of the queue (ABI 5): the count stays on the device (plan), the host waits for the plan

@@ -717,6 +717,28 @@ int gs_loss_forward_backward(gs_ctx* ctx, const float* render, const float* targ
 int gs_loss_target_cache_floats(gs_ctx* ctx, long long* n /*HOST*/);
 int gs_set_loss_target_cache(gs_ctx* ctx, float* cache /*DEVICE or NULL*/, int filled);
 
+/* Per-pixel loss mask (not in the reference; DESIGN.md "Loss masks"): regions of a training view to ignore, as gsplat's
+ * masks= and Inria's alpha_mask take them -- both multiply the render and the ground truth by the mask before the loss.
+ * mask DEVICE uint8 [H, W] (the ctx's image size), caller-owned and kept alive while set; pixel weight w = (float)v / 255.0f,
+ * one correctly rounded division: 255 is exactly 1.0f (keep), 0 exactly 0.0f (ignore), the values between are soft weights
+ * (an anti-aliased matte edge).  While a mask is set, the colour loss of each gs_loss_forward_backward is the loss above of
+ * the weighted images w R' and w G, with R' the render after a set exposure or bilateral grid (the render itself without):
+ *   L = (1-l) sum|w R' - w G| / (3P) + l (1 - sum ssim(w R', w G) / (3P)),   P = H W.
+ * Both sums and the divisor run over ALL pixels, as in gsplat and Inria; there is no re-normalisation by sum w.  A fully
+ * masked neighbourhood has ssim exactly 1 and L1 exactly 0 (it costs nothing and pushes nothing), and a kept pixel's gradient
+ * has the scale it has without a mask, so no learning rate changes.  cot_color = w * dL/d(w R'), the multiply by w being the
+ * last operation: exactly 0.0f wherever v = 0, and bit for bit w times the cotangent of the unmasked loss of images weighted
+ * beforehand; loss_out likewise equals that loss's.  A mask of all 255 gives the unmasked loss and cotangent bit for bit.
+ * With an exposure or a bilateral grid set the order is correction -> masked loss -> the correction's backward, fed the
+ * already weighted cotangent: the correction learns from kept pixels only.  The target cache (gs_set_loss_target_cache) then
+ * holds the statistics of the MASKED target -- refill it (filled = 0) when the mask changes -- and the three cache modes
+ * stay bit-identical.  The depth term (with its own depth_mask), the render, alpha, depth and every forward / backward entry
+ * point are unchanged: the blend backward, the densification statistics, sparse Adam and MCMC see the mask through cot_color
+ * alone.  Sticky like gs_set_exposure: read by gs_loss_forward_backward only, from this call until a NULL call.  NULL (the
+ * default) issues the loss's launches exactly as without it, kernel for kernel.  The op-level gs_ssim_* ignore the setting.
+ * No reference call site (GaussianTrainer.swift:689-714 takes the loss of every pixel). */
+int gs_set_loss_mask(gs_ctx* ctx, const unsigned char* mask /*DEVICE [H,W] or NULL*/);
+
 /* ---- next row: optimizer step ---------------------------------------------------------------- */
 
 /* Adam over one flat parameter arena, as the trainer applies it per tensor (GaussianTrainer.swift:941-948,

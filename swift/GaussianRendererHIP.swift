@@ -154,6 +154,10 @@ public final class GaussianRendererHIP {
         try check(gs_set_loss_target_cache(ctx, cache, filled ? 1 : 0))
     }
 
+    /// Per-pixel loss mask (gs_set_loss_mask): while mask (device uint8 [H, W], weight v / 255) is set, the loss is that of
+    /// the weighted render and target; nil (the default) turns it off.
+    public func setLossMask(_ mask: UnsafePointer<UInt8>?) throws { try check(gs_set_loss_mask(ctx, mask)) }
+
     /// Mip-Splatting's 3-D smoothing filter (include/gsplat.h gs_set_filter3d): the training cameras the widths are measured
     /// against, the widths of a set of positions, the filter of the following forwards (nil = off), and the baked export.
     public func setFilterCameras(_ cameras: [gs_camera]) throws {
