@@ -43,6 +43,12 @@ class gs_mcmc_params(C.Structure):
                 ("iteration", C.c_int), ("seed", C.c_ulonglong)]
 
 
+class gs_depth_loss_params(C.Structure):
+    # (`lambda` is the header's name for the second field; a Python attribute cannot be called that)
+    _fields_ = [("mode", C.c_int), ("lambda_", C.c_float), ("alpha_min", C.c_float), ("scale", C.c_float), ("offset", C.c_float)]
+
+
+GS_DEPTH_ACCUMULATED, GS_DEPTH_EXPECTED, GS_DEPTH_DISPARITY = 0, 1, 2
 GS_DP_ALLREDUCE, GS_DP_SH_COMPRESSED = 0, 1
 GS_DP_UNIQUE_ID_BYTES = 128
 
@@ -128,6 +134,8 @@ _SIGS = {
     "gs_set_loss_target_cache": (C.c_int, [_vp, _vp, C.c_int]),
     "gs_set_loss_mask": (C.c_int, [_vp, _vp]),
     "gs_loss_forward_backward": (C.c_int, [_vp] + [_vp] * 5 + [C.c_float, C.c_float] + [_vp] * 3),
+    "gs_depth_loss": (C.c_int, [_vp, C.POINTER(gs_depth_loss_params)] + [_vp] * 7),
+    "gs_depth_normalize": (C.c_int, [_vp, C.c_longlong, _vp, _vp, C.c_float, _vp]),
     "gs_adam_step": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4 + [C.c_int, _vp, _vp] + [C.c_float] * 4),
     "gs_profile_enable": (C.c_int, [_vp, C.c_uint]),
     "gs_profile_read": (C.c_int, [_vp, _vp, _vp]),

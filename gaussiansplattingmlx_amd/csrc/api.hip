@@ -538,7 +538,7 @@ int gs_ctx_destroy(gs_ctx* c)
     free_pair_ws(c);
     dev_free(c->segState);
     dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk); dev_free(c->wideTotal); dev_free(c->rowTotal); dev_free(c->sortBits); dev_free(c->bucketStart); dev_free(c->ssChunk); dev_free(c->sortSplit[0]); dev_free(c->sortSplit[1]); dev_free(c->tileRanges); dev_free(c->tileCounts); dev_free(c->superCut);
-    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->windowDev);
+    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->windowDev);
     dev_free(c->counters); dev_free(c->blockWorkOwn); dev_free(c->blockOrder); dev_free(c->fwdQueue); dev_free(c->bwdQueue); dev_free(c->segBase); dev_free(c->finalT);
     for (auto& e : c->profPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (c->countersHost) (void)hipHostFree(c->countersHost);
@@ -1513,6 +1513,40 @@ int gs_loss_forward_backward(gs_ctx* c, const float* render, const float* target
     return grid ? launch_bilateral_backward(c, c->W, c->H, c->bgGrid, c->bgW, c->bgH, c->bgL, c->bgChunks, c->bgTv, render,
                                             cot_color, c->bgPartials, c->bgGrad)
                 : launch_exposure_backward(c, np, c->expoM, render, cot_color, c->expoPartials, c->expoGrad);
+}
+
+// ---- depth supervision (include/gsplat.h gs_depth_loss; depth_loss.hip) ---------------------------------------------------
+int gs_depth_loss(gs_ctx* c, const gs_depth_loss_params* p, const float* render_depth, const float* render_alpha,
+                  const float* target, const unsigned char* mask, float* loss, float* cot_depth, float* cot_alpha)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!p) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_loss: null params");
+    if (p->mode != GS_DEPTH_ACCUMULATED && p->mode != GS_DEPTH_EXPECTED && p->mode != GS_DEPTH_DISPARITY)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_depth_loss: mode is GS_DEPTH_ACCUMULATED, GS_DEPTH_EXPECTED or GS_DEPTH_DISPARITY");
+    if (!(p->alpha_min >= 0.0f) || !isfinite(p->alpha_min))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_depth_loss: alpha_min is finite and >= 0");
+    if (!isfinite(p->lambda) || !isfinite(p->scale) || !isfinite(p->offset))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_depth_loss: lambda, scale and offset are finite");
+    if (!render_depth || !target || !loss || !cot_depth) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_loss: null buffer");
+    if (p->mode != GS_DEPTH_ACCUMULATED && (!render_alpha || !cot_alpha))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_depth_loss: the expected and disparity modes need render_alpha and cot_alpha");
+    { const int orc = deferred_overflow(c); if (orc) return orc; }
+    if (!c->depthLossWs) {      // the first call: a step never allocates after it
+        GS_HIP_CHECK(c, hipSetDevice(c->device));
+        if (const int rc = dev_alloc(c, &c->depthLossWs, (size_t)depth_loss_ws_doubles())) return rc;
+    }
+    GsStageTimer t(c, GS_STAGE_LOSS);
+    return launch_depth_loss(c, p->mode, p->lambda, p->alpha_min, p->scale, p->offset, render_depth, render_alpha, target, mask,
+                             loss, cot_depth, cot_alpha);
+}
+
+int gs_depth_normalize(gs_ctx* c, long long n_pixels, const float* depth, const float* alpha, float alpha_min, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: negative n_pixels");
+    if (!(alpha_min >= 0.0f) || !isfinite(alpha_min)) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: alpha_min is finite and >= 0");
+    if (!depth || !alpha || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: null pointer");
+    return launch_depth_normalize(c, n_pixels, depth, alpha, alpha_min, out);
 }
 
 int gs_loss_target_cache_floats(gs_ctx* c, long long* n)

@@ -327,6 +327,7 @@ struct gs_ctx {
     bool lossTargetCacheFilled = false;
     const unsigned char* lossMask = nullptr;   // gs_set_loss_mask: caller-owned [H][W] per-pixel loss weights v / 255, nullptr = off
     int lossPartialBlocks = 0;
+    double* depthLossWs = nullptr;    // gs_depth_loss: [depth_loss_ws_doubles()] per-block (sum, count) partials + n, allocated at the first call
     float* windowDev = nullptr;       // [121] default SSIM window
     // densify scan scratch: [densifyTileCap] tile sums + 8 counters, grown on demand
     int* densifyTiles = nullptr;
@@ -474,6 +475,11 @@ int launch_bilateral_apply(gs_ctx* c, int W, int H, const float* G, int gw, int 
 int launch_bilateral_backward(gs_ctx* c, int W, int H, const float* G, int gw, int gh, int gl, int nch, float tvWeight,
                               const float* render, float* cot, float* partials, float* grad);
 int launch_composite_target(gs_ctx* c, long long n, const float* rgb, const float* alpha, const float bg[3], float* out);   // background.hip
+long long depth_loss_ws_doubles();      // depth_loss.hip
+int launch_depth_loss(gs_ctx* c, int mode, float lambda, float alphaMin, float scale, float offset, const float* depth,
+                      const float* alpha, const float* target, const unsigned char* mask, float* loss, float* cotDepth,
+                      float* cotAlpha);
+int launch_depth_normalize(gs_ctx* c, long long n, const float* depth, const float* alpha, float alphaMin, float* out);
 // filter3d.hip: the camera table's row is view[0..3][0], view[0..3][1], view[0..3][2], limX, limY, focalX, 0
 int launch_filter3d_width(gs_ctx* c, int N, const float* xyz, float* filter);
 int launch_filter3d_bake(gs_ctx* c, int N, const float* scalesRaw, const float* opacityRaw, const float* filter, float* outScales,

@@ -3,7 +3,8 @@ Data/BlenderDataLoader.swift): file formats, pose / intrinsics conventions, the 
 
 What is mirrored exactly: the binary / JSON / PLY parsing, quaternion -> rotation, world-to-camera inversion, the
 OpenGL -> OpenCV flip (rows 1-2 of w2c negated), intrinsics scaling by resizeFactor, white-background compositing,
-the tile size rule (W/4, H/4).  Not in the reference: per-view loss masks (readMask, TrainData.maskArray).
+the tile size rule (W/4, H/4).  Not in the reference: per-view loss masks (readMask, TrainData.maskArray)
+and COLMAP sets with Inria's inverse-depth priors (readInverseDepth, TrainData.depthArray / depthAlign).
 What is not mirrored: image decoding and resampling (the reference goes through UIKit /
 CoreGraphics; here PIL, bilinear) and the downloads / unzipping of the demo sets (no network: loaders take paths)."""
 from __future__ import annotations
@@ -31,6 +32,7 @@ class TrainData:
     alphaArray: np.ndarray
     depthArray: np.ndarray | None = None
     maskArray: np.ndarray | None = None       # uint8 [n, H, W] loss masks (255 keeps a pixel), None when no view has one
+    depthAlign: np.ndarray | None = None      # float32 [n, 2]: (scale, offset) to apply to depthArray's view (trainStep's depthAlign)
 
     def getCameraParams(self):
         return self.Hs, self.Ws, self.intrinsicArray, self.c2wArray
@@ -59,6 +61,33 @@ def readMask(path, resizeFactor: float = 1.0):
     if resizeFactor != 1.0:
         img = img.resize((int(img.size[0] * resizeFactor), int(img.size[1] * resizeFactor)), Image.BILINEAR)
     return np.array(img, np.uint8)
+
+
+def readInverseDepth(path, resizeFactor: float = 1.0):
+    """A view's depth prior in Inria's layout: a 16-bit PNG whose value / 65536 is the inverse depth, float32 [H, W], under the
+    images' own bilinear resize (taken on the float values).  0 is a hole."""
+    from PIL import Image
+    raw = np.array(Image.open(path))
+    if raw.ndim != 2 or raw.dtype.kind not in "ui":
+        raise ValueError(f"depth map {path}: a single-channel integer PNG (16-bit) is expected")
+    inv = raw.astype(np.float32) / np.float32(65536.0)
+    if resizeFactor != 1.0:
+        img = Image.fromarray(inv)          # (float32: mode "F")
+        img = img.resize((int(img.size[0] * resizeFactor), int(img.size[1] * resizeFactor)), Image.BILINEAR)
+        inv = np.array(img, np.float32)
+    return inv
+
+
+def readDepthParams(depthParams) -> dict:
+    """Inria's depth_params.json -- {image stem: {"scale": s, "offset": o, ...}} -- as a dict, from a dict or a path to the file."""
+    if depthParams is None:
+        return {}
+    if isinstance(depthParams, (str, os.PathLike)):
+        with open(depthParams) as f:
+            depthParams = json.load(f)
+    if not isinstance(depthParams, dict):
+        raise ValueError("depthParams is the depth_params.json dict or a path to it")
+    return depthParams
 
 
 def _stack_masks(paths, Hs, Ws, resizeFactor: float):
@@ -162,11 +191,33 @@ def colmapReadPointSet(points3DPath):
 
 
 class ColmapDataLoader:
-    def __init__(self, binRoot, imageRoot, maskRoot=None):
+    def __init__(self, binRoot, imageRoot, maskRoot=None, depthRoot=None, depthParams=None):
         """maskRoot: a directory of per-view loss masks (TrainData.maskArray).  A view's mask is <maskRoot>/<image file
         name>.png (COLMAP's own convention: "frame.jpg.png") or, failing that, <maskRoot>/<image file name without its
-        extension>.png; a view with neither keeps every pixel."""
+        extension>.png; a view with neither keeps every pixel.
+
+        depthRoot: a directory of per-view depth priors in Inria's layout, <depthRoot>/<image stem>.png, 16-bit, value / 65536
+        the inverse depth (TrainData.depthArray, the target of DepthConfig(mode="disparity")); a view without a file gets
+        zeros, which the depth term's default mask (target > 0) leaves out.  depthParams: Inria's depth_params.json (the dict
+        or a path to it): a view's "scale" and "offset" go to TrainData.depthAlign, (1, 0) for a view without an entry."""
         self.binRoot, self.imageRoot, self.maskRoot = binRoot, imageRoot, maskRoot
+        self.depthRoot, self.depthParams = depthRoot, readDepthParams(depthParams)
+        if depthRoot is None and depthParams is not None:
+            raise ValueError("depthParams go with a depthRoot")
+
+    def _depths(self, poses, Hs, Ws, resizeFactor: float):
+        """(depthArray [n, H, W], depthAlign [n, 2]) of the views."""
+        depths, align = [], []
+        for p, H, W in zip(poses, Hs, Ws):
+            stem = os.path.splitext(os.path.relpath(p.filePath, self.imageRoot))[0]
+            path = os.path.join(self.depthRoot, stem + ".png")
+            d = readInverseDepth(path, resizeFactor) if os.path.exists(path) else np.zeros((int(H), int(W)), np.float32)
+            if d.shape != (int(H), int(W)):
+                raise ValueError(f"depth map {path}: {d.shape[1]} x {d.shape[0]} after the resize, its image is {int(W)} x {int(H)}")
+            depths.append(d)
+            e = self.depthParams.get(stem, self.depthParams.get(os.path.basename(stem), {}))
+            align.append((float(e.get("scale", 1.0)), float(e.get("offset", 0.0))))
+        return np.stack(depths).astype(np.float32), np.asarray(align, np.float32).reshape(-1, 2)
 
     def _maskPath(self, imagePath):
         name = os.path.relpath(imagePath, self.imageRoot)
@@ -192,7 +243,8 @@ class ColmapDataLoader:
         ch = cols.astype(np.float32) / np.float32(255.0)
         pcd = PointCloud(pts.astype(np.float32), dict(R=ch[:, 0], G=ch[:, 1], B=ch[:, 2]))
         masks = None if self.maskRoot is None else _stack_masks([self._maskPath(p.filePath) for p in poses], Hs, Ws, resizeFactor)
-        return (TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, None, masks), pcd,
+        depths, align = (None, None) if self.depthRoot is None else self._depths(poses, Hs, Ws, resizeFactor)
+        return (TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, depths, masks, align), pcd,
                 TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
 
 

@@ -1128,6 +1128,61 @@ class GaussianRenderer:
             ent[2] = 1          # filled -- only now that the kernel which fills it has been queued without an error
         return lossOut, cotColor, cotDepth
 
+    # -- depth supervision (include/gsplat.h gs_depth_loss; depth_loss.py) ------------------------------
+    @staticmethod
+    def depthLossParams(mode, weight: float, alpha_min: float = 0.05, scale: float = 1.0, offset: float = 0.0):
+        """gs_depth_loss_params: mode by name (depth_loss.MODES) or number, the term's weight (the header's lambda), alpha_min,
+        and the target's scale and offset (t = scale * target + offset)."""
+        from .depth_loss import MODES
+        if isinstance(mode, str):
+            if mode not in MODES:
+                raise ValueError(f"depthLossParams: unknown mode {mode!r} (one of {', '.join(MODES)})")
+            mode = MODES.index(mode)
+        return _lib.gs_depth_loss_params(int(mode), float(weight), float(alpha_min), float(scale), float(offset))
+
+    def depthLoss(self, renderDepth, renderAlpha, target, mask, params, out=None):
+        """gs_depth_loss on a render's depth and alpha images ([H, W] or [H, W, 1]): returns (loss, cotDepth, cotAlpha), the
+        cotangents [H, W] as the fused backwards take them.  mask: uint8 or bool, tensor or array, non-zero = the pixel takes
+        part, or None = all (the depth term's own mask: setLossMask's is not read).  params: depthLossParams(...) or a dict of
+        its arguments.  out: dict(loss=, cotDepth=, cotAlpha=) of buffers to use; loss is the float[4] a lossForwardBackward
+        has written -- loss[3] becomes the depth term and loss[0] gains weight times it -- and starts at zero without out.
+        renderAlpha and cotAlpha may be None in the accumulated mode (the returned cotAlpha is then None)."""
+        p = params if isinstance(params, _lib.gs_depth_loss_params) else self.depthLossParams(**params)
+        P = self.H * self.W
+        rd, tg = self._t(renderDepth), self._t(target)
+        ra = None if renderAlpha is None else self._t(renderAlpha)
+        if rd.numel() != P or tg.numel() != P or (ra is not None and ra.numel() != P):
+            raise ValueError(f"depthLoss: render depth, render alpha and target are [H, W] = [{self.H}, {self.W}] images")
+        dm = None
+        if mask is not None:
+            dm = mask if torch.is_tensor(mask) else torch.as_tensor(np.ascontiguousarray(mask))
+            if dm.dtype not in (torch.uint8, torch.bool) or dm.numel() != P:
+                raise ValueError(f"depthLoss: mask is a uint8 or bool [H, W] = [{self.H}, {self.W}] image, or None")
+            dm = dm.to(device=self.device, dtype=torch.uint8).contiguous()
+        out = out or {}
+        loss = out["loss"] if "loss" in out else torch.zeros(4, device=self.device)
+        cotDepth = out["cotDepth"] if "cotDepth" in out else self._empty(self.H, self.W)
+        cotAlpha = out["cotAlpha"] if "cotAlpha" in out else (None if ra is None else self._empty(self.H, self.W))
+        for name, t, n in (("loss", loss, 4), ("cotDepth", cotDepth, P), ("cotAlpha", cotAlpha, P)):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or t.numel() != n):
+                raise ValueError(f"depthLoss: out[{name!r}] is a contiguous float32 device tensor of {n} elements")
+        self._check(self.lib.gs_depth_loss(self.ctx, C.byref(p), _p(rd), _p(ra), _p(tg), _p(dm), _p(loss), _p(cotDepth),
+                                           _p(cotAlpha)))
+        return loss, cotDepth, cotAlpha
+
+    def expectedDepth(self, res, alpha_min: float = 0.05):
+        """gs_depth_normalize: the expected depth D / a of a render (a RenderResult with its depth image, or a (depth, alpha)
+        pair) where a >= alpha_min and a > 0, 0 elsewhere; a new tensor of the depth image's shape."""
+        depth, alpha = (res.depth, res.alpha) if hasattr(res, "depth") else res
+        if depth is None:
+            raise ValueError("expectedDepth: the render has no depth image (renderForward(wantDepth=True))")
+        d, a = self._t(depth), self._t(alpha)
+        if d.numel() != a.numel():
+            raise ValueError("expectedDepth: depth and alpha are images of one size")
+        out = torch.empty_like(d)
+        self._check(self.lib.gs_depth_normalize(self.ctx, d.numel(), _p(d), _p(a), C.c_float(alpha_min), _p(out)))
+        return out
+
     def invalidateTarget(self, targetKey=None):
         """Forget the cached SSIM statistics of one target key (None: of all): its next loss recomputes them."""
         if targetKey is None:

@@ -454,7 +454,7 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None, sparse_adam: bool = False, background=None):
+                 absgrad=None, sparse_adam: bool = False, background=None, depth=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -564,7 +564,31 @@ class GaussianTrainer:
         loss without a target key (the target statistics cache cannot serve an image that changes every step); mode "fixed"
         keeps it.  The feature only sets a blend-level colour and swaps the target: it composes with pose_opt, exposure_opt,
         bilateral_grid, absgrad, sparse_adam, filter_3d, contrib_prune, strategy='mcmc', an anti-aliased renderer and fuse_adam
-        on or off; single-device steps with one view only.  Off (the default): no kernel, buffer or result differs."""
+        on or off; single-device steps with one view only.  Off (the default): no kernel, buffer or result differs.
+
+        depth: depth-supervised training (depth_loss.DepthConfig, include/gsplat.h gs_depth_loss; the
+        reference's depth term, GaussianTrainer.swift:689-714 and :949, Inria's depth regularisation, gsplat's depth_loss).
+        Every step takes trainStep's targetDepth (and depthMask, depthAlign), renders WITH the depth image and with the
+        forward's depth sums checkpointed (depth_gradient = 1, put back behind the step), runs the colour loss as always and
+        then gs_depth_loss on the render's depth and alpha in depth.mode -- "accumulated" (the reference's), "expected" (D / a)
+        or "disparity" (a / D against an inverse depth) -- at depth.weight_at(iteration, iterationCount), and hands the two
+        cotangents to the backward beside the colour's: renderBackwardAdam with fuse_adam, renderBackward without.  The depth
+        loss sits where the colour loss does, so a forward repeated for an overflow or a depth-cut miss repeats it on the new
+        images; the step's loss[3] is the depth term and loss[0] includes weight times it.  The depth term has its own mask,
+        not lossMask.  It adds a loss and two cotangents the library's backwards already take: it composes with pose_opt,
+        exposure_opt, bilateral_grid, absgrad, sparse_adam, filter_3d, contrib_prune, lossMask, background (whose g . b term the
+        library adds to the alpha cotangent it is handed), strategy='mcmc', an anti-aliased renderer and fuse_adam on or off;
+        single-device steps with one view only.  Off (the default): no kernel, launch, buffer or result differs, and the step
+        still renders without a depth image."""
+        self.depth = None
+        self._depthStep = None          # the running step's depth inputs (trainStep sets and clears it)
+        if depth is not None:
+            from .depth_loss import DepthConfig
+            if not isinstance(depth, DepthConfig):
+                raise ValueError("depth must be a DepthConfig")
+            depth.validate()
+            _require_single_device("depth", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            self.depth = depth
         self.background = None
         self.lastBackground = None
         self._bgTarget = None
@@ -692,12 +716,17 @@ class GaussianTrainer:
         if dp_bootstrap is not None:
             _, self.rank, self.world = dp_bootstrap
         r = gaussRender
-        # this trainer's loss has no depth term (lambda_depth = 0, the reference's default: GaussianTrainer.swift:280,
-        # 949), so no backward of ITS forwards ever brings a depth cotangent and they need not checkpoint the depth sums:
-        # the knob is turned off around the trainer's own steps only (_trainStep) -- the renderer is the caller's, and
-        # its other users keep whatever they had set
+        # without depth= this trainer's loss has no depth term (lambda_depth = 0, the reference's default:
+        # GaussianTrainer.swift:280, 949), so no backward of ITS forwards ever brings a depth cotangent and they need not
+        # checkpoint the depth sums: the knob is turned off around the trainer's own steps only (_trainStep) -- the renderer
+        # is the caller's, and its other users keep whatever they had set.  With depth= it is turned on around them.
         self._loss = r._empty(4)
         self._cot = r._empty(r.H, r.W, 3)
+        self._cotDepth = self._cotAlpha = None
+        if self.depth is not None:
+            self._cotDepth = r._empty(r.H, r.W)
+            if self.depth.mode != "accumulated":      # (the accumulated depth has no cotangent into alpha)
+                self._cotAlpha = r._empty(r.H, r.W)
         self._seg_end = (C.c_longlong * 6)(*[int(x) for x in model.seg_end])
         self.iteration = 0
         # densification (GaussianTrainer.swift:293-300, 304)
@@ -1455,7 +1484,8 @@ class GaussianTrainer:
         return exchange_summary(self.exchange_impl, self.dp_exchange, self.world, m.N, int(m.geom_numel), int(m.numel), n, sums,
                                 counts, version, source, self.viewsPerRank)
 
-    def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None, targetAlpha=None, lossMask=None):
+    def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None, targetAlpha=None, lossMask=None, targetDepth=None,
+                  depthMask=None, depthAlign=(1.0, 0.0)):
         """One iteration: forward, loss, backward, (gradient exchange), Adam.  Asynchronous; returns the device
         loss[4].  stepCameras: the cameras of ALL ranks for this step in rank order (every rank derives them from the
         shared view permutation, see view_for), or just their centres [R,3]; required by the sh_compressed exchange.
@@ -1479,7 +1509,12 @@ class GaussianTrainer:
         A uint8 device tensor that stays where it is keeps the view's target statistics cached; a host array is uploaded anew
         every step and refills them.  Needs no constructor argument; composes with pose_opt, exposure_opt, bilateral_grid,
         absgrad, sparse_adam, filter_3d, contrib_prune, background, strategy='mcmc', an anti-aliased renderer and fuse_adam on
-        or off; single-device steps with one view only.  None (the default): no kernel, buffer or result differs."""
+        or off; single-device steps with one view only.  None (the default): no kernel, buffer or result differs.
+
+        targetDepth: the view's depth map, [H, W], with a trainer built with depth= (and only then): a metric depth in the
+        accumulated and expected modes, an inverse depth in the disparity mode.  depthMask: uint8 or bool [H, W], non-zero =
+        the pixel takes part in the depth term; None means targetDepth > 0 (sensor holes are 0).  depthAlign = (scale, offset):
+        the term compares with scale * targetDepth + offset (Inria's depth_params.json pair; TrainData.depthAlign)."""
         if lossMask is not None:
             if self.viewsPerRank != 1:
                 raise ValueError("trainStep: lossMask takes one view per step only (views_per_rank > 1 is not supported)")
@@ -1489,6 +1524,13 @@ class GaussianTrainer:
             raise ValueError("trainStep: targetAlpha goes with a trainer built with background=BackgroundConfig(...)"
                              if self.background is None else
                              "trainStep: a trainer built with background= needs targetAlpha (the view's alpha, [H, W])")
+        depth = self.depth
+        if (targetDepth is None) != (depth is None):
+            raise ValueError("trainStep: targetDepth goes with a trainer built with depth=DepthConfig(...)"
+                             if depth is None else
+                             "trainStep: a trainer built with depth= needs targetDepth (the view's depth map, [H, W])")
+        if depth is None and depthMask is not None:
+            raise ValueError("trainStep: depthMask goes with a trainer built with depth=DepthConfig(...)")
         profiled = self.enableIntervalProfiling and (self.iteration % self.profilingLogInterval == 0
                                                      or self.iteration == self.iterationCount - 1)
         step = self._profiledStep if profiled else (self._trainStepMulti if self.viewsPerRank > 1 else self._trainStep)
@@ -1505,7 +1547,9 @@ class GaussianTrainer:
         tables = list(self._perView.values())
         row = tables[0].row(viewKey) if tables else None       # (one n_views for all of them)
         try:
-            r.setTuning(depth_gradient=0)
+            if depth is not None:
+                self._depthStep = self._depthInputs(targetDepth, depthMask, depthAlign)
+            r.setTuning(depth_gradient=0 if depth is None else 1)
             if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
                 r.setMCMC(self._mcmcParams())
             if self.filter_3d:
@@ -1533,6 +1577,7 @@ class GaussianTrainer:
                         raise      # (data-parallel steps never raise it: host_overflow_errors is off, see __init__)
                     self._recover_overflow()      # (every regrow is by half at least: a few rounds reach any need)
         finally:
+            self._depthStep = None
             r.setTuning(**restore)
             if self.mcmc is not None:
                 r.setMCMC(None)
@@ -1546,6 +1591,36 @@ class GaussianTrainer:
                 r.setLossMask(mask_was[0])
             for t in tables:
                 t.unbind(r)
+
+    def _depthInputs(self, targetDepth, depthMask, depthAlign):
+        """The step's depth target and mask on the device and its gs_depth_loss_params."""
+        r = self.gaussRender
+        try:
+            scale, offset = (float(x) for x in depthAlign)
+        except (TypeError, ValueError):
+            scale = offset = float("nan")
+        if not (math.isfinite(scale) and math.isfinite(offset)):
+            raise ValueError("trainStep: depthAlign = (scale, offset), both finite")
+        td = r._t(targetDepth)
+        if td.numel() != r.H * r.W or td.dim() not in (2, 3):
+            raise ValueError(f"trainStep: targetDepth is [H, W] = [{r.H}, {r.W}]")
+        if depthMask is None:
+            dm = (td > 0).to(torch.uint8)          # sensor holes are 0; taken anew every step, from the map the step was given
+        else:
+            dm = depthMask if torch.is_tensor(depthMask) else torch.as_tensor(np.ascontiguousarray(depthMask))
+            if dm.dtype not in (torch.uint8, torch.bool) or dm.numel() != r.H * r.W:
+                raise ValueError(f"trainStep: depthMask is a uint8 or bool [H, W] = [{r.H}, {r.W}] image, or None")
+            dm = dm.to(device=r.device, dtype=torch.uint8).contiguous()
+        params = r.depthLossParams(self.depth.mode, self.depth.weight_at(self.iteration, self.iterationCount), self.depth.alpha_min,
+                                   scale, offset)
+        return dict(target=td, mask=dm, params=params)
+
+    def _depthLoss(self, res, lossOut):
+        """gs_depth_loss behind the colour loss that wrote lossOut: lossOut[3], lossOut[0] and the step's two cotangents."""
+        r, d = self.gaussRender, self._depthStep
+        r._measure("train.loss.depth", lambda: r.depthLoss(
+            res.depth, None if self._cotAlpha is None else res.alpha, d["target"], d["mask"], d["params"],
+            out=dict(loss=lossOut, cotDepth=self._cotDepth, cotAlpha=self._cotAlpha)))
 
     def _compositeTarget(self, targetRGB, targetAlpha, b):
         """The step's target: targetRGB over b by targetAlpha, in the trainer's own buffer (allocated once)."""
@@ -1670,26 +1745,31 @@ class GaussianTrainer:
 
     def _forwardAndLoss(self, camera, targetRGB, viewKey, lossOut):
         """lossFn of one view (GaussianTrainer.swift:627-723): forward, L1 + DSSIM loss -> lossOut[4] and the colour cotangent
-        in self._cot; the forward is repeated once if it overflowed on the view's first visit, and once without depth cuts if
+        in self._cot -- with depth= also the depth term and the depth and alpha cotangents; the forward is repeated once if it overflowed on the view's first visit, and once without depth cuts if
         it missed under them."""
         r, m = self.gaussRender, self.model
-        res = r._measure("train.forward", lambda: r.renderForward(m.getParams(), camera, viewKey=viewKey, wantDepth=False))
+        wd = self._depthStep is not None          # (without a depth term the step renders no depth image)
+        res = r._measure("train.forward", lambda: r.renderForward(m.getParams(), camera, viewKey=viewKey, wantDepth=wd))
         if viewKey is not None and viewKey not in self._checked_views:
             # first visit of a view: its pair count is unknown -- wait for the forward once and make sure it fitted
             # (rank-local also in a data-parallel job: a forward is no collective, and gs_sync reports whatever the knob says)
             self._checked_views.add(viewKey)
             if self.checkOverflow():
-                res = r.renderForward(m.getParams(), camera, viewKey=viewKey, wantDepth=False)
+                res = r.renderForward(m.getParams(), camera, viewKey=viewKey, wantDepth=wd)
         r._measure("train.loss.total", lambda: r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim,
                                                                       out=dict(loss=lossOut, cotColor=self._cot),
                                                                       targetKey=self._lossTargetKey(viewKey)))
+        if wd:
+            self._depthLoss(res, lossOut)
         # depth cuts (renderer.renderForward): nothing that changes state has been queued yet; the loss kernel above
         # keeps the GPU busy while the host learns whether the forward has to be repeated in full
         if viewKey is not None and r.forwardMissed():
             self.forwardMisses += 1
-            res = r.renderForward(m.getParams(), camera, viewKey=viewKey, depthCuts=False, wantDepth=False)
+            res = r.renderForward(m.getParams(), camera, viewKey=viewKey, depthCuts=False, wantDepth=wd)
             r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim, out=dict(loss=lossOut, cotColor=self._cot),
                                   targetKey=self._lossTargetKey(viewKey))
+            if wd:
+                self._depthLoss(res, lossOut)
 
     def _geometryAdam(self, lr: dict, scale: float):
         """Adam on the geometry slice after the all-reduce; the xyz segment's gradient = reduced + the view-direction terms the
@@ -1766,6 +1846,12 @@ class GaussianTrainer:
         torch.mean(self._loss_v, dim=0, out=self._loss)          # this rank's views; the step's loss is the mean over all of them
         return self._finishIteration()
 
+    def _depthCots(self) -> dict:
+        """The backward's depth and alpha cotangents: none without a depth term (the calls are then today's)."""
+        if self._depthStep is None:
+            return {}
+        return dict(cotDepth=self._cotDepth, cotAlpha=self._cotAlpha)
+
     def _trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None):
         r, m = self.gaussRender, self.model
         self._beginIteration()
@@ -1784,12 +1870,12 @@ class GaussianTrainer:
             fused = True
         elif not self._exchange and self.fuse_adam:
             r._measure("bwd.fused+train.optimizer.applySingle", lambda: r.renderBackwardAdam(
-                self._cot, m.arena, m.m, m.v, getLearningRates(self.iteration, self.iterationCount)))
+                self._cot, m.arena, m.m, m.v, getLearningRates(self.iteration, self.iterationCount), **self._depthCots()))
             if self.densify:
                 self.addGradientAccumulation()
             fused = True
         elif not self._exchange:
-            r.renderBackward(self._cot, out=m.getGrads())
+            r.renderBackward(self._cot, out=m.getGrads(), **self._depthCots())
             if self.mcmc is not None:
                 g = m.getGrads()
                 r.mcmcRegularizerGrad(m.getParams()["scales"], m.getParams()["opacity"], g["scales"], g["opacity"],

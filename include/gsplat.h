@@ -739,6 +739,49 @@ int gs_set_loss_target_cache(gs_ctx* ctx, float* cache /*DEVICE or NULL*/, int f
  * No reference call site (GaussianTrainer.swift:689-714 takes the loss of every pixel). */
 int gs_set_loss_mask(gs_ctx* ctx, const unsigned char* mask /*DEVICE [H,W] or NULL*/);
 
+/* Depth supervision on the render's depth and alpha images (tests/depth_loss_numpy.py restates it).  The depth term
+ * of gs_loss_forward_backward above is the reference's (GaussianTrainer.swift:689-714, :949): it compares the ACCUMULATED depth
+ * D = sum T alpha z with a metric depth map, which is right only where the render is opaque.  This entry point has that form and
+ * the two that need the render's alpha a inside the loss and a cotangent into it: gsplat's depth_loss (L1 in disparity on the
+ * normalised, "expected", depth) and Inria's depth regularisation (inverse depth against a prior with a per-image scale and
+ * offset, depth_params.json).  With t = scale * target + offset (two float32 roundings, never contracted), per pixel of the
+ * ctx's H x W image:
+ *   GS_DEPTH_ACCUMULATED  x = D      valid iff mask                                 cot_depth = g          cot_alpha = 0
+ *   GS_DEPTH_EXPECTED     x = D / a  valid iff mask, a >= alpha_min and a > 0       cot_depth = g / a      cot_alpha = -g D / a^2
+ *   GS_DEPTH_DISPARITY    x = a / D  valid iff mask, a >= alpha_min, a > 0, D > 0   cot_depth = -g a / D^2 cot_alpha = g / D
+ *   n = max(number of valid pixels, 1e-6),  Ld = sum_valid |x - t| / n,  g = lambda sign(x - t) / n (sign 0 on a tie).
+ * (a > 0 matters with alpha_min = 0 only: a pixel nothing was blended into has no expected depth.)  In the disparity mode the
+ * target is an inverse depth.  mask: uint8, non-zero = the pixel takes part, NULL = all; it is the depth term's OWN mask (sensor
+ * holes), not the colour loss's gs_set_loss_mask, which this call does not read.  loss: the float[4] a
+ * gs_loss_forward_backward on this ctx's stream has written: loss[3] = Ld, loss[0] += lambda Ld (read and written; the call is
+ * queued behind that loss).  cot_depth and cot_alpha are what the fused backwards take as theirs; EVERY element of both is
+ * written -- exactly 0.0f on an invalid pixel, nothing stale --, and nothing is NaN or Inf for a = 0, D = 0 or an image
+ * without a valid pixel (Ld = 0, cotangents 0), nor for any finite input whose quotients fit float32: a valid pixel's D / a,
+ * a / D and the cotangents above are formed as written, so a positive a or D below about 1e-19 beside an ordinary partner
+ * (possible only with alpha_min = 0, or a near-zero D in the disparity mode) overflows like any float32 division.  cot_alpha may be NULL in GS_DEPTH_ACCUMULATED, where
+ * render_alpha is not read and may be NULL too.  With scale = 1, offset = 0 that mode is gs_loss_forward_backward's depth term:
+ * cot_depth agrees with its cot_depth bit for bit.  Three launches (partial sums, one workgroup that finishes them, cotangents),
+ * every one a grid-stride loop, no float atomics -- two calls on the same inputs give the same bits --, no wait; the first
+ * call allocates 8 KB of workspace, no later one allocates.  GS_ERR_INVALID_ARG: mode out of range, alpha_min < 0 or not finite,
+ * a non-finite lambda / scale / offset, cot_alpha or render_alpha NULL in the expected and disparity modes, a NULL params,
+ * render_depth, target, loss or cot_depth. */
+enum { GS_DEPTH_ACCUMULATED = 0, GS_DEPTH_EXPECTED = 1, GS_DEPTH_DISPARITY = 2 };
+typedef struct gs_depth_loss_params {
+    int mode;
+    float lambda;
+    float alpha_min;
+    float scale, offset;
+} gs_depth_loss_params;
+int gs_depth_loss(gs_ctx* ctx, const gs_depth_loss_params* p /*HOST*/, const float* render_depth /*DEVICE [H,W]*/,
+                  const float* render_alpha /*DEVICE [H,W]*/, const float* target /*DEVICE [H,W]*/,
+                  const unsigned char* mask /*DEVICE [H,W] or NULL = all*/, float* loss /*DEVICE [4], read and written*/,
+                  float* cot_depth /*DEVICE [H,W]*/, float* cot_alpha /*DEVICE [H,W]; may be NULL in mode 0*/);
+/* The expected depth of a render, for a viewer or an evaluation: out = D / a where a >= alpha_min and a > 0, 0 elsewhere, for
+ * n_pixels pixels.  out may be depth itself.  Asynchronous on the ctx stream, allocates nothing.  n_pixels < 0, alpha_min < 0
+ * or not finite, or a NULL pointer: GS_ERR_INVALID_ARG; n_pixels == 0: nothing is launched. */
+int gs_depth_normalize(gs_ctx* ctx, long long n_pixels, const float* depth /*DEVICE [n]*/, const float* alpha /*DEVICE [n]*/,
+                       float alpha_min, float* out /*DEVICE [n]*/);
+
 /* ---- next row: optimizer step ---------------------------------------------------------------- */
 
 /* Adam over one flat parameter arena, as the trainer applies it per tensor (GaussianTrainer.swift:941-948,
