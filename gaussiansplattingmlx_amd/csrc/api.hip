@@ -1308,9 +1308,7 @@ int gs_render_backward(gs_ctx* c, const float* cot_color, const float* cot_depth
     if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha, c->absgrad, nullptr)) return rc;
     AbsgradScope noNorm(c);
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
-    return launch_projection_fused_backward(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
-                                            c->fwd.opacity, c->fwd.cam, grad_xyz, grad_features_dc, grad_features_rest,
-                                            grad_scales, grad_rotation, grad_opacity);
+    return launch_projection_fused_backward(c, grad_xyz, grad_features_dc, grad_features_rest, grad_scales, grad_rotation, grad_opacity);
 }
 
 int gs_render_contrib(gs_ctx* c, float* max_w, float* sum_w)
@@ -1347,9 +1345,7 @@ int gs_render_backward_adam(gs_ctx* c, const float* cot_color, const float* cot_
     c->fwd.consumed = true;     // the parameters the forward saw are gone after this call
     AbsgradScope noNorm(c);
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
-    return launch_projection_fused_backward_adam(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
-                                                 c->fwd.opacity, c->fwd.cam, params_base, m_base, v_base, lr, beta1, beta2,
-                                                 eps, grad_scale);
+    return launch_projection_fused_backward_adam(c, params_base, m_base, v_base, lr, beta1, beta2, eps, grad_scale);
 }
 
 int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha,
@@ -1382,9 +1378,7 @@ int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales,
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_finish: null gradient buffer");
     c->fwd.blendBackwardDone = false;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
-    return launch_projection_fused_backward(c, N, K, c->fwd.xyz, c->fwd.fdc, c->fwd.frest, c->fwd.scales, c->fwd.rot,
-                                            c->fwd.opacity, c->fwd.cam, grad_xyz, nullptr, nullptr, grad_scales,
-                                            grad_rotation, grad_opacity, true);
+    return launch_projection_fused_backward(c, grad_xyz, nullptr, nullptr, grad_scales, grad_rotation, grad_opacity, true);
 }
 
 int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity,
@@ -1401,8 +1395,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_finish_geom: null buffer");
     c->fwd.blendBackwardDone = false;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
-    return launch_projection_geom_backward(c, N, c->fwd.xyz, c->fwd.scales, c->fwd.rot, c->fwd.opacity, c->fwd.cam, grad_xyz,
-                                           grad_scales, grad_rotation, grad_opacity, xyz_own);
+    return launch_projection_geom_backward(c, grad_xyz, grad_scales, grad_rotation, grad_opacity, xyz_own);
 }
 
 int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha, float* color_cot,
@@ -1419,8 +1412,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_geom: null buffer");
     if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha)) return rc;
     GsStageTimer t(c, GS_STAGE_PROJ_BWD);
-    return launch_projection_geom_backward(c, N, c->fwd.xyz, c->fwd.scales, c->fwd.rot, c->fwd.opacity, c->fwd.cam, grad_xyz,
-                                           grad_scales, grad_rotation, grad_opacity, xyz_own, color_cot);
+    return launch_projection_geom_backward(c, grad_xyz, grad_scales, grad_rotation, grad_opacity, xyz_own, color_cot);
 }
 
 int gs_sh_grad_from_views_adam_dir(gs_ctx* c, int N, int K, int R, const float* xyz, const float* color_cot_all,

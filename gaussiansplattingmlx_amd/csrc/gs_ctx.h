@@ -451,14 +451,11 @@ int launch_projection_backward(gs_ctx* c, int N, int K, const float* scales, con
 int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
                                     const float* scales, const float* rot, const float* opacity,
                                     const CamParams& cam, float* radii);
-int launch_projection_fused_backward(gs_ctx* c, int N, int K, const float* xyz, const float* fdc,
-                                     const float* frest, const float* scales, const float* rot,
-                                     const float* opacity, const CamParams& cam, float* gXyz, float* gFdc,
-                                     float* gFrest, float* gScales, float* gRot, float* gOpacity, bool emitColorCot = false);
-int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* xyz, const float* fdc,
-                                          const float* frest, const float* scales, const float* rot,
-                                          const float* opacity, const CamParams& cam, const float* pBase, float* mBase,
-                                          float* vBase, const float lr[6], float b1, float b2, float eps, float gscale);
+// (the backwards of the context's forward: its tensors, camera and settings are c->fwd's)
+int launch_projection_fused_backward(gs_ctx* c, float* gXyz, float* gFdc, float* gFrest, float* gScales, float* gRot, float* gOpacity,
+                                     bool emitColorCot = false);
+int launch_projection_fused_backward_adam(gs_ctx* c, const float* pBase, float* mBase, float* vBase, const float lr[6], float b1,
+                                          float b2, float eps, float gscale);
 int launch_vis_mask(gs_ctx* c, int N, const float* radii);      // sparse Adam: radii > 0 -> c->visMask
 bool depth_sort_takes_splitters(const gs_ctx* c, int N);      // binning.hip
 int launch_pose_camera(gs_ctx* c, const gs::CamParams& host, const float* delta);   // projection.hip, pose refinement
@@ -492,9 +489,8 @@ int launch_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* 
                                    const float* camCentersHost, const float* fdcParam, const float* frestParam,
                                    const float* pBase, float* mBase, float* vBase, float lrDc, float lrRest, float b1,
                                    float b2, float eps, float gscale);
-int launch_projection_geom_backward(gs_ctx* c, int N, const float* xyz, const float* scales, const float* rot,
-                                    const float* opacity, const CamParams& cam, float* gXyz, float* gScales, float* gRot,
-                                    float* gOpacity, float* xyzOwn, float* colorCot = nullptr);
+int launch_projection_geom_backward(gs_ctx* c, float* gXyz, float* gScales, float* gRot, float* gOpacity, float* xyzOwn,
+                                    float* colorCot = nullptr);
 int launch_sh_views_dir_adam(gs_ctx* c, int N, int K, int R, const float* xyz, const float* mgAll, const float* camCentersHost,
                              const float* const* ownXyzHost, const float* fdcParam, const float* frestParam, const float* pBase,
                              float* mBase, float* vBase, float lrDc, float lrRest, float b1, float b2, float eps, float gscale,

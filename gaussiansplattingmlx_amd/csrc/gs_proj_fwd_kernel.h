@@ -1,21 +1,31 @@
-// gs_proj_fwd_kernel.h -- the fused projection forward (projection.hip), included twice: as proj_fwd_fused_kernel, the camera
-// a kernel argument, and as proj_fwd_fused_pose_kernel, the camera the one pose_camera_kernel composed on the device (pose
-// refinement, gs_set_pose_correction).  One text, so that the default kernels compile exactly as they did before the pose
-// form existed.  The includer defines GS_FWD_KERNEL, GS_FWD_CAM_PARAM and GS_FWD_CAM_INIT.
+// gs_proj_fwd_kernel.h -- the fused projection forward (projection.hip).
+// POSE: the camera is *dcam, the one pose_camera_kernel composed on the device (pose refinement, gs_set_pose_correction), instead of
+// the kernel argument hostCam; with COLOUR only -- no riders: the binning kernels and colour_rest_kernel see only the host camera.
+// dcam is the last argument, so that the others keep the offsets they had: the unposed forms compile to the registers they did.
 // AA: the anti-aliased mode (gs_set_antialiasing): the packed opacity is sigma(o) rho (aa_opacity_scale, gs_math.h).
 // F3D: the 3-D smoothing filter (gs_set_filter3d): the scales are sqrt(s^2 + f^2), f = filter3d[p], and the opacity gains kappa
-// (filter3d_activate, gs_math.h).  The default instantiations never read filter3d, the last kernel argument.
-template <bool TWO_PHASE, bool COLOUR, bool SELF = false, bool AA = false, bool F3D = false>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void GS_FWD_KERNEL(
-    int N, int K, int degree, GS_FWD_CAM_PARAM, int tileW, int tileH, int gridW, int gridH,
+// (filter3d_activate, gs_math.h).  The other instantiations never read filter3d, the argument before dcam.
+// The forms that exist: {riders' geometry, SELF, one kernel in one or two phases, the same posed} x AA x F3D (24)
+constexpr bool proj_fwd_form_exists(bool TWO_PHASE, bool COLOUR, bool SELF, bool POSE)
+{
+    return COLOUR ? !SELF : (TWO_PHASE && !POSE);
+}
+
+template <bool TWO_PHASE, bool COLOUR, bool SELF, bool AA, bool F3D, bool POSE>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_fwd_fused_kernel(
+    int N, int K, int degree, CamParams hostCam, int tileW, int tileH, int gridW, int gridH,
     const float* __restrict__ xyz, const float* __restrict__ fdc, const float* __restrict__ frest,
     const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw, const float* __restrict__ opacityRaw,
     float* __restrict__ packed12, float* __restrict__ radiiOut, ushort4* __restrict__ tileRect,
     uint32_t* __restrict__ tilesTouched, uint32_t* __restrict__ depthKey, uint32_t* __restrict__ depthVal,
     uint32_t* __restrict__ visPerBlock, uint32_t* __restrict__ counters, int flags, ColourRider self,
-    GsVirtGeom vg, GsCutCoarse cc, uint4* __restrict__ tilePieces, const float* __restrict__ filter3d)
+    GsVirtGeom vg, GsCutCoarse cc, uint4* __restrict__ tilePieces, const float* __restrict__ filter3d,
+    const CamParams* __restrict__ dcam)
 {
-    GS_FWD_CAM_INIT
+    static_assert(proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE), "no such form of the fused projection forward");
+    CamParams posed;
+    if constexpr (POSE) posed = *dcam;
+    const CamParams& cam = POSE ? posed : hostCam;
     const int noKeyForUntouched = flags & 1;
     const bool trimRects = (flags & 2) && !vg.nbx && tileW == 16 && tileH == 16;
     extern __shared__ float shLds[];

@@ -11,6 +11,8 @@
 //    and emit what binning needs (tile rectangle, tiles touched, depth key), so
 //    the per-Gaussian data crosses HBM once.
 // One lane per Gaussian; HBM-bound (408 B/Gaussian forward, 728 B backward at K=25).
+#include <type_traits>
+
 #include "gs_ctx.h"
 #include "gs_mcmc.h"
 #include "gs_rider.h"
@@ -230,23 +232,7 @@ __device__ __forceinline__ void sh_rows_out(const float* __restrict__ lds, float
 #ifndef GS_DEGENERATE_INVISIBLE
 #define GS_DEGENERATE_INVISIBLE 1
 #endif
-#define GS_FWD_KERNEL proj_fwd_fused_kernel
-#define GS_FWD_CAM_PARAM CamParams cam
-#define GS_FWD_CAM_INIT
 #include "gs_proj_fwd_kernel.h"
-#undef GS_FWD_KERNEL
-#undef GS_FWD_CAM_PARAM
-#undef GS_FWD_CAM_INIT
-
-// Pose refinement (gs_set_pose_correction): the same kernel reading the camera pose_camera_kernel composed on the device,
-// instantiated with COLOUR only -- no riders: the binning kernels and colour_rest_kernel see only the host camera
-#define GS_FWD_KERNEL proj_fwd_fused_pose_kernel
-#define GS_FWD_CAM_PARAM const CamParams* __restrict__ dcam
-#define GS_FWD_CAM_INIT const CamParams cam = *dcam;
-#include "gs_proj_fwd_kernel.h"
-#undef GS_FWD_KERNEL
-#undef GS_FWD_CAM_PARAM
-#undef GS_FWD_CAM_INIT
 
 // ---------------------------------------------------------------------------------------------
 // fused backward: gradAcc16 (d packed) + raw parameters -> raw-parameter gradients
@@ -492,9 +478,6 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials,
     McmcFuse mc = McmcFuse{}, const float* __restrict__ filter3d = nullptr, const unsigned char* __restrict__ visMask = nullptr)
 {
-    static_assert(!MCMC || MODE == 2, "the MCMC step is fused into the Adam form only");
-    static_assert(!SPARSE || (MODE == 2 && !MCMC && !F3D), "sparse Adam: the plain fused Adam form only");
-    static_assert(!F3D || (!MCMC && MODE != 1), "the 3-D filter: single-device steps and the reference strategy only");
     constexpr bool EMIT_MG = MODE == 1, ADAM = MODE == 2;
     extern __shared__ float shLds[];
     // no update from a forward that did not render (gs_ctx.h adamGate).  The word is requested here and looked at only
@@ -728,117 +711,51 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     }
 }
 
-template <int MODE, bool AA = false>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(
-    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
-    float* gFdc, float* gFrest, float* gScales, float* gRot,
-    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam)
+// The forms that exist: MODE 2 {plain, F3D, MCMC, SPARSE} x POSE x AA, MODE 0 {plain, F3D} x POSE x AA, MODE 1 plain x AA (26)
+constexpr bool proj_bwd_form_exists(int MODE, bool POSE, bool MCMC, bool F3D, bool SPARSE)
 {
-    proj_bwd_fused_body<MODE, false, AA>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
-                                     gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, nullptr);
+    return (MODE == 0 || MODE == 1 || MODE == 2) &&
+           (!POSE || MODE != 1) &&                          // no pose refinement in the data-parallel form
+           (!MCMC || MODE == 2) &&                          // the MCMC step is fused into the Adam form only
+           (!SPARSE || (MODE == 2 && !MCMC && !F3D)) &&     // sparse Adam: the plain fused Adam form only
+           (!F3D || (!MCMC && MODE != 1));                  // the 3-D filter: single-device steps and the reference strategy only
 }
 
-// Pose refinement: the camera pose_camera_kernel composed, and the pose partials (MODE 0 and 2 only)
-template <int MODE, bool AA = false>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_kernel(
-    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
-    float* gFdc, float* gFrest, float* gScales, float* gRot,
-    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials)
+// The arguments of every form.  A form reads the fields its template flags name and no others, so the unused ones cost the default
+// forms nothing: every instantiation has the VGPRs, scratch and occupancy of the per-feature kernel it replaced (the four MODE 0 POSE
+// forms one VGPR fewer), measured and timed in DESIGN.md section 21.  dcam stands last so that the fields in front of it keep the
+// kernel-argument offsets they had.
+struct ProjBwdArgs {
+    int N, K, degree;
+    CamParams cam;               // the host camera; POSE reads *dcam instead
+    const float *xyz, *fdc, *frest, *scalesRaw, *rotRaw, *opacityRaw, *gradAcc16;
+    float *gXyz, *gFdc, *gFrest, *gScales, *gRot, *gOpacity;      // MODE 0 / 1 (MODE 1: gFdc receives mg[N,3]); MODE 2: unused
+    float* gradNormAccum;
+    AdamFuse adam;
+    float* posePartials;           // POSE
+    McmcFuse mc;                   // MCMC
+    const float* filter3d;         // F3D
+    const unsigned char* visMask;  // SPARSE
+    const CamParams* dcam;         // POSE: the camera pose_camera_kernel composed on the device
+};
+
+template <int MODE, bool POSE, bool AA, bool MCMC, bool F3D, bool SPARSE>
+__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(ProjBwdArgs a)
 {
-    static_assert(MODE == 0 || MODE == 2, "no pose refinement in the data-parallel form");
-    const CamParams cam = *dcam;
-    proj_bwd_fused_body<MODE, true, AA>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gFdc,
-                                    gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials);
+    static_assert(proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE), "no such form of the fused projection backward");
+    CamParams posed;
+    if constexpr (POSE) posed = *a.dcam;
+    proj_bwd_fused_body<MODE, POSE, AA, MCMC, F3D, SPARSE>(a.N, a.K, a.degree, POSE ? posed : a.cam, a.xyz, a.fdc, a.frest, a.scalesRaw,
+                                                           a.rotRaw, a.opacityRaw, a.gradAcc16, a.gXyz, a.gFdc, a.gFrest, a.gScales,
+                                                           a.gRot, a.gOpacity, a.gradNormAccum, a.adam, a.posePartials, a.mc, a.filter3d,
+                                                           a.visMask);
 }
 
-// The 3-D smoothing filter's forms (gs_set_filter3d): MODE 0 and 2, plain and posed, either anti-aliasing mode.  Kernels of their
-// own, so that the ones above keep their arguments and their code.
-template <int MODE, bool AA>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_f3d_kernel(
-    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
-    float* gFdc, float* gFrest, float* gScales, float* gRot,
-    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, const float* __restrict__ filter3d)
-{
-    proj_bwd_fused_body<MODE, false, AA, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
-                                                      gXyz, gFdc, gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, nullptr,
-                                                      McmcFuse{}, filter3d);
-}
-template <int MODE, bool AA>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_f3d_kernel(
-    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* gXyz,
-    float* gFdc, float* gFrest, float* gScales, float* gRot,
-    float* gOpacity, float* __restrict__ gradNormAccum, AdamFuse adam, float* __restrict__ posePartials,
-    const float* __restrict__ filter3d)
-{
-    const CamParams cam = *dcam;
-    proj_bwd_fused_body<MODE, true, AA, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
-                                                     gXyz, gFdc, gFrest, gScales, gRot, gOpacity, gradNormAccum, adam, posePartials,
-                                                     McmcFuse{}, filter3d);
-}
-
-// Sparse Adam (gs_set_sparse_adam): MODE 2 with the forward's visibility mask, plain and posed.  Kernels of their own, so that
-// the default ones above keep their arguments and their code.
-template <bool AA>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_sparse_kernel(
-    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
-    const unsigned char* __restrict__ visMask)
-{
-    proj_bwd_fused_body<2, false, AA, false, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
-                                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam,
-                                                          nullptr, McmcFuse{}, nullptr, visMask);
-}
-template <bool AA>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_sparse_kernel(
-    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
-    float* __restrict__ posePartials, const unsigned char* __restrict__ visMask)
-{
-    const CamParams cam = *dcam;
-    proj_bwd_fused_body<2, true, AA, false, false, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam,
-                                                         posePartials, McmcFuse{}, nullptr, visMask);
-}
-
-// ... and what the fused forward leaves for them: radius > 0 of every Gaussian, as a byte (gs_get_visibility reads the same)
+// what the fused forward leaves for the SPARSE forms: radius > 0 of every Gaussian, as a byte (gs_get_visibility reads the same)
 __global__ __launch_bounds__(256) void vis_mask_kernel(int N, const float* __restrict__ radii, unsigned char* __restrict__ mask)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p < N) mask[p] = radii[p] > 0.0f ? 1 : 0;
-}
-
-// The MCMC strategy's step (gs_set_mcmc): MODE 2 with the regularisers and the noise, plain and posed.  Kernels of their own,
-// so that the default ones above keep their code.
-template <bool AA>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_mcmc_kernel(
-    int N, int K, int degree, CamParams cam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
-    McmcFuse mc)
-{
-    proj_bwd_fused_body<2, false, AA, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, nullptr,
-                                            nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam, nullptr, mc);
-}
-template <bool AA>
-__global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_pose_mcmc_kernel(
-    int N, int K, int degree, const CamParams* __restrict__ dcam, const float* xyz, const float* fdc,
-    const float* frest, const float* scalesRaw, const float* rotRaw,
-    const float* opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gradNormAccum, AdamFuse adam,
-    float* __restrict__ posePartials, McmcFuse mc)
-{
-    const CamParams cam = *dcam;
-    proj_bwd_fused_body<2, true, AA, true>(N, K, degree, cam, xyz, fdc, frest, scalesRaw, rotRaw, opacityRaw, gradAcc16, nullptr,
-                                           nullptr, nullptr, nullptr, nullptr, nullptr, gradNormAccum, adam, posePartials, mc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -956,8 +873,8 @@ struct ViewCentersOwn {
 };
 
 template <bool AA>       // (the anti-aliased mode: proj_bwd_fused_body's AA)
-__device__ __forceinline__ void proj_bwd_geom_body(
-    int N, const CamParams& cam, const float* __restrict__ xyz, const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw,
+__global__ __launch_bounds__(256) void proj_bwd_geom_kernel(
+    int N, CamParams cam, const float* __restrict__ xyz, const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw,
     const float* __restrict__ opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gXyz,
     float* __restrict__ gScales, float* __restrict__ gRot, float* __restrict__ gOpacity, float* __restrict__ xyzOwn,
     const float* __restrict__ packed12, float* __restrict__ ccOut, const uint32_t* __restrict__ ovf, float* __restrict__ rider)
@@ -1019,17 +936,6 @@ __device__ __forceinline__ void proj_bwd_geom_body(
     const float sg = 1.0f / (1.0f + expf(-opacityRaw[p]));
     gOpacity[p] = (AA ? cotOpacity * aaRho : cotOpacity) * sg * (1.0f - sg);
 }
-
-#define GS_GEOM_PARAMS                                                                                                             \
-    int N, CamParams cam, const float* __restrict__ xyz, const float* __restrict__ scalesRaw, const float* __restrict__ rotRaw,   \
-        const float* __restrict__ opacityRaw, const float* __restrict__ gradAcc16, float* __restrict__ gXyz,                      \
-        float* __restrict__ gScales, float* __restrict__ gRot, float* __restrict__ gOpacity, float* __restrict__ xyzOwn,          \
-        const float* __restrict__ packed12, float* __restrict__ ccOut, const uint32_t* __restrict__ ovf, float* __restrict__ rider
-#define GS_GEOM_ARGS N, cam, xyz, scalesRaw, rotRaw, opacityRaw, gradAcc16, gXyz, gScales, gRot, gOpacity, xyzOwn, packed12, ccOut, ovf, rider
-__global__ __launch_bounds__(256) void proj_bwd_geom_kernel(GS_GEOM_PARAMS) { proj_bwd_geom_body<false>(GS_GEOM_ARGS); }
-__global__ __launch_bounds__(256) void proj_bwd_geom_aa_kernel(GS_GEOM_PARAMS) { proj_bwd_geom_body<true>(GS_GEOM_ARGS); }
-#undef GS_GEOM_PARAMS
-#undef GS_GEOM_ARGS
 
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void sh_views_dir_adam_kernel(
     int N, int K, int degree, ViewCentersOwn views, const float* __restrict__ xyz, const float* __restrict__ mgAll,
@@ -1171,44 +1077,15 @@ int launch_projection_backward(gs_ctx* c, int N, int K, const float* scales, con
     return GS_OK;
 }
 
-// the forward's kernel, in the anti-aliased mode's form (AA: gs_set_antialiasing) or the default one
-template <bool AA, bool F3D = false>
-static void launch_fwd_fused_kernel(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
-                                    const float* scales, const float* rot, const float* opacity, const CamParams& cam,
-                                    float* radii, bool posed, bool twoPhase, bool selfColour, size_t lds, int pflags,
-                                    const ColourRider& a, const GsCutCoarse& cc, uint4* pieces, const float* f3d = nullptr)
+// Runtime flags as template parameters: f(std::bool_constant<flag>{}...), one per flag and in their order.  f is a generic lambda
+// that guards its launch with `if constexpr (..._form_exists(...))`, so only the forms that exist are instantiated.
+template <class F>
+static int with_flags(F&& f) { return f(); }
+template <class F, class... Rest>
+static int with_flags(F&& f, bool flag, Rest... rest)
 {
-    if (c->rider.on)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           0, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
-    else if (posed && twoPhase)
-        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<true, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
-    else if (posed)
-        hipLaunchKernelGGL((proj_fwd_fused_pose_kernel<false, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, c->poseCam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
-    else if (selfColour)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, false, true, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW, c->stream, N, K, c->degree, cam, c->tileW,
-                           c->tileH, c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
-                           c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters,
-                           pflags, a, c->virt, cc, pieces, f3d);
-    else if (twoPhase)
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<true, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
-    else
-        hipLaunchKernelGGL((proj_fwd_fused_kernel<false, true, false, AA, F3D>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH, c->gridW, c->gridH, xyz, fdc, frest,
-                           scales, rot, opacity, c->packed12, radii, c->tileRect, c->tilesTouched, c->depthKey[0],
-                           c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc, pieces, f3d);
+    if (flag) return with_flags([&](auto... r) { return f(std::true_type{}, r...); }, rest...);
+    return with_flags([&](auto... r) { return f(std::false_type{}, r...); }, rest...);
 }
 
 int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fdc, const float* frest,
@@ -1257,19 +1134,27 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
         c->rider.next = 0;
         c->rider.total = gs_div_up(N, 64);
     }
-    // (the 3-D smoothing filter's forms, gs_set_filter3d: kernels of their own, the ones below are the ones they were)
-    if (c->filter3d && c->antialias)
-        launch_fwd_fused_kernel<true, true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
-                                            lds, pflags, a, cc, pieces, c->filter3d);
-    else if (c->filter3d)
-        launch_fwd_fused_kernel<false, true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
-                                             lds, pflags, a, cc, pieces, c->filter3d);
-    else if (c->antialias)
-        launch_fwd_fused_kernel<true>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
-                                      lds, pflags, a, cc, pieces);
-    else
-        launch_fwd_fused_kernel<false>(c, N, K, xyz, fdc, frest, scales, rot, opacity, cam, radii, posed, twoPhase, selfColour,
-                                       lds, pflags, a, cc, pieces);
+    // the form: geometry only under riders; the posed camera with the colours in the same kernel; geometry, then the wave's own
+    // colours; else the colours in the same kernel -- in two phases where the rows allow it
+    const bool colour = !c->rider.on && !selfColour;
+    const size_t dynLds = c->rider.on ? 0 : colour ? lds : sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW;
+    const int rc = with_flags(
+        [&](auto TWO_PHASE, auto COLOUR, auto SELF, auto AA, auto F3D, auto POSE) {
+            if constexpr (proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE)) {
+                hipLaunchKernelGGL((proj_fwd_fused_kernel<TWO_PHASE, COLOUR, SELF, AA, F3D, POSE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
+                                   dim3(PROJ_FUSED_THREADS), dynLds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH,
+                                   c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
+                                   c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc,
+                                   pieces, c->filter3d, c->poseCam);
+                return GS_OK;
+            } else {      // unreachable: rider.on and selfColour each imply !posed and exclude one another, so the form exists;
+                          // the branch is here for the lambda to compile for the combinations that have no kernel
+                c->err = "fused projection forward: no kernel for this combination of settings";
+                return GS_ERR_INVALID_ARG;
+            }
+        },
+        !colour || twoPhase, colour, selfColour, c->antialias, c->filter3d != nullptr, posed);
+    if (rc) return rc;
     c->visBlocks = gs_div_up(N, PROJ_FUSED_THREADS);
     GS_HIP_CHECK(c, hipGetLastError());
     if (c->sparseAdam) return launch_vis_mask(c, N, radii);      // (gs_render_forward hands a radii buffer of the context's in then)
@@ -1305,123 +1190,68 @@ int launch_colour_rest(gs_ctx* c)
     return GS_OK;
 }
 
-int launch_projection_fused_backward(gs_ctx* c, int N, int K, const float* xyz, const float* fdc,
-                                     const float* frest, const float* scales, const float* rot,
-                                     const float* opacity, const CamParams& cam, float* gXyz, float* gFdc,
-                                     float* gFrest, float* gScales, float* gRot, float* gOpacity, bool emitColorCot)
+// The fused backward of the context's forward (c->fwd), in the form its settings ask for.  mode: 0 gradients out, 1 the data-parallel
+// variant (g.fdc receives mg[N,3]), 2 the fused Adam step (no gradient leaves the kernel).  The filter beats the MCMC step beats sparse
+// Adam (api.hip lets no two of them be on together); a posed forward gets its pose gradient behind the kernel.
+struct ProjBwdGrads { float *xyz, *fdc, *frest, *scales, *rot, *opacity; };
+static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, const AdamFuse& adam)
 {
-    if (N == 0) return c->fwd.poseDelta && !emitColorCot ? launch_pose_grad(c, 0) : GS_OK;
+    const int N = c->fwd.N, K = c->fwd.K;
+    if (N == 0) return c->fwd.poseDelta && mode != 1 ? launch_pose_grad(c, 0) : GS_OK;
+    const bool f3d = c->fwd.filter3d != nullptr;       // (the filter this backward's forward ran with; no data-parallel form: api.hip refuses)
+    if (f3d && mode == 1) mode = 0;
+    const bool pose = c->fwd.poseDelta && mode != 1;
+    const bool mcmc = mode == 2 && !f3d && c->mcmcOn;
+    const bool sparse = mode == 2 && !f3d && !mcmc && c->sparseAdam;      // (api.hip has checked that the forward left its mask)
+    ProjBwdArgs a = {};
+    a.N = N; a.K = K; a.degree = c->degree;
+    a.cam = c->fwd.cam; a.dcam = c->poseCam;
+    a.xyz = c->fwd.xyz; a.fdc = c->fwd.fdc; a.frest = c->fwd.frest; a.scalesRaw = c->fwd.scales; a.rotRaw = c->fwd.rot;
+    a.opacityRaw = c->fwd.opacity; a.gradAcc16 = c->gradAcc16;
+    a.gXyz = g.xyz; a.gFdc = g.fdc; a.gFrest = g.frest; a.gScales = g.scales; a.gRot = g.rot; a.gOpacity = g.opacity;
+    a.gradNormAccum = c->gradNormAccum;
+    a.adam = adam;
+    a.posePartials = c->posePartials;
+    if (mcmc) a.mc = mcmc_fuse(c->mcmc, N, adam.lr[0]);
+    a.filter3d = c->fwd.filter3d;
+    a.visMask = c->visMask;
     const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
-    const bool aa = c->fwd.antialias;       // (the mode this backward's forward ran in)
-    AdamFuse none = {};
-    if (!emitColorCot) { none.ovf = c->counters + GS_CNT_OVERFLOW; none.rider = c->overflowRider; }
-    if (const float* f3d = c->fwd.filter3d) {      // (the filter this backward's forward ran with; no data-parallel form: api.hip refuses)
-        if (c->fwd.poseDelta) {
-            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_f3d_kernel<0, true> : proj_bwd_fused_pose_f3d_kernel<0, false>),
-                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam,
-                               xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz, gFdc, gFrest, gScales, gRot, gOpacity,
-                               c->gradNormAccum, none, c->posePartials, f3d);
-            GS_HIP_CHECK(c, hipGetLastError());
-            return launch_pose_grad(c, N);
-        }
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_f3d_kernel<0, true> : proj_bwd_fused_f3d_kernel<0, false>),
-                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam, xyz, fdc,
-                           frest, scales, rot, opacity, c->gradAcc16, gXyz, gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum,
-                           none, f3d);
-        GS_HIP_CHECK(c, hipGetLastError());
-        return GS_OK;
-    }
-    if (c->fwd.poseDelta && !emitColorCot) {
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_kernel<0, true> : proj_bwd_fused_pose_kernel<0>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
-                           dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity,
-                           c->gradAcc16, gXyz, gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum, none, c->posePartials);
-        GS_HIP_CHECK(c, hipGetLastError());
-        return launch_pose_grad(c, N);
-    }
-    if (!emitColorCot)
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_kernel<0, true> : proj_bwd_fused_kernel<0>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
-                           gFdc, gFrest, gScales, gRot, gOpacity, c->gradNormAccum, none);
-    else   // data-parallel variant: gFdc receives mg[N,3]
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_kernel<1, true> : proj_bwd_fused_kernel<1>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                           lds, c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, gXyz,
-                           gFdc, nullptr, gScales, gRot, gOpacity, c->gradNormAccum, none);
+    const int rc = with_flags(
+        [&](auto ADAM, auto EMIT_MG, auto POSE, auto AA, auto MCMC, auto F3D, auto SPARSE) {
+            constexpr int MODE = ADAM ? 2 : EMIT_MG ? 1 : 0;
+            if constexpr (!(ADAM && EMIT_MG) && proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE)) {
+                hipLaunchKernelGGL((proj_bwd_fused_kernel<MODE, POSE, AA, MCMC, F3D, SPARSE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
+                                   dim3(PROJ_FUSED_THREADS), lds, c->stream, a);
+                return GS_OK;
+            } else {      // unreachable: f3d, mcmc and sparse are derived above to exclude one another and, like pose, mode 1;
+                          // the branch is here for the lambda to compile for the combinations that have no kernel
+                c->err = "fused projection backward: no kernel for this combination of settings";
+                return GS_ERR_INVALID_ARG;
+            }
+        },
+        mode == 2, mode == 1, pose, c->fwd.antialias, mcmc, f3d, sparse);
+    if (rc) return rc;
     GS_HIP_CHECK(c, hipGetLastError());
-    return GS_OK;
+    return pose ? launch_pose_grad(c, N) : GS_OK;
 }
 
-int launch_projection_fused_backward_adam(gs_ctx* c, int N, int K, const float* xyz, const float* fdc,
-                                          const float* frest, const float* scales, const float* rot,
-                                          const float* opacity, const CamParams& cam, const float* pBase, float* mBase,
-                                          float* vBase, const float lr[6], float b1, float b2, float eps, float gscale)
+int launch_projection_fused_backward(gs_ctx* c, float* gXyz, float* gFdc, float* gFrest, float* gScales, float* gRot, float* gOpacity,
+                                     bool emitColorCot)
 {
-    if (N == 0) return c->fwd.poseDelta ? launch_pose_grad(c, 0) : GS_OK;
-    const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
-    AdamFuse a;
+    AdamFuse none = {};
+    if (!emitColorCot) { none.ovf = c->counters + GS_CNT_OVERFLOW; none.rider = c->overflowRider; }
+    return launch_proj_bwd_fused(c, emitColorCot ? 1 : 0, ProjBwdGrads{gXyz, gFdc, gFrest, gScales, gRot, gOpacity}, none);
+}
+
+int launch_projection_fused_backward_adam(gs_ctx* c, const float* pBase, float* mBase, float* vBase, const float lr[6], float b1,
+                                          float b2, float eps, float gscale)
+{
+    AdamFuse a = {};
     a.pBase = pBase; a.mBase = mBase; a.vBase = vBase;
     for (int i = 0; i < 6; i++) a.lr[i] = lr[i];
     a.b1 = b1; a.b2 = b2; a.eps = eps; a.gscale = gscale;
     a.gate = c->adamGate;
-    const bool aa = c->fwd.antialias;
-    if (const float* f3d = c->fwd.filter3d) {      // (never with the MCMC step: gs_set_filter3d and gs_set_mcmc refuse each other)
-        if (c->fwd.poseDelta) {
-            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_f3d_kernel<2, true> : proj_bwd_fused_pose_f3d_kernel<2, false>),
-                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, c->poseCam,
-                               xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               c->gradNormAccum, a, c->posePartials, f3d);
-            GS_HIP_CHECK(c, hipGetLastError());
-            return launch_pose_grad(c, N);
-        }
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_f3d_kernel<2, true> : proj_bwd_fused_f3d_kernel<2, false>),
-                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam, xyz, fdc,
-                           frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           c->gradNormAccum, a, f3d);
-        GS_HIP_CHECK(c, hipGetLastError());
-        return GS_OK;
-    }
-    if (c->mcmcOn) {
-        const McmcFuse mc = mcmc_fuse(c->mcmc, N, lr[0]);
-        if (c->fwd.poseDelta) {
-            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_mcmc_kernel<true> : proj_bwd_fused_pose_mcmc_kernel<false>),
-                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree,
-                               c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a,
-                               c->posePartials, mc);
-            GS_HIP_CHECK(c, hipGetLastError());
-            return launch_pose_grad(c, N);
-        }
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_mcmc_kernel<true> : proj_bwd_fused_mcmc_kernel<false>),
-                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam,
-                           xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a, mc);
-        GS_HIP_CHECK(c, hipGetLastError());
-        return GS_OK;
-    }
-    if (c->sparseAdam) {       // (api.hip has checked that the forward left its mask; never with a filter or the MCMC step: refused)
-        if (c->fwd.poseDelta) {
-            hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_sparse_kernel<true> : proj_bwd_fused_pose_sparse_kernel<false>),
-                               dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree,
-                               c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a,
-                               c->posePartials, c->visMask);
-            GS_HIP_CHECK(c, hipGetLastError());
-            return launch_pose_grad(c, N);
-        }
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_sparse_kernel<true> : proj_bwd_fused_sparse_kernel<false>),
-                           dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N, K, c->degree, cam,
-                           xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, c->gradNormAccum, a, c->visMask);
-        GS_HIP_CHECK(c, hipGetLastError());
-        return GS_OK;
-    }
-    if (c->fwd.poseDelta) {
-        hipLaunchKernelGGL((aa ? proj_bwd_fused_pose_kernel<2, true> : proj_bwd_fused_pose_kernel<2>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
-                           c->stream, N, K, c->degree, c->poseCam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, c->gradNormAccum, a, c->posePartials);
-        GS_HIP_CHECK(c, hipGetLastError());
-        return launch_pose_grad(c, N);
-    }
-    hipLaunchKernelGGL((aa ? proj_bwd_fused_kernel<2, true> : proj_bwd_fused_kernel<2>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds,
-                       c->stream, N, K, c->degree, cam, xyz, fdc, frest, scales, rot, opacity, c->gradAcc16, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, c->gradNormAccum, a);
-    GS_HIP_CHECK(c, hipGetLastError());
-    return GS_OK;
+    return launch_proj_bwd_fused(c, 2, ProjBwdGrads{}, a);
 }
 
 // gs_set_gathered_gate: the gathered colour cotangents come as `count` blocks of ccBlockFloats floats, every block's word
@@ -1482,15 +1312,18 @@ int launch_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* 
     return GS_OK;
 }
 
-int launch_projection_geom_backward(gs_ctx* c, int N, const float* xyz, const float* scales, const float* rot,
-                                    const float* opacity, const CamParams& cam, float* gXyz, float* gScales, float* gRot,
-                                    float* gOpacity, float* xyzOwn, float* colorCot)
+int launch_projection_geom_backward(gs_ctx* c, float* gXyz, float* gScales, float* gRot, float* gOpacity, float* xyzOwn, float* colorCot)
 {
+    const int N = c->fwd.N;
     if (N == 0) return GS_OK;
-    hipLaunchKernelGGL((c->fwd.antialias ? proj_bwd_geom_aa_kernel : proj_bwd_geom_kernel), dim3(gs_div_up(N, 256)), dim3(256), 0,
-                       c->stream, N, cam, xyz, scales, rot, opacity,
-                       c->gradAcc16, gXyz, gScales, gRot, gOpacity, xyzOwn, c->packed12, colorCot, c->counters + GS_CNT_OVERFLOW,
-                       c->overflowRider);
+    with_flags(
+        [&](auto AA) {
+            hipLaunchKernelGGL(proj_bwd_geom_kernel<AA>, dim3(gs_div_up(N, 256)), dim3(256), 0, c->stream, N, c->fwd.cam, c->fwd.xyz,
+                               c->fwd.scales, c->fwd.rot, c->fwd.opacity, c->gradAcc16, gXyz, gScales, gRot, gOpacity, xyzOwn,
+                               c->packed12, colorCot, c->counters + GS_CNT_OVERFLOW, c->overflowRider);
+            return GS_OK;
+        },
+        c->fwd.antialias);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }
@@ -1613,7 +1446,7 @@ __global__ __launch_bounds__(64) void pose_camera_kernel(CamParams host, const f
     *out = o;
 }
 
-// dL/d delta from the wave partials of proj_bwd_fused_pose_kernel: one workgroup, sums in a fixed order (no atomics), the
+// dL/d delta from the wave partials of proj_bwd_fused_kernel's POSE forms: one workgroup, sums in a fixed order (no atomics), the
 // chain rule in float64.  G[k][a] = dL/dV'[k][a] = part [3 k + a] (k < 4, a < 3), gc = dL/dcam' = parts [12 .. 14].  With dA = G^T (dL/d w2c'[:3, :4]),
 // B = [Rw | tw - tau]:  dL/dtau = -(R dA)[:, 3] + Rw gc,  dL/dw_i = sum_ja (B dA^T)[j][a] dR[j][a]/dw_i,
 // dR/dw_i = C w_i K + A E_i + D w_i K^2 + B (E_i K + K E_i), E_i = [e_i]x.
@@ -1696,7 +1529,7 @@ int launch_pose_camera(gs_ctx* c, const CamParams& host, const float* delta)
     return GS_OK;
 }
 
-// floats of the backward's pose partials: a row of 16 per wave of proj_bwd_fused_pose_kernel
+// floats of the backward's pose partials: a row of 16 per wave of proj_bwd_fused_kernel's POSE forms
 long long pose_partials_floats(int N)
 {
     return 16LL * gs_div_up(N, PROJ_FUSED_THREADS) * (PROJ_FUSED_THREADS / 64);

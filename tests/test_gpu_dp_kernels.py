@@ -7,8 +7,8 @@ multi-rank run would feed them is reproduced here on one GPU:
     the wave (64) and the workgroup (128), R = 1, 3, 16, every (K, degree) pair, in a GaussModel arena and in hand-built arenas
     with features_rest off the 16-byte grid;
   the gates: gs_set_update_gate, gs_set_gathered_gate (more than one block on a device), gs_set_gate_seen, gs_set_overflow_rider;
-  per view on a rendered scene: gs_render_backward_dp_geom and gs_render_backward_dp_begin + _finish_geom (proj_bwd_geom_kernel,
-    proj_bwd_geom_aa_kernel) against the oracle, the view-direction term of the xyz gradient from the restatement.
+  per view on a rendered scene: gs_render_backward_dp_geom and gs_render_backward_dp_begin + _finish_geom
+    (proj_bwd_geom_kernel<false / true>) against the oracle, the view-direction term of the xyz gradient from the restatement.
 
 Bars.  SH gradient, xyz_add, densify statistic: the project's for gradShs / gradMeans3d (test_projection_forward_backward), rtol 2e-4
 and atol 2e-5 max|want|, against float64.  Adam: test_adam_step_matches_numpy's (rtol 2e-6; atol 1e-7 / 1e-9 / 1e-12 for p / m / v)
@@ -739,7 +739,7 @@ def test_per_view_backward_forms_against_the_oracle(renderer_of, oracle32, confi
 
 def test_zero_raw_quaternion_leaves_the_same_pattern_in_every_backward_form(renderer_of, oracle32):
     """A visible and an invisible Gaussian whose raw quaternion is exactly zero: the normalisation's VJP divides by |q| = 0 in
-    proj_bwd_geom_body and in the fused body alike.  Every data-parallel form must leave the finite / non-finite pattern
+    proj_bwd_geom_kernel and in the fused body alike.  Every data-parallel form must leave the finite / non-finite pattern
     gs_render_backward leaves on those rows, every other row finite and within the bars.  The oracle (float32) gives NaN in all
     four rotation entries of such a row, visible or not (0 x inf), and finite values everywhere else."""
     p, cams, W, H = dn.e2e_scene()

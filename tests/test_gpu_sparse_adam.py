@@ -1,5 +1,5 @@
 """Sparse Adam on the device (include/gsplat.h gs_set_sparse_adam): the mask the fused forward leaves, one
-fused step against the same step with the setting off (csrc/projection.hip, the SPARSE instantiations of proj_bwd_fused_body),
+fused step against the same step with the setting off (csrc/projection.hip, the SPARSE forms of proj_bwd_fused_kernel),
 the unfused path and gs_adam_step_visible (csrc/optim.hip, adam_visible_kernel) against the numpy rule
 (gaussiansplattingmlx_amd/sparse_adam.py), the trainer, the overflow gate, the refusals, and that off is off.
 
