@@ -25,8 +25,9 @@
 //    device queue; the first item of a wave is its blockIdx.x (thousands of simultaneous pops on one counter take
 //    ~6 ns each to resolve: 15 % of the kernel).  With a per-view block-work buffer (gs_set_block_work_buffer) the
 //    queue is ordered deepest-first, which takes the slowest wave from 1.55x to 1.16x the mean.  Every SEG list
-//    positions the running state (T, C, D) is saved per pixel.  blend_fwd_v2_kernel is the older 16x8, two pixels
-//    per lane, packed-f32 variant (gs_ctx_set_tuning(GS_TUNE_FWD_QUADRANTS, 0) selects it): same results, ~25 % slower.
+//    positions the running state (T, C, D) is saved per pixel.  blend_fwd_v2p_kernel (a staging wave beside every
+//    sweeping wave, for deep lists) and blend_fwd_v2w_kernel (four waves per quadrant, for images with fewer quadrants
+//    than wave slots) are the same sweep on other schedules; the three share their pieces ("forward" below).
 //  * Backward (blend_bwd_v2_kernel): the saved states make a tile's list SEGMENT-parallel.  The work items are
 //    (pixel block, segment) pairs of at most SEG list positions, pulled from a device queue by persistent
 //    single-wave workgroups.  Inside an item the sweep runs FORWARD (T by multiplication, as the forward pass), with
@@ -192,18 +193,17 @@ __global__ __launch_bounds__(1024) void bwd_items_kernel(BwdPrepArgs prep, int c
 }
 
 // ---------------------------------------------------------------------------------------------
-// packed-f32 helpers.  The f32 VALU of gfx950 retires one wave64 instruction per 4 cycles per SIMD (measured:
-// both blend kernels ran at >90 % of that issue rate while "using" 25 % of the 157 TFLOP/s headline, which
-// counts v_pk_fma_f32).  Each lane therefore owns pixel PAIRS (x, x+8) on one image row and does the pair's
-// arithmetic with v_pk_mul/add/fma_f32; the row term dy is shared by the pair and stays scalar per lane.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ f2 splat2(float v) { return (f2){v, v}; }
-__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-
-// ---------------------------------------------------------------------------------------------
 // forward: one wavefront per 8x8 quadrant (h, k) of a 16x16 block, one pixel per lane, scalar f32.  (Rounds 1-2 also
 // kept a 16x8 variant, two pixels per lane in packed f32: the same instruction slots -- v_pk_* has no throughput
 // advantage -- but twice the per-splat dependent chain and a cull over 128 pixels instead of 64; 25 % slower, retired.)
+//
+// Three kernels serve it (launch_blend_forward_v2 picks one per forward): blend_fwd_v2q_kernel, one wave per quadrant (the
+// default); blend_fwd_v2p_kernel, a staging wave beside every sweeping wave (deep lists); blend_fwd_v2w_kernel, four waves
+// per quadrant (fewer quadrants than wave slots).  What they share exists once, in front of them: the argument struct, the
+// pop of the next item, its decode, the staging (fwd_stage_compact), the per-entry arithmetic (fwd_pre / fwd_post /
+// fwd_trips), the checkpoint allocator and store (ckpt_save) and the epilogue (fwd_finish).  The three differ in who does
+// what when, not in what is computed: test_staging_wave_forward_leaves_the_same_bits holds the pair kernel to the one-wave
+// kernel's bits.
 //
 // Checkpoints.  Every SEG list entries a quadrant that still has a live pixel saves its running state (T, R, G, B[, D])
 // for the segment-parallel backward.  Round 2 addressed the slots by list position (slot = first slot of the block +
@@ -216,19 +216,332 @@ __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementw
 // then this forward wrote the entry.  An arena that runs out raises the overflow word like a pair reserve that does
 // (the render itself is complete; the step is gated, the host regrows: gs_ctx_reserve).
 // ---------------------------------------------------------------------------------------------
+// what a forward kernel is launched with: one struct by value, filled once by launch_blend_forward_v2
+struct BlendFwdArgs {
+    int W, H, tileW, tileH, gridW, blocksX, nItems;
+    GsBackground bgc;
+    const float4* rec12;
+    const uint32_t* sortedIdx;
+    uint32_t idxMask;
+    const uint32_t *tileRanges, *segBase;
+    uint32_t segCap;
+    int statePlanes;                // 0: a render-only forward, no checkpoints
+    float *outColor, *outDepth, *outAlpha;
+    uint32_t* lastContrib;
+    float* finalT;
+    float* segState;
+    uint32_t* segSlot;
+    uint32_t qslotCap, qslotOwn, qslotShared0, qslotPart, ckptPool;      // the checkpoint arena (CkptPool, ckpt_save)
+    uint32_t *blockWork, *counters, *fwdQueue;
+    uint32_t nq;
+    const uint32_t *blockOrder, *cutStore;
+    uint32_t* hostWords;
+    GsVirtGeom vg;
+    unsigned long long* trace;      // blend_fwd_v2q_kernel only
+    uint32_t slowSlot;              // blend_fwd_v2q_kernel only
+    float foldScale;                // blend_fwd_v2w_kernel only
+};
+
+// Work distribution (round 4).  An item is one 8x8 quadrant of the pixel block at position p of the launch order
+// (blockOrder, deepest first).  The four quadrant waves of a block gather the same records; workgroups go to the eight
+// XCDs round-robin, each XCD with an L2 of its own, and rounds 1-3 gave the four items of a block to four consecutive
+// waves = four XCDs: every record was fetched from the fabric four times (PMC: 3.9x the algorithmic bytes).  Now block
+// position p belongs to XCD p mod 8: the taker (a wave of the one-wave kernel, a workgroup of the other two) with slot
+// s on XCD x starts on quadrant s mod 4 of position 8 (s / 4) + x -- its static first item: thousands of simultaneous
+// pops on one counter take ~6 ns each to resolve, 15 % of the kernel --, and the positions behind the statically assigned
+// ones are handed out by EIGHT queues, one per XCD (four consecutive pops = one block), so the quadrants of a block meet in
+// one L2 -- and the pops, which resolve at ~6 ns each on one address, spread over eight.  A taker whose XCD's queue has run
+// dry takes from the others'.
+// nq = 8 queues (default) / 1 (rounds 1-3's mapping: one queue; GS_TUNE_FWD_QUEUES, A/B)
+// (workgroup g sits on XCD g mod nq)
+struct FwdQueue {
+    uint32_t xcd, slot;       // this taker's XCD and its slot there
+    uint32_t nPos;            // positions of the launch order: the pixel blocks, padded to whole rows of nq (gs_bwd_prep.h, seg_base_body)
+    uint32_t staticRows;      // rows of nq positions covered by the takers' first items
+    uint32_t dead;            // queues found empty
+};
+__device__ __forceinline__ FwdQueue fwd_queue(const BlendFwdArgs& a, uint32_t slot, uint32_t takers)
+{
+    FwdQueue q;
+    q.xcd = blockIdx.x % a.nq; q.slot = slot;
+    q.nPos = a.nq * ((((uint32_t)a.nItems >> 2) + a.nq - 1u) / a.nq);
+    q.staticRows = takers / (4u * a.nq);
+    q.dead = 0;
+    return q;
+}
+// the taker's next (position, quadrant), called by one whole wave: the static item first, then the queues (mayPop).  pos stays
+// >= nPos when there is none: every queue is empty, and they only grow, so every taker gets there
+__device__ __forceinline__ void fwd_pop(const BlendFwdArgs& a, FwdQueue& q, bool first, bool mayPop, int lane, uint32_t& pos, uint32_t& quad)
+{
+    pos = 0xFFFFFFFFu; quad = 0;
+    if (first && (q.slot >> 2) < q.staticRows) { pos = a.nq * (q.slot >> 2) + q.xcd; quad = q.slot & 3u; }
+    else if (mayPop) {
+        for (uint32_t t = 0; t < a.nq && pos == 0xFFFFFFFFu; t++) {
+            const uint32_t y = (q.xcd + t) % a.nq;
+            if ((q.dead >> y) & 1u) continue;
+            // (no look before the pop: a load of the line the pops hammer queues behind them -- measured, one queue:
+            // blend forward 0.19 -> 0.49 ms with a relaxed load in front of every atomicAdd)
+            uint32_t k = 0;
+            if (lane == 0) k = atomicAdd(&a.fwdQueue[y * 32u], 1u);
+            k = __builtin_amdgcn_readfirstlane(k);
+            const uint32_t p = a.nq * (q.staticRows + (k >> 2)) + y;
+            if (p < q.nPos) { pos = p; quad = k & 3u; }
+            else q.dead |= 1u << y;
+        }
+    }
+}
+
+// an item, decoded: the block, its quadrant, its list, this lane's pixel
+struct FwdItem {
+    int b, h, k, tile;
+    uint32_t start, count, sbase;      // the tile's list, the block's first saved state (segBase)
+    int X0, Y0, XL, YL;                // the block's pixel origin and limits (block lists: blocks are enumerated per tile)
+    int x, y;
+    bool in;                           // the lane's pixel lies in the image
+    float px, py;
+    float qx0, qx1, qy0, qy1;          // the quadrant's pixel-centre rectangle, for the lane-private reach test at staging time
+};
+// A word of a table the forward only reads (blockOrder, tileRanges, segBase, the depth cuts: written by the launches in front
+// of it), through the constant address space: at a wave-uniform index it is a scalar load.  The kernels' flat __restrict__
+// arguments used to say as much; the members of a by-value struct carry no such promise, and the item's dependent chain of
+// three look-ups came out as vector loads + v_readfirstlane (blend forward on the 300 k / 800x800 scene: 0.1658 -> 0.1676 ms,
+// one-wave kernel).
+__device__ __forceinline__ uint32_t fwd_table_word(const uint32_t* table, uint32_t i)
+{
+    return ((const __attribute__((address_space(4))) uint32_t*)table)[i];
+}
+// false: a position a short last stripe leaves over (an empty list, no pixel in the image)
+__device__ __forceinline__ bool fwd_decode(const BlendFwdArgs& a, uint32_t pos, uint32_t quad, int lane, FwdItem& it)
+{
+    const uint32_t bRaw = __builtin_amdgcn_readfirstlane(fwd_table_word(a.blockOrder, pos));
+    const bool valid = bRaw != 0xFFFFFFFFu;
+    it.b = (int)bRaw;
+    it.h = (int)((quad >> 1) & 1u); it.k = (int)(quad & 1u);
+    it.start = 0; it.count = 0; it.sbase = 0;
+    it.tile = 0; it.X0 = 0; it.Y0 = 0; it.XL = 0; it.YL = 0;
+    if (valid) {
+        const int by = it.b / a.blocksX, bx = it.b - by * a.blocksX;
+        it.tile = ((by * BLK) / a.tileH) * a.gridW + (bx * BLK) / a.tileW;
+        it.start = __builtin_amdgcn_readfirstlane(fwd_table_word(a.tileRanges, 2 * it.tile));
+        const uint32_t end = __builtin_amdgcn_readfirstlane(fwd_table_word(a.tileRanges, 2 * it.tile + 1));
+        it.count = end > it.start ? end - it.start : 0u;
+        it.sbase = __builtin_amdgcn_readfirstlane(fwd_table_word(a.segBase, it.b));
+        gs_block_pixels(a.vg, bx, by, a.W, a.H, it.X0, it.Y0, it.XL, it.YL);
+    }
+    it.x = it.X0 + it.k * 8 + (lane & 7); it.y = it.Y0 + it.h * 8 + (lane >> 3);
+    it.in = valid && it.x < it.XL && it.y < it.YL;
+    it.px = (float)it.x; it.py = (float)it.y;
+    it.qx0 = (float)(it.X0 + it.k * 8); it.qx1 = it.qx0 + 7.0f; it.qy0 = (float)(it.Y0 + it.h * 8); it.qy1 = it.qy0 + 7.0f;
+    return valid;
+}
+
+// Staging compacts the chunk: lane j holds list entry c0 + j and tests it against the whole quadrant -- the
+// minimum of its quadratic form over the pixel rectangle (rect_min_q) -- and only entries that can reach a
+// pixel are parked in LDS, each with its list position.  An entry whose weight is below 2^-29 everywhere
+// moves no pixel's state by more than ~5e-8 (CULL_QMIN), so skipping it changes nothing but the work: no LDS
+// broadcast (the CU's LDS port is what saturates first with one pixel per lane), no exponent, no exp.
+// Returns the entries parked, a multiple of four.
+__device__ __forceinline__ uint32_t fwd_stage_compact(f4* slot, const RecV& v, uint32_t c0, const FwdItem& it, int lane)
+{
+    const float qmin = rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, it.qx0 - v.a.x, it.qx1 - v.a.x, it.qy0 - v.a.y, it.qy1 - v.a.y);
+    const bool keep = (c0 + lane < it.count) && !(qmin > CULL_QMIN);
+    const unsigned long long m = __ballot(keep);
+    // kept entries in the lanes below this one (v_mbcnt: written as popc(m & ((1 << lane) - 1)), the 64-bit lane mask became a
+    // loop invariant of the item loop that the four-wave kernel, at its register budget, kept in scratch)
+    const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (keep) {
+        slot[pos * 3] = v.a; slot[pos * 3 + 1] = v.b;
+        slot[pos * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(c0 + (uint32_t)lane + 1u)};
+    }
+    // pad to a multiple of four with null splats (opacity 0: alpha = 0, state untouched) so that the loop runs
+    // whole groups only; a pixel still live at a pad entry is live at the end of the chunk, hence its nContrib
+    const uint32_t n = (uint32_t)__popcll(m), n4 = (n + 3u) & ~3u;
+    if ((uint32_t)lane < n4 - n) {
+        const f4 z = (f4){0.f, 0.f, 0.f, 0.f};
+        slot[(n + lane) * 3] = z; slot[(n + lane) * 3 + 1] = z;
+        slot[(n + lane) * 3 + 2] = (f4){0.f, 0.f, 0.f, __uint_as_float(min(c0 + 64u, it.count))};
+    }
+    return n4;
+}
+
+// a lane's pixel while its list is swept.  Round 6: the colour (depth) sums are kept as BASE + CHUNK -- the entries of the
+// current 64-position chunk accumulate from zero, and the chunk's sum is added to the base at the chunk's end (one rounding
+// of the size of the total per chunk instead of one per entry).  The backward takes what the rest of a list still owes from
+// the difference between the final image and a checkpoint (a base); deep in a list that difference is small against both,
+// and its error was the forward's per-entry roundings at the size of the TOTAL.  Same instruction
+// count per entry.  (The four-wave kernel keeps its base in LDS meanwhile, not here: trips_abs.)
+struct FwdPixel {
+    float T;
+    float cr, cg, cb, dd;          // this chunk's sums
+    float br, bgr, bb, bd;         // the sums of the chunks in front of it
+    uint32_t nc;
+};
+__device__ __forceinline__ FwdPixel fwd_pixel(bool in)
+{
+    FwdPixel s;
+    s.T = in ? 1.0f : 0.0f;        // pixels outside the image start dead and are never stored
+    s.cr = s.cg = s.cb = s.dd = 0.f;
+    s.br = s.bgr = s.bb = s.bd = 0.f;
+    s.nc = 0;
+    return s;
+}
+// the chunk behind us joins the base
+template <bool DEPTH>
+__device__ __forceinline__ void fwd_join_chunk(FwdPixel& s)
+{
+    s.br += s.cr; s.bgr += s.cg; s.bb += s.cb; s.cr = 0.f; s.cg = 0.f; s.cb = 0.f;
+    if (DEPTH) { s.bd += s.dd; s.dd = 0.f; }
+}
+
+// what of a staged entry does not depend on the running state (the exponents and exps first, the short serial chain
+// through T second: fwd_trips)
+struct Pre {
+    float aclamp, r, g, b, depth;
+    uint32_t ncv;              // list position + 1 of the splat: nContrib of a pixel that is live when it arrives
+};
+__device__ __forceinline__ void fwd_pre(const f4* slot, uint32_t j, float px, float py, Pre& o)
+{
+    const Rec s = unpack(slot[j * 3], slot[j * 3 + 1], slot[j * 3 + 2]);
+    const float dx = px - s.mx, dy = py - s.my;
+    const float dxdy = dx * dy, dx2 = dx * dx, dy2 = dy * dy;
+    const float q = ((dx2 * s.c00 + dy2 * s.c11) + dxdy * s.c01) + dxdy * s.c10;
+#ifdef GS_FWD_LIBM_EXP   // experiment: the oracle's exp(-0.5 q) through the device math library instead of v_exp_f32
+    o.aclamp = fminf(s.op * expf(-0.5f * q), 0.99f);
+#else
+    o.aclamp = fminf(gauss_alpha_raw(q, s.op), 0.99f);
+#endif
+    o.r = s.r; o.g = s.g; o.b = s.b; o.depth = s.depth;
+    o.ncv = __float_as_uint(slot[j * 3 + 2].w);
+}
+template <bool DEPTH>
+__device__ __forceinline__ void fwd_post(FwdPixel& s, const Pre& o)
+{
+    const bool a = s.T >= 1e-4f;
+    s.nc = a ? o.ncv : s.nc;
+    const float alpha = a ? o.aclamp : 0.0f;
+    const float w = s.T * alpha;
+#ifdef GS_FWD_UNFUSED   // experiment (DESIGN.md section 2, "the 1e-4 bar"): the reference's two-rounding C + w c
+    s.cr = s.cr + w * o.r; s.cg = s.cg + w * o.g; s.cb = s.cb + w * o.b; if (DEPTH) s.dd = s.dd + w * o.depth;
+#else
+    s.cr = fmaf(w, o.r, s.cr); s.cg = fmaf(w, o.g, s.cg); s.cb = fmaf(w, o.b, s.cb); if (DEPTH) s.dd = fmaf(w, o.depth, s.dd);
+#endif
+    s.T = s.T * (1.0f - alpha);
+}
+__device__ __forceinline__ bool fwd_any_live(float T) { return __any(T >= 1e-4f); }
+// the n staged entries (a multiple of four) against the running state, four per trip, until the quadrant has no live pixel
+// left (live = false); returns the entries gone through
+template <bool DEPTH>
+__device__ __forceinline__ uint32_t fwd_trips(const f4* slot, uint32_t n, float px, float py, FwdPixel& s, bool& live)
+{
+    live = true;
+    uint32_t j = 0;
+    for (; j < n; j += 4) {
+        Pre p0, p1, p2, p3;
+        fwd_pre(slot, j, px, py, p0); fwd_pre(slot, j + 1, px, py, p1); fwd_pre(slot, j + 2, px, py, p2); fwd_pre(slot, j + 3, px, py, p3);
+        fwd_post<DEPTH>(s, p0); fwd_post<DEPTH>(s, p1); fwd_post<DEPTH>(s, p2); fwd_post<DEPTH>(s, p3);
+        if (!fwd_any_live(s.T)) { live = false; break; }
+    }
+    return j;
+}
+
+// A wave's pool of checkpoint slots (wave-uniform): qslotOwn slots of the arena are its own from the start -- every
+// wave reaches its first boundary at about the same time, and that many pops on one counter would take ~6 ns each
+// to resolve (measured: blend forward 0.19 -> 0.30 ms with a shared counter only) -- and only a wave that uses them
+// up draws ckptPool (up to 8) more at a time from the shared part behind them, which is split in eight with a counter each
+// (workgroups go round-robin over the eight XCDs: a wave's counter lives in its own L2).  With ONE counter behind
+// a static share of 12 slots the 100 k / 800x800 config, whose waves need ~20, lost 54 us of its 175 (blend forward).
+struct CkptPool {
+    uint32_t next, end;
+    uint32_t part, partsEmpty;      // the wave's own eighth of the shared part; the eighths found empty
+};
+// wave: the dense id of this wave among those that own a pool.  The host sized the arena for their number (launch_blend_forward_v2:
+// every wave of the one-wave kernel, the sweeping wave of a pair, all four waves of a four-wave workgroup): qslotOwn each, the
+// shared part from qslotShared0 = their number x qslotOwn on -- one value, the host's, under all three kernels
+__device__ __forceinline__ CkptPool ckpt_pool_of(const BlendFwdArgs& a, uint32_t wave)
+{
+    CkptPool p;
+    p.next = wave * a.qslotOwn; p.end = p.next + a.qslotOwn;
+    p.part = blockIdx.x & 7u; p.partsEmpty = 0;
+    return p;
+}
+// the checkpoint in front of list entry i of the item: draws a slot and stores the state (sT .. sd: the state before splat i,
+// absolute; called only while some pixel of the quadrant is live there)
+template <int SEG, bool DEPTH>
+__device__ __forceinline__ void ckpt_save(const BlendFwdArgs& a, CkptPool& pl, const FwdItem& it, int lane, uint32_t i,
+                                          float sT, float sr, float sg, float sb, float sd)
+{
+    if (pl.next == pl.end) {
+        // the wave's own eighth of the shared part first, then the others': since round 4 an XCD works on one stripe
+        // of the image, and a deep stripe needs more slots than its eighth holds while a shallow one leaves its
+        // own unused (grown bench scene: the arena "ran out" with most of it free).  A part found empty is not
+        // asked again (every failed draw still advances its counter: gs_ctx_reserve sizes a regrow from their sum).
+        pl.next = a.qslotCap;      // (all parts used up: positions beyond the arena, which the test below reports)
+        for (uint32_t t = 0; t < 8u && pl.next == a.qslotCap; t++) {
+            const uint32_t y = (pl.part + t) & 7u;
+            if ((pl.partsEmpty >> y) & 1u) continue;
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(&a.counters[GS_CNT_QSLOTS + y], a.ckptPool);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + a.ckptPool <= a.qslotPart) pl.next = a.qslotShared0 + y * a.qslotPart + base;
+            else {      // (give the failed draw back: the counters' sum stays what was drawn + what was wanted and not had)
+                pl.partsEmpty |= 1u << y;
+                if (lane == 0) atomicSub(&a.counters[GS_CNT_QSLOTS + y], a.ckptPool);
+            }
+        }
+        // nothing left anywhere: keep counting what would have been drawn (the size of the regrow)
+        if (pl.next == a.qslotCap && pl.partsEmpty == 0xFFu && lane == 0) atomicAdd(&a.counters[GS_CNT_QSLOTS + pl.part], a.ckptPool);
+        pl.end = pl.next + a.ckptPool;
+    }
+    const uint32_t phys = pl.next++;
+    const uint32_t vslot = it.sbase + i / SEG - 1;
+    if (phys < a.qslotCap && vslot < a.segCap) {
+        if (lane == 0) a.segSlot[(size_t)vslot * 4 + (it.h * 2 + it.k)] = phys;
+        // a pixel that has terminated is never read back (the backward loads state only where nContrib > i0)
+        float* st = a.segState + (size_t)phys * (a.statePlanes * 64) + lane;
+        if (sT >= 1e-4f) {
+            st[0] = sT; st[64] = sr; st[128] = sg; st[192] = sb;
+            if (DEPTH && a.statePlanes == 5) st[256] = sd;   // wave-uniform: the depth sum only when a depth cotangent may come
+        }
+    } else if (lane == 0) {
+        // out of checkpoint slots: the image is still complete, but no backward can be taken from this forward
+        a.counters[GS_CNT_OVERFLOW] = 1u;
+        a.hostWords[4] = 2u;        // 2: "the checkpoint arena", 1: "the pair reserve" (binning.hip)
+    }
+}
+
+// the end of an item, by the wave that holds its final state: the cut-miss flag, the pixel's five outputs, the block's sweep
+// length.  The pixel is rebuilt from the lane here, so that a kernel need not keep it across its sweep (the four-wave kernel
+// spilled its item-invariant values to scratch at five workgroups per CU).
+template <bool DEPTH>
+__device__ __forceinline__ void fwd_finish(const BlendFwdArgs& a, const FwdItem& it, int lane, float T, float r, float g, float b,
+                                           float d, uint32_t nc)
+{
+    // depth cuts: live pixels at the end of a list that was cut short -- this forward has to be repeated without
+    // cuts (pixels outside the image carry T = 0).  The flag word lives in host memory.
+    if (a.cutStore && fwd_any_live(T) && lane == 0 && fwd_table_word(a.cutStore, it.tile) != 0u) a.hostWords[0] = 1u;
+    const int x = it.X0 + it.k * 8 + (lane & 7), y = it.Y0 + it.h * 8 + (lane >> 3);
+    const bool in = x < it.XL && y < it.YL;
+    if (in) {
+        const size_t pix = (size_t)y * a.W + x;
+        float bg0, bg1, bg2;
+        gs_bg_terms(a.bgc, T, bg0, bg1, bg2);
+        a.outColor[3 * pix] = r + bg0; a.outColor[3 * pix + 1] = g + bg1; a.outColor[3 * pix + 2] = b + bg2;
+        if (DEPTH) a.outDepth[pix] = d;
+        a.outAlpha[pix] = 1.0f - T; a.lastContrib[pix] = nc; a.finalT[pix] = T;
+    }
+    uint32_t m = in ? nc : 0u;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
+    if (lane == 0 && m) atomicMax(&a.blockWork[it.b], m);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the one-wave kernel (the default)
+// ---------------------------------------------------------------------------------------------
 // DEPTH = false: the caller takes no depth image (gs_render_forward with out_depth NULL): no depth sum in the sweep (one of
 // its ~30 vector instructions per splat), none in the checkpoints, nothing stored.
 template <int SEG, bool DEPTH>
-__global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, GsBackground bgc,
-    const float4* __restrict__ rec12, const uint32_t* __restrict__ sortedIdx, uint32_t idxMask,
-    const uint32_t* __restrict__ tileRanges, const uint32_t* __restrict__ segBase, uint32_t segCap, int statePlanes,
-    float* __restrict__ outColor, float* __restrict__ outDepth,
-    float* __restrict__ outAlpha, uint32_t* __restrict__ lastContrib, float* __restrict__ finalT,
-    float* __restrict__ segState, uint32_t* __restrict__ segSlot, uint32_t qslotCap, uint32_t qslotOwn, uint32_t qslotPart, uint32_t ckptPool,
-    uint32_t* __restrict__ blockWork, uint32_t* __restrict__ counters, uint32_t* __restrict__ fwdQueue, uint32_t nq,
-    const uint32_t* __restrict__ blockOrder, unsigned long long* __restrict__ trace,
-    const uint32_t* __restrict__ cutStore, uint32_t* __restrict__ hostWords, uint32_t slowSlot, GsVirtGeom vg)
+__global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(BlendFwdArgs a)
 {
     static_assert(SEG % 64 == 0, "segment length must be a multiple of the 64-record chunk");
     // Round 6: the launch is workgroups of FOUR independent waves (no barrier between them, every wave its own LDS slots) instead
@@ -248,180 +561,25 @@ __global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
     // never changed a bit of the result (test_forward_queue_count_leaves_the_same_bits).
     const uint32_t hwSlot = (uint32_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (3 << 11));      // HW_ID[3:0]: wave slot in the SIMD
     const int lane = threadIdx.x & 63;
-    const uint32_t nWaves = gridDim.x * 4u;
+    const uint32_t nWaves = gridDim.x * 4u;                   // every wave takes items and owns a checkpoint pool
     const uint32_t dw = blockIdx.x * 4u + (uint32_t)wvg;      // dense wave id (checkpoint pools, trace)
-    // this wave's pool of checkpoint slots (wave-uniform): qslotOwn slots of the arena are its own from the start -- every
-    // wave reaches its first boundary at about the same time, and that many pops on one counter would take ~6 ns each
-    // to resolve (measured: blend forward 0.19 -> 0.30 ms with a shared counter only) -- and only a wave that uses them
-    // up draws ckptPool (up to 8) more at a time from the shared part behind them, which is split in eight with a counter each
-    // (workgroups go round-robin over the eight XCDs: a wave's counter lives in its own L2).  With ONE counter behind
-    // a static share of 12 slots the 100 k / 800x800 config, whose waves need ~20, lost 54 us of its 175 (blend forward).
-    uint32_t poolNext = dw * qslotOwn, poolEnd = poolNext + qslotOwn;
-    const uint32_t part = blockIdx.x & 7u;
-    uint32_t partsEmpty = 0;
-    // Work distribution (round 4).  An item is one 8x8 quadrant of the pixel block at position p of the launch order
-    // (blockOrder, deepest first).  The four quadrant waves of a block gather the same records; workgroups go to the eight
-    // XCDs round-robin, each XCD with an L2 of its own, and rounds 1-3 gave the four items of a block to four consecutive
-    // waves = four XCDs: every record was fetched from the fabric four times (PMC: 3.9x the algorithmic bytes).  Now block
-    // position p belongs to XCD p mod 8: the wave with blockIdx.x = 8 s + x starts on quadrant s mod 4 of position
-    // 8 (s / 4) + x, and the positions behind the statically assigned ones are handed out by EIGHT queues, one per XCD
-    // (four consecutive pops = one block), so the quadrants of a block meet in one L2 -- and the pops, which resolve at
-    // ~6 ns each on one address, spread over eight.  A wave whose XCD's queue has run dry takes from the others'.
-    // nq = 8 queues (default) / 1 (rounds 1-3's mapping: position p = blockIdx.x / 4, one queue; GS_TUNE_FWD_QUEUES, A/B)
-    // (workgroup g sits on XCD g mod nq; its wave w is "slot" 4 (g / nq) + w of that XCD: first item = quadrant w of position
-    // nq (g / nq) + g mod nq)
-    const uint32_t xcd = blockIdx.x % nq, slot = (blockIdx.x / nq) * 4u + (uint32_t)wvg;
-    const uint32_t nPos = nq * ((((uint32_t)nItems >> 2) + nq - 1u) / nq);      // positions of the launch order: the pixel blocks,
-                                                                                // padded to whole rows of nq (gs_bwd_prep.h, seg_base_body)
-    const uint32_t staticRows = nWaves / (4u * nq);           // rows of nq positions covered by the waves' first items
-    uint32_t dead = 0;                                        // queues found empty
+    CkptPool pool = ckpt_pool_of(a, dw);
+    // (wave w of workgroup g is slot 4 (g / nq) + w of its XCD: first item = quadrant w of position nq (g / nq) + g mod nq)
+    FwdQueue qc = fwd_queue(a, (blockIdx.x / a.nq) * 4u + (uint32_t)wvg, nWaves);
     for (bool first = true;; first = false) {
-        uint32_t pos = 0xFFFFFFFFu, quad = 0;
-        if (first && (slot >> 2) < staticRows) { pos = nq * (slot >> 2) + xcd; quad = slot & 3u; }
-        else if (hwSlot >= slowSlot) break;       // (a slow slot: no item beyond the static one)
-        else {
-            for (uint32_t t = 0; t < nq && pos == 0xFFFFFFFFu; t++) {
-                const uint32_t y = (xcd + t) % nq;
-                if ((dead >> y) & 1u) continue;
-                // (no look before the pop: a load of the line the pops hammer queues behind them -- measured, one queue:
-                // blend forward 0.19 -> 0.49 ms with a relaxed load in front of every atomicAdd)
-                uint32_t k = 0;
-                if (lane == 0) k = atomicAdd(&fwdQueue[y * 32u], 1u);
-                k = __builtin_amdgcn_readfirstlane(k);
-                const uint32_t p = nq * (staticRows + (k >> 2)) + y;
-                if (p < nPos) { pos = p; quad = k & 3u; }
-                else dead |= 1u << y;
-            }
-        }
-        if (pos >= nPos) {
+        uint32_t pos, quad;
+        fwd_pop(a, qc, first, hwSlot < a.slowSlot, lane, pos, quad);      // (a slow slot: no item beyond the static one)
+        if (pos >= qc.nPos) {
             if (first) continue;          // (a wave beyond the static rows, or an image smaller than the grid: try the queues)
-            break;                        // every queue is empty; they only grow: every wave reaches this exit
+            break;
         }
         const uint32_t item = pos * 4u + quad;
-        const unsigned long long tStart = trace ? clock64() : 0ull;
+        const unsigned long long tStart = a.trace ? clock64() : 0ull;
         uint32_t itersDone = 0, chunksDone = 0;
-        const uint32_t bRaw = __builtin_amdgcn_readfirstlane(blockOrder[pos]);
-        if (bRaw == 0xFFFFFFFFu) continue;        // (a position a short last stripe leaves over)
-        const int b = (int)bRaw;
-        const int h = (int)((quad >> 1) & 1u), k = (int)(quad & 1u);
-        const int by = b / blocksX, bx = b - by * blocksX;
-        const int tile = ((by * BLK) / tileH) * gridW + (bx * BLK) / tileW;
-        const uint32_t start = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile]);
-        const uint32_t end = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile + 1]);
-        const uint32_t count = end > start ? end - start : 0u;
-        const uint32_t sbase = __builtin_amdgcn_readfirstlane(segBase[b]);
-
-        int X0, Y0, XL, YL;       // the block's pixel origin and limits (block lists: blocks are enumerated per tile)
-        gs_block_pixels(vg, bx, by, W, H, X0, Y0, XL, YL);
-        const int x = X0 + k * 8 + (lane & 7), y = Y0 + h * 8 + (lane >> 3);
-        const bool in = x < XL && y < YL;
-        const float px = (float)x, py = (float)y;
-        // the quadrant's pixel-centre rectangle, for the lane-private reach test at staging time
-        const float qx0 = (float)(X0 + k * 8), qx1 = qx0 + 7.0f, qy0 = (float)(Y0 + h * 8), qy1 = qy0 + 7.0f;
-        float T = in ? 1.0f : 0.0f;               // pixels outside the image start dead and are never stored
-        // Round 6: the colour (depth) sums are kept as BASE + CHUNK -- the entries of the current 64-position chunk accumulate
-        // from zero, and the chunk's sum is added to the base at the chunk's end (one rounding of the size of the total per
-        // chunk instead of one per entry).  The backward takes what the rest of a list still owes from the difference between
-        // the final image and a checkpoint (a base); deep in a list that difference is small against both, and its error was
-        // the forward's per-entry roundings at the size of the TOTAL.  Same instruction count per entry.
-        float cr = 0.f, cg = 0.f, cb = 0.f, dd = 0.f;          // this chunk's sums
-        float br = 0.f, bgr = 0.f, bb = 0.f, bd = 0.f;         // the sums of the chunks in front of it
-        uint32_t nc = 0;
-
-        const uint32_t* __restrict__ idx = sortedIdx + start;
-        auto save_state = [&](uint32_t i) {       // (called only while some pixel of the quadrant is live)
-            if (poolNext == poolEnd) {
-                // the wave's own eighth of the shared part first, then the others': since round 4 an XCD works on one stripe
-                // of the image, and a deep stripe needs more slots than its eighth holds while a shallow one leaves its
-                // own unused (grown bench scene: the arena "ran out" with most of it free).  A part found empty is not
-                // asked again (every failed draw still advances its counter: gs_ctx_reserve sizes a regrow from their sum).
-                poolNext = qslotCap;      // (all parts used up: positions beyond the arena, which the test below reports)
-                for (uint32_t t = 0; t < 8u && poolNext == qslotCap; t++) {
-                    const uint32_t y = (part + t) & 7u;
-                    if ((partsEmpty >> y) & 1u) continue;
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&counters[GS_CNT_QSLOTS + y], ckptPool);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base + ckptPool <= qslotPart) poolNext = nWaves * qslotOwn + y * qslotPart + base;
-                    else {      // (give the failed draw back: the counters' sum stays what was drawn + what was wanted and not had)
-                        partsEmpty |= 1u << y;
-                        if (lane == 0) atomicSub(&counters[GS_CNT_QSLOTS + y], ckptPool);
-                    }
-                }
-                // nothing left anywhere: keep counting what would have been drawn (the size of the regrow)
-                if (poolNext == qslotCap && partsEmpty == 0xFFu && lane == 0) atomicAdd(&counters[GS_CNT_QSLOTS + part], ckptPool);
-                poolEnd = poolNext + ckptPool;
-            }
-            const uint32_t phys = poolNext++;
-            const uint32_t vslot = sbase + i / SEG - 1;
-            if (phys < qslotCap && vslot < segCap) {
-                if (lane == 0) segSlot[(size_t)vslot * 4 + (h * 2 + k)] = phys;
-                // a pixel that has terminated is never read back (the backward loads state only where nContrib > i0)
-                float* st = segState + (size_t)phys * (statePlanes * 64) + lane;
-                if (T >= 1e-4f) {
-                    st[0] = T; st[64] = br; st[128] = bgr; st[192] = bb;
-                    if (DEPTH && statePlanes == 5) st[256] = bd;   // wave-uniform: the depth sum only when a depth cotangent may come
-                }
-            } else if (lane == 0) {
-                // out of checkpoint slots: the image is still complete, but no backward can be taken from this forward
-                counters[GS_CNT_OVERFLOW] = 1u;
-                hostWords[4] = 2u;        // 2: "the checkpoint arena", 1: "the pair reserve" (binning.hip)
-            }
-        };
-        struct Pre {
-            float aclamp, r, g, b, depth;
-            uint32_t ncv;              // list position + 1 of the splat: nContrib of a pixel that is live when it arrives
-        };
-        // Staging compacts the chunk: lane j holds list entry c0 + j and tests it against the whole quadrant -- the
-        // minimum of its quadratic form over the pixel rectangle (rect_min_q) -- and only entries that can reach a
-        // pixel are parked in LDS, each with its list position.  An entry whose weight is below 2^-29 everywhere
-        // moves no pixel's state by more than ~5e-8 (CULL_QMIN), so skipping it changes nothing but the work: no LDS
-        // broadcast (the CU's LDS port is what saturates first with one pixel per lane), no exponent, no exp.
-        auto stage_compact = [&](f4* slot, const RecV& v, uint32_t c0) -> uint32_t {
-            const float qmin = rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, qx0 - v.a.x, qx1 - v.a.x, qy0 - v.a.y, qy1 - v.a.y);
-            const bool keep = (c0 + lane < count) && !(qmin > CULL_QMIN);
-            const unsigned long long m = __ballot(keep);
-            const uint32_t pos = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (keep) {
-                slot[pos * 3] = v.a; slot[pos * 3 + 1] = v.b;
-                slot[pos * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(c0 + (uint32_t)lane + 1u)};
-            }
-            // pad to a multiple of four with null splats (opacity 0: alpha = 0, state untouched) so that the loop runs
-            // whole groups only; a pixel still live at a pad entry is live at the end of the chunk, hence its nContrib
-            const uint32_t n = (uint32_t)__popcll(m), n4 = (n + 3u) & ~3u;
-            if ((uint32_t)lane < n4 - n) {
-                const f4 z = (f4){0.f, 0.f, 0.f, 0.f};
-                slot[(n + lane) * 3] = z; slot[(n + lane) * 3 + 1] = z;
-                slot[(n + lane) * 3 + 2] = (f4){0.f, 0.f, 0.f, __uint_as_float(min(c0 + 64u, count))};
-            }
-            return n4;
-        };
-        auto pre = [&](const f4* slot, uint32_t j, Pre& o) {
-            const Rec s = unpack(slot[j * 3], slot[j * 3 + 1], slot[j * 3 + 2]);
-            const float dx = px - s.mx, dy = py - s.my;
-            const float dxdy = dx * dy, dx2 = dx * dx, dy2 = dy * dy;
-            const float q = ((dx2 * s.c00 + dy2 * s.c11) + dxdy * s.c01) + dxdy * s.c10;
-#ifdef GS_FWD_LIBM_EXP   // experiment: the oracle's exp(-0.5 q) through the device math library instead of v_exp_f32
-            o.aclamp = fminf(s.op * expf(-0.5f * q), 0.99f);
-#else
-            o.aclamp = fminf(gauss_alpha_raw(q, s.op), 0.99f);
-#endif
-            o.r = s.r; o.g = s.g; o.b = s.b; o.depth = s.depth;
-            o.ncv = __float_as_uint(slot[j * 3 + 2].w);
-        };
-        auto post = [&](const Pre& o) {
-            const bool a = T >= 1e-4f;
-            nc = a ? o.ncv : nc;
-            const float alpha = a ? o.aclamp : 0.0f;
-            const float w = T * alpha;
-#ifdef GS_FWD_UNFUSED   // experiment (DESIGN.md section 2, "the 1e-4 bar"): the reference's two-rounding C + w c
-            cr = cr + w * o.r; cg = cg + w * o.g; cb = cb + w * o.b; if (DEPTH) dd = dd + w * o.depth;
-#else
-            cr = fmaf(w, o.r, cr); cg = fmaf(w, o.g, cg); cb = fmaf(w, o.b, cb); if (DEPTH) dd = fmaf(w, o.depth, dd);
-#endif
-            T = T * (1.0f - alpha);
-        };
-        auto any_live = [&]() { return __any(T >= 1e-4f); };
+        FwdItem it;
+        if (!fwd_decode(a, pos, quad, lane, it)) continue;
+        FwdPixel s = fwd_pixel(it.in);
+        const uint32_t* __restrict__ idx = a.sortedIdx + it.start;
 
         // The list runs through GS_FWD_PREFETCH register sets in turn: the set that holds chunk c's records is refilled, right after
         // they are staged, with the records of chunk c + D from indices loaded D chunks earlier, and then takes the indices of chunk
@@ -434,63 +592,41 @@ __global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
         uint32_t gis[D];
 #pragma unroll
         for (int d = 0; d < D; d++) {
-            recs[d] = load_chunk(rec12, idx, idxMask, 64u * d, count, lane);
-            gis[d] = load_chunk_index(idx, idxMask, 64u * (D + d), count, lane);
+            recs[d] = load_chunk(a.rec12, idx, a.idxMask, 64u * d, it.count, lane);
+            gis[d] = load_chunk_index(idx, a.idxMask, 64u * (D + d), it.count, lane);
         }
         auto chunk = [&](uint32_t c0, RecV& rec, uint32_t& gi) -> bool {      // false: the quadrant has no live pixel left
             f4* slot = sg[(c0 >> 6) & 1];
-            const uint32_t n = stage_compact(slot, rec, c0);
-            if (c0 + 64u * D < count) {
-                rec = gather_chunk(rec12, gi);
-                gi = load_chunk_index(idx, idxMask, c0 + 128u * D, count, lane);
+            const uint32_t n = fwd_stage_compact(slot, rec, c0, it, lane);
+            if (c0 + 64u * D < it.count) {
+                rec = gather_chunk(a.rec12, gi);
+                gi = load_chunk_index(idx, a.idxMask, c0 + 128u * D, it.count, lane);
             }
-            br += cr; bgr += cg; bb += cb; cr = 0.f; cg = 0.f; cb = 0.f;          // the chunk behind us joins the base
-            if (DEPTH) { bd += dd; dd = 0.f; }
-            if (statePlanes != 0 && c0 != 0 && (c0 % SEG) == 0) save_state(c0);
-            bool live = true;
-            uint32_t j = 0;
-            for (; j < n; j += 4) {      // n is a multiple of 4
-                Pre p0, p1, p2, p3;
-                pre(slot, j, p0); pre(slot, j + 1, p1); pre(slot, j + 2, p2); pre(slot, j + 3, p3);
-                post(p0); post(p1); post(p2); post(p3);
-                if (!any_live()) { live = false; break; }
-            }
-            itersDone += j; chunksDone++;
+            fwd_join_chunk<DEPTH>(s);
+            if (a.statePlanes != 0 && c0 != 0 && (c0 % SEG) == 0) ckpt_save<SEG, DEPTH>(a, pool, it, lane, c0, s.T, s.br, s.bgr, s.bb, s.bd);
+            bool live;
+            itersDone += fwd_trips<DEPTH>(slot, n, it.px, it.py, s, live); chunksDone++;
             if (!live) return false;
-            if (T >= 1e-4f) nc = min(c0 + 64u, count);      // still live: went through the whole chunk
-            return any_live();
+            if (s.T >= 1e-4f) s.nc = min(c0 + 64u, it.count);      // still live: went through the whole chunk
+            return fwd_any_live(s.T);
         };
-        for (uint32_t c0 = 0; c0 < count; c0 += 64u * D) {
+        for (uint32_t c0 = 0; c0 < it.count; c0 += 64u * D) {
             bool go = true;
 #pragma unroll
             for (int d = 0; d < D; d++)
-                if (go && c0 + 64u * d < count) go = chunk(c0 + 64u * d, recs[d], gis[d]);
+                if (go && c0 + 64u * d < it.count) go = chunk(c0 + 64u * d, recs[d], gis[d]);
             if (!go) break;
         }
-        if (trace && lane == 0 && item < (uint32_t)nItems) {
-            trace[(size_t)item * 4 + 0] = tStart;
-            trace[(size_t)item * 4 + 1] = clock64();
-            trace[(size_t)item * 4 + 2] = (unsigned long long)itersDone | ((unsigned long long)chunksDone << 32);      // blended entries (with pads) | chunks
+        if (a.trace && lane == 0 && item < (uint32_t)a.nItems) {
+            a.trace[(size_t)item * 4 + 0] = tStart;
+            a.trace[(size_t)item * 4 + 1] = clock64();
+            a.trace[(size_t)item * 4 + 2] = (unsigned long long)itersDone | ((unsigned long long)chunksDone << 32);      // blended entries (with pads) | chunks
             // blockIdx.x | XCC_ID (4 bits) << 32 | HW_ID[15:0] (wave, SIMD, pipe, CU, SH, SE) << 36
-            trace[(size_t)item * 4 + 3] = (unsigned long long)dw |
-                                          ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 32) |
-                                          ((unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (15 << 11)) << 36);
+            a.trace[(size_t)item * 4 + 3] = (unsigned long long)dw |
+                                            ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 32) |
+                                            ((unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (15 << 11)) << 36);
         }
-        // depth cuts: live pixels at the end of a list that was cut short -- this forward has to be repeated without
-        // cuts (pixels outside the image carry T = 0).  The flag word lives in host memory.
-        if (cutStore && any_live() && lane == 0 && cutStore[tile] != 0u) hostWords[0] = 1u;
-        if (in) {
-            const size_t pix = (size_t)y * W + x;
-            float bg0, bg1, bg2;
-            gs_bg_terms(bgc, T, bg0, bg1, bg2);
-            outColor[3 * pix] = (br + cr) + bg0; outColor[3 * pix + 1] = (bgr + cg) + bg1; outColor[3 * pix + 2] = (bb + cb) + bg2;
-            if (DEPTH) outDepth[pix] = bd + dd;
-            outAlpha[pix] = 1.0f - T; lastContrib[pix] = nc; finalT[pix] = T;
-        }
-        uint32_t m = in ? nc : 0u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-        if (lane == 0 && m) atomicMax(&blockWork[b], m);
+        fwd_finish<DEPTH>(a, it, lane, s.T, s.br + s.cr, s.bgr + s.cg, s.bb + s.cb, s.bd + s.dd, s.nc);
     }
 }
 
@@ -515,15 +651,7 @@ __global__ __launch_bounds__(256) void blend_fwd_v2q_kernel(
 #endif
 #define GS_V2P_WGS (2 * GS_V2P_WAVES)      // workgroups (pairs) per CU at that occupancy
 template <int SEG, bool DEPTH>
-__global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, GsBackground bgc,
-    const float4* __restrict__ rec12, const uint32_t* __restrict__ sortedIdx, uint32_t idxMask,
-    const uint32_t* __restrict__ tileRanges, const uint32_t* __restrict__ segBase, uint32_t segCap, int statePlanes,
-    float* __restrict__ outColor, float* __restrict__ outDepth,
-    float* __restrict__ outAlpha, uint32_t* __restrict__ lastContrib, float* __restrict__ finalT,
-    float* __restrict__ segState, uint32_t* __restrict__ segSlot, uint32_t qslotCap, uint32_t qslotOwn, uint32_t qslotPart, uint32_t ckptPool,
-    uint32_t* __restrict__ blockWork, uint32_t* __restrict__ counters, uint32_t* __restrict__ fwdQueue, uint32_t nq,
-    const uint32_t* __restrict__ blockOrder, const uint32_t* __restrict__ cutStore, uint32_t* __restrict__ hostWords, GsVirtGeom vg)
+__global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(BlendFwdArgs a)
 {
     static_assert(SEG % 64 == 0, "segment length must be a multiple of the 64-record chunk");
     __shared__ f4 sg[2][192];          // two 64-record slots: one being blended, one being staged
@@ -532,102 +660,53 @@ __global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
     __shared__ uint32_t sStop;         // set by the sweeping wave when the item is finished
     const int lane = threadIdx.x & 63;
     const bool stager = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;      // wave-uniform by construction
-    uint32_t poolNext = blockIdx.x * qslotOwn, poolEnd = poolNext + qslotOwn;
-    const uint32_t part = blockIdx.x & 7u;
-    uint32_t partsEmpty = 0;
-    const uint32_t xcd = blockIdx.x % nq, slot = blockIdx.x / nq;
-    const uint32_t nPos = nq * ((((uint32_t)nItems >> 2) + nq - 1u) / nq);
-    const uint32_t staticRows = gridDim.x / (4u * nq);
-    uint32_t dead = 0;                                        // (wave 0) queues found empty
+    CkptPool pool = ckpt_pool_of(a, blockIdx.x);                 // (the sweeping wave's: one wave per workgroup saves)
+    FwdQueue qc = fwd_queue(a, blockIdx.x / a.nq, gridDim.x);    // (the sweeping wave's: the workgroup is the taker)
     for (bool first = true;; first = false) {
-        if (!stager) {      // the item of the workgroup: as in blend_fwd_v2q_kernel, popped by the sweeping wave
-            uint32_t pos = 0xFFFFFFFFu, quad = 0;
-            if (first && (slot >> 2) < staticRows) { pos = nq * (slot >> 2) + xcd; quad = slot & 3u; }
-            else {
-                for (uint32_t t = 0; t < nq && pos == 0xFFFFFFFFu; t++) {
-                    const uint32_t y = (xcd + t) % nq;
-                    if ((dead >> y) & 1u) continue;
-                    uint32_t k = 0;
-                    if (lane == 0) k = atomicAdd(&fwdQueue[y * 32u], 1u);
-                    k = __builtin_amdgcn_readfirstlane(k);
-                    const uint32_t p = nq * (staticRows + (k >> 2)) + y;
-                    if (p < nPos) { pos = p; quad = k & 3u; }
-                    else dead |= 1u << y;
-                }
-            }
+        if (!stager) {      // the item of the workgroup, popped by the sweeping wave
+            uint32_t pos, quad;
+            fwd_pop(a, qc, first, true, lane, pos, quad);
             if (lane == 0) { sItem[0] = pos; sItem[1] = quad; sStop = 0u; }
         }
         __syncthreads();
         const uint32_t pos = sItem[0], quad = sItem[1];
-        if (pos >= nPos) {
+        if (pos >= qc.nPos) {
             __syncthreads();              // (sItem is written again by the next round's pop)
             if (first) continue;
             break;
         }
-        const uint32_t bRaw = __builtin_amdgcn_readfirstlane(blockOrder[pos]);
-        const int b = (int)bRaw;
-        const int h = (int)((quad >> 1) & 1u), k = (int)(quad & 1u);
-        uint32_t start = 0, count = 0, sbase = 0;
-        int tile = 0, X0 = 0, Y0 = 0, XL = 0, YL = 0;
-        if (bRaw != 0xFFFFFFFFu) {
-            const int by = b / blocksX, bx = b - by * blocksX;
-            tile = ((by * BLK) / tileH) * gridW + (bx * BLK) / tileW;
-            start = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile]);
-            const uint32_t end = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile + 1]);
-            count = end > start ? end - start : 0u;
-            sbase = __builtin_amdgcn_readfirstlane(segBase[b]);
-            gs_block_pixels(vg, bx, by, W, H, X0, Y0, XL, YL);
-        }
-        const int x = X0 + k * 8 + (lane & 7), y = Y0 + h * 8 + (lane >> 3);
-        const bool in = bRaw != 0xFFFFFFFFu && x < XL && y < YL;
-        const float px = (float)x, py = (float)y;
-        const float qx0 = (float)(X0 + k * 8), qx1 = qx0 + 7.0f, qy0 = (float)(Y0 + h * 8), qy1 = qy0 + 7.0f;
-        const uint32_t* __restrict__ idx = sortedIdx + start;
+        // (a position a short last stripe leaves over goes through the item's barriers with an empty list and stores nothing)
+        FwdItem it;
+        const bool valid = fwd_decode(a, pos, quad, lane, it);
+        const uint32_t* __restrict__ idx = a.sortedIdx + it.start;
 
-        // ---- the staging wave's half: load, reach test, compaction (blend_fwd_v2q_kernel, stage_compact) ----
-        auto stage_compact = [&](f4* sl, const RecV& v, uint32_t c0) -> uint32_t {
-            const float qmin = rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, qx0 - v.a.x, qx1 - v.a.x, qy0 - v.a.y, qy1 - v.a.y);
-            const bool keep = (c0 + lane < count) && !(qmin > CULL_QMIN);
-            const unsigned long long m = __ballot(keep);
-            const uint32_t ps = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (keep) {
-                sl[ps * 3] = v.a; sl[ps * 3 + 1] = v.b;
-                sl[ps * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(c0 + (uint32_t)lane + 1u)};
-            }
-            const uint32_t n = (uint32_t)__popcll(m), n4 = (n + 3u) & ~3u;
-            if ((uint32_t)lane < n4 - n) {
-                const f4 z = (f4){0.f, 0.f, 0.f, 0.f};
-                sl[(n + lane) * 3] = z; sl[(n + lane) * 3 + 1] = z;
-                sl[(n + lane) * 3 + 2] = (f4){0.f, 0.f, 0.f, __uint_as_float(min(c0 + 64u, count))};
-            }
-            return n4;
-        };
         // The two roles run SEPARATE loops with the same number of barriers (a barrier counts arriving waves, not program
         // locations; `stager` is wave-uniform): in one shared loop the staging wave's prefetch registers and the sweeping wave's
         // pixel state were all loop-carried together (100 VGPRs: four waves per SIMD instead of six).
         if (stager) {
+            // ---- the staging wave's half: load, reach test, compaction ----
             RecV nxt;
             nxt.a = nxt.b = nxt.c = (f4){0.f, 0.f, 0.f, 0.f};
             uint32_t gNext = 0xFFFFFFFFu;
-            if (count > 0) {          // chunk 0 into slot 0 before the sweep starts; chunk 1's records and chunk 2's indices in flight
-                gNext = load_chunk_index(idx, idxMask, 64, count, lane);
-                nxt = load_chunk(rec12, idx, idxMask, 0, count, lane);
-                const uint32_t n = stage_compact(sg[0], nxt, 0);
+            if (it.count > 0) {       // chunk 0 into slot 0 before the sweep starts; chunk 1's records and chunk 2's indices in flight
+                gNext = load_chunk_index(idx, a.idxMask, 64, it.count, lane);
+                nxt = load_chunk(a.rec12, idx, a.idxMask, 0, it.count, lane);
+                const uint32_t n = fwd_stage_compact(sg[0], nxt, 0, it, lane);
                 if (lane == 0) sN[0] = n;
-                if (64 < count) {
-                    nxt = gather_chunk(rec12, gNext);
-                    gNext = load_chunk_index(idx, idxMask, 128, count, lane);
+                if (64 < it.count) {
+                    nxt = gather_chunk(a.rec12, gNext);
+                    gNext = load_chunk_index(idx, a.idxMask, 128, it.count, lane);
                 }
             }
             V2P_BARRIER();                // slot 0 is staged (and sItem has been read by both waves)
-            for (uint32_t c0 = 0; c0 < count; c0 += 64) {
+            for (uint32_t c0 = 0; c0 < it.count; c0 += 64) {
                 const uint32_t cur = (c0 >> 6) & 1u;
-                if (c0 + 64 < count) {    // the next chunk into the other slot while the sweeping wave blends this one
-                    const uint32_t n = stage_compact(sg[cur ^ 1u], nxt, c0 + 64);
+                if (c0 + 64 < it.count) { // the next chunk into the other slot while the sweeping wave blends this one
+                    const uint32_t n = fwd_stage_compact(sg[cur ^ 1u], nxt, c0 + 64, it, lane);
                     if (lane == 0) sN[cur ^ 1u] = n;
-                    if (c0 + 128 < count) {
-                        nxt = gather_chunk(rec12, gNext);
-                        gNext = load_chunk_index(idx, idxMask, c0 + 192, count, lane);
+                    if (c0 + 128 < it.count) {
+                        nxt = gather_chunk(a.rec12, gNext);
+                        gNext = load_chunk_index(idx, a.idxMask, c0 + 192, it.count, lane);
                     }
                 }
                 V2P_BARRIER();
@@ -637,104 +716,26 @@ __global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
             continue;
         }
         // ---- the sweeping wave's half: the running state and everything that depends on it ----
-        float T = in ? 1.0f : 0.0f;
-        float cr = 0.f, cg = 0.f, cb = 0.f, dd = 0.f;          // this chunk's sums; the chunks in front of it (blend_fwd_v2q_kernel):
-        float br = 0.f, bgr = 0.f, bb = 0.f, bd = 0.f;
-        uint32_t nc = 0;
-        auto save_state = [&](uint32_t i) {       // (blend_fwd_v2q_kernel, save_state)
-            if (poolNext == poolEnd) {
-                poolNext = qslotCap;
-                for (uint32_t t = 0; t < 8u && poolNext == qslotCap; t++) {
-                    const uint32_t yy = (part + t) & 7u;
-                    if ((partsEmpty >> yy) & 1u) continue;
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&counters[GS_CNT_QSLOTS + yy], ckptPool);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base + ckptPool <= qslotPart) poolNext = gridDim.x * qslotOwn + yy * qslotPart + base;
-                    else {
-                        partsEmpty |= 1u << yy;
-                        if (lane == 0) atomicSub(&counters[GS_CNT_QSLOTS + yy], ckptPool);
-                    }
-                }
-                if (poolNext == qslotCap && partsEmpty == 0xFFu && lane == 0) atomicAdd(&counters[GS_CNT_QSLOTS + part], ckptPool);
-                poolEnd = poolNext + ckptPool;
-            }
-            const uint32_t phys = poolNext++;
-            const uint32_t vslot = sbase + i / SEG - 1;
-            if (phys < qslotCap && vslot < segCap) {
-                if (lane == 0) segSlot[(size_t)vslot * 4 + (h * 2 + k)] = phys;
-                float* st = segState + (size_t)phys * (statePlanes * 64) + lane;
-                if (T >= 1e-4f) {
-                    st[0] = T; st[64] = br; st[128] = bgr; st[192] = bb;
-                    if (DEPTH && statePlanes == 5) st[256] = bd;
-                }
-            } else if (lane == 0) {
-                counters[GS_CNT_OVERFLOW] = 1u;
-                hostWords[4] = 2u;
-            }
-        };
-        struct Pre {
-            float aclamp, r, g, b, depth;
-            uint32_t ncv;
-        };
-        auto pre = [&](const f4* sl, uint32_t j, Pre& o) {
-            const Rec s = unpack(sl[j * 3], sl[j * 3 + 1], sl[j * 3 + 2]);
-            const float dx = px - s.mx, dy = py - s.my;
-            const float dxdy = dx * dy, dx2 = dx * dx, dy2 = dy * dy;
-            const float q = ((dx2 * s.c00 + dy2 * s.c11) + dxdy * s.c01) + dxdy * s.c10;
-            o.aclamp = fminf(gauss_alpha_raw(q, s.op), 0.99f);
-            o.r = s.r; o.g = s.g; o.b = s.b; o.depth = s.depth;
-            o.ncv = __float_as_uint(sl[j * 3 + 2].w);
-        };
-        auto post = [&](const Pre& o) {
-            const bool a = T >= 1e-4f;
-            nc = a ? o.ncv : nc;
-            const float alpha = a ? o.aclamp : 0.0f;
-            const float w = T * alpha;
-            cr = fmaf(w, o.r, cr); cg = fmaf(w, o.g, cg); cb = fmaf(w, o.b, cb); if (DEPTH) dd = fmaf(w, o.depth, dd);
-            T = T * (1.0f - alpha);
-        };
-        auto any_live = [&]() { return __any(T >= 1e-4f); };
-
+        FwdPixel s = fwd_pixel(it.in);
         V2P_BARRIER();                    // slot 0 is staged
-        for (uint32_t c0 = 0; c0 < count; c0 += 64) {
+        for (uint32_t c0 = 0; c0 < it.count; c0 += 64) {
             const uint32_t cur = (c0 >> 6) & 1u;
             const f4* sl = sg[cur];
             const uint32_t n = __builtin_amdgcn_readfirstlane(*(volatile uint32_t*)&sN[cur]);
-            br += cr; bgr += cg; bb += cb; cr = 0.f; cg = 0.f; cb = 0.f;          // the chunk behind us joins the base
-            if (DEPTH) { bd += dd; dd = 0.f; }
-            if (statePlanes != 0 && c0 != 0 && (c0 % SEG) == 0) save_state(c0);
-            bool live = true;
-            for (uint32_t j = 0; j < n; j += 4) {      // n is a multiple of 4
-                Pre p0, p1, p2, p3;
-                pre(sl, j, p0); pre(sl, j + 1, p1); pre(sl, j + 2, p2); pre(sl, j + 3, p3);
-                post(p0); post(p1); post(p2); post(p3);
-                if (!any_live()) { live = false; break; }
-            }
+            fwd_join_chunk<DEPTH>(s);
+            if (a.statePlanes != 0 && c0 != 0 && (c0 % SEG) == 0) ckpt_save<SEG, DEPTH>(a, pool, it, lane, c0, s.T, s.br, s.bgr, s.bb, s.bd);
+            bool live;
+            fwd_trips<DEPTH>(sl, n, it.px, it.py, s, live);
             if (live) {
-                if (T >= 1e-4f) nc = min(c0 + 64u, count);      // still live: went through the whole chunk
-                live = any_live();
+                if (s.T >= 1e-4f) s.nc = min(c0 + 64u, it.count);      // still live: went through the whole chunk
+                live = fwd_any_live(s.T);
             }
             if (!live && lane == 0) sStop = 1u;
             V2P_BARRIER();
             if (*(volatile uint32_t*)&sStop) break;
         }
         V2P_BARRIER();                    // (sStop / sItem / the slots are written again by the next item)
-        if (bRaw != 0xFFFFFFFFu) {
-            if (cutStore && any_live() && lane == 0 && cutStore[tile] != 0u) hostWords[0] = 1u;
-            if (in) {
-                const size_t pix = (size_t)y * W + x;
-                float bg0, bg1, bg2;
-                gs_bg_terms(bgc, T, bg0, bg1, bg2);
-                outColor[3 * pix] = (br + cr) + bg0; outColor[3 * pix + 1] = (bgr + cg) + bg1; outColor[3 * pix + 2] = (bb + cb) + bg2;
-                if (DEPTH) outDepth[pix] = bd + dd;
-                outAlpha[pix] = 1.0f - T; lastContrib[pix] = nc; finalT[pix] = T;
-            }
-            uint32_t m = in ? nc : 0u;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-            if (lane == 0 && m) atomicMax(&blockWork[b], m);
-        }
+        if (valid) fwd_finish<DEPTH>(a, it, lane, s.T, s.br + s.cr, s.bgr + s.cg, s.bb + s.cb, s.bd + s.dd, s.nc);
     }
 }
 #undef V2P_BARRIER
@@ -763,16 +764,7 @@ __global__ __launch_bounds__(128, GS_V2P_WAVES) void blend_fwd_v2p_kernel(
 // four, 0.130 with five (six does not launch); two staging slots per wave and 36 KB: four at most
 #define GS_V2W_WGS 5
 template <int SEG, bool DEPTH>
-__global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, int nItems, GsBackground bgc,
-    const float4* __restrict__ rec12, const uint32_t* __restrict__ sortedIdx, uint32_t idxMask,
-    const uint32_t* __restrict__ tileRanges, const uint32_t* __restrict__ segBase, uint32_t segCap, int statePlanes,
-    float* __restrict__ outColor, float* __restrict__ outDepth,
-    float* __restrict__ outAlpha, uint32_t* __restrict__ lastContrib, float* __restrict__ finalT,
-    float* __restrict__ segState, uint32_t* __restrict__ segSlot, uint32_t qslotCap, uint32_t qslotOwn, uint32_t qslotPart, uint32_t ckptPool,
-    uint32_t* __restrict__ blockWork, uint32_t* __restrict__ counters, uint32_t* __restrict__ fwdQueue, uint32_t nq,
-    const uint32_t* __restrict__ blockOrder, const uint32_t* __restrict__ cutStore, uint32_t* __restrict__ hostWords, float foldScale,
-    GsVirtGeom vg)
+__global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(BlendFwdArgs a)
 {
     static_assert(SEG == 64, "a part is one 64-entry chunk = one segment: its only checkpoint is its prefix");
     __shared__ f4 sgAll[4][192];               // per wave: one 64-record slot (DS operations of a wave complete in order)
@@ -782,188 +774,84 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
     __shared__ uint32_t sPop[2];
     const int lane = threadIdx.x & 63, hw = threadIdx.x >> 6;
     f4* sg = sgAll[hw];
-    uint32_t poolNext = (blockIdx.x * 4u + (uint32_t)hw) * qslotOwn, poolEnd = poolNext + qslotOwn;
-    const uint32_t part = blockIdx.x & 7u;
-    uint32_t partsEmpty = 0;
-    const uint32_t xcd = blockIdx.x % nq, slot = blockIdx.x / nq;
-    const uint32_t nPos = nq * ((((uint32_t)nItems >> 2) + nq - 1u) / nq);
-    const uint32_t staticRows = gridDim.x / (4u * nq);
-    uint32_t dead = 0;                                        // (thread 0) queues found empty
+    CkptPool pool = ckpt_pool_of(a, blockIdx.x * 4u + (uint32_t)hw);      // (every wave saves its own part's checkpoint)
+    FwdQueue qc = fwd_queue(a, blockIdx.x / a.nq, gridDim.x);                             // (wave 0's: the workgroup is the taker)
     for (bool first = true;; first = false) {
-        // the item of the workgroup: as in blend_fwd_v2q_kernel, popped by one thread
-        if (threadIdx.x == 0) {
-            uint32_t pos = 0xFFFFFFFFu, quad = 0;
-            if (first && (slot >> 2) < staticRows) { pos = nq * (slot >> 2) + xcd; quad = slot & 3u; }
-            else {
-                for (uint32_t t = 0; t < nq && pos == 0xFFFFFFFFu; t++) {
-                    const uint32_t y = (xcd + t) % nq;
-                    if ((dead >> y) & 1u) continue;
-                    const uint32_t k = atomicAdd(&fwdQueue[y * 32u], 1u);
-                    const uint32_t p = nq * (staticRows + (k >> 2)) + y;
-                    if (p < nPos) { pos = p; quad = k & 3u; }
-                    else dead |= 1u << y;
-                }
-            }
-            sPop[0] = pos; sPop[1] = quad;
+        if (hw == 0) {      // the item of the workgroup, popped by wave 0
+            uint32_t pos, quad;
+            fwd_pop(a, qc, first, true, lane, pos, quad);
+            if (lane == 0) { sPop[0] = pos; sPop[1] = quad; }
         }
         __syncthreads();
         const uint32_t pos = sPop[0], quad = sPop[1];
         __syncthreads();
-        if (pos >= nPos) {
+        if (pos >= qc.nPos) {
             if (first) continue;
             break;
         }
-        const uint32_t bRaw = __builtin_amdgcn_readfirstlane(blockOrder[pos]);
-        if (bRaw == 0xFFFFFFFFu) continue;
-        const int b = (int)bRaw;
-        const int h = (int)((quad >> 1) & 1u), k = (int)(quad & 1u);
-        const int by = b / blocksX, bx = b - by * blocksX;
-        const int tile = ((by * BLK) / tileH) * gridW + (bx * BLK) / tileW;
-        const uint32_t start = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile]);
-        const uint32_t end = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile + 1]);
-        const uint32_t count = end > start ? end - start : 0u;
-        const uint32_t sbase = __builtin_amdgcn_readfirstlane(segBase[b]);
-
-        int X0, Y0, XL, YL;
-        gs_block_pixels(vg, bx, by, W, H, X0, Y0, XL, YL);
-        const int x = X0 + k * 8 + (lane & 7), y = Y0 + h * 8 + (lane >> 3);
-        const bool in = x < XL && y < YL;
-        const float px = (float)x, py = (float)y;
-        const float qx0 = (float)(X0 + k * 8), qx1 = qx0 + 7.0f, qy0 = (float)(Y0 + h * 8), qy1 = qy0 + 7.0f;
-        // the quadrant's running state S: the same bits in all four waves
-        float T = in ? 1.0f : 0.0f;
-        float cr = 0.f, cg = 0.f, cb = 0.f, dd = 0.f;
-        uint32_t nc = 0;
-
-        const uint32_t* __restrict__ idx = sortedIdx + start;
-        // (sT .. sd: the state before splat i, absolute; called only while some pixel of the quadrant is live there)
-        auto save_state_vals = [&](uint32_t i, float sT, float sr, float sgr, float sb, float sd) {
-            if (poolNext == poolEnd) {
-                poolNext = qslotCap;
-                for (uint32_t t = 0; t < 8u && poolNext == qslotCap; t++) {
-                    const uint32_t yy = (part + t) & 7u;
-                    if ((partsEmpty >> yy) & 1u) continue;
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&counters[GS_CNT_QSLOTS + yy], ckptPool);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if (base + ckptPool <= qslotPart) poolNext = gridDim.x * 4u * qslotOwn + yy * qslotPart + base;
-                    else {
-                        partsEmpty |= 1u << yy;
-                        if (lane == 0) atomicSub(&counters[GS_CNT_QSLOTS + yy], ckptPool);
-                    }
-                }
-                if (poolNext == qslotCap && partsEmpty == 0xFFu && lane == 0) atomicAdd(&counters[GS_CNT_QSLOTS + part], ckptPool);
-                poolEnd = poolNext + ckptPool;
-            }
-            const uint32_t phys = poolNext++;
-            const uint32_t vslot = sbase + i / SEG - 1;
-            if (phys < qslotCap && vslot < segCap) {
-                if (lane == 0) segSlot[(size_t)vslot * 4 + (h * 2 + k)] = phys;
-                float* st = segState + (size_t)phys * (statePlanes * 64) + lane;
-                if (sT >= 1e-4f) {
-                    st[0] = sT; st[64] = sr; st[128] = sgr; st[192] = sb;
-                    if (DEPTH && statePlanes == 5) st[256] = sd;
-                }
-            } else if (lane == 0) {
-                counters[GS_CNT_OVERFLOW] = 1u;
-                hostWords[4] = 2u;
-            }
-        };
-        auto save_state = [&](uint32_t i) { save_state_vals(i, T, cr, cg, cb, dd); };
-        struct Pre {
-            float aclamp, r, g, b, depth;
-            uint32_t ncv;
-        };
-        auto stage_compact = [&](f4* sl, const RecV& v, uint32_t c0) -> uint32_t {
-            const float qmin = rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, qx0 - v.a.x, qx1 - v.a.x, qy0 - v.a.y, qy1 - v.a.y);
-            const bool keep = (c0 + lane < count) && !(qmin > CULL_QMIN);
-            const unsigned long long m = __ballot(keep);
-            const uint32_t ps = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (keep) {
-                sl[ps * 3] = v.a; sl[ps * 3 + 1] = v.b;
-                sl[ps * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(c0 + (uint32_t)lane + 1u)};
-            }
-            const uint32_t n = (uint32_t)__popcll(m), n4 = (n + 3u) & ~3u;
-            if ((uint32_t)lane < n4 - n) {
-                const f4 z = (f4){0.f, 0.f, 0.f, 0.f};
-                sl[(n + lane) * 3] = z; sl[(n + lane) * 3 + 1] = z;
-                sl[(n + lane) * 3 + 2] = (f4){0.f, 0.f, 0.f, __uint_as_float(min(c0 + 64u, count))};
-            }
-            return n4;
-        };
-        auto pre = [&](const f4* sl, uint32_t j, Pre& o) {
-            const Rec s = unpack(sl[j * 3], sl[j * 3 + 1], sl[j * 3 + 2]);
-            const float dx = px - s.mx, dy = py - s.my;
-            const float dxdy = dx * dy, dx2 = dx * dx, dy2 = dy * dy;
-            const float q = ((dx2 * s.c00 + dy2 * s.c11) + dxdy * s.c01) + dxdy * s.c10;
-            o.aclamp = fminf(gauss_alpha_raw(q, s.op), 0.99f);
-            o.r = s.r; o.g = s.g; o.b = s.b; o.depth = s.depth;
-            o.ncv = __float_as_uint(sl[j * 3 + 2].w);
-        };
-        auto post = [&](const Pre& o) {
-            const bool a = T >= 1e-4f;
-            nc = a ? o.ncv : nc;
-            const float alpha = a ? o.aclamp : 0.0f;
-            const float wgt = T * alpha;
-            cr = fmaf(wgt, o.r, cr); cg = fmaf(wgt, o.g, cg); cb = fmaf(wgt, o.b, cb); if (DEPTH) dd = fmaf(wgt, o.depth, dd);
-            T = T * (1.0f - alpha);
-        };
-        auto any_live = [&]() { return __any(T >= 1e-4f); };
+        FwdItem it;
+        if (!fwd_decode(a, pos, quad, lane, it)) continue;
+        // the quadrant's running state S: the same bits in all four waves (cr .. dd: the whole sums, the base included)
+        FwdPixel s = fwd_pixel(it.in);
+        const uint32_t* __restrict__ idx = a.sortedIdx + it.start;
         // the staged chunk's entries against the running state, as the one-wave kernel takes them (liveness gate, nContrib)
-        // (round 6, as in blend_fwd_v2q_kernel: the chunk's entries accumulate from zero and join the state the chunk started
-        // from at its end -- one rounding at the size of the total per chunk, not one per entry)
+        // (round 6, as there: the chunk's entries accumulate from zero and join the state the chunk started from at its end --
+        // one rounding at the size of the total per chunk, not one per entry)
         // (the state the chunk starts from waits in LDS meanwhile -- `park`, four rows of 64 this wave owns at that moment --, not
         // in four registers across the loop: the kernel sits at its register budget for five workgroups per CU)
         auto trips_abs = [&](const f4* sl, uint32_t n, uint32_t c0, float* park) {
-            park[lane] = cr; park[64 + lane] = cg; park[128 + lane] = cb; if (DEPTH) park[192 + lane] = dd;
-            cr = 0.f; cg = 0.f; cb = 0.f; dd = 0.f;
+            park[lane] = s.cr; park[64 + lane] = s.cg; park[128 + lane] = s.cb; if (DEPTH) park[192 + lane] = s.dd;
+            s.cr = 0.f; s.cg = 0.f; s.cb = 0.f; s.dd = 0.f;
+            // (fwd_trips' entries in fwd_trips' order, with the exit folded into the loop's condition: through fwd_trips itself,
+            // whose loop leaves by a break, this kernel's blend forward of the 10 k / 400x400 scene took 0.1274 ms against 0.1240,
+            // with this form 0.1246 -- the inner loop then is the instructions it was, 101 + 18 + 4 vector and 23 scalar per trip)
             bool live = true;
             for (uint32_t j = 0; j < n && live; j += 4) {
                 Pre p0, p1, p2, p3;
-                pre(sl, j, p0); pre(sl, j + 1, p1); pre(sl, j + 2, p2); pre(sl, j + 3, p3);
-                post(p0); post(p1); post(p2); post(p3);
-                live = any_live();
+                fwd_pre(sl, j, it.px, it.py, p0); fwd_pre(sl, j + 1, it.px, it.py, p1); fwd_pre(sl, j + 2, it.px, it.py, p2); fwd_pre(sl, j + 3, it.px, it.py, p3);
+                fwd_post<DEPTH>(s, p0); fwd_post<DEPTH>(s, p1); fwd_post<DEPTH>(s, p2); fwd_post<DEPTH>(s, p3);
+                live = fwd_any_live(s.T);
             }
-            if (live && T >= 1e-4f) nc = min(c0 + 64u, count);     // still live: went through the whole chunk
-            cr = park[lane] + cr; cg = park[64 + lane] + cg; cb = park[128 + lane] + cb; if (DEPTH) dd = park[192 + lane] + dd;
+            if (live && s.T >= 1e-4f) s.nc = min(c0 + 64u, it.count);     // still live: went through the whole chunk
+            s.cr = park[lane] + s.cr; s.cg = park[64 + lane] + s.cg; s.cb = park[128 + lane] + s.cb; if (DEPTH) s.dd = park[192 + lane] + s.dd;
         };
 
         // chunk of this wave in round r: c(r) = 256 r + 64 ((hw + r) & 3); records run one round ahead, indices two
         auto chunk_of = [&](uint32_t r) { return 256u * r + 64u * (((uint32_t)hw + r) & 3u); };
-        RecV nx = load_chunk(rec12, idx, idxMask, chunk_of(0), count, lane);
-        uint32_t gN = load_chunk_index(idx, idxMask, chunk_of(1), count, lane);
-        for (uint32_t r = 0; 256u * r < count; r++) {
-            if (!any_live()) break;                                // (S is the same in every wave: a uniform exit)
+        RecV nx = load_chunk(a.rec12, idx, a.idxMask, chunk_of(0), it.count, lane);
+        uint32_t gN = load_chunk_index(idx, a.idxMask, chunk_of(1), it.count, lane);
+        for (uint32_t r = 0; 256u * r < it.count; r++) {
+            if (!fwd_any_live(s.T)) break;                         // (S is the same in every wave: a uniform exit)
             const uint32_t s0 = 256u * r;
             const int w = (int)(((uint32_t)hw + r) & 3u);          // this wave's part of the round
             const uint32_t c0 = s0 + 64u * (uint32_t)w;
-            const uint32_t nParts = min(4u, (count - s0 + 63u) / 64u);
+            const uint32_t nParts = min(4u, (it.count - s0 + 63u) / 64u);
             const bool mine = (uint32_t)w < nParts;
             f4* sl = sg;
             uint32_t n = 0;
-            if (mine) n = stage_compact(sl, nx, c0);
-            nx = gather_chunk(rec12, gN);                          // (0xFFFFFFFF beyond the list: nothing is loaded)
-            gN = load_chunk_index(idx, idxMask, chunk_of(r + 2), count, lane);
+            if (mine) n = fwd_stage_compact(sl, nx, c0, it, lane);
+            nx = gather_chunk(a.rec12, gN);                        // (0xFFFFFFFF beyond the list: nothing is loaded)
+            gN = load_chunk_index(idx, a.idxMask, chunk_of(r + 2), it.count, lane);
             // (parts 1-3 are swept from T = 1; the running state comes back from the fold, where part 0's end state is absolute)
             if (w == 0) {
-                if (statePlanes != 0 && c0 != 0) save_state(c0);
+                if (a.statePlanes != 0 && c0 != 0) ckpt_save<SEG, DEPTH>(a, pool, it, lane, c0, s.T, s.cr, s.cg, s.cb, s.dd);
                 trips_abs(sl, n, c0, &xPre[hw][0][0]);          // (wave 0's xPre rows are written in the fold below, behind this)
             } else if (mine) {
-                T = in ? 1.0f : 0.0f; cr = 0.f; cg = 0.f; cb = 0.f; dd = 0.f;
+                s.T = it.in ? 1.0f : 0.0f; s.cr = 0.f; s.cg = 0.f; s.cb = 0.f; s.dd = 0.f;
                 for (uint32_t j = 0; j < n; j += 4) {              // (no liveness gate: the sums are used only where every entry was live)
                     Pre p0, p1, p2, p3;
-                    pre(sl, j, p0); pre(sl, j + 1, p1); pre(sl, j + 2, p2); pre(sl, j + 3, p3);
+                    fwd_pre(sl, j, it.px, it.py, p0); fwd_pre(sl, j + 1, it.px, it.py, p1); fwd_pre(sl, j + 2, it.px, it.py, p2); fwd_pre(sl, j + 3, it.px, it.py, p3);
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const Pre& o = u == 0 ? p0 : u == 1 ? p1 : u == 2 ? p2 : p3;
-                        const float wgt = T * o.aclamp;
-                        cr = fmaf(wgt, o.r, cr); cg = fmaf(wgt, o.g, cg); cb = fmaf(wgt, o.b, cb); if (DEPTH) dd = fmaf(wgt, o.depth, dd);
-                        T = T * (1.0f - o.aclamp);
+                        const float wgt = s.T * o.aclamp;
+                        s.cr = fmaf(wgt, o.r, s.cr); s.cg = fmaf(wgt, o.g, s.cg); s.cb = fmaf(wgt, o.b, s.cb); if (DEPTH) s.dd = fmaf(wgt, o.depth, s.dd);
+                        s.T = s.T * (1.0f - o.aclamp);
                     }
                 }
             }
-            if (mine) { xEnd[w][0][lane] = T; xEnd[w][1][lane] = cr; xEnd[w][2][lane] = cg; xEnd[w][3][lane] = cb; xEnd[w][4][lane] = dd; }
-            if (w == 0) xDead[0][5][lane] = __uint_as_float(nc);   // (nContrib after part 0)
+            if (mine) { xEnd[w][0][lane] = s.T; xEnd[w][1][lane] = s.cr; xEnd[w][2][lane] = s.cg; xEnd[w][3][lane] = s.cb; xEnd[w][4][lane] = s.dd; }
+            if (w == 0) xDead[0][5][lane] = __uint_as_float(s.nc);   // (nContrib after part 0)
             __syncthreads();
             // Fold, for this lane's pixel: P = the absolute state behind the parts [0, qDone) of the round.  A part q the pixel
             // is live through (T only falls: P.T x its end T >= 1e-4 says so) is composed onto P; a pixel dead at the part's
@@ -991,11 +879,11 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
                         if (q == w) { myPT = PT; xPre[hw][0][lane] = Pr; xPre[hw][1][lane] = Pg; xPre[hw][2][lane] = Pb; if (DEPTH) xPre[hw][3][lane] = Pd; }
                         if (PT >= 1e-4f) {
                             const float Tend = PT * xEnd[q][0][lane];
-                            if (Tend * foldScale >= 1e-4f) {       // (foldScale: 1 exactly, but for the tests' forced second takes)
+                            if (Tend * a.foldScale >= 1e-4f) {     // (foldScale: 1 exactly, but for the tests' forced second takes)
                                 Pr = fmaf(PT, xEnd[q][1][lane], Pr); Pg = fmaf(PT, xEnd[q][2][lane], Pg); Pb = fmaf(PT, xEnd[q][3][lane], Pb);
                                 if (DEPTH) Pd = fmaf(PT, xEnd[q][4][lane], Pd);
                                 PT = Tend;
-                                Pnc = min(s0 + 64u * (uint32_t)(q + 1), count);
+                                Pnc = min(s0 + 64u * (uint32_t)(q + 1), it.count);
                             } else crossedIn = q;
                         }
                         if (!crossedIn) qDone = (uint32_t)q + 1u;
@@ -1005,11 +893,11 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
                 if (w != 0 && mine && __any(crossedIn == w)) {
                     // pixels finish inside this part: its entries again, in sequence from the folded prefix (the chunk is
                     // still staged); the other lanes idle with T = 0
-                    T = crossedIn == w ? PT : 0.0f; cr = Pr; cg = Pg; cb = Pb; dd = Pd; nc = 0;
+                    s.T = crossedIn == w ? PT : 0.0f; s.cr = Pr; s.cg = Pg; s.cb = Pb; s.dd = Pd; s.nc = 0;
                     trips_abs(sl, n, c0, &xDead[w][1][0]);          // (this part's xDead rows are written right below, by this wave)
                     if (crossedIn == w) {
-                        xDead[w][0][lane] = T; xDead[w][1][lane] = cr; xDead[w][2][lane] = cg; xDead[w][3][lane] = cb; xDead[w][4][lane] = dd;
-                        xDead[w][5][lane] = __uint_as_float(nc);
+                        xDead[w][0][lane] = s.T; xDead[w][1][lane] = s.cr; xDead[w][2][lane] = s.cg; xDead[w][3][lane] = s.cb; xDead[w][4][lane] = s.dd;
+                        xDead[w][5][lane] = __uint_as_float(s.nc);
                     }
                 }
                 __syncthreads();
@@ -1025,28 +913,11 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
             }
             // the part's checkpoint, now that every pixel's prefix of it is final (the one-wave kernel saves one iff some
             // pixel reaches the chunk live)
-            if (statePlanes != 0 && w != 0 && mine && __any(myPT >= 1e-4f))
-                save_state_vals(c0, myPT, xPre[hw][0][lane], xPre[hw][1][lane], xPre[hw][2][lane], DEPTH ? xPre[hw][3][lane] : 0.0f);
-            T = PT; cr = Pr; cg = Pg; cb = Pb; dd = Pd; nc = Pnc;
+            if (a.statePlanes != 0 && w != 0 && mine && __any(myPT >= 1e-4f))
+                ckpt_save<SEG, DEPTH>(a, pool, it, lane, c0, myPT, xPre[hw][0][lane], xPre[hw][1][lane], xPre[hw][2][lane], DEPTH ? xPre[hw][3][lane] : 0.0f);
+            s.T = PT; s.cr = Pr; s.cg = Pg; s.cb = Pb; s.dd = Pd; s.nc = Pnc;
         }
-        if (hw == 0) {
-            if (cutStore && any_live() && lane == 0 && cutStore[tile] != 0u) hostWords[0] = 1u;
-            // (the pixel is rebuilt from the lane here instead of being kept across the rounds: the kernel spilled its item-invariant
-            // values to scratch at five workgroups per CU)
-            const int xe = X0 + k * 8 + (lane & 7), ye = Y0 + h * 8 + (lane >> 3);
-            if (xe < XL && ye < YL) {
-                const size_t pix = (size_t)ye * W + xe;
-                float bg0, bg1, bg2;
-                gs_bg_terms(bgc, T, bg0, bg1, bg2);
-                outColor[3 * pix] = cr + bg0; outColor[3 * pix + 1] = cg + bg1; outColor[3 * pix + 2] = cb + bg2;
-                if (DEPTH) outDepth[pix] = dd;
-                outAlpha[pix] = 1.0f - T; lastContrib[pix] = nc; finalT[pix] = T;
-            }
-            uint32_t m = (xe < XL && ye < YL) ? nc : 0u;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
-            if (lane == 0 && m) atomicMax(&blockWork[b], m);
-        }
+        if (hw == 0) fwd_finish<DEPTH>(a, it, lane, s.T, s.cr, s.cg, s.cb, s.dd, s.nc);
     }
 }
 
@@ -1054,6 +925,13 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(
 // backward
 // ---------------------------------------------------------------------------------------------
 // (wave_sum10_transposed: gs_wavesum.h)
+
+// packed-f32 helpers.  The f32 VALU of gfx950 retires one wave64 instruction per 4 cycles per SIMD (measured:
+// both blend kernels ran at >90 % of that issue rate while "using" 25 % of the 157 TFLOP/s headline, which
+// counts v_pk_fma_f32).  Each lane of the backward therefore owns pixel PAIRS (x, x+8) on one image row and does the pair's
+// arithmetic with v_pk_mul/add/fma_f32; the row term dy is shared by the pair and stays scalar per lane.
+__device__ __forceinline__ f2 splat2(float v) { return (f2){v, v}; }
+__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 // A list entry as the backward keeps it in LDS: the conic pre-multiplied by C = -1/(2 ln 2), so that the exponent of
 // 2^e comes out of two fused multiply-adds, e = dx^2 A + dxdy B + dy^2 Dq (A = c00 C, B = (c01 + c10) C, Dq = c11 C).
@@ -1370,7 +1248,7 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
 constexpr int SEGLEN = GS_SEG_LEN;
 // the grid the fused forward is launched with (its queue starts behind the waves' static first items)
 // four waves per quadrant (blend_fwd_v2w_kernel) where the image has fewer quadrants than the chip has wave slots
-// (gs_ctx::fwdWide: 1 / 0 force, -1 by that rule; the trace buffer and the 16x8 variant keep the one-wave kernel)
+// (gs_ctx::fwdWide: 1 / 0 force, -1 by that rule; the trace buffer and GS_TUNE_FWD_QUADRANTS 0 keep the one-wave kernel)
 bool blend_forward_v2_wide(const gs_ctx* c)
 {
     if (c->fwdTrace || !c->fwdQuadrants) return false;
@@ -1418,59 +1296,49 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
     // (render-only forwards keep no checkpoints at all: the arena's arithmetic below then runs on four planes and is not used)
     const int planes = c->depthGradient && outDepth ? 5 : 4;
     c->fwd.statePlanes = planes;
-    const int blocksX = c->blocksX, nBlocks = c->numPixBlocks;
-    const int nItems = nBlocks * 4, grid = blend_forward_v2_grid(c);
+    const int grid = blend_forward_v2_grid(c);
     if (c->segBaseDone) c->segBaseDone = false;        // the tile sort's launch has done it (binning.hip)
     else {
         SegBaseArgs sa;
         fill_seg_base(c, sa);
         hipLaunchKernelGGL(seg_base_kernel<SEGLEN>, dim3(1), dim3(1024), 0, c->stream, sa);
     }
-    const uint32_t* cuts = c->fwd.cutsActive ? c->fwd.cutStore : nullptr;
+    const bool wide = blend_forward_v2_wide(c), pair = !wide && blend_forward_v2_pair(c);
     // capacity in slots of THIS forward's planes (the arena is sized for five)
     const uint32_t qcap = (uint32_t)(c->qslotCap * 5 / c->fwd.statePlanes);
     c->fwd.qslotCap = qcap;
+    // the waves that own a checkpoint pool: every wave of the one-wave kernel (its grid counts waves), the sweeping wave of a
+    // pair, all four waves of a four-wave workgroup
+    const uint32_t poolWaves = (uint32_t)grid * (wide ? 4u : 1u);
     // three quarters of the arena at most are handed out statically, up to 32 slots (2048 list entries of one quadrant)
     // per wave; the rest is the shared part, in eight
-    uint32_t own = (uint32_t)(((unsigned long long)qcap * 3ull / 4ull) / (unsigned long long)grid);
+    uint32_t own = (uint32_t)(((unsigned long long)qcap * 3ull / 4ull) / (unsigned long long)poolWaves);
     if (own > 32u) own = 32u;
-    c->fwd.qslotStatic = own * (uint32_t)grid;
+    c->fwd.qslotStatic = own * poolWaves;
     const uint32_t partSlots = (qcap - c->fwd.qslotStatic) / 8u;
     // test knob (GS_TUNE_POISON_CHECKPOINTS): every checkpoint lane this forward does not write reads back as NaN
     if (c->poisonCheckpoints && c->segState)
         GS_HIP_CHECK(c, hipMemsetAsync(c->segState, 0xFF, (size_t)c->qslotCap * 5 * 64 * sizeof(float), c->stream));
-    if (blend_forward_v2_wide(c)) {     // four waves per quadrant: the grid is workgroups, the arena's static shares go per wave
-        uint32_t ownW = (uint32_t)(((unsigned long long)qcap * 3ull / 4ull) / (unsigned long long)(grid * 4));
-        if (ownW > 32u) ownW = 32u;
-        c->fwd.qslotStatic = ownW * (uint32_t)grid * 4u;
-        const uint32_t partW = (qcap - c->fwd.qslotStatic) / 8u;
-        auto kw = outDepth ? blend_fwd_v2w_kernel<SEGLEN, true> : blend_fwd_v2w_kernel<SEGLEN, false>;
-        hipLaunchKernelGGL(kw, dim3(grid), dim3(256), 0, c->stream, c->W, c->H, c->tileW,
-                           c->tileH, c->gridW, blocksX, nItems, c->bg, reinterpret_cast<const float4*>(c->packed12),
-                           c->sortedRaw, c->idxMask, c->tileRanges, c->segBase, (uint32_t)c->segCap, c->renderOnly ? 0 : c->fwd.statePlanes, outColor, outDepth,
-                           outAlpha, c->lastContrib, c->finalT, c->segState, c->segSlot, qcap, ownW, partW, ckpt_pool(partW, (uint32_t)grid * 4u), c->blockWork, c->counters, c->fwdQueue,
-                           (uint32_t)c->fwdQueues, c->blockOrder, cuts, c->missDev, c->fwdFoldScale, c->virt);
-        GS_HIP_CHECK(c, hipGetLastError());
-        if (c->renderOnly) c->fwd.statePlanes = 0;      // (backward_preflight refuses such a forward)
-        return GS_OK;
-    }
-    if (blend_forward_v2_pair(c)) {
-        auto kp = outDepth ? blend_fwd_v2p_kernel<SEGLEN, true> : blend_fwd_v2p_kernel<SEGLEN, false>;
-        hipLaunchKernelGGL(kp, dim3(grid), dim3(128), 0, c->stream, c->W, c->H, c->tileW,
-                           c->tileH, c->gridW, blocksX, nItems, c->bg, reinterpret_cast<const float4*>(c->packed12),
-                           c->sortedRaw, c->idxMask, c->tileRanges, c->segBase, (uint32_t)c->segCap, c->renderOnly ? 0 : c->fwd.statePlanes, outColor, outDepth,
-                           outAlpha, c->lastContrib, c->finalT, c->segState, c->segSlot, qcap, own, partSlots, ckpt_pool(partSlots, (uint32_t)grid), c->blockWork, c->counters, c->fwdQueue, (uint32_t)c->fwdQueues, c->blockOrder,
-                           cuts, c->missDev, c->virt);
-        GS_HIP_CHECK(c, hipGetLastError());
-        if (c->renderOnly) c->fwd.statePlanes = 0;
-        return GS_OK;
-    }
-    auto kern = outDepth ? blend_fwd_v2q_kernel<SEGLEN, true> : blend_fwd_v2q_kernel<SEGLEN, false>;
-    hipLaunchKernelGGL(kern, dim3(grid / 4), dim3(256), 0, c->stream, c->W, c->H, c->tileW,      // (grid = waves, a multiple of four)
-                       c->tileH, c->gridW, blocksX, nItems, c->bg, reinterpret_cast<const float4*>(c->packed12),
-                       c->sortedRaw, c->idxMask, c->tileRanges, c->segBase, (uint32_t)c->segCap, c->renderOnly ? 0 : c->fwd.statePlanes, outColor, outDepth,
-                       outAlpha, c->lastContrib, c->finalT, c->segState, c->segSlot, qcap, own, partSlots, ckpt_pool(partSlots, (uint32_t)grid), c->blockWork, c->counters, c->fwdQueue, (uint32_t)c->fwdQueues, c->blockOrder,
-                       c->fwdTrace, cuts, c->missDev, (uint32_t)c->fwdSlowSlot, c->virt);
+    BlendFwdArgs a;
+    a.W = c->W; a.H = c->H; a.tileW = c->tileW; a.tileH = c->tileH; a.gridW = c->gridW; a.blocksX = c->blocksX;
+    a.nItems = c->numPixBlocks * 4;
+    a.bgc = c->bg;
+    a.rec12 = reinterpret_cast<const float4*>(c->packed12); a.sortedIdx = c->sortedRaw; a.idxMask = c->idxMask;
+    a.tileRanges = c->tileRanges; a.segBase = c->segBase; a.segCap = (uint32_t)c->segCap;
+    a.statePlanes = c->renderOnly ? 0 : c->fwd.statePlanes;
+    a.outColor = outColor; a.outDepth = outDepth; a.outAlpha = outAlpha; a.lastContrib = c->lastContrib; a.finalT = c->finalT;
+    a.segState = c->segState; a.segSlot = c->segSlot;
+    a.qslotCap = qcap; a.qslotOwn = own; a.qslotShared0 = c->fwd.qslotStatic; a.qslotPart = partSlots; a.ckptPool = ckpt_pool(partSlots, poolWaves);
+    a.blockWork = c->blockWork; a.counters = c->counters; a.fwdQueue = c->fwdQueue; a.nq = (uint32_t)c->fwdQueues;
+    a.blockOrder = c->blockOrder; a.cutStore = c->fwd.cutsActive ? c->fwd.cutStore : nullptr; a.hostWords = c->missDev;
+    a.vg = c->virt;
+    a.trace = c->fwdTrace; a.slowSlot = (uint32_t)c->fwdSlowSlot; a.foldScale = c->fwdFoldScale;
+    auto kw = outDepth ? blend_fwd_v2w_kernel<SEGLEN, true> : blend_fwd_v2w_kernel<SEGLEN, false>;
+    auto kp = outDepth ? blend_fwd_v2p_kernel<SEGLEN, true> : blend_fwd_v2p_kernel<SEGLEN, false>;
+    auto kq = outDepth ? blend_fwd_v2q_kernel<SEGLEN, true> : blend_fwd_v2q_kernel<SEGLEN, false>;
+    if (wide) hipLaunchKernelGGL(kw, dim3(grid), dim3(256), 0, c->stream, a);               // four waves per quadrant: the grid is workgroups
+    else if (pair) hipLaunchKernelGGL(kp, dim3(grid), dim3(128), 0, c->stream, a);          // a sweeping and a staging wave: the grid is workgroups
+    else hipLaunchKernelGGL(kq, dim3(grid / 4), dim3(256), 0, c->stream, a);                // four independent waves: the grid is waves, a multiple of four
     GS_HIP_CHECK(c, hipGetLastError());
     if (c->renderOnly) c->fwd.statePlanes = 0;          // (backward_preflight refuses such a forward)
     return GS_OK;

@@ -281,7 +281,9 @@ struct gs_ctx {
                                      // that are not multiples of 16 -- the 16x16 blocks enumerated per tile
     // launch tuning (gs_ctx_set_tuning; per context): measured optima of tools/sweep.sh as defaults
     int fwdWavesPerSimd = 4, bwdWavesPerCu = 16;
-    int fwdQuadrants = 1;            // (retired knob: the forward's items are always 8x8 quadrants)
+    int fwdQuadrants = 1;            // GS_TUNE_FWD_QUADRANTS: the forward's items are always 8x8 quadrants (the 16x8 variant it once
+                                     // selected is gone); 0 still forces the one-wave kernel over the pair and four-wave kernels
+                                     // (blend_forward_v2_wide, blend_forward_v2_pair_decide)
     int scatterThreads = 0;          // threads per sort tile of the one-pass tile sort: 256 / 512 / 1024, 0 = by the Gaussian count (binning.hip)
     int lsdThreads = 0;              // threads per tile of the LSD depth passes' scatter: 256 / 1024, 0 = by the tile count (binning.hip)
     int fwdWide = -1;                // blend forward with four waves per quadrant: 1 / 0, -1 = where the image has fewer quadrants than wave slots (blend_v2.hip)

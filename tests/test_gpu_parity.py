@@ -942,6 +942,71 @@ def test_staging_wave_forward_leaves_the_same_bits(W, H, N, scale):
         _renderer(W, H).setTuning(fwd_pair=17)
 
 
+_CKPT_SCENE = (160, 120, 20000)        # the four-wave tests' scene: lists of ~1100 entries, 80 pixel blocks
+_ckpt_reference_cache = {}
+
+
+def _ckpt_scene_run(depth, **tuning):
+    """One forward + backward of the scene above under `tuning`: (render, alpha, nContrib, blockWork, depth or None, gradients)."""
+    W, H, N = _CKPT_SCENE
+    p, cam = _scene(77, N, W, H, spread=0.5, scale=0.12)
+    rng = np.random.default_rng(6)
+    cC, cD = rng.normal(size=(H, W, 3)).astype(np.float32), rng.normal(size=H * W).astype(np.float32)
+    r = _renderer(W, H)
+    r.setTuning(**tuning)
+    res = r.renderForward({k: torch.as_tensor(v, device=r.device) for k, v in p.items()}, cam, wantDepth=depth)
+    out = [res.render.clone(), res.alpha.clone(), r.lastContrib().clone(), r.blockWork().clone(),
+           res.depth.clone() if depth else None]
+    g = r.renderBackward(cC, cD) if depth else r.renderBackward(cC)
+    out.append({k: _np(v).astype(np.float64) for k, v in g.items()})
+    assert r.stats()["overflow"] == 0
+    r.close()
+    return out
+
+
+def _ckpt_reference(depth):
+    """The unpoisoned one-wave forward and its gradients: computed once per depth setting, shared, never written."""
+    if depth not in _ckpt_reference_cache:
+        _ckpt_reference_cache[depth] = _ckpt_scene_run(depth, fwd_four_waves=0, fwd_pair=0)
+    return _ckpt_reference_cache[depth]
+
+
+@pytest.mark.parametrize("tuning", [dict(fwd_four_waves=0, fwd_pair=0), dict(fwd_four_waves=0, fwd_pair=1),
+                                    dict(fwd_four_waves=0, fwd_pair=3), dict(fwd_four_waves=1)],
+                         ids=["one_wave", "pair", "pair_3_per_cu", "four_waves"])
+def test_every_forward_kernel_writes_the_checkpoints_its_backward_reads(tuning):
+    """The checkpoint allocator and store (ckpt_save) is one function under the three forward kernels.  Under
+    GS_TUNE_POISON_CHECKPOINTS (the arena is NaN in front of the forward: a checkpoint lane the backward reads and the forward
+    did not write makes a NaN gradient) each of them -- the one-wave kernel, the pair kernel at 12 and at 3 workgroups per CU,
+    the four-wave kernel -- on lists of several segments, with a depth image and depth cotangent (five planes) and with
+    neither (four): every gradient finite; the one-wave and pair forwards the bits of the unpoisoned one-wave forward and
+    their gradients within 1e-4 of its (test_staging_wave_forward_leaves_the_same_bits' bar: float atomics); the four-wave
+    forward within test_four_waves_per_quadrant_forward_against_the_one_wave_forward's bars of it."""
+    for depth in (True, False):
+        ref = _ckpt_reference(depth)
+        got = _ckpt_scene_run(depth, poison_checkpoints=1, **tuning)
+        assert int(got[2].max()) > 256, depth               # several segments per list: checkpoints are drawn and read
+        for k in GRAD_KEYS:
+            assert np.isfinite(got[5][k]).all(), (k, depth)   # a NaN = a checkpoint lane nobody wrote
+        if tuning.get("fwd_four_waves") == 1:
+            for i, name in ((0, "render"), (1, "alpha"), (4, "depth")):
+                if got[i] is None:
+                    assert ref[i] is None
+                    continue
+                scale = float(ref[i].abs().max())
+                assert float((ref[i] - got[i]).abs().max()) <= 1e-5 * max(scale, 1.0), (name, depth)
+            diff = ref[2] != got[2]
+            assert float(diff.float().mean()) <= 1e-3 and int((ref[2].long() - got[2].long()).abs().max()) <= 64, depth
+            for k in GRAD_KEYS:
+                assert np.abs(ref[5][k] - got[5][k]).max() <= 1e-4 * np.abs(ref[5][k]).max(), (k, depth)
+        else:
+            for i in range(4):
+                assert torch.equal(got[i], ref[i]), (i, depth)
+            assert (got[4] is None) == (ref[4] is None) and (got[4] is None or torch.equal(got[4], ref[4])), depth
+            for k in GRAD_KEYS:
+                assert _rel(got[5][k], ref[5][k]) <= 1e-4, (k, depth)
+
+
 def test_four_waves_per_quadrant_forward_against_the_one_wave_forward():
     """blend_fwd_v2w_kernel (images with fewer quadrants than wave slots; GS_TUNE_FWD_FOUR_WAVES) against blend_fwd_v2q_kernel on a
     dense scene whose pixels finish at all depths of lists of ~1100 entries (rounds of four chunks with pixels crossing
