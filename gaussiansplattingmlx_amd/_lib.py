@@ -48,6 +48,10 @@ class gs_depth_loss_params(C.Structure):
     _fields_ = [("mode", C.c_int), ("lambda_", C.c_float), ("alpha_min", C.c_float), ("scale", C.c_float), ("offset", C.c_float)]
 
 
+class gs_lens(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
+
+
 GS_DEPTH_ACCUMULATED, GS_DEPTH_EXPECTED, GS_DEPTH_DISPARITY = 0, 1, 2
 GS_DP_ALLREDUCE, GS_DP_SH_COMPRESSED = 0, 1
 GS_DP_UNIQUE_ID_BYTES = 128
@@ -163,6 +167,7 @@ _SIGS = {
     "gs_compute_filter3d": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gs_set_filter3d": (C.c_int, [_vp, _vp]),
     "gs_filter3d_bake": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
+    "gs_undistort": (C.c_int, [_vp, C.POINTER(gs_lens)] + [C.c_int] * 6 + [_vp, _vp, _vp]),
     "gs_set_mcmc": (C.c_int, [_vp, _vp]),
     "gs_mcmc_regularizer_grad": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_mcmc_inject_noise": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [C.c_float, _vp]),

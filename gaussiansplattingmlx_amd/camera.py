@@ -4,7 +4,10 @@
 view  = (c2w^-1)^T stored row-major, so p_view = [p, 1] @ view (translation in row 3)
 proj  = rows (2n/(r-l),0,0,0), (0,2n/(t-b),0,0), (0,0,f/(f-n),1), (0,0,-nf/(f-n),0)
 FoV   = 2 atan(pixels / (2 focal)) evaluated in f32; matrices built in f64, cast to f32.
-The principal point is ignored, as in the reference (CameraUtil.swift:26-27).
+The reference ignores the principal point (CameraUtil.swift:26-27); here it is optional: Camera(cx=, cy=)
+puts offX = (2 cx - W) / W, offY = (2 cy - H) / H into row 2 of proj, so that a view-space point (x, y, z) lands at
+means2d = (fx x / z + cx - 0.5, fy y / z + cy - 0.5): pixel i covers [i, i + 1), COLMAP's and nerfstudio's convention.  Without
+cx, cy the camera is the reference's centred one, bit for bit.
 """
 from __future__ import annotations
 
@@ -28,16 +31,18 @@ def fov2focal(fov: float, pixels: float) -> float:
     return pixels / (2.0 * np.tan(fov / 2.0))
 
 
-def getProjectionMatrix(znear: float, zfar: float, fovX: float, fovY: float) -> np.ndarray:
-    """Row-major array the reference hands to its kernels (P.transpose.toMLXArray())."""
+def getProjectionMatrix(znear: float, zfar: float, fovX: float, fovY: float, offX: float = 0.0, offY: float = 0.0) -> np.ndarray:
+    """Row-major array the reference hands to its kernels (P.transpose.toMLXArray()).  offX = (2 cx - W) / W and offY =
+    (2 cy - H) / H move the principal point off the centre: with this code base's clip w = +z the off-centre term
+    -(r + l) / (r - l) of the frustum is +offX (Inria's w = -z form carries the other sign and would mirror the shift)."""
     tanHalfY, tanHalfX = np.tan(fovY / 2.0), np.tan(fovX / 2.0)
     top, right = tanHalfY * znear, tanHalfX * znear
     bottom, left = -top, -right
     P = np.zeros((4, 4), np.float64)
     P[0, 0] = 2 * znear / (right - left)
     P[1, 1] = 2 * znear / (top - bottom)
-    P[2, 0] = (right + left) / (right - left)
-    P[2, 1] = (top + bottom) / (top - bottom)
+    P[2, 0] = (right + left) / (right - left) + offX       # (the symmetric frustum's 0, plus the offset)
+    P[2, 1] = (top + bottom) / (top - bottom) + offY
     P[2, 2] = zfar / (zfar - znear)
     P[2, 3] = 1.0
     P[3, 2] = -znear * zfar / (zfar - znear)
@@ -46,7 +51,10 @@ def getProjectionMatrix(znear: float, zfar: float, fovX: float, fovY: float) -> 
 
 class Camera:
     def __init__(self, width: int, height: int, focalX: float, focalY: float, c2w, znear: float = 0.1,
-                 zfar: float = 100.0):
+                 zfar: float = 100.0, cx: float | None = None, cy: float | None = None):
+        """cx, cy: the principal point in pixels (pixel i covers [i, i + 1)); None is the image centre W / 2, H / 2, and then
+        every field is the reference's.  FoVx / FoVy stay 2 atan(pixels / (2 focal)): they feed the EWA clamp's symmetric
+        limX / limY, which the principal point does not enter."""
         c2w = np.asarray(c2w, dtype=np.float64).reshape(4, 4)
         self.imageWidth, self.imageHeight = int(width), int(height)
         self.focalX, self.focalY = np.float32(focalX), np.float32(focalY)
@@ -55,15 +63,19 @@ class Camera:
         # simd_double4x4.fromMlxArray(c2w).inverse.transpose.toMLXArray() (CameraUtil.swift:30, :34): fromMlxArray /
         # toMLXArray are the row-major <-> column-storage pair above, so in array terms this is inv(c2w)^T
         self.worldViewTransform = np.ascontiguousarray(np.linalg.inv(c2w).T.astype(np.float32))
+        self.principalX = float(width) / 2.0 if cx is None else float(cx)
+        self.principalY = float(height) / 2.0 if cy is None else float(cy)
+        offX = (2.0 * self.principalX - float(width)) / float(width)
+        offY = (2.0 * self.principalY - float(height)) / float(height)
         self.projectionMatrix = np.ascontiguousarray(
-            getProjectionMatrix(znear, zfar, float(self.FoVx), float(self.FoVy)).astype(np.float32))
+            getProjectionMatrix(znear, zfar, float(self.FoVx), float(self.FoVy), offX, offY).astype(np.float32))
         self.cameraCenter = c2w[:3, 3].copy()
         self.c2w = c2w.copy()
 
     def as_dict(self):
         return dict(view=self.worldViewTransform, proj=self.projectionMatrix, fovX=float(self.FoVx),
                     fovY=float(self.FoVy), focalX=float(self.focalX), focalY=float(self.focalY),
-                    camCenter=self.cameraCenter.astype(np.float32))
+                    camCenter=self.cameraCenter.astype(np.float32), principalX=self.principalX, principalY=self.principalY)
 
 
 def look_at_c2w(eye, target=(0.0, 0.0, 0.0), up=(0.0, 0.0, 1.0)) -> np.ndarray:
@@ -117,6 +129,19 @@ def apply_pose_correction(camera: Camera, delta) -> Camera:
     c2w = getattr(camera, "c2w", None)
     if c2w is None:
         c2w = np.linalg.inv(np.asarray(camera.worldViewTransform, np.float64).T)
-    out = Camera(camera.imageWidth, camera.imageHeight, camera.focalX, camera.focalY, np.asarray(c2w, np.float64) @ pose_delta_matrix(delta))
+    out = Camera(camera.imageWidth, camera.imageHeight, camera.focalX, camera.focalY, np.asarray(c2w, np.float64) @ pose_delta_matrix(delta),
+                 cx=getattr(camera, "principalX", None), cy=getattr(camera, "principalY", None))
     out.projectionMatrix = camera.projectionMatrix.copy()
     return out
+
+
+def cameras_from_train_data(trainData, principal_point: bool = True, znear: float = 0.1, zfar: float = 100.0):
+    """[Camera] of a loader's TrainData (Hs, Ws, intrinsicArray, c2wArray): focal lengths and, with principal_point, cx, cy from
+    each view's intrinsics -- the camera model pointcloud.getRaysFromImages back-projects with.  principal_point=False gives
+    the reference's centred cameras."""
+    Hs, Ws, intr, c2ws = trainData.getCameraParams()
+    cams = []
+    for H, W, K, c2w in zip(Hs, Ws, np.asarray(intr, np.float64), np.asarray(c2ws, np.float64)):
+        cx, cy = (float(K[0, 2]), float(K[1, 2])) if principal_point else (None, None)
+        cams.append(Camera(int(W), int(H), K[0, 0], K[1, 1], c2w, znear, zfar, cx=cx, cy=cy))
+    return cams

@@ -1086,6 +1086,17 @@ int gs_set_filter3d_cameras(gs_ctx* c, int V, const gs_camera* cams)
         r[12] = tanf(cams[v].fov_x * 0.5f) * 1.3f;      // (make_cam's limX / limY: the EWA clamp's constant)
         r[13] = tanf(cams[v].fov_y * 0.5f) * 1.3f;
         r[14] = cams[v].focal_x;
+        // an off-centre principal point: |p.x / z + ox| <= limX is |(p.x + ox z) / z| <= limX, so the
+        // offset goes into the row and the kernel is unchanged; a zero offset leaves the row's bits
+        const float* P = cams[v].proj;
+        if (P[8] != 0.0f && P[0] != 0.0f) {
+            const float ox = P[8] / P[0];
+            for (int k = 0; k < 4; k++) r[k] += ox * cams[v].view[4 * k + 2];
+        }
+        if (P[9] != 0.0f && P[5] != 0.0f) {
+            const float oy = P[9] / P[5];
+            for (int k = 0; k < 4; k++) r[4 + k] += oy * cams[v].view[4 * k + 2];
+        }
     }
     GS_HIP_CHECK(c, hipMemcpy(c->f3dCams, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
     c->f3dCamCount = V;
@@ -1246,6 +1257,27 @@ int gs_apply_exposure(gs_ctx* c, long long n_pixels, const float* M, const float
     if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_exposure: negative n_pixels");
     if (n_pixels > 0 && (!M || !in || !out)) return fail(c, GS_ERR_INVALID_ARG, "gs_apply_exposure: null buffer");
     return launch_exposure_apply(c, n_pixels, M, in, out);
+}
+
+// ---- lens undistortion (include/gsplat.h gs_undistort; lens.hip) ----------------------------------------------------------------
+int gs_undistort(gs_ctx* c, const gs_lens* lens, int src_w, int src_h, int dst_w, int dst_h, int channels, int mode,
+                 const void* src, void* dst, unsigned char* valid)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!lens || !src || !dst) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: null pointer");
+    if (mode < 0 || mode > 2) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: mode is 0 (colour), 1 (mask) or 2 (depth)");
+    if (channels < 1 || channels > 4) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: channels in 1 .. 4");
+    if (mode != 0 && channels != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: mask and depth images have one channel");
+    if (src_w < 1 || src_h < 1 || dst_w < 1 || dst_h < 1) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: sizes are positive");
+    if (dst_h > 4 * 65535) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: at most 262140 destination rows");
+    const float focal[4] = {lens->fx, lens->fy, lens->dst_fx, lens->dst_fy};
+    for (float f : focal)
+        if (!(f > 0.0f) || !isfinite(f)) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: focal lengths are finite and > 0");
+    const float rest[8] = {lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->dst_cx, lens->dst_cy};
+    for (float f : rest)
+        if (!isfinite(f)) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort: principal points and coefficients are finite");
+    GS_HIP_CHECK(c, hipSetDevice(c->device));
+    return launch_undistort(c, *lens, src_w, src_h, dst_w, dst_h, channels, mode, src, dst, valid);
 }
 
 int gs_set_bilateral_grid(gs_ctx* c, const float* grid, float* grad, int grid_w, int grid_h, int grid_l, float tv_weight)

@@ -483,6 +483,8 @@ int launch_depth_normalize(gs_ctx* c, long long n, const float* depth, const flo
 int launch_filter3d_width(gs_ctx* c, int N, const float* xyz, float* filter);
 int launch_filter3d_bake(gs_ctx* c, int N, const float* scalesRaw, const float* opacityRaw, const float* filter, float* outScales,
                          float* outOpacity);
+int launch_undistort(gs_ctx* c, const gs_lens& lens, int srcW, int srcH, int dstW, int dstH, int channels, int mode, const void* src,
+                     void* dst, unsigned char* valid);      // lens.hip
 int launch_colour_rest(gs_ctx* c);      // gs_rider.h: the colour units the binning kernels have not taken along
 int launch_color_cot(gs_ctx* c, int N, float* out);
 int launch_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, const float* mgAll,

@@ -4,7 +4,8 @@ Data/BlenderDataLoader.swift): file formats, pose / intrinsics conventions, the 
 What is mirrored exactly: the binary / JSON / PLY parsing, quaternion -> rotation, world-to-camera inversion, the
 OpenGL -> OpenCV flip (rows 1-2 of w2c negated), intrinsics scaling by resizeFactor, white-background compositing,
 the tile size rule (W/4, H/4).  Not in the reference: per-view loss masks (readMask, TrainData.maskArray)
-and COLMAP sets with Inria's inverse-depth priors (readInverseDepth, TrainData.depthArray / depthAlign).
+and COLMAP sets with Inria's inverse-depth priors (readInverseDepth, TrainData.depthArray / depthAlign; DESIGN.md section 20);
+COLMAP's own camera-model table and lens undistortion at load time (cameraModels="colmap", undistort=True).
 What is not mirrored: image decoding and resampling (the reference goes through UIKit /
 CoreGraphics; here PIL, bilinear) and the downloads / unzipping of the demo sets (no network: loaders take paths)."""
 from __future__ import annotations
@@ -112,9 +113,74 @@ def _stack_frames(frames, whiteBackground: bool):
     return Hs, Ws, rgbs.astype(np.float32), alphas.astype(np.float32)
 
 
+# ---- lens undistortion (lens.py; not in the reference) ---------------------------------------------------
+def _host(x):
+    """A numpy array of what an undistorter returned (lens.undistort_image: numpy; GaussianRenderer.undistortImage: tensors)."""
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def _undistort_views(lenses, frames, masks, depths, undistorter=None):
+    """The loaders' undistort=True pass, after the resize: every view i whose lenses[i] (a lens.LensModel with the view's
+    SCALED K; None or a pinhole: the view is not resampled at all) has a non-zero coefficient is remapped into the pinhole
+    with the same K -- RGBA in one colour call with four channels, the mask in mask mode, the depth prior in depth mode -- and
+    its validity image is folded into the mask as an elementwise min.  frames: [(rgb, alpha, H, W)]; masks: uint8 [n, H, W]
+    or None (created, all 255, when a view is resampled); depths: float32 [n, H, W] or None.  Returns (frames, masks, depths).
+    undistorter(img, lens, mode=) -> (out, valid): lens.undistort_image by default (no GPU needed), or a renderer's
+    undistortImage (the kernel)."""
+    if undistorter is None:
+        from .lens import undistort_image as undistorter
+    todo = [i for i, L in enumerate(lenses) if L is not None and not L.is_pinhole]
+    if not todo:
+        return frames, masks, depths
+    frames = list(frames)
+    if masks is None:
+        masks = np.stack([np.full((int(f[2]), int(f[3])), 255, np.uint8) for f in frames])
+    else:
+        masks = np.array(masks, np.uint8, copy=True)
+    if depths is not None:
+        depths = np.array(depths, np.float32, copy=True)
+    for i in todo:
+        rgb, alpha, H, W = frames[i]
+        rgba = np.ascontiguousarray(np.concatenate([rgb, alpha[..., None]], axis=-1), np.float32)
+        out, valid = undistorter(rgba, lenses[i], mode="color")
+        out, valid = _host(out), _host(valid)
+        frames[i] = (out[..., :3], out[..., 3], H, W)
+        if not (masks[i] == 255).all():
+            masks[i] = _host(undistorter(masks[i], lenses[i], mode="mask")[0])
+        masks[i] = np.minimum(masks[i], valid)
+        if depths is not None:
+            depths[i] = _host(undistorter(depths[i], lenses[i], mode="depth")[0])
+    return frames, masks, depths
+
+
 # ---- COLMAP (ColmapDataLoader.swift:165-500) ---------------------------------------------------------------------
-ColmapCamera = namedtuple("ColmapCamera", "id width height fx fy cx cy k1 k2 p1 p2")
+ColmapCamera = namedtuple("ColmapCamera", "id width height fx fy cx cy k1 k2 p1 p2 model", defaults=(None,))
 ImageWithPose = namedtuple("ImageWithPose", "filePath pose cameraId")
+
+# COLMAP's own camera models (src/colmap/sensor/models.h): id -> (name, number of doubles in cameras.bin)
+COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
+                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
+                 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+# the models lens.LensModel inverts (k1, k2, p1, p2); the others load as pinholes and raise under undistort=True
+UNDISTORTABLE = {"SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", None}
+
+
+def _colmapCamera(camId, model, width, height, p):
+    """A COLMAP model's parameters (its own table) as a ColmapCamera: models 0-4 fill it; 5-10 keep their focal lengths and
+    principal point (single-focal models: f, cx, cy) and no coefficients."""
+    name = COLMAP_MODELS[model][0]
+    k1 = k2 = p1 = p2 = None
+    if name in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE"):
+        fx, cx, cy = p[:3]; fy = fx
+        if name == "SIMPLE_RADIAL":
+            k1 = p[3]
+        elif name == "RADIAL":
+            k1, k2 = p[3:5]
+    else:
+        fx, fy, cx, cy = p[:4]
+        if name == "OPENCV":
+            k1, k2, p1, p2 = p[4:8]
+    return ColmapCamera(camId, width, height, fx, fy, cx, cy, k1, k2, p1, p2, name)
 
 
 def quatToRotMat(q):
@@ -129,10 +195,14 @@ def _intrinsics3(fx, fy, cx, cy):
     return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32)
 
 
-def colmapReadCamerasAndPoses(binRoot, imageRoot):
+def colmapReadCamerasAndPoses(binRoot, imageRoot, cameraModels: str = "reference"):
     """cameras.bin + images.bin -> ({camera id: ColmapCamera}, [ImageWithPose]); pose = camera-to-world
-    [R^T | -R^T t] of the stored world-to-camera (qvec, tvec) (:258-296).  Unknown camera models parse as PINHOLE
-    (:199)."""
+    [R^T | -R^T t] of the stored world-to-camera (qvec, tvec) (:258-296).  cameraModels="reference" is the reference app's
+    model table (id 3 is OPENCV with 8 doubles, unknown models parse as PINHOLE, :199); "colmap" is COLMAP's own
+    (COLMAP_MODELS: id 3 is RADIAL with 5 doubles, id 4 OPENCV with 8), every model read with its own count so that the file
+    stays in step, and an unknown id raises."""
+    if cameraModels not in ("reference", "colmap"):
+        raise ValueError('cameraModels is "reference" or "colmap"')
     cam_path, img_path = os.path.join(binRoot, "cameras.bin"), os.path.join(binRoot, "images.bin")
     if not (os.path.exists(cam_path) and os.path.exists(img_path)):
         raise FileNotFoundError("Colmap files missing")
@@ -143,16 +213,22 @@ def colmapReadCamerasAndPoses(binRoot, imageRoot):
         for _ in range(n):
             camId, model = rd("Ii")
             width, height = rd("QQ")
+            if cameraModels == "colmap":
+                if model not in COLMAP_MODELS:
+                    raise ValueError(f"cameras.bin: camera {camId} has the unknown model id {model}")
+                camMap[camId] = _colmapCamera(camId, model, width, height, rd("d" * COLMAP_MODELS[model][1]))
+                continue
             k1 = k2 = p1 = p2 = None
+            name = "PINHOLE"
             if model == 0:                      # SIMPLE_PINHOLE
-                fx, cx, cy = rd("ddd"); fy = fx
+                fx, cx, cy = rd("ddd"); fy = fx; name = "SIMPLE_PINHOLE"
             elif model == 2:                    # SIMPLE_RADIAL
-                fx, cx, cy, k1 = rd("dddd"); fy = fx
+                fx, cx, cy, k1 = rd("dddd"); fy = fx; name = "SIMPLE_RADIAL"
             elif model == 3:                    # OPENCV
-                fx, fy, cx, cy, k1, k2, p1, p2 = rd("dddddddd")
+                fx, fy, cx, cy, k1, k2, p1, p2 = rd("dddddddd"); name = "OPENCV"
             else:                               # PINHOLE, and anything unknown
                 fx, fy, cx, cy = rd("dddd")
-            camMap[camId] = ColmapCamera(camId, width, height, fx, fy, cx, cy, k1, k2, p1, p2)
+            camMap[camId] = ColmapCamera(camId, width, height, fx, fy, cx, cy, k1, k2, p1, p2, name)
     poses = []
     with open(img_path, "rb") as f:
         rd = lambda fmt: struct.unpack("<" + fmt, f.read(struct.calcsize("<" + fmt)))
@@ -191,8 +267,17 @@ def colmapReadPointSet(points3DPath):
 
 
 class ColmapDataLoader:
-    def __init__(self, binRoot, imageRoot, maskRoot=None, depthRoot=None, depthParams=None):
-        """maskRoot: a directory of per-view loss masks (TrainData.maskArray).  A view's mask is <maskRoot>/<image file
+    def __init__(self, binRoot, imageRoot, maskRoot=None, depthRoot=None, depthParams=None, cameraModels: str = "reference",
+                 undistort: bool = False):
+        """cameraModels: "reference" reads cameras.bin with the reference app's model table, "colmap" with COLMAP's own
+        (colmapReadCamerasAndPoses); a real COLMAP reconstruction needs "colmap".
+
+        undistort: resample every view whose camera has a non-zero lens coefficient (k1, k2, p1, p2) into its pinhole camera at
+        load time (_undistort_views; the principal point is kept, camera.cameras_from_train_data renders it) and fold the
+        validity of the resampling into TrainData.maskArray, so that the border the lens leaves empty is ignored by the loss.
+        A camera model the lens module does not invert (fisheye, FULL_OPENCV, FOV) raises a ValueError in load().
+
+        maskRoot: a directory of per-view loss masks (TrainData.maskArray).  A view's mask is <maskRoot>/<image file
         name>.png (COLMAP's own convention: "frame.jpg.png") or, failing that, <maskRoot>/<image file name without its
         extension>.png; a view with neither keeps every pixel.
 
@@ -202,6 +287,9 @@ class ColmapDataLoader:
         or a path to it): a view's "scale" and "offset" go to TrainData.depthAlign, (1, 0) for a view without an entry."""
         self.binRoot, self.imageRoot, self.maskRoot = binRoot, imageRoot, maskRoot
         self.depthRoot, self.depthParams = depthRoot, readDepthParams(depthParams)
+        self.cameraModels, self.undistort = cameraModels, bool(undistort)
+        if cameraModels not in ("reference", "colmap"):
+            raise ValueError('cameraModels is "reference" or "colmap"')
         if depthRoot is None and depthParams is not None:
             raise ValueError("depthParams go with a depthRoot")
 
@@ -227,23 +315,37 @@ class ColmapDataLoader:
         return None
 
     def getOriginalImageSize(self):
-        camMap, poses = colmapReadCamerasAndPoses(self.binRoot, self.imageRoot)
+        camMap, poses = colmapReadCamerasAndPoses(self.binRoot, self.imageRoot, self.cameraModels)
         cam = camMap[poses[0].cameraId]
         return int(cam.width), int(cam.height)
 
-    def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA):
-        """loadTrainDataAndPointCloud (:441-500) -> (TrainData, PointCloud, TILE_SIZE_H_W)."""
-        camMap, poses = colmapReadCamerasAndPoses(self.binRoot, self.imageRoot)
+    def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA, undistorter=None):
+        """loadTrainDataAndPointCloud (:441-500) -> (TrainData, PointCloud, TILE_SIZE_H_W).  undistorter: what resamples a view
+        under undistort=True (_undistort_views): None is lens.undistort_image on the host, a GaussianRenderer's undistortImage
+        is the kernel."""
+        camMap, poses = colmapReadCamerasAndPoses(self.binRoot, self.imageRoot, self.cameraModels)
         intr = np.stack([_intrinsics3(*(camMap[p.cameraId][3:7])) for p in poses])
         if resizeFactor != 1.0:
             intr[:, :2, :3] *= np.float32(resizeFactor)
         c2ws = np.stack([p.pose.astype(np.float32) for p in poses])
-        Hs, Ws, rgbs, alphas = _stack_frames([readImage(p.filePath, resizeFactor) for p in poses], whiteBackground)
+        frames = [readImage(p.filePath, resizeFactor) for p in poses]
+        Hs, Ws = [f[2] for f in frames], [f[3] for f in frames]
+        masks = None if self.maskRoot is None else _stack_masks([self._maskPath(p.filePath) for p in poses], Hs, Ws, resizeFactor)
+        depths, align = (None, None) if self.depthRoot is None else self._depths(poses, Hs, Ws, resizeFactor)
+        if self.undistort:
+            from .lens import LensModel
+            lenses = []
+            for p, K in zip(poses, intr):
+                cam = camMap[p.cameraId]
+                if cam.model not in UNDISTORTABLE:
+                    raise ValueError(f"undistort=True: camera {cam.id} has the model {cam.model}, which is not inverted here "
+                                     "(SIMPLE_RADIAL, RADIAL and OPENCV are)")
+                lenses.append(LensModel(K[0, 0], K[1, 1], K[0, 2], K[1, 2], cam.k1, cam.k2, cam.p1, cam.p2))
+            frames, masks, depths = _undistort_views(lenses, frames, masks, depths, undistorter)
+        Hs, Ws, rgbs, alphas = _stack_frames(frames, whiteBackground)
         pts, cols = colmapReadPointSet(os.path.join(self.binRoot, "points3D.bin"))
         ch = cols.astype(np.float32) / np.float32(255.0)
         pcd = PointCloud(pts.astype(np.float32), dict(R=ch[:, 0], G=ch[:, 1], B=ch[:, 2]))
-        masks = None if self.maskRoot is None else _stack_masks([self._maskPath(p.filePath) for p in poses], Hs, Ws, resizeFactor)
-        depths, align = (None, None) if self.depthRoot is None else self._depths(poses, Hs, Ws, resizeFactor)
         return (TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, depths, masks, align), pcd,
                 TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
 
@@ -285,12 +387,15 @@ def parsePLY(path):
 
 
 class NerfStudioDataLoader:
-    def __init__(self, directory):
-        self.directory = directory
+    def __init__(self, directory, undistort: bool = False):
+        """undistort: as ColmapDataLoader's, from the frame's k1, k2, p1, p2 or, when the frame has none of them, the file
+        header's; a "camera_model" other than OPENCV or PINHOLE (or none) raises a ValueError in load()."""
+        self.directory, self.undistort = directory, bool(undistort)
 
-    def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA):
+    def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA, undistorter=None):
         """loadTrainDataAndPointCloud (:385-416): transforms.json + its ply_file_path.  A frame's "mask_path" (relative to the
-        dataset directory, as nerfstudio writes it) is its loss mask (TrainData.maskArray)."""
+        dataset directory, as nerfstudio writes it) is its loss mask (TrainData.maskArray).  undistorter: as
+        ColmapDataLoader.load's."""
         meta = json.load(open(os.path.join(self.directory, "transforms.json")))
         xyz, rgb = parsePLY(os.path.join(self.directory, meta["ply_file_path"]))
         ch = rgb.astype(np.float32) / np.float32(255.0)
@@ -298,8 +403,15 @@ class NerfStudioDataLoader:
 
         def intrinsic(d):
             return _intrinsics3(d["fl_x"], d["fl_y"], d["cx"], d["cy"]) if all(k in d for k in ("fl_x", "fl_y", "cx", "cy")) else None
-        intr, c2ws, frames, maskPaths = [], [], [], []
+        COEFFS = ("k1", "k2", "p1", "p2")
+        intr, c2ws, frames, maskPaths, coeffs = [], [], [], [], []
         for fr in meta["frames"]:
+            if self.undistort:
+                model = fr.get("camera_model", meta.get("camera_model"))
+                if model not in (None, "OPENCV", "PINHOLE"):
+                    raise ValueError(f'undistort=True: camera_model "{model}" is not inverted here (OPENCV and PINHOLE are)')
+                src = fr if any(k in fr for k in COEFFS) else meta
+                coeffs.append([float(src.get(k, 0.0)) for k in COEFFS])
             maskPaths.append(os.path.join(self.directory, fr["mask_path"]) if fr.get("mask_path") else None)
             K = intrinsic(fr)
             K = intrinsic(meta) if K is None else K
@@ -311,9 +423,13 @@ class NerfStudioDataLoader:
             frames.append(readImage(os.path.join(self.directory, fr["file_path"]), resizeFactor))
             # the reference reads transform_matrix as Float before widening (:359)
             c2ws.append(opengl_c2w_to_opencv(np.asarray(fr["transform_matrix"], np.float32).astype(np.float64)).astype(np.float32))
+        masks = _stack_masks(maskPaths, [f[2] for f in frames], [f[3] for f in frames], resizeFactor)
+        if self.undistort:
+            from .lens import LensModel
+            lenses = [LensModel(K[0, 0], K[1, 1], K[0, 2], K[1, 2], *c) for K, c in zip(intr, coeffs)]
+            frames, masks, _ = _undistort_views(lenses, frames, masks, None, undistorter)
         Hs, Ws, rgbs, alphas = _stack_frames(frames, whiteBackground)
-        return (TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None,
-                          _stack_masks(maskPaths, Hs, Ws, resizeFactor)), pcd,
+        return (TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None, masks), pcd,
                 TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
 
 

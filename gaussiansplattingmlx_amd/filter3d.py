@@ -1,7 +1,8 @@
 """The 3-D smoothing filter in float64 (include/gsplat.h gs_set_filter3d): Mip-Splatting's second filter.
 
     width        f_i = sqrt(0.2) min over the cameras n that SEE x_i of z / focal_x,n,   p = [x_i, 1] . view_n, z = p.z,
-                 seen iff z >= 0.2, |p.x / z| <= 1.3 tan(fov_x / 2), |p.y / z| <= 1.3 tan(fov_y / 2);
+                 seen iff z >= 0.2, |p.x / z + ox| <= 1.3 tan(fov_x / 2), |p.y / z + oy| <= 1.3 tan(fov_y / 2), with
+                 (ox, oy) = (proj[8] / proj[0], proj[9] / proj[5]) the camera's off-centre principal point (0 when centred);
                  a Gaussian no camera sees gets the largest f among the seen ones; nothing seen: all 0
     activations  s_eff = sqrt(s^2 + f^2),  kappa = prod_a s_a / s_eff_a,  opacity = sigma kappa (rho)
     VJP          dL/dscales_raw_a = g_a s_a^2 / s_eff_a + c sigma rho kappa f^2 / s_eff_a^2,  dL/dopacity_raw = c kappa rho sigma (1 - sigma)
@@ -26,25 +27,45 @@ def _cam(c):
     return np.asarray(c.worldViewTransform, np.float64).reshape(4, 4), float(c.FoVx), float(c.FoVy), float(c.focalX)
 
 
-def camera_terms(xyz, cam):
-    """One camera's share per point: (seen [N] bool, T = z / focal_x [N], p [N, 3] the view-space point, (limX, limY))."""
+def _offsets(c, fold: bool = True):
+    """(ox, oy) = (proj[8] / proj[0], proj[9] / proj[5]) of a Camera or of a Camera.as_dict(): the off-centre principal point in
+    units of x / z.  (0, 0) for a centred camera, for one without a projection matrix, and with
+    fold=False (the table gs_set_filter3d_cameras builds for a centred camera)."""
+    P = c.get("proj") if isinstance(c, dict) else getattr(c, "projectionMatrix", None)
+    if P is None or not fold:
+        return 0.0, 0.0
+    P = np.asarray(P, np.float64).reshape(16)
+    return (float(P[8] / P[0]) if P[8] != 0.0 and P[0] != 0.0 else 0.0,
+            float(P[9] / P[5]) if P[9] != 0.0 and P[5] != 0.0 else 0.0)
+
+
+def camera_terms(xyz, cam, fold: bool = True):
+    """One camera's share per point: (seen [N] bool, T = z / focal_x [N], p [N, 3] the view-space point, (limX, limY)).  For an
+    off-centre camera p.x and p.y carry the offset, p.x + ox z and p.y + oy z (the fold of gs_set_filter3d_cameras), so that
+    seen is |p.x / z| <= limX, |p.y / z| <= limY for every camera; fold=False ignores the offset."""
     view, fx, fy, focal = _cam(cam)
+    ox, oy = _offsets(cam, fold)
     x = np.asarray(xyz, np.float64).reshape(-1, 3)
     p = x @ view[:3, :3] + view[3, :3]
     z = p[:, 2]
+    if ox != 0.0:
+        p[:, 0] += ox * z
+    if oy != 0.0:
+        p[:, 1] += oy * z
     lim = (MARGIN * np.tan(fx / 2.0), MARGIN * np.tan(fy / 2.0))
     with np.errstate(divide="ignore", invalid="ignore"):
         seen = (z >= Z_NEAR) & (np.abs(p[:, 0] / z) <= lim[0]) & (np.abs(p[:, 1] / z) <= lim[1])
     return seen, z / focal, p, lim
 
 
-def filter_width(xyz, cameras, details: bool = False):
-    """f [N] float64.  details=True: also (seen_any [N], argmin camera [N] (-1 where unseen))."""
+def filter_width(xyz, cameras, details: bool = False, fold: bool = True):
+    """f [N] float64.  details=True: also (seen_any [N], argmin camera [N] (-1 where unseen)).  fold=False: the cameras'
+    principal points are ignored (every frustum centred)."""
     x = np.asarray(xyz, np.float64).reshape(-1, 3)
     best = np.full(x.shape[0], np.inf)
     arg = np.full(x.shape[0], -1, np.int64)
     for n, c in enumerate(cameras):
-        seen, T, _, _ = camera_terms(x, c)
+        seen, T, _, _ = camera_terms(x, c, fold)
         take = seen & (T < best)
         best[take] = T[take]
         arg[take] = n

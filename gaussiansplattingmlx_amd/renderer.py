@@ -572,6 +572,35 @@ class GaussianRenderer:
         self._check(self.lib.gs_apply_exposure(self.ctx, img.numel() // 3, _p(M), _p(img), _p(out)))
         return out
 
+    def undistortImage(self, img, lens, dstK=None, dstSize=None, mode: str = "color", wantValid: bool = True):
+        """gs_undistort: (out, valid) device tensors -- the image seen through `lens` (lens.LensModel) resampled into the pinhole
+        dstK = (fx, fy, cx, cy) of size dstSize = (W, H); None: the lens's own fx, fy, cx, cy and the source's size.  mode
+        "color": float32 [H, W, C], C in 1 .. 4 (or [H, W]); "mask": uint8 [H, W]; "depth": float32 [H, W], 0 = hole.  valid is
+        uint8 [H, W], 255 where the four taps lie in the source and the lens has not folded back (None with wantValid=False).
+        What lens.undistort_image states in float64; a loader's `undistorter` (data.py)."""
+        from . import lens as _lens
+        if mode not in _lens.MODES:
+            raise ValueError(f"undistortImage: mode is one of {sorted(_lens.MODES)}")
+        dtype = torch.uint8 if mode == "mask" else torch.float32
+        if not isinstance(img, torch.Tensor):
+            img = torch.from_numpy(np.ascontiguousarray(img))
+        if mode == "mask" and img.dtype != torch.uint8:
+            raise ValueError("undistortImage: a mask is uint8 [H, W]")
+        src = img.to(device=self.device, dtype=dtype).contiguous()
+        if src.dim() not in (2, 3) or (src.dim() == 3 and (mode != "color" or not 1 <= src.shape[2] <= 4)):
+            raise ValueError("undistortImage: a colour image is [H, W, C] with C in 1 .. 4, a mask or a depth [H, W]")
+        srcH, srcW = int(src.shape[0]), int(src.shape[1])
+        chans = int(src.shape[2]) if src.dim() == 3 else 1
+        nfx, nfy, ncx, ncy = (float(v) for v in (lens.K if dstK is None else dstK))
+        W, H = (srcW, srcH) if dstSize is None else (int(dstSize[0]), int(dstSize[1]))
+        if W < 1 or H < 1:
+            raise ValueError("undistortImage: dstSize = (width, height), both positive")
+        L = _lib.gs_lens(*lens.K, *lens.coefficients, nfx, nfy, ncx, ncy)
+        out = torch.empty((H, W) + tuple(src.shape[2:]), dtype=dtype, device=self.device)
+        valid = torch.empty((H, W), dtype=torch.uint8, device=self.device) if wantValid else None
+        self._check(self.lib.gs_undistort(self.ctx, C.byref(L), srcW, srcH, W, H, chans, _lens.MODES[mode], _p(src), _p(out), _p(valid)))
+        return out, valid
+
     @staticmethod
     def _grid_shape(shape, what):
         try:

@@ -444,8 +444,12 @@ int gs_get_visibility(gs_ctx* ctx, int N, unsigned char* out /* DEVICE [N] */);
  *     f is not differentiated.  A backward uses the filter pointer its forward ran with; keep the array unchanged between
  *     the two, as the parameter tensors.
  *
- * gs_set_filter3d_cameras: the training cameras gs_compute_filter3d measures against, V >= 0 HOST structs (view, fov_x, fov_y
- * and focal_x are read), copied into a table the context owns.  The table is allocated or grown here only; V = 0 frees it.
+ * gs_set_filter3d_cameras: the training cameras gs_compute_filter3d measures against, V >= 0 HOST structs (view, fov_x, fov_y,
+ * focal_x and proj[0], proj[5], proj[8], proj[9] are read), copied into a table the context owns.  The table is allocated or
+ * grown here only; V = 0 frees it.  A camera with an off-centre principal point (proj[8] or proj[9] non-zero, DESIGN.md
+ * section 23) is SEEN-tested against its own frustum with the same margin: |p.x / z + ox| <= 1.3 tan(fov_x / 2) with
+ * ox = proj[8] / proj[0], and |p.y / z + oy| likewise with oy = proj[9] / proj[5]; the offset is folded into the table's
+ * row (view column 0 gains ox times column 2, column 1 gains oy times column 2), and a zero offset leaves the row's bits.
  * [sync] */
 int gs_set_filter3d_cameras(gs_ctx* ctx, int V, const gs_camera* cams /*HOST [V]*/);
 /* filter[i] = f_i of xyz[i] against the cameras set above (GS_ERR_INVALID_ARG without any).  Asynchronous on the context's
@@ -465,6 +469,29 @@ int gs_set_filter3d(gs_ctx* ctx, const float* filter /*DEVICE [>= N] or NULL*/);
  * `filter`).  Asynchronous on the context's stream. */
 int gs_filter3d_bake(gs_ctx* ctx, int N, const float* scales_raw /*[N,3]*/, const float* opacity_raw /*[N]*/,
                      const float* filter /*[N]*/, float* out_scales_raw /*[N,3]*/, float* out_opacity_raw /*[N]*/);
+
+/* Lens undistortion (not in the reference; lens.py restates it in float64): resamples a view taken
+ * through OpenCV's / COLMAP's radial-tangential lens (fx, fy, cx, cy, k1, k2, p1, p2) into the pinhole camera (dst_fx, dst_fy,
+ * dst_cx, dst_cy), once per view when a dataset is loaded.  Pixel i covers [i, i + 1): its centre is at i + 0.5 (COLMAP's and
+ * nerfstudio's convention).  For destination pixel (i, j), in float32 and in this order of operations (no contraction):
+ *   x = ((i + 0.5) - dst_cx) / dst_fx,  y = ((j + 0.5) - dst_cy) / dst_fy,  r2 = x x + y y,  r4 = r2 r2,
+ *   radial = (1 + k1 r2) + k2 r4,
+ *   xd = (x radial + (2 p1) (x y)) + p2 (r2 + 2 (x x)),  yd = (y radial + p1 (r2 + 2 (y y))) + (2 p2) (x y),
+ *   su = (fx xd + cx) - 0.5,  sv = (fy yd + cy) - 0.5,  x0 = floor(su), y0 = floor(sv), a = su - x0, b = sv - y0.
+ * The pixel is VALID iff the four taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) lie inside the source and the
+ * radial map has not folded back, (1 + (3 k1) r2) + (5 k2) r4 > 0.  An invalid pixel gets 0 in every channel and valid 0; a
+ * valid one gets valid 255 and, from its taps t00, t10 (x0 + 1), t01 (y0 + 1), t11:
+ *   mode 0  colour, float32 [src_h, src_w, channels] interleaved, channels in 1 .. 4:
+ *           (t00 (1 - a) + t10 a) (1 - b) + (t01 (1 - a) + t11 a) b per channel;
+ *   mode 1  mask, uint8, channels = 1: the same blend of the levels, then floor(v + 0.5);
+ *   mode 2  depth, float32, channels = 1, 0 = hole: sum w_i d_i / sum w_i over the taps with d_i > 0, w00 = (1 - a) (1 - b),
+ *           w10 = a (1 - b), w01 = (1 - a) b, w11 = a b, summed in that order; 0 when the weights' sum is 0.
+ * Independent of the context's W, H; src and dst do not alias; valid may be NULL.  channels outside 1 .. 4, mask or depth with
+ * channels != 1, non-positive or non-finite focal lengths, non-finite coefficients, non-positive sizes or a destination of
+ * more than 262140 rows return GS_ERR_INVALID_ARG.  Asynchronous on the context's stream, allocates nothing. */
+typedef struct gs_lens { float fx, fy, cx, cy, k1, k2, p1, p2; float dst_fx, dst_fy, dst_cx, dst_cy; } gs_lens;
+int gs_undistort(gs_ctx* ctx, const gs_lens* lens /*HOST*/, int src_w, int src_h, int dst_w, int dst_h, int channels,
+                 int mode, const void* src /*DEVICE*/, void* dst /*DEVICE*/, unsigned char* valid /*DEVICE [dst_h,dst_w] or NULL*/);
 
 /* MCMC densification strategy (not in the reference; DESIGN.md "MCMC strategy"): "3D Gaussian Splatting as Markov Chain Monte
  * Carlo" (Kheradmand et al. 2024), gsplat's MCMCStrategy, with its defaults in brackets.  Notation: o = sigmoid(opacity_raw),
