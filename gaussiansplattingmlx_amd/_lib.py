@@ -140,6 +140,8 @@ _SIGS = {
     "gs_loss_forward_backward": (C.c_int, [_vp] + [_vp] * 5 + [C.c_float, C.c_float] + [_vp] * 3),
     "gs_depth_loss": (C.c_int, [_vp, C.POINTER(gs_depth_loss_params)] + [_vp] * 7),
     "gs_depth_normalize": (C.c_int, [_vp, C.c_longlong, _vp, _vp, C.c_float, _vp]),
+    "gs_image_metrics": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 4),
+    "gs_colour_moments": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4),
     "gs_adam_step": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4 + [C.c_int, _vp, _vp] + [C.c_float] * 4),
     "gs_profile_enable": (C.c_int, [_vp, C.c_uint]),
     "gs_profile_read": (C.c_int, [_vp, _vp, _vp]),

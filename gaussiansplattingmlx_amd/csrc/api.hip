@@ -538,7 +538,7 @@ int gs_ctx_destroy(gs_ctx* c)
     free_pair_ws(c);
     dev_free(c->segState);
     dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk); dev_free(c->wideTotal); dev_free(c->rowTotal); dev_free(c->sortBits); dev_free(c->bucketStart); dev_free(c->ssChunk); dev_free(c->sortSplit[0]); dev_free(c->sortSplit[1]); dev_free(c->tileRanges); dev_free(c->tileCounts); dev_free(c->superCut);
-    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->windowDev);
+    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->metricsWs); dev_free(c->windowDev);
     dev_free(c->counters); dev_free(c->blockWorkOwn); dev_free(c->blockOrder); dev_free(c->fwdQueue); dev_free(c->bwdQueue); dev_free(c->segBase); dev_free(c->finalT);
     for (auto& e : c->profPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (c->countersHost) (void)hipHostFree(c->countersHost);
@@ -1571,6 +1571,47 @@ int gs_depth_normalize(gs_ctx* c, long long n_pixels, const float* depth, const 
     if (!(alpha_min >= 0.0f) || !isfinite(alpha_min)) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: alpha_min is finite and >= 0");
     if (!depth || !alpha || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: null pointer");
     return launch_depth_normalize(c, n_pixels, depth, alpha, alpha_min, out);
+}
+
+// ---- held-out evaluation (include/gsplat.h gs_image_metrics / gs_colour_moments; metrics.hip) ------------------------------
+namespace {
+// the partials of both entry points: allocated at the first call, regrown only when a larger image needs more
+int ensure_metrics_ws(gs_ctx* c, int H, int W)
+{
+    const long long want = metrics_ws_doubles(H, W);
+    if (want <= c->metricsWsDoubles) return GS_OK;
+    GS_HIP_CHECK(c, hipSetDevice(c->device));
+    if (c->metricsWs) {
+        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a queued call still sums the old buffer)
+        c->ws_bytes -= (size_t)c->metricsWsDoubles * sizeof(double);
+        dev_free(c->metricsWs);
+    }
+    c->metricsWsDoubles = 0;
+    if (const int rc = dev_alloc(c, &c->metricsWs, (size_t)want)) return rc;
+    c->metricsWsDoubles = want;
+    return GS_OK;
+}
+}  // namespace
+
+int gs_image_metrics(gs_ctx* c, int H, int W, const float* render, const float* target, const unsigned char* mask, double* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (H < 0 || W < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_image_metrics: negative H or W");
+    if (!render || !target || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_image_metrics: null render, target or out");
+    if (H > 0 && W > 0)
+        if (const int rc = ensure_metrics_ws(c, H, W)) return rc;
+    return launch_image_metrics(c, H, W, render, target, mask, out);
+}
+
+int gs_colour_moments(gs_ctx* c, long long n_pixels, const float* render, const float* target, const unsigned char* mask,
+                      double* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_colour_moments: negative n_pixels");
+    if (!render || !target || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_colour_moments: null render, target or out");
+    if (n_pixels > 0)
+        if (const int rc = ensure_metrics_ws(c, 1, 1)) return rc;      // (its 512 x 22 partials are the workspace's least size)
+    return launch_colour_moments(c, n_pixels, render, target, mask, out);
 }
 
 int gs_loss_target_cache_floats(gs_ctx* c, long long* n)

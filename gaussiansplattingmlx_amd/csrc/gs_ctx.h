@@ -330,6 +330,8 @@ struct gs_ctx {
     const unsigned char* lossMask = nullptr;   // gs_set_loss_mask: caller-owned [H][W] per-pixel loss weights v / 255, nullptr = off
     int lossPartialBlocks = 0;
     double* depthLossWs = nullptr;    // gs_depth_loss: [depth_loss_ws_doubles()] per-block (sum, count) partials + n, allocated at the first call
+    double* metricsWs = nullptr;      // gs_image_metrics / gs_colour_moments: [metricsWsDoubles] per-block partials, allocated at the
+    long long metricsWsDoubles = 0;   //   first call, regrown only for a larger image (metrics.hip metrics_ws_doubles)
     float* windowDev = nullptr;       // [121] default SSIM window
     // densify scan scratch: [densifyTileCap] tile sums + 8 counters, grown on demand
     int* densifyTiles = nullptr;
@@ -479,6 +481,9 @@ int launch_depth_loss(gs_ctx* c, int mode, float lambda, float alphaMin, float s
                       const float* alpha, const float* target, const unsigned char* mask, float* loss, float* cotDepth,
                       float* cotAlpha);
 int launch_depth_normalize(gs_ctx* c, long long n, const float* depth, const float* alpha, float alphaMin, float* out);
+long long metrics_ws_doubles(int H, int W);      // metrics.hip
+int launch_image_metrics(gs_ctx* c, int H, int W, const float* render, const float* target, const unsigned char* mask, double* out);
+int launch_colour_moments(gs_ctx* c, long long n, const float* render, const float* target, const unsigned char* mask, double* out);
 // filter3d.hip: the camera table's row is view[0..3][0], view[0..3][1], view[0..3][2], limX, limY, focalX, 0
 int launch_filter3d_width(gs_ctx* c, int N, const float* xyz, float* filter);
 int launch_filter3d_bake(gs_ctx* c, int N, const float* scalesRaw, const float* opacityRaw, const float* filter, float* outScales,

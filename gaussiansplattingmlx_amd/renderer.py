@@ -1212,6 +1212,45 @@ class GaussianRenderer:
         self._check(self.lib.gs_depth_normalize(self.ctx, d.numel(), _p(d), _p(a), C.c_float(alpha_min), _p(out)))
         return out
 
+    # -- held-out evaluation (include/gsplat.h gs_image_metrics / gs_colour_moments; evaluation.py) ------
+    def _metric_mask(self, who, mask, H, W):
+        """A uint8 or bool [H, W] mask, tensor or array, as the contiguous uint8 device tensor the kernels read (itself if it is one)."""
+        loss_mask.validate(mask, H, W, who)
+        if not torch.is_tensor(mask):
+            mask = torch.from_numpy(np.ascontiguousarray(loss_mask.as_uint8(mask)))
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8) * 255
+        return mask.to(self.device).contiguous()
+
+    def _metric_args(self, who, render, target, mask, out, n_out):
+        render, target = self._t(render), self._t(target)
+        if render.dim() != 3 or render.shape[-1] != 3 or render.shape != target.shape:
+            raise ValueError(f"{who}: render and target are [H, W, 3] images of one size")
+        H, W = int(render.shape[0]), int(render.shape[1])
+        if mask is not None:
+            mask = self._metric_mask(who, mask, H, W)
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device or out.numel() != n_out:
+            raise ValueError(f"{who}: out is a contiguous float64 device tensor of {n_out} elements")
+        return render, target, mask, out, H, W
+
+    def imageMetrics(self, render, target, mask=None, out=None):
+        """gs_image_metrics: {sse, ssim_sum, wsum, 3 wsum} of a render against its target, both [H, W, 3] of any one size and
+        clamped to [0, 1] by the kernel -- a device float64 tensor [4] (evaluation.metrics_from_sums turns it into PSNR and
+        SSIM).  mask: uint8 (weight v / 255) or bool [H, W], tensor or array, or None.  out: a float64 device tensor of 4
+        elements to write into (a row of a [V, 4] buffer).  Does not wait."""
+        render, target, mask, out, H, W = self._metric_args("imageMetrics", render, target, mask, out, 4)
+        self._check(self.lib.gs_image_metrics(self.ctx, H, W, _p(render), _p(target), _p(mask), _p(out)))
+        return out
+
+    def colourMoments(self, render, target, mask=None, out=None):
+        """gs_colour_moments: the 22 moment sums of the affine colour fit of render onto target (evaluation.fit_affine_colour
+        solves them for M) -- a device float64 tensor [22].  Arguments as imageMetrics'.  Does not wait."""
+        render, target, mask, out, H, W = self._metric_args("colourMoments", render, target, mask, out, 22)
+        self._check(self.lib.gs_colour_moments(self.ctx, H * W, _p(render), _p(target), _p(mask), _p(out)))
+        return out
+
     def invalidateTarget(self, targetKey=None):
         """Forget the cached SSIM statistics of one target key (None: of all): its next loss recomputes them."""
         if targetKey is None:

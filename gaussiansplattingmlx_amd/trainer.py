@@ -1247,6 +1247,101 @@ class GaussianTrainer:
             self._updateFilter3D()
         return st
 
+    def evaluate(self, cameras, targets, masks=None, targetAlphas=None, color_correct=None, viewKeys=None):
+        """PSNR and SSIM of the current model over `cameras` against `targets` ([H, W, 3] each, the context's size): an
+        evaluation.EvalResult.  Every view is rendered as a step renders it -- the 3-D filter set, the
+        renderer's anti-aliasing mode as it is -- with renderChecked, and measured by gs_image_metrics: the sums of all views go
+        to one [V, 4] device buffer that is read once at the end.
+
+        viewKeys=None: held-out views.  No learnt pose and no per-view correction is applied, and the forwards are not keyed: a
+        test view shares no depth cuts or hints with a training view.  viewKeys (one per camera): training views, rendered
+        under their refined pose and measured under their trained exposure or grid (exposedRender / bilateralRender).
+        masks: per view a uint8 (weight v / 255) or bool [H, W] image or None; pixels weigh in as in the masked training loss.
+        color_correct: also cc_psnr / cc_ssim, the metrics after the least-squares affine colour transform of the (corrected)
+        render onto the target; costs one read-back per view (the fit is on the host).  None: on exactly when the trainer
+        trains an exposure or a bilateral grid.  targetAlphas: with a trainer built with background= (and only then) the views'
+        alphas; render and target are composited over the config's fixed colour, black in the random mode.
+
+        Trains nothing: the iteration counter, the arena, the densify accumulators and the loss's target caches are not
+        touched, and the renderer's filter, background, pose binding and tuning knobs are put back whatever happens.
+        Single-device trainers only."""
+        from .evaluation import EvalResult, fit_affine_colour
+        r, m = self.gaussRender, self.model
+        if self._dp:
+            raise ValueError("evaluate: single-device trainers only (no process group, dp_bootstrap, native exchange or views_per_rank > 1)")
+        cams, tgts = list(cameras), list(targets)
+        V = len(cams)
+        per_view = dict(targets=tgts, masks=masks, targetAlphas=targetAlphas, viewKeys=viewKeys)
+        for name, seq in per_view.items():
+            if seq is not None and len(seq) != V:
+                raise ValueError(f"evaluate: {name} has one entry per camera")
+        if (targetAlphas is None) != (self.background is None):
+            raise ValueError("evaluate: targetAlphas goes with a trainer built with background=BackgroundConfig(...)"
+                             if self.background is None else
+                             "evaluate: a trainer built with background= needs targetAlphas (the views' alphas, [H, W])")
+        for t in tgts:
+            if tuple(t.shape) != (r.H, r.W, 3):
+                raise ValueError(f"evaluate: every target is [H, W, 3] = [{r.H}, {r.W}, 3], not {tuple(t.shape)}")
+        cc = bool(self.exposure_opt or self.bilateral_grid) if color_correct is None else bool(color_correct)
+        pose = self._perView.get("pose_opt")
+        rows = None
+        if viewKeys is not None and self._perView:
+            rows = [next(iter(self._perView.values())).row(k) for k in viewKeys]
+        bg = None
+        if self.background is not None:
+            bg = self.background.color_at(0) if self.background.mode == "fixed" else np.zeros(3, np.float32)
+        sums = torch.zeros((V, 4), dtype=torch.float64, device=r.device)
+        ccSums = torch.zeros((V, 4), dtype=torch.float64, device=r.device) if cc else None
+        moments = torch.zeros(22, dtype=torch.float64, device=r.device) if cc else None
+
+        def views():
+            for i, cam in enumerate(cams):
+                if pose is not None:
+                    if rows is None:
+                        pose.unbind(r)
+                    else:
+                        pose.bindRow(r, rows[i])      # (a forward reads the correction; only a backward writes its gradient)
+                img = r.renderChecked(m.getParams(), cam, wantDepth=False).render
+                if rows is not None and self.exposure_opt:
+                    img = self.exposedRender(img, viewKeys[i])
+                elif rows is not None and self.bilateral_grid:
+                    img = self.bilateralRender(img, viewKeys[i])
+                tgt = r._t(tgts[i])           # (uploaded once for the view's two or three calls, as is its mask)
+                if bg is not None:
+                    tgt = r.compositeTarget(tgt, targetAlphas[i], bg)
+                mask = None if masks is None or masks[i] is None else r._metric_mask("evaluate", masks[i], r.H, r.W)
+                r.imageMetrics(img, tgt, mask, out=sums[i])
+                if cc:
+                    M = fit_affine_colour(r.colourMoments(img, tgt, mask, out=moments).cpu().numpy())
+                    # (the fit's p is the CLAMPED render: M is applied to that, and the metrics clamp M p again)
+                    r.imageMetrics(r.applyExposure(img.clamp(0.0, 1.0), M), tgt, mask, out=ccSums[i])
+
+        restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
+        filter_was, bg_was, pose_was = r.filter3D, getattr(r, "_background", None), getattr(r, "_pose", (None, None))
+        try:
+            if self.filter_3d:
+                r.setFilter3D(self._filter)
+            if bg is not None:
+                r.setBackground(bg)
+            for attempt in range(4):
+                try:
+                    views()
+                    r.sync()
+                    break
+                except GsplatError as e:      # (a forward that overflowed the reserved pairs is blank: regrow, measure again)
+                    if e.code != GS_ERR_WORKSPACE_OVERFLOW or attempt == 3:
+                        raise
+                    self._recover_overflow()
+            return EvalResult.from_sums(sums.cpu().numpy(), None if ccSums is None else ccSums.cpu().numpy())
+        finally:
+            r.setTuning(**restore)
+            if self.filter_3d:
+                r.setFilter3D(filter_was)
+            if bg is not None:
+                r.setBackground(bg_was)
+            if pose is not None:
+                r.setPoseCorrection(*pose_was)
+
     def checkReplicas(self, deferred: bool = False):
         """Every rank of a data-parallel job calls this at the same point (after every committed densify event): one
         fixed-size collective over (N, checksum, checksum of magnitudes) of the parameter arena; ReplicaMismatch on EVERY

@@ -809,6 +809,38 @@ int gs_depth_loss(gs_ctx* ctx, const gs_depth_loss_params* p /*HOST*/, const flo
 int gs_depth_normalize(gs_ctx* ctx, long long n_pixels, const float* depth /*DEVICE [n]*/, const float* alpha /*DEVICE [n]*/,
                        float alpha_min, float* out /*DEVICE [n]*/);
 
+/* Held-out evaluation (tests/metrics_numpy.py restates both calls): the sums behind the PSNR and the SSIM
+ * that 3DGS papers report, of a render against its target, in one pass and without a statistic map in device memory.  Both images
+ * are clamped to [0, 1] first, as Inria's render.py / metrics.py do; r and g below are the clamped render and target.  mask:
+ * uint8, pixel weight w = (float)v / 255.0f as gs_set_loss_mask's (255 is exactly 1, 0 exactly 0), NULL = every w is 1; it is
+ * this call's own argument, the ctx's loss mask is not read.
+ *   out[0] sse      = sum_pixels w sum_c (r_c - g_c)^2
+ *   out[1] ssim_sum = sum_{pixels, c} w ssim_map(w r, w g)
+ *   out[2] wsum     = sum_pixels w  (once per pixel)          out[3] = 3 wsum
+ *   psnr = -10 log10(out[0] / out[3])  (inf for identical images, nan where wsum = 0),  ssim = out[1] / out[3]
+ * ssim_map is Inria's loss_utils.ssim: an 11 x 11 Gaussian window of sigma 1.5 that is CENTRED (exp(-(i - 5)^2 / 2 sigma^2),
+ * normalised, outer product) -- not gs_ssim_window's, which is off-centre as the reference app's is --, taps outside the image
+ * count as zero, C1 = 1e-4, C2 = 9e-4; evaluated separably (rows, then columns, taps ascending) in float32.  With a mask the
+ * statistics are those of the weighted images, as in the masked training loss; without one ssim is Inria's plain mean.
+ * H, W are the call's own (any ctx measures any image size).  Asynchronous on the ctx stream; out is written by the device.
+ * The sums are double, reduced in a fixed order without float atomics: two calls on the same inputs give the same bits, and a
+ * mask of all 255 gives the bits of no mask.  The first call allocates the per-block partials (88 KB), a later one only when a
+ * larger image needs more (it then waits for the stream).  H or W == 0: no kernel, out = zeros.  GS_ERR_INVALID_ARG: a NULL
+ * render, target or out, H or W < 0.  No reference call site (the reference app has no evaluation). */
+int gs_image_metrics(gs_ctx* ctx, int H, int W, const float* render /*DEVICE [H,W,3]*/, const float* target /*DEVICE [H,W,3]*/,
+                     const unsigned char* mask /*DEVICE [H,W] or NULL*/, double* out /*DEVICE [4]*/);
+/* The moments of the best affine colour transform of a render onto its target -- the colour-corrected metrics gsplat reports when a
+ * per-view appearance is trained, a held-out view having none.  p = (r, g, b, 1) the clamped render, t the clamped target, w as
+ * above:
+ *   out[0..9]   S[i][j] = sum w p_i p_j, the upper triangle by rows: 00 01 02 03 11 12 13 22 23 33  (S[3][3] = sum w)
+ *   out[10..21] T[i][c] = sum w p_i t_c, out[10 + 3 i + c]
+ * The host solves S M^T = T (least squares, minimum norm where S is singular) for M = [A | b], 3 x 4 as gs_apply_exposure takes it;
+ * the corrected metrics are gs_image_metrics of gs_apply_exposure(M, render).  Products and sums in double, a grid-stride loop of at
+ * most 512 blocks, the same fixed-order reduction and workspace as above.  n_pixels == 0: no kernel, out = zeros.
+ * GS_ERR_INVALID_ARG: a NULL render, target or out, n_pixels < 0.  No reference call site. */
+int gs_colour_moments(gs_ctx* ctx, long long n_pixels, const float* render /*DEVICE [n,3]*/, const float* target /*DEVICE [n,3]*/,
+                      const unsigned char* mask /*DEVICE [n] or NULL*/, double* out /*DEVICE [22]*/);
+
 /* ---- next row: optimizer step ---------------------------------------------------------------- */
 
 /* Adam over one flat parameter arena, as the trainer applies it per tensor (GaussianTrainer.swift:941-948,
