@@ -52,6 +52,11 @@ class gs_lens(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
 
 
+class gs_adc_params(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("grad_threshold", "percent_dense", "min_opacity", "max_screen_size", "prune_world",
+                                         "scene_extent")]
+
+
 GS_DEPTH_ACCUMULATED, GS_DEPTH_EXPECTED, GS_DEPTH_DISPARITY = 0, 1, 2
 GS_DP_ALLREDUCE, GS_DP_SH_COMPRESSED = 0, 1
 GS_DP_UNIQUE_ID_BYTES = 128
@@ -162,6 +167,12 @@ _SIGS = {
     "gs_composite_target": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp, _vp]),
     "gs_set_absgrad": (C.c_int, [_vp, C.c_int]),
     "gs_get_absgrad": (C.c_int, [_vp, C.c_int, _vp]),
+    "gs_set_adc_stats": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "gs_adc_accumulate": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "gs_adc_classify": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [C.c_int, _vp, C.POINTER(gs_adc_params), C.c_int, C.c_int, _vp, _vp]),
+    "gs_adc_gather": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 9 + [C.c_int] + [_vp] * 6),
+    "gs_adc_gather_moments": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "gs_adc_reset_opacity": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_float]),
     "gs_set_sparse_adam": (C.c_int, [_vp, C.c_int]),
     "gs_get_visibility": (C.c_int, [_vp, C.c_int, _vp]),
     "gs_adam_step_visible": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4 + [C.c_int, _vp, _vp, _vp] + [C.c_float] * 4 + [C.c_int, _vp]),

@@ -22,6 +22,7 @@ SOURCES = {
     "ssim.hip": [],
     "optim.hip": [],
     "densify.hip": ["-ffp-contract=off"],
+    "adc.hip": ["-ffp-contract=off"],
     "ply.hip": [],
     "knn.hip": ["-ffp-contract=off"],
     "dp.hip": [],

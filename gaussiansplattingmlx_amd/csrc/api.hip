@@ -277,12 +277,21 @@ int backward_preflight(gs_ctx* c, const char* who, bool wantsDepth)
 int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* cot_depth, const float* cot_alpha,
                               bool absgrad = false, const uint32_t* gate = nullptr)
 {
+    if (c->adcGradSum && !c->fwd.radii)      // (before anything is launched: the forward stays usable)
+        return fail(c, GS_ERR_NO_FORWARD, "the ADC statistic is set, but the forward kept no radii (gs_set_adc_stats comes before "
+                                          "gs_render_forward)");
     GsStageTimer t(c, GS_STAGE_BLEND_BWD);
     c->absgradN = -1;
     if (!c->fast16) return launch_blend_backward(c, c->fwd.bg, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
     if (const int rc = launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
                                                 c->fwd.outAlpha, absgrad))
         return rc;
+    // the ADC statistic (gs_set_adc_stats), from the signed mean gradient in columns 0 and 1 -- the absolute sums under absgrad
+    if (c->adcGradSum) {
+        if (const int rc = launch_adc_accum(c, c->fwd.N, c->gradAcc16, c->fwd.radii, absgrad, gate, c->adcGradSum, c->adcCount,
+                                            c->adcMaxRadius))
+            return rc;
+    }
     if (!absgrad) return GS_OK;
     c->absgradN = c->fwd.N;
     return c->gradNormAccum ? launch_absgrad_accum(c, c->fwd.N, gate, c->gradNormAccum) : GS_OK;
@@ -393,6 +402,13 @@ int refuse_absgrad(gs_ctx* c, const char* who)
     if (!c->absgrad) return GS_OK;
     return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": absgrad is on (gs_set_absgrad): only gs_render_backward and "
                                        "gs_render_backward_adam accumulate the absolute sums");
+}
+
+int refuse_adc_stats(gs_ctx* c, const char* who)
+{
+    if (!c->adcGradSum) return GS_OK;
+    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": the ADC statistic is set (gs_set_adc_stats): only gs_render_backward and "
+                                       "gs_render_backward_adam accumulate it");
 }
 
 int refuse_sparse_adam(gs_ctx* c, const char* who)
@@ -889,7 +905,8 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: null parameter tensor");
     c->fwd.valid = false;
     c->visN = -1;
-    if (c->sparseAdam && N > c->visCap) {       // sparse Adam's mask and radii: grown by the first forward that needs more rows
+    const bool keepRadii = c->sparseAdam || c->adcGradSum != nullptr;      // (the ADC statistic reads the radii in the backward)
+    if (keepRadii && N > c->visCap) {           // sparse Adam's mask and radii: grown by the first forward that needs more rows
         GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
         if (c->visMask) c->ws_bytes -= (size_t)c->visCap * (sizeof(unsigned char) + sizeof(float));
         dev_free(c->visMask); dev_free(c->visRadii);
@@ -903,7 +920,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
         }
         c->visCap = cap;
     }
-    if (c->sparseAdam && !radii) radii = c->visRadii;      // (the mask is taken from the radii the projection writes)
+    if (keepRadii && !radii) radii = c->visRadii;          // (the mask is taken from the radii the projection writes)
     c->binIsBlockLists = c->virt.nbx != 0;
     const bool reserved = c->pairsReserved && c->capN >= N;
     if (reserved) { const int orc = deferred_overflow(c); if (orc) return orc; }
@@ -964,6 +981,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.antialias = c->antialias;
     c->fwd.bg = c->bg;
     c->fwd.filter3d = c->filter3d;
+    c->fwd.radii = keepRadii ? radii : nullptr;      // (a caller's buffer is remembered only where a backward will read it)
     if (c->sparseAdam) c->visN = N;
     return GS_OK;
 }
@@ -1013,6 +1031,91 @@ int gs_get_absgrad(gs_ctx* c, int N, float* out)
     if (N != c->absgradN) return fail(c, GS_ERR_SIZE_MISMATCH, "gs_get_absgrad: N differs from the backward's N");
     if (N > 0 && !out) return fail(c, GS_ERR_INVALID_ARG, "gs_get_absgrad: null buffer");
     return launch_absgrad_copy(c, N, out);
+}
+
+// ---- adaptive density control (include/gsplat.h gs_set_adc_stats; adc.hip) ---------------------------------------------------
+int gs_set_adc_stats(gs_ctx* c, float* grad_sum, float* count, float* max_radius)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    const int given = (grad_sum != nullptr) + (count != nullptr) + (max_radius != nullptr);
+    if (given != 0 && given != 3) return fail(c, GS_ERR_INVALID_ARG, "gs_set_adc_stats: all three accumulators, or all three NULL");
+    if (given && !c->fast16)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_set_adc_stats: this context's tile size is served by the generic blend kernels, whose "
+                                           "backward leaves no gradient rows");
+    c->adcGradSum = grad_sum;
+    c->adcCount = count;
+    c->adcMaxRadius = max_radius;
+    return GS_OK;
+}
+
+int gs_adc_accumulate(gs_ctx* c, int N, const float* rows16, const float* radii, int use_abs, float* grad_sum, float* count,
+                      float* max_radius)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (N < 0 || (use_abs != 0 && use_abs != 1)) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_accumulate: bad N / use_abs");
+    if (N > 0 && (!rows16 || !radii || !grad_sum || !count || !max_radius))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adc_accumulate: null buffer");
+    if ((uintptr_t)rows16 & 7) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_accumulate: rows16 must be 8-byte aligned");
+    return launch_adc_accum(c, N, rows16, radii, use_abs == 1, nullptr, grad_sum, count, max_radius);
+}
+
+int gs_adc_classify(gs_ctx* c, int N, const float* grad_sum, const float* count, const float* max_radius, const float* scales,
+                    int scale_stride, const float* opacity, const gs_adc_params* params, int allow_densify, int size_prune,
+                    int* actions, int* output_counts)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (N < 0 || scale_stride < 3 || !params) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_classify: bad N / scale_stride / params");
+    if (N > 0 && (!grad_sum || !count || !max_radius || !scales || !opacity || !actions || !output_counts))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adc_classify: null buffer");
+    const gs_adc_params& p = *params;
+    if (!(p.grad_threshold >= 0.0f) || !(p.percent_dense >= 0.0f) || !(p.prune_world >= 0.0f) || !(p.scene_extent > 0.0f) ||
+        !isfinite(p.scene_extent) || !(p.min_opacity >= 0.0f) || p.max_screen_size != p.max_screen_size)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adc_classify: thresholds must be >= 0 (scene_extent > 0 and finite; max_screen_size "
+                                           "any number, <= 0 for no screen test)");
+    return launch_adc_classify(c, N, grad_sum, count, max_radius, scales, scale_stride, opacity, p.grad_threshold,
+                               p.percent_dense * p.scene_extent, p.min_opacity, p.max_screen_size, p.prune_world * p.scene_extent,
+                               allow_densify != 0, size_prune != 0, actions, output_counts);
+}
+
+int gs_adc_gather(gs_ctx* c, int total, int K, const float* xyz, const float* features_dc, const float* features_rest,
+                  const float* scales, const float* rotation, const float* opacity, const int* gather_indices, const int* noise_mode,
+                  const float* noise, int revised_opacity, float* out_xyz, float* out_features_dc, float* out_features_rest,
+                  float* out_scales, float* out_rotation, float* out_opacity)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (total < 0 || K < 1 || (revised_opacity != 0 && revised_opacity != 1))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adc_gather: bad total / K / revised_opacity");
+    if (total > 0 && (!xyz || !features_dc || !scales || !rotation || !opacity || !gather_indices || !noise_mode || !noise ||
+                      !out_xyz || !out_features_dc || !out_scales || !out_rotation || !out_opacity ||
+                      (K > 1 && (!features_rest || !out_features_rest))))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adc_gather: null buffer");
+    return launch_adc_gather(c, total, K, xyz, features_dc, features_rest, scales, rotation, opacity, gather_indices, noise_mode,
+                             noise, revised_opacity, out_xyz, out_features_dc, out_features_rest, out_scales, out_rotation,
+                             out_opacity);
+}
+
+int gs_adc_gather_moments(gs_ctx* c, int total, int K, const int* gather_indices, const int* noise_mode, const int* actions,
+                          const float* const in[6], float* const out[6])
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (total < 0 || K < 1) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_gather_moments: bad total / K");
+    if (!in || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_gather_moments: null tensor table");
+    if (total > 0) {
+        if (!gather_indices || !noise_mode || !actions) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_gather_moments: null buffer");
+        for (int t = 0; t < 6; t++)
+            if ((t != 2 || K > 1) && (!in[t] || !out[t])) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_gather_moments: null buffer");
+    }
+    return launch_adc_gather_moments(c, total, K, gather_indices, noise_mode, actions, in, out);
+}
+
+int gs_adc_reset_opacity(gs_ctx* c, int N, float* opacity, float* m_opacity, float* v_opacity, float reset_value)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (N < 0 || !(reset_value > 0.0f && reset_value < 1.0f))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_adc_reset_opacity: bad N, or reset_value not in (0, 1)");
+    if (N > 0 && (!opacity || !m_opacity || !v_opacity)) return fail(c, GS_ERR_INVALID_ARG, "gs_adc_reset_opacity: null buffer");
+    const double rv = (double)reset_value;
+    return launch_adc_reset_opacity(c, N, opacity, m_opacity, v_opacity, (float)log(rv / (1.0 - rv)));
 }
 
 int gs_set_antialiasing(gs_ctx* c, int enable)
@@ -1388,6 +1491,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_begin")) return rc;
+    if (const int rc = refuse_adc_stats(c, "gs_render_backward_dp_begin")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && !color_cot)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: null buffer");
@@ -1438,6 +1542,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_geom")) return rc;
+    if (const int rc = refuse_adc_stats(c, "gs_render_backward_dp_geom")) return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && (!color_cot || !grad_xyz || !grad_scales || !grad_rotation || !grad_opacity || !xyz_own)))

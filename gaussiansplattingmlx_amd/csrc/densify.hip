@@ -373,8 +373,9 @@ __global__ __launch_bounds__(DN_THREADS) void gather_rows4_kernel(long long tota
 }
 
 // table != nullptr: `out` is the BASE of the packed arena (its alignment is the segments' alignment)
-static void launch_gather_rows(gs_ctx* c, long long rows, int L, const float* in, const int* gather, float* out, const uint32_t* plan,
-                               float* const* table = nullptr)
+// (declared in gs_ctx.h: adc.hip's gather takes its features_rest rows through it)
+void launch_gather_rows(gs_ctx* c, long long rows, int L, const float* in, const int* gather, float* out, const uint32_t* plan,
+                        float* const* table)
 {
     if ((L & 3) == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0) {
         const long long quads = rows * (L / 4);

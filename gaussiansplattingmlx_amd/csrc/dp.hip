@@ -379,6 +379,7 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
     if (const int rc = gs::refuse_pose_correction(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_filter3d(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_absgrad(c, "gs_dp_step")) return rc;
+    if (const int rc = gs::refuse_adc_stats(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_sparse_adam(c, "gs_dp_step")) return rc;
     if (!d) { c->err = "gs_dp_step: no communicator (gs_dp_init / gs_dp_attach)"; return GS_ERR_INVALID_ARG; }
     if (!a || (mode != GS_DP_ALLREDUCE && mode != GS_DP_SH_COMPRESSED)) { c->err = "gs_dp_step: bad mode / arguments"; return GS_ERR_INVALID_ARG; }

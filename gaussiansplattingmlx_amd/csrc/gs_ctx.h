@@ -251,6 +251,12 @@ struct gs_ctx {
     float* visRadii = nullptr;
     int visCap = 0;
     int visN = -1;                       // N of the last fused forward made under the setting (its mask is in visMask); -1: none
+    // adaptive density control (gs_set_adc_stats): caller-owned [N] accumulators, all set or all nullptr.
+    // While set, every fused forward keeps its radii (the caller's buffer, or visRadii as under sparse Adam) and the blend backward
+    // of gs_render_backward / gs_render_backward_adam adds the step's statistic (adc.hip adc_accum_kernel)
+    float* adcGradSum = nullptr;
+    float* adcCount = nullptr;
+    float* adcMaxRadius = nullptr;
     // 3-D smoothing filter (gs_set_filter3d): the caller-owned device widths [>= N] of the following forwards, nullptr = off; the
     // training cameras' table for gs_compute_filter3d (GS_F3D_CAM_FLOATS floats per camera) and the max word of its never-seen
     // rule, both allocated or grown by gs_set_filter3d_cameras only
@@ -378,6 +384,7 @@ struct gs_ctx {
         bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
         GsBackground bg;                   // the background this forward composited over (its backward's)
         const float* filter3d = nullptr;   // the 3-D filter widths this forward ran with (its backward's; nullptr: none)
+        const float* radii = nullptr;      // where this forward's projection wrote its radii (nullptr: nowhere)
         uint32_t* cutStore = nullptr;  // the view's cut words at the time of this forward (nullptr: none kept)
         bool cutsActive = false;     // this forward binned under depth cuts
         bool missChecked = true;     // ... and gs_forward_missed has been asked since
@@ -439,6 +446,7 @@ int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_A
 int refuse_filter3d(gs_ctx* c, const char* who);             // GS_ERR_INVALID_ARG while a 3-D filter is set (or the forward ran with one)
 int refuse_absgrad(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while absgrad is on (gs_set_absgrad)
 int refuse_sparse_adam(gs_ctx* c, const char* who);          // GS_ERR_INVALID_ARG while sparse Adam is on (gs_set_sparse_adam)
+int refuse_adc_stats(gs_ctx* c, const char* who);            // GS_ERR_INVALID_ARG while the ADC statistic is set (gs_set_adc_stats)
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
 CamParams make_cam(const gs_camera* cam, int W, int H);
@@ -577,6 +585,21 @@ int launch_densify_gather_planned_packed(gs_ctx* c, int cap, int K, const float*
                                          const float* scales, const float* rot, const float* opacity, const int* gather,
                                          const int* noiseMode, unsigned long long noiseSeed, float* outBase, const int order[6]);
 int launch_densify_noise(gs_ctx* c, unsigned long long seed, int rows, float* out);
+// out[j, :] = in[gather[j], :] for rows of L floats (plan / table: the planned and the packed forms, nullptr without)
+void launch_gather_rows(gs_ctx* c, long long rows, int L, const float* in, const int* gather, float* out, const uint32_t* plan,
+                        float* const* table = nullptr);
+// adc.hip (include/gsplat.h gs_set_adc_stats and the gs_adc_* entry points; arguments checked by api.hip)
+int launch_adc_accum(gs_ctx* c, int N, const float* rows16, const float* radii, bool useAbs, const uint32_t* gate, float* gradSum,
+                     float* count, float* maxRadius);
+int launch_adc_classify(gs_ctx* c, int N, const float* gradSum, const float* count, const float* maxRadius, const float* scales,
+                        int scaleStride, const float* opacity, float gradThreshold, float denseMax, float minOpacity,
+                        float maxScreenSize, float worldMax, int allowDensify, int sizePrune, int* actions, int* outputCounts);
+int launch_adc_gather(gs_ctx* c, int total, int K, const float* xyz, const float* fdc, const float* frest, const float* scales,
+                      const float* rot, const float* opacity, const int* gather, const int* noiseMode, const float* noise,
+                      int revisedOpacity, float* oXyz, float* oFdc, float* oFrest, float* oScales, float* oRot, float* oOpacity);
+int launch_adc_gather_moments(gs_ctx* c, int total, int K, const int* gather, const int* noiseMode, const int* actions,
+                              const float* const in[6], float* const out[6]);
+int launch_adc_reset_opacity(gs_ctx* c, int N, float* opacity, float* m, float* v, float resetRaw);
 // mcmc.hip (include/gsplat.h gs_set_mcmc and the gs_mcmc_* entry points; arguments checked by api.hip)
 struct McmcRows {            // the six tensors of rows [0, capacity) and where their moments lie
     float* t[6];             // xyz, f_dc, f_rest, scales, rotation, opacity

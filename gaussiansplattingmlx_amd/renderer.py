@@ -445,7 +445,8 @@ class GaussianRenderer:
                                                _p(p["features_rest"]), _p(p["scales"]), _p(p["rotation"]),
                                                _p(p["opacity"]), C.byref(cam), _p(color),
                                                _p(depth if wantDepth else None), _p(alpha), _p(radii)))
-        self._fused = dict(params=p, color=color, depth=depth if wantDepth else None, alpha=alpha)
+        # (radii: the backward of a forward made under setADCStats reads the caller's radii buffer -- it lives until the next forward)
+        self._fused = dict(params=p, color=color, depth=depth if wantDepth else None, alpha=alpha, radii=radii)
         return RenderResult(color.view(self.H, self.W, 3), depth.view(self.H, self.W, 1) if wantDepth else None,
                             alpha.view(self.H, self.W, 1), None if radii is None else radii > 0, radii)
 
@@ -737,6 +738,64 @@ class GaussianRenderer:
         out = self._empty(N, 2)
         self._check(self.lib.gs_get_absgrad(self.ctx, N, _p(out)))
         return out
+
+    # -- adaptive density control (include/gsplat.h gs_set_adc_stats; adc.py states the rule) -------------
+    _ADC_ORDER = ("xyz", "features_dc", "features_rest", "scales", "rotation", "opacity")
+
+    def setADCStats(self, gradSum=None, count=None, maxRadius=None):
+        """gs_set_adc_stats: the following renderBackward / fused train steps add, for every Gaussian their forward saw,
+        hypot(W/2 gx, H/2 gy) of its 2-D mean gradient to gradSum, 1 to count and the radius into maxRadius's running maximum
+        (float32 [N] on the device, all three or none; they must stay alive while set).  Single-device steps; refused on a
+        renderer whose tile size is served by the generic blend kernels.  None (the default): no kernel, buffer or result differs."""
+        self._check(self.lib.gs_set_adc_stats(self.ctx, _p(gradSum), _p(count), _p(maxRadius)))
+        self._adc_stats = None if gradSum is None else (gradSum, count, maxRadius)
+
+    def adcAccumulate(self, rows16, radii, useAbs: bool, gradSum, count, maxRadius):
+        """gs_adc_accumulate: the step's statistic kernel on the caller's rows [N, 16] and radii [N], in place."""
+        rows16, radii = self._t(rows16), self._t(radii)
+        self._check(self.lib.gs_adc_accumulate(self.ctx, int(radii.shape[0]), _p(rows16), _p(radii), int(bool(useAbs)),
+                                               _p(gradSum), _p(count), _p(maxRadius)))
+
+    def adcClassify(self, gradSum, count, maxRadius, scales, opacity, gradThreshold=0.0002, percentDense=0.01, minOpacity=0.005,
+                    maxScreenSize=20.0, pruneWorld=0.1, sceneExtent=1.0, allowDensify=True, sizePrune=False):
+        """gs_adc_classify: (actions, counts) int32 [N] in classifyGaussians' words."""
+        gradSum, count, maxRadius = self._t(gradSum), self._t(count), self._t(maxRadius)
+        scales, opacity = self._t(scales), self._t(opacity)
+        N = int(gradSum.shape[0])
+        actions, counts = self._empty(N, dtype=torch.int32), self._empty(N, dtype=torch.int32)
+        prm = _lib.gs_adc_params(float(gradThreshold), float(percentDense), float(minOpacity), float(maxScreenSize),
+                                 float(pruneWorld), float(sceneExtent))
+        self._check(self.lib.gs_adc_classify(self.ctx, N, _p(gradSum), _p(count), _p(maxRadius), _p(scales),
+                                             int(scales.shape[1]) if N else 3, _p(opacity), C.byref(prm),
+                                             int(bool(allowDensify)), int(bool(sizePrune)), _p(actions), _p(counts)))
+        return actions, counts
+
+    def adcGather(self, params: dict, gather, noiseMode, noise, revisedOpacity: bool = False, out: dict | None = None):
+        """gs_adc_gather: densifyGather's sibling -- split children sampled from the Gaussian, clones copied exactly."""
+        p = {k: self._t(v) for k, v in params.items()}
+        total, K = int(gather.shape[0]), int(p["features_rest"].shape[1]) + 1
+        o = out or {k: self._empty(total, *v.shape[1:]) for k, v in p.items()}
+        self._check(self.lib.gs_adc_gather(self.ctx, total, K, _p(p["xyz"]), _p(p["features_dc"]), _p(p["features_rest"]),
+                                           _p(p["scales"]), _p(p["rotation"]), _p(p["opacity"]), _p(gather), _p(noiseMode),
+                                           _p(self._t(noise)), int(bool(revisedOpacity)), _p(o["xyz"]), _p(o["features_dc"]),
+                                           _p(o["features_rest"]), _p(o["scales"]), _p(o["rotation"]), _p(o["opacity"])))
+        return o
+
+    def adcGatherMoments(self, moments: dict, gather, noiseMode, actions, out: dict | None = None):
+        """gs_adc_gather_moments on one moment arena's six tensors (a dict keyed like the parameters): kept rows and clone
+        originals copied bit for bit, split children and clone copies zero."""
+        mo = {k: self._t(v) for k, v in moments.items()}
+        total, K = int(gather.shape[0]), int(mo["features_rest"].shape[1]) + 1
+        o = out or {k: self._empty(total, *v.shape[1:]) for k, v in mo.items()}
+        tin = (C.c_void_p * 6)(*[_p(mo[k]) for k in self._ADC_ORDER])
+        tout = (C.c_void_p * 6)(*[_p(o[k]) for k in self._ADC_ORDER])
+        self._check(self.lib.gs_adc_gather_moments(self.ctx, total, K, _p(gather), _p(noiseMode), _p(actions), tin, tout))
+        return o
+
+    def adcResetOpacity(self, opacity, mOpacity, vOpacity, resetValue: float = 0.01):
+        """gs_adc_reset_opacity, in place: opacity = min(opacity, logit(resetValue)); the segment's two moments zeroed."""
+        self._check(self.lib.gs_adc_reset_opacity(self.ctx, int(opacity.numel()), _p(opacity), _p(mOpacity), _p(vOpacity),
+                                                  C.c_float(resetValue)))
 
     # -- sparse Adam (include/gsplat.h gs_set_sparse_adam, DESIGN.md section 17; sparse_adam.py restates the rule) ---------------
     def setSparseAdam(self, enable: bool = True):

@@ -245,6 +245,7 @@ class GaussModel:
         self._pbuf = [None, None]
         self._cur = 0
         self._gbuf = self._mbuf = self._vbuf = None
+        self._mspare = self._vspare = None      # the moments' staging (stagingMoments): allocated by the first event that keeps them
         self._staged = None
         self.stride = N
         self._layout(N, max(int(capacity or N), N))
@@ -330,15 +331,37 @@ class GaussModel:
         self._staged = (None, cap, None)
         return self._pbuf[other]
 
-    def commitStaged(self, N_new=None, zero=True):
+    def getMoments(self):
+        """(m, v): the two Adam moment arenas as views keyed like the parameters."""
+        return self._carve(self.m, self.N, self.stride), self._carve(self.v, self.N, self.stride)
+
+    def stagingMoments(self):
+        """(m, v) views for the rows stagingViews has just staged (packed layout), in spare moment buffers: an event that
+        keeps the Adam state gathers the moments into them (strategy="adc"), and commitStaged(moments=True) flips to them."""
+        N_new, cap, stride = self._staged
+        if N_new is None or stride != N_new:
+            raise ValueError("stagingMoments: after stagingViews(N_new) in the packed layout")
+        floats = self._offsets(max(cap, stride))[1]
+        self._mspare, self._vspare = self._buf(self._mspare, floats, zero=True), self._buf(self._vspare, floats, zero=True)
+        n = self._offsets(stride)[1]
+        return self._carve(self._mspare[:n], N_new, stride), self._carve(self._vspare[:n], N_new, stride)
+
+    def commitStaged(self, N_new=None, zero=True, moments=False):
         """Flip to the staged buffer (split_and_prune phase 6, GaussianTrainer.swift:900-905); gradients and Adam
         moments are zeroed (the reference re-creates the optimizer state, :1104-1109).  N_new: the row count when it was
         not known at staging time (the planned event stages `capacity` rows' worth of pointers); zero=False: the caller
-        has zeroed the buffers whole already."""
+        has zeroed the buffers whole already.  moments=True: flip to the moments staged by stagingMoments as well (they are
+        then kept, whatever `zero` says; the gradients are zeroed)."""
         n_staged, cap, stride = self._staged
         N_new = n_staged if N_new is None else int(N_new)
         self._staged = None
         self._cur = 1 - self._cur
+        if moments:
+            self._mbuf, self._mspare = self._mspare, self._mbuf
+            self._vbuf, self._vspare = self._vspare, self._vbuf
+            self._layout(N_new, cap, pads=("arena", "m", "v"))
+            self.grad.zero_()
+            return
         self._layout(N_new, cap, pads=("arena",), stride=None if stride is None or (stride == n_staged and N_new == n_staged) else stride)
         if zero:
             self.grad.zero_()                          # gradients and moments are zeroed whole, pads included
@@ -454,7 +477,7 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None, sparse_adam: bool = False, background=None, depth=None):
+                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -501,7 +524,8 @@ class GaussianTrainer:
         under one.  Off (the default): no kernel, buffer or result differs.
 
         strategy: "reference" (the default: the reference's densification -- clone / split by accumulated |grad xyz|, prune,
-        optimizer reset every 100 steps -- when densify is on) or "mcmc": the MCMC strategy (mcmc.MCMCConfig, include/gsplat.h
+        optimizer reset every 100 steps -- when densify is on), "adc" (adaptive density control: the last paragraph) or "mcmc":
+        the MCMC strategy (mcmc.MCMCConfig, include/gsplat.h
         gs_set_mcmc) with the settings `mcmc` (None: MCMCConfig()).  Every step adds the regularisers'
         gradients and, behind Adam, the position noise; behind steps refine_start < t < refine_stop, t % refine_every == 0, dead
         Gaussians are relocated onto live ones and the count grows by grow_rate up to cap_max.  The reference strategy is then
@@ -537,7 +561,8 @@ class GaussianTrainer:
         split.  gradientThreshold becomes absgrad.threshold; the global step denominator, classifyGaussians and the event code
         stay as they are: only what is summed changes.  The default threshold, 0.0008, is gsplat's documented value for absgrad,
         where the sum is divided by a per-Gaussian visibility count; this trainer keeps the reference's global step count, and
-        nobody has tuned the value here.  Single-device steps and the reference strategy with densify on only; composes with
+        nobody has tuned the value here.  Single-device steps; the reference strategy with densify on, or strategy="adc", where
+        the absolute sums are averaged over the steps that saw the Gaussian, as in gsplat; composes with
         pose_opt, exposure_opt, bilateral_grid, filter_3d, contrib_prune, an anti-aliased renderer and referenceParamReload.
         Off (the default): no kernel, buffer or result differs.
 
@@ -579,7 +604,23 @@ class GaussianTrainer:
         exposure_opt, bilateral_grid, absgrad, sparse_adam, filter_3d, contrib_prune, lossMask, background (whose g . b term the
         library adds to the alpha cotangent it is handed), strategy='mcmc', an anti-aliased renderer and fuse_adam on or off;
         single-device steps with one view only.  Off (the default): no kernel, launch, buffer or result differs, and the step
-        still renders without a depth image."""
+        still renders without a depth image.
+
+        strategy="adc", adc: adaptive density control, the densification of the original 3DGS (adc.ADCConfig, include/gsplat.h
+        gs_set_adc_stats; Inria's densify_and_prune and reset_opacity, gsplat's DefaultStrategy) with the
+        settings `adc` -- required, for its scene_extent (adc.scene_extent(cameras)).  The trainer owns three [N] accumulators
+        and sets them as the renderer's ADC statistic around its steps up to densify_until: every such step's backward adds, for each Gaussian its view
+        saw, hypot(W/2 gx, H/2 gy) of the 2-D mean gradient, one visit and the radius.  Behind steps densify_from <= t <=
+        densify_until, t % densify_interval == 0 the event (_adcEvent): classify on the per-Gaussian average, splits sampled
+        from the Gaussian itself, exact clones, the Adam moments of what survives kept, the accumulators zeroed; one host wait
+        per event.  Behind steps t % opacity_reset_interval == 0 (t <= densify_until) the opacities are capped at reset_value,
+        and from the first reset on the events also prune by screen and world size.  allowDensify = N < maxGaussians; an event
+        that would still exceed maxGaussians only prunes.  The reference strategy is off (densify is ignored);
+        lastDensifyStats holds the last event's counts, lastADCStats those and reset / size_prune.  With absgrad= the absolute
+        sums are what is accumulated and absgrad.threshold replaces grad_threshold (gsplat's DefaultStrategy(absgrad=True)).
+        Composes with pose_opt, exposure_opt, bilateral_grid, background, depth, lossMask, an anti-aliased renderer and
+        fuse_adam on or off; single-device steps with one view only, not with filter_3d, contrib_prune, sparse_adam or
+        referenceParamReload."""
         self.depth = None
         self._depthStep = None          # the running step's depth inputs (trainStep sets and clears it)
         if depth is not None:
@@ -609,9 +650,28 @@ class GaussianTrainer:
             if filter_3d:
                 raise ValueError("sparse_adam: not with filter_3d=True")
             _require_single_device("sparse_adam", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-        if strategy not in ("reference", "mcmc"):
-            raise ValueError(f"unknown strategy {strategy!r} (\"reference\" or \"mcmc\")")
+        if strategy not in ("reference", "mcmc", "adc"):
+            raise ValueError(f"unknown strategy {strategy!r} (\"reference\", \"mcmc\" or \"adc\")")
         self.strategy = strategy
+        self.adc = None
+        self.lastADCStats = None
+        self.adcSizePrune = False       # size pruning: on once the first opacity reset has happened
+        self._adcAcc = None             # [3, N]: gradSum, count, maxRadius
+        if strategy == "adc":
+            from .adc import ADCConfig
+            if adc is None:
+                raise ValueError("strategy='adc' needs adc=ADCConfig(scene_extent=adc.scene_extent(cameras))")
+            if not isinstance(adc, ADCConfig):
+                raise ValueError("adc must be an ADCConfig")
+            adc.validate()
+            _require_single_device("strategy='adc'", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            for on, name in ((filter_3d, "filter_3d"), (contrib_prune is not None, "contrib_prune"), (sparse_adam, "sparse_adam")):
+                if on:
+                    raise ValueError(f"strategy='adc': not with {name}")
+            self.adc = adc
+            densify = False
+        elif adc is not None:
+            raise ValueError("adc settings need strategy='adc'")
         self.contribPrune = None
         self.lastContribPruneStats = None
         if contrib_prune is not None:
@@ -630,8 +690,8 @@ class GaussianTrainer:
                 raise ValueError("absgrad must be an AbsGradConfig")
             absgrad.validate()
             if strategy == "mcmc":
-                raise ValueError("absgrad: the reference strategy only (not with strategy='mcmc')")
-            if not densify:
+                raise ValueError("absgrad: the reference strategy or strategy='adc' (not with strategy='mcmc')")
+            if not densify and strategy != "adc":
                 raise ValueError("absgrad changes the densification criterion: not with densify=False")
             _require_single_device("absgrad", views_per_rank, process_group, dp_bootstrap, exchange_impl)
             self.absgrad = absgrad
@@ -731,6 +791,8 @@ class GaussianTrainer:
         self.iteration = 0
         # densification (GaussianTrainer.swift:293-300, 304)
         self.gradientThreshold, self.minOpacity, self.maxScale = 0.0002, 0.005, 0.01
+        if self.adc is not None:
+            self.gradientThreshold, self.minOpacity = float(self.adc.grad_threshold), float(self.adc.min_opacity)
         if self.absgrad is not None:
             self.gradientThreshold = float(self.absgrad.threshold)
         self.densifyFromIter, self.densifyUntilIter, self.maxGaussians = 500, 15000, 1_000_000
@@ -859,6 +921,8 @@ class GaussianTrainer:
     def referenceParamReload(self, value):
         if value and self.mcmc is not None:
             raise ValueError("referenceParamReload mirrors the reference strategy's commits: not with strategy='mcmc'")
+        if value and getattr(self, "adc", None) is not None:
+            raise ValueError("referenceParamReload mirrors the reference strategy's commits: not with strategy='adc'")
         self._referenceParamReload = value
 
     def _updateFilter3D(self):
@@ -896,6 +960,72 @@ class GaussianTrainer:
         if r.reserved is not None and N_new > r.reserved[0]:
             r.reserve(N_new, int(r.reserved[1] * (N_new / max(r.reserved[0], 1)) * 1.1))
         return self.lastMCMCStats
+
+    # -- adaptive density control (adc.py, include/gsplat.h gs_set_adc_stats) --------------------------------
+    def _adcAccumulators(self):
+        """(gradSum, count, maxRadius), each [N]: rows of one zeroed tensor, allocated anew when N has changed."""
+        if self._adcAcc is None or int(self._adcAcc.shape[1]) != self.model.N:
+            self._adcAcc = self.gaussRender._empty(3, max(self.model.N, 1)).zero_()[:, :self.model.N]
+        return self._adcAcc[0], self._adcAcc[1], self._adcAcc[2]
+
+    def _adcEvent(self, it: int):
+        """The ADC event behind step `it`: classify on the accumulators, densify.hip's scan and output map, the noise, the
+        parameter gather and the moments' gather into staged buffers, commit, accumulators zeroed.  The unplanned sequence: one
+        host wait (the output count).  Returns the action counts, or None for an empty model."""
+        r, m, cfg = self.gaussRender, self.model, self.adc
+        N = m.N
+        if N <= 0:
+            return None
+        gradSum, count, maxRadius = self._adcAccumulators()
+        p = m.getParams()
+
+        def classify(allow):
+            actions, counts = r.adcClassify(gradSum, count, maxRadius, p["scales"], p["opacity"].reshape(-1),
+                                            gradThreshold=self.gradientThreshold, percentDense=cfg.percent_dense,
+                                            minOpacity=self.minOpacity, maxScreenSize=cfg.max_screen_size,
+                                            pruneWorld=cfg.prune_world, sceneExtent=cfg.scene_extent, allowDensify=allow,
+                                            sizePrune=self.adcSizePrune)
+            return (actions, counts) + r.densifyOffsets(actions, counts)
+
+        allow = N < self.maxGaussians
+        actions, counts, offsets, st = classify(allow)
+        if allow and st["total"] > self.maxGaussians:
+            allow = False                   # growing would pass maxGaussians: this event only prunes
+            actions, counts, offsets, st = classify(allow)
+        self.lastDensifyStats = st
+        self.lastADCStats = dict(st, N=N, allow_densify=allow, reset=False, size_prune=self.adcSizePrune)
+        total = st["total"]
+        if total <= 0 or (st["split"] == 0 and st["clone"] == 0 and st["prune"] == 0):
+            self._adcAcc.zero_()            # everything pruned, or nothing to do: the model stays, the statistic starts anew
+            return st
+        gather, mode = r.buildDensifyOutputMap(actions, offsets, total)
+        noise = r.densifyNoise(self.noise_seed + int(it), total)
+        r.adcGather(p, gather, mode, noise, revisedOpacity=cfg.revised_opacity, out=m.stagingViews(total))
+        mOld, vOld = m.getMoments()
+        mNew, vNew = m.stagingMoments()
+        r.adcGatherMoments(mOld, gather, mode, actions, out=mNew)
+        r.adcGatherMoments(vOld, gather, mode, actions, out=vNew)
+        m.commitStaged(zero=False, moments=True)
+        self._committed = True
+        self._adcAcc = None
+        self._adcAccumulators()
+        if st["split"] > 0 or st["clone"] > 0:
+            r.dropDepthCuts()               # (new Gaussians lengthen the sweeps: see split_and_prune)
+        if r.reserved is not None and total > r.reserved[0]:
+            r.reserve(total, int(r.reserved[1] * (total / max(r.reserved[0], 1)) * 1.1))
+        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in m.seg_end])
+        self._alloc_exchange_buffers()
+        return st
+
+    def _adcResetOpacity(self):
+        """The opacity reset: opacity = min(opacity, logit(reset_value)), the opacity segment's moments zeroed; size pruning is
+        on from here."""
+        r, m = self.gaussRender, self.model
+        if m.N > 0:
+            mo, vo = m.getMoments()
+            r.adcResetOpacity(m.getParams()["opacity"], mo["opacity"], vo["opacity"], self.adc.reset_value)
+        self.adcSizePrune = True
+        self.lastADCStats = dict(self.lastADCStats or {}, reset=True, size_prune=True)
 
     def _dp_connect(self, bootstrap):
         """gs_dp_init: rank 0 draws the RCCL id, every rank gets it (through process_group, whatever its backend), and the
@@ -1680,6 +1810,8 @@ class GaussianTrainer:
                 r.setFilter3D(None)
             if self.sparse_adam and not sparse_was:
                 r.setSparseAdam(False)
+            if self.adc is not None and getattr(r, "_adc_stats", None) is not None:
+                r.setADCStats(None)       # (set by _beginIteration: the accumulators are this trainer's, the renderer the caller's)
             if bg_was is not None:
                 r.setBackground(bg_was[0])
             if mask_was is not None:
@@ -1837,6 +1969,9 @@ class GaussianTrainer:
             r.setGradNormAccum(None)
         if self.absgrad is not None and not getattr(r, "_absgrad", False):
             r.setAbsgrad(True)          # the backward below adds hypot(W/2 Ax, H/2 Ay) instead (absgrad.py)
+        if self.adc is not None and self.iteration <= self.adc.densify_until:
+            # the backward below adds the view's statistic (adc.py); behind densify_until no event reads it any more
+            r.setADCStats(*self._adcAccumulators())
 
     def _forwardAndLoss(self, camera, targetRGB, viewKey, lossOut):
         """lossFn of one view (GaussianTrainer.swift:627-723): forward, L1 + DSSIM loss -> lossOut[4] and the colour cotangent
@@ -2054,6 +2189,14 @@ class GaussianTrainer:
             # the event has just waited for the device (its count reads): the overflow flag is cheap to look at now
             if self._overflow_reported():
                 self.checkOverflow()
+        if self.adc is not None:
+            if self.adc.is_event(it):
+                self._adcEvent(it)
+                # the event has just waited for the device (its count read): the overflow flag is cheap to look at now
+                if self._overflow_reported():
+                    self.checkOverflow()
+            if self.adc.is_reset(it):
+                self._adcResetOpacity()
         moved = False         # (filter_3d: the model's rows or positions changed other than by the step)
         if self.densify and it % self.split_and_prune_per_iteration == 0:
             self._committed = False

@@ -942,6 +942,88 @@ int gs_densify_gather_planned_packed(gs_ctx* ctx, int capacity, int K, const flo
                                      unsigned long long noise_seed, float* out_base, const int arena_order[6] /*HOST*/);
 int gs_densify_noise(gs_ctx* ctx, unsigned long long seed, int rows, float* out /*[rows,3]*/);
 
+/* ---- adaptive density control (not in the reference) ---------------------------------
+ * The densification of the original 3DGS (Kerbl et al. 2023: Inria's densify_and_prune / reset_opacity; gsplat's
+ * DefaultStrategy), beside the reference's rule above, which it replaces under the trainer's strategy="adc":
+ * classify_gaussians (GaussianTrainer.swift:343-393) divides one sum by one global step count and has no size test, and the
+ * gather (:858-893) moves a split child by +/- 0.1 mean scale noise along no axis of the Gaussian.  Here the statistic is
+ * averaged over the steps that SAW the Gaussian, a split samples its children from the Gaussian itself, the Adam moments
+ * of what survives an event survive it, and the opacities are reset periodically.  The scan, the plan and the output map
+ * between classify and gather are gs_densify_offsets / gs_build_densify_output_map, unchanged.  All of it is asynchronous
+ * on the context's stream and allocates nothing, except where noted.  None of these entry points returns
+ * GS_ERR_SIZE_MISMATCH: every buffer is the caller's and carries no size the library could compare N with (the accumulators
+ * of gs_set_adc_stats must hold the N of the forwards made while they are set). */
+
+/* The step's statistic.  grad_sum, count, max_radius: caller-owned DEVICE [N] float accumulators (N of the forwards that
+ * follow; the caller zeroes them), all three set, or all three NULL to turn it off (the default: no kernel, buffer or result
+ * differs).  While set, every gs_render_forward keeps the radii it computed -- in the caller's radii buffer, which must then
+ * stay alive until the backward, or in memory of the context's (the buffer sparse Adam uses; allocated by the first forward
+ * that needs it, regrown only when N outgrows it) --, and the blend backward of gs_render_backward and
+ * gs_render_backward_adam adds, for every Gaussian p that forward gave a radius > 0,
+ *   grad_sum[p] += hypot(W/2 gx, H/2 gy),   count[p] += 1,   max_radius[p] = max(max_radius[p], radius[p]),
+ * (gx, gy) the gradient of the loss with respect to the Gaussian's 2-D mean in pixel units (gsplat's and Inria's NDC scaling;
+ * with absgrad on -- gs_set_absgrad -- the absolute sums (Ax, Ay) in their place: gsplat's DefaultStrategy(absgrad=True)).  A
+ * Gaussian of radius 0 keeps the bits of its three words; count, a float, is exact up to 2^24 visits.  A step whose forward
+ * overflowed its reserved pairs adds nothing (the gate of the fused Adam).  Every render, gradient and parameter update is what
+ * it is with the statistic off; a grad-norm accumulator (gs_set_grad_norm_accum) is independent of it.
+ * GS_ERR_INVALID_ARG: one or two of the three NULL; a context whose tile size is served by the generic blend kernels.  A
+ * backward whose forward was made before the statistic was set (and kept no radii) returns GS_ERR_NO_FORWARD.  Single-device
+ * steps only: while it is set, gs_render_backward_dp* and gs_dp_step return GS_ERR_INVALID_ARG. */
+int gs_set_adc_stats(gs_ctx* ctx, float* grad_sum, float* count, float* max_radius);
+/* The same kernel on the caller's rows: rows16 DEVICE [N,16] (8-byte aligned; a blend backward's accumulator rows: columns
+ * 0, 1 are read, columns 12, 13 with use_abs = 1), radii DEVICE [N], W and H the context's.  No gate. */
+int gs_adc_accumulate(gs_ctx* ctx, int N, const float* rows16, const float* radii, int use_abs, float* grad_sum, float* count,
+                      float* max_radius);
+
+typedef struct gs_adc_params {
+    float grad_threshold;   /* densify where grad_sum / count >= this (Inria's densify_grad_threshold, 0.0002) */
+    float percent_dense;    /* clone up to, split above, max exp(scale) = percent_dense * scene_extent (0.01) */
+    float min_opacity;      /* prune below this sigmoid(opacity) (0.005) */
+    float max_screen_size;  /* size pruning: prune above this max_radius in pixels (20); <= 0: no screen test */
+    float prune_world;      /* size pruning: prune above max exp(scale) = prune_world * scene_extent (0.1) */
+    float scene_extent;     /* Inria's cameras_extent: 1.1 x the largest distance of a camera from the cameras' mean */
+} gs_adc_params;
+
+/* The decision per Gaussian, in gs_classify_gaussians' words (actions 0 keep / 1 split / 2 clone / 3 prune; output_counts
+ * 1 / 2 / 2 / 0), which it replaces (GaussianTrainer.swift:343-393).  avg = count > 0 ? grad_sum / count : 0,
+ * smax = max exp(scales[i,0..2]), op = sigmoid(opacity); the first that holds:
+ *   1. op < min_opacity                                                                        prune
+ *   2. allow_densify and avg >= grad_threshold          clone if smax <= percent_dense scene_extent, else split
+ *   3. size_prune and (max_radius > max_screen_size or smax > prune_world scene_extent)         prune
+ *   4.                                                                                         keep
+ * (max_screen_size <= 0: no screen test.)  Inria grows first and then prunes the grown set; this one pass differs in two
+ * corners: a Gaussian over the gradient threshold AND over a size bound is split, not pruned, and a split child still over
+ * the world bound lives until the next event.  The two products are taken in float.  GS_ERR_INVALID_ARG: a negative or NaN
+ * threshold, scene_extent not positive and finite, scale_stride < 3, a NULL buffer with N > 0. */
+int gs_adc_classify(gs_ctx* ctx, int N, const float* grad_sum, const float* count, const float* max_radius,
+                    const float* scales, int scale_stride, const float* opacity, const gs_adc_params* params /*HOST*/,
+                    int allow_densify, int size_prune, int* actions, int* output_counts);
+/* gs_densify_gather's sibling, on the same gather_indices / noise_mode (gs_build_densify_output_map) and a noise[total,3]
+ * standard normal (gs_densify_noise); replaces the gather of GaussianTrainer.swift:858-893.  out_X = X[gather_indices], and
+ *   split children (modes 1, 2): xyz + R(q) (exp(scales) * noise[j]), each child with its own row's noise, q the source's
+ *                                rotation over max(|q|, 1e-8) as the projection normalises it; scales + Float(-log 1.6);
+ *   a clone's copy (mode 3):     every parameter copied exactly -- no noise.
+ * revised_opacity (0 / 1; Bulo et al. 2024, gsplat's revised_opacity): every split child and both copies of a clone get the
+ * raw opacity of alpha' with 1 - (1 - alpha')^2 = alpha.  Outputs must not alias inputs.  GS_ERR_INVALID_ARG: total < 0,
+ * K < 1, revised_opacity not 0 or 1, a NULL buffer with total > 0. */
+int gs_adc_gather(gs_ctx* ctx, int total, int K, const float* xyz, const float* features_dc, const float* features_rest,
+                  const float* scales, const float* rotation, const float* opacity, const int* gather_indices,
+                  const int* noise_mode, const float* noise, int revised_opacity, float* out_xyz, float* out_features_dc,
+                  float* out_features_rest, float* out_scales, float* out_rotation, float* out_opacity);
+/* The Adam moments through the event (Inria's _prune_optimizer / cat_tensors_to_optimizer; the reference re-creates the
+ * optimizer state instead, GaussianTrainer.swift:1104-1109): for each of the six tensors t of one moment arena, in the order
+ * xyz, features_dc, features_rest, scales, rotation, opacity (rows of 3, 3, 3 (K - 1), 3, 4, 1 floats),
+ *   out[t][j,:] = noise_mode[j] == 0 && actions[gather_indices[j]] != 1 ? in[t][gather_indices[j],:] : 0
+ * -- a kept Gaussian and a clone's original keep their rows bit for bit, both children of a split and a clone's copy start at
+ * zero.  Called once for the first and once for the second moments.  in / out: HOST arrays of six DEVICE pointers (entry 2
+ * may be NULL when K = 1).  GS_ERR_INVALID_ARG: total < 0, K < 1, a NULL table, a NULL buffer with total > 0. */
+int gs_adc_gather_moments(gs_ctx* ctx, int total, int K, const int* gather_indices, const int* noise_mode, const int* actions,
+                          const float* const in[6] /*HOST*/, float* const out[6] /*HOST*/);
+/* The opacity reset (Inria's reset_opacity): opacity[i] = min(opacity[i], logit(reset_value)) on the raw values -- which is
+ * inverse_sigmoid(min(sigmoid(o), reset_value)) --, and the opacity segment's two moments m_opacity, v_opacity set to 0.
+ * GS_ERR_INVALID_ARG: N < 0, reset_value not in (0, 1), a NULL buffer with N > 0. */
+int gs_adc_reset_opacity(gs_ctx* ctx, int N, float* opacity, float* m_opacity, float* v_opacity, float reset_value);
+
 /* ---- next row: snapshot format ---------------------------------------------------------------
  * Data/PlyWriter.swift: binary little-endian PLY, header comment `features_rest_shape M 3`, vertex = x y z,
  * f_dc_0..2, f_rest_0..3M-1 (coefficient-major, channel-minor: [M][3] flattened, NOT INRIA's channel-major),
