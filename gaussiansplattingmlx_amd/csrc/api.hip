@@ -478,11 +478,6 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     }
     if (const char* e = getenv("GSPLAT_COLOUR_RIDERS")) c->colourRiders = atoi(e);      // tuning experiments (tools/rider_ab.py)
     if (const char* e = getenv("GSPLAT_FWD_WIDE")) c->fwdWide = atoi(e) < 0 ? -1 : atoi(e) != 0;
-    if (const char* e = getenv("GSPLAT_RANK_SORT")) c->rankSort = atoi(e) != 0;
-    if (const char* e = getenv("GSPLAT_FWD_SPATIAL")) c->fwdSpatial = atoi(e) != 0;
-    if (const char* e = getenv("GSPLAT_LSD_THREADS")) { const int v = atoi(e); c->lsdThreads = (v == 256 || v == 1024) ? v : 0; }
-    if (const char* e = getenv("GSPLAT_SCATTER_THREADS")) { const int v = atoi(e); c->scatterThreads = (v == 256 || v == 512 || v == 1024) ? v : 0; }
-    if (const char* e = getenv("GSPLAT_BWD_QUEUES")) { const int q = atoi(e); if (q == 1 || q == 2 || q == 4 || q == 8) c->bwdQueues = q; }
     if (const char* e = getenv("GSPLAT_FWD_QUEUES")) { const int q = atoi(e); if (q == 1 || q == 2 || q == 4 || q == 8) c->fwdQueues = q; }
     if (const char* e = getenv("GSPLAT_RIDER_SHARES")) {      // tuning experiments: permille of the colour units per host kernel
         // exactly GS_RIDE_HOSTS comma-separated values, in the enum's order (ss_hist, ss_scatter, wide_tile); anything else
@@ -519,14 +514,12 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             c->numCUs = prop.multiProcessorCount;
     }
-    if (const char* e = getenv("GSPLAT_CUT_SUPER")) c->cutSuper = atoi(e) != 0;
     if (dev_alloc(c, &c->superCut, (size_t)c->T + 16) || dev_alloc(c, &c->tileRanges, (size_t)c->T * 2) || dev_alloc(c, &c->tileCounts, (size_t)c->T) ||
         dev_alloc(c, &c->lastContrib, P) ||
         dev_alloc(c, &c->lossPartials, (size_t)(c->lossPartialBlocks = gs_div_up(W, 16) * gs_div_up(H, 16) * 3) * 4 + 16) || dev_alloc(c, &c->windowDev, 121) ||
         dev_alloc(c, &c->counters, GS_CNT_COUNT) || dev_alloc(c, &c->rowTotal, 256) ||
         dev_alloc(c, &c->sortBits, GS_SMALL_SORT_BLOCKS) || dev_alloc(c, &c->wideTotal, GS_WIDE_BINS) ||
-        dev_alloc(c, &c->bucketStart, 520) || dev_alloc(c, &c->sortSplit[0], 256) || dev_alloc(c, &c->sortSplit[1], 256) ||
-        dev_alloc(c, &c->ssChunk, 65 * 512))
+        dev_alloc(c, &c->bucketStart, 520) || dev_alloc(c, &c->sortSplit[0], 256) || dev_alloc(c, &c->sortSplit[1], 256))
         return bail(GS_ERR_HIP);
     if (hipHostMalloc((void**)&c->countersHost, sizeof(uint32_t) * GS_CNT_COUNT) != hipSuccess) return bail(GS_ERR_HIP);
     // the depth cuts' miss word: host memory the forward kernel writes directly, read after the fwdDone event
@@ -553,7 +546,7 @@ int gs_ctx_destroy(gs_ctx* c)
     free_gaussian_ws(c);
     free_pair_ws(c);
     dev_free(c->segState);
-    dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk); dev_free(c->wideTotal); dev_free(c->rowTotal); dev_free(c->sortBits); dev_free(c->bucketStart); dev_free(c->ssChunk); dev_free(c->sortSplit[0]); dev_free(c->sortSplit[1]); dev_free(c->tileRanges); dev_free(c->tileCounts); dev_free(c->superCut);
+    dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk); dev_free(c->wideTotal); dev_free(c->rowTotal); dev_free(c->sortBits); dev_free(c->bucketStart); dev_free(c->sortSplit[0]); dev_free(c->sortSplit[1]); dev_free(c->tileRanges); dev_free(c->tileCounts); dev_free(c->superCut);
     dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->metricsWs); dev_free(c->windowDev);
     dev_free(c->counters); dev_free(c->blockWorkOwn); dev_free(c->blockOrder); dev_free(c->fwdQueue); dev_free(c->bwdQueue); dev_free(c->segBase); dev_free(c->finalT);
     for (auto& e : c->profPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -1834,7 +1827,7 @@ int gs_ctx_set_tuning(gs_ctx* c, int knob, long long value)
     case GS_TUNE_HOST_OVERFLOW_ERRORS:
         c->hostOverflowErrors = value != 0; return GS_OK;
     case GS_TUNE_SPLITTER_DEPTH_SORT:
-        c->splitterSort = value < 0 ? 0 : (value > 2 ? 2 : (int)value); c->haveSplitters = false; return GS_OK;
+        c->splitterSort = value > 0; c->haveSplitters = false; return GS_OK;      // (2, once a second form, is 1)
     case GS_TUNE_COLOUR_RIDERS:
         c->colourRiders = (int)value; return GS_OK;
     case GS_TUNE_FWD_FOLD_TEST_SCALE:

@@ -385,7 +385,7 @@ __global__ __launch_bounds__(GS_SCAN_BLOCK) void expand_kernel(int N, int gridW,
         // the Gaussians that are not beyond every super-cut of theirs: cut_super_kernel)
         const uint32_t myKey = i < N ? sortedKey[i] : 0u;
         ushort4 rr = area ? tileRect[g] : make_ushort4(0, 0, 1, 1);
-        if (area && superCut) {
+        if (area) {
             bool reach = false;
             const int sx1 = (rr.z - 1) / GS_CUT_SUPER, sy1 = (rr.w - 1) / GS_CUT_SUPER;
             for (int sy = rr.y / GS_CUT_SUPER; sy <= sy1 && !reach; sy++)
@@ -812,122 +812,21 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_kernel(
     }
 }
 
-// ---- the depth sort of at most GS_TINY_SORT_MAX records: ONE workgroup, one launch ---------------------------
-// 10 k Gaussians are three sort tiles: the eight launches of the passes above were eight kernel boundaries with three
-// busy CUs each (58 us of the 10 k / 400x400 forward's 294).  Here sixteen waves keep the records in registers (wave w
-// owns the contiguous records [w T/16, (w+1) T/16), as in radix_scatter_kernel), rank them per pass with the same
-// wave-private match tables, exchange them through one LDS copy and read them back in place; bytes that are the same
-// in every real key are skipped (their pass is the identity on a stable sort).  Same order as the multi-launch path,
-// bit for bit (tests/test_gpu_parity.py::test_tile_bin_bit_exact runs N = 3000 and 6000 through it).
-constexpr int GS_TINY_THREADS = 1024, GS_TINY_ITEMS = 16, GS_TINY_SORT_MAX = GS_TINY_THREADS * GS_TINY_ITEMS;
-__global__ __launch_bounds__(GS_TINY_THREADS) void radix_sort_tiny_kernel(const uint32_t* __restrict__ keysIn,
-                                                                           const uint32_t* __restrict__ valsIn,
-                                                                           uint32_t* __restrict__ keysOut,
-                                                                           uint32_t* __restrict__ valsOut, uint32_t n)
-{
-    constexpr int NW = GS_TINY_THREADS / 64, PER_WAVE = GS_TINY_SORT_MAX / NW;        // 16 waves x 1024 records
-    __shared__ __attribute__((aligned(16))) uint32_t keyS[GS_TINY_SORT_MAX];          // doubles as the match tables
-    __shared__ uint32_t valS[GS_TINY_SORT_MAX];
-    __shared__ uint32_t waveRun[NW][256];          // per wave: running count of digit d, then its first position
-    __shared__ uint32_t sm[4];
-    __shared__ uint32_t sBits[2];
-    unsigned long long (*match)[256] = reinterpret_cast<unsigned long long (*)[256]>(keyS);
-    static_assert(sizeof(unsigned long long) * NW * 256 <= sizeof(keyS), "match tables must fit in keyS");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const unsigned long long myBit = 1ull << lane;
-    uint32_t key[GS_TINY_ITEMS], val[GS_TINY_ITEMS], rank[GS_TINY_ITEMS];
-    const uint32_t lastIdx = n - 1u;
-    uint32_t a = 0xFFFFFFFFu, o = 0u;
-#pragma unroll
-    for (int r = 0; r < GS_TINY_ITEMS; r++) {      // unconditional loads from clamped addresses
-        const uint32_t i = (uint32_t)(w * PER_WAVE + r * 64 + lane);
-        key[r] = keysIn[min(i, lastIdx)];
-        val[r] = valsIn[min(i, lastIdx)];
-        if (i < n && key[r] != GS_SORT_NO_KEY) { a &= key[r]; o |= key[r]; }
-    }
-    if (tid == 0) { sBits[0] = 0xFFFFFFFFu; sBits[1] = 0u; }
-    __syncthreads();
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a &= (uint32_t)__shfl_xor((int)a, d, 64); o |= (uint32_t)__shfl_xor((int)o, d, 64); }
-    if (lane == 0) { atomicAnd(&sBits[0], a); atomicOr(&sBits[1], o); }
-    __syncthreads();
-    const uint32_t varying = sBits[0] ^ sBits[1];          // bits that differ among the keys that have pairs
-    for (int shift = 0; shift < 32; shift += 8) {
-        if (shift != 0 && ((varying >> shift) & 255u) == 0u) continue;       // block-uniform
-        for (int d = tid; d < NW * 256; d += GS_TINY_THREADS) { (&waveRun[0][0])[d] = 0u; (&match[0][0])[d] = 0ull; }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < GS_TINY_ITEMS; r++) {
-            const uint32_t i = (uint32_t)(w * PER_WAVE + r * 64 + lane);
-            const bool valid = i < n;
-            const uint32_t d = valid ? (key[r] >> shift) & 255u : 0u;
-            if (valid) atomicOr(&match[w][d], myBit);
-            const unsigned long long peers = valid ? reinterpret_cast<volatile unsigned long long*>(&match[w][0])[d] : 0ull;
-            const uint32_t before = valid ? reinterpret_cast<volatile uint32_t*>(&waveRun[w][0])[d] : 0u;
-            const uint32_t inRound = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
-            rank[r] = before + inRound;                  // rank among the wave's records of digit d
-            if (valid && inRound == 0) {                 // group leader, after every lane's reads (program order)
-                match[w][d] = 0ull;
-                waveRun[w][d] = before + (uint32_t)__popcll(peers);
-            }
-        }
-        __syncthreads();
-        // thread d < 256 (the first four waves): first position of digit d, then of every wave's share of it
-        uint32_t c[NW], tot = 0, incl = 0;
-        if (tid < 256) {
-#pragma unroll
-            for (int k = 0; k < NW; k++) { c[k] = waveRun[k][tid]; tot += c[k]; }
-            incl = wave_incl_scan(tot);
-            if (lane == 63) sm[w] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-            uint32_t run = incl - tot;
-            for (int k = 0; k < w; k++) run += sm[k];
-#pragma unroll
-            for (int k = 0; k < NW; k++) { waveRun[k][tid] = run; run += c[k]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < GS_TINY_ITEMS; r++) {
-            const uint32_t i = (uint32_t)(w * PER_WAVE + r * 64 + lane);
-            if (i < n) {
-                const uint32_t d = (key[r] >> shift) & 255u;
-                const uint32_t pos = waveRun[w][d] + rank[r];
-                keyS[pos] = key[r];
-                valS[pos] = val[r];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < GS_TINY_ITEMS; r++) {
-            const uint32_t i = (uint32_t)(w * PER_WAVE + r * 64 + lane);
-            if (i < n) { key[r] = keyS[i]; val[r] = valS[i]; }
-        }
-        __syncthreads();          // keyS doubles as the next pass's match tables
-    }
-#pragma unroll
-    for (int r = 0; r < GS_TINY_ITEMS; r++) {
-        const uint32_t i = (uint32_t)(w * PER_WAVE + r * 64 + lane);
-        if (i < n) { keysOut[i] = key[r]; valsOut[i] = val[r]; }
-    }
-}
-
-// ---- the depth sort of at most GS_TINY_SORT_MAX records by RANK (round 4): one launch on the whole chip --------------------
+// ---- the depth sort of at most GS_RANK_SORT_MAX records by RANK (round 4): one launch on the whole chip --------------------
 // The position of record i in the stable sort is the number of records j with key_j < key_i, or key_j == key_i and j < i.
 // N^2 compares are nothing at these sizes (10 k records: 2 x 10^8 / 64 wave-instructions = 5 us of the chip's issue slots)
-// and, unlike the passes of radix_sort_tiny_kernel (26 us on ONE CU, each pass a chain of LDS round trips), they spread:
+// and, unlike the passes of a radix sort in one workgroup (26 us on ONE CU, each pass a chain of LDS round trips), they spread:
 // workgroup b owns the 64 records [64 b, 64 b + 64), keeps ALL keys in LDS, and its sixteen waves count over a sixteenth of
 // the keys each -- the keys come as broadcast 16-byte LDS reads, the tie-break only where j can be below i (the slice that
 // holds the workgroup's own records; before it every key counts if <=, behind it if <) --, sum in LDS and store the 64
 // records at their ranks.  Same order as the LSD passes, bit for bit (the binning tests run N = 1 ... 16384 through it).
-constexpr int GS_RANK_THREADS = 1024;
+constexpr int GS_RANK_THREADS = 1024, GS_RANK_SORT_MAX = 16384;      // (every key in one workgroup's LDS: 64 KB)
 __global__ __launch_bounds__(GS_RANK_THREADS) void rank_sort_kernel(const uint32_t* __restrict__ keysIn,
                                                                      const uint32_t* __restrict__ valsIn,
                                                                      uint32_t* __restrict__ keysOut,
                                                                      uint32_t* __restrict__ valsOut, uint32_t n)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t keyS[GS_TINY_SORT_MAX];
+    __shared__ __attribute__((aligned(16))) uint32_t keyS[GS_RANK_SORT_MAX];
     __shared__ uint32_t cnt[GS_RANK_THREADS / 64][64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t n4 = (n + 3u) & ~3u;
@@ -984,30 +883,29 @@ __global__ __launch_bounds__(GS_RANK_THREADS) void rank_sort_kernel(const uint32
 // digit cut out of the key's bits does not work for float depths: the highest bit in which two depths differ is an
 // exponent bit, and one octave's bucket then holds most of the scene -- measured 0.20 -> 0.56 ms)
 // A context's first depth sort has no splitters yet and takes the LSD passes, followed by ss_refresh_kernel.
-// NS splitters make NB = 2 (NS + 1) buckets: 127 / 256 up to GS_SMALL_SORT_BLOCKS sort tiles (655 k records), 255 / 512 above
-// (round 4: a bucket should hold a few thousand records -- at 1 M records 256 buckets of 7.8 k each overran the local sort's
-// register path, at 2 M they would hold 15.6 k).
-template <int NS>
-__device__ __forceinline__ uint32_t ss_bucket_of(const uint32_t* __restrict__ sp /*LDS, [NS + 1], sp[NS] = 0xFFFFFFFF*/, uint32_t key)
+// Larger sorts stay with the LSD passes: a bucket should hold a few thousand records (at 1 M records 256 buckets of 7.8 k
+// each overrun the local sort's register path), and more buckets measure slower than the LSD passes of those sizes
+// (EXPERIMENTS.md).
+constexpr int GS_SS_SPLITTERS = 127, GS_SS_BUCKETS = 2 * (GS_SS_SPLITTERS + 1);      // a bucket id is a byte, a bucket a thread
+static_assert(GS_SS_BUCKETS == GS_SORT_THREADS, "ss_scatter_kernel: thread d owns bucket d");
+
+__device__ __forceinline__ uint32_t ss_bucket_of(const uint32_t* __restrict__ sp /*LDS, [128], sp[127] = 0xFFFFFFFF*/, uint32_t key)
 {
     uint32_t lo = 0;
 #pragma unroll
-    for (uint32_t step = (NS + 1) / 2; step >= 1; step >>= 1)
-        if (sp[lo + step - 1] < key) lo += step;              // lo = number of splitters below the key, 0 .. NS
-    return 2u * lo + ((lo < (uint32_t)NS && sp[lo] == key) ? 1u : 0u);
+    for (uint32_t step = (GS_SS_SPLITTERS + 1) / 2; step >= 1; step >>= 1)
+        if (sp[lo + step - 1] < key) lo += step;              // lo = number of splitters below the key, 0 .. 127
+    return 2u * lo + ((lo < (uint32_t)GS_SS_SPLITTERS && sp[lo] == key) ? 1u : 0u);
 }
 
-template <int NS> struct SsBucketId { typedef unsigned char type; };
-template <> struct SsBucketId<255> { typedef unsigned short type; };
-
-template <int ITEMS, int NS>
+template <int ITEMS>
 __global__ __launch_bounds__(GS_SORT_THREADS) void ss_hist_kernel(const uint32_t* __restrict__ keys, uint32_t n,
                                                                   const uint32_t* __restrict__ splitters,
-                                                                  typename SsBucketId<NS>::type* __restrict__ bucketId,
+                                                                  unsigned char* __restrict__ bucketId,
                                                                   uint32_t* __restrict__ histB, ColourRider rider, int ownBlocks)
 {
     if ((int)blockIdx.x >= ownBlocks) { colour_rider_block(rider, (int)blockIdx.x - ownBlocks); return; }   // gs_rider.h
-    constexpr int NB = 2 * (NS + 1);
+    constexpr int NS = GS_SS_SPLITTERS, NB = GS_SS_BUCKETS;
     __shared__ uint32_t h[NB];
     __shared__ uint32_t sp[NS + 1];
     GS_PROBE_MARK(3072 + blockIdx.x, 0);
@@ -1037,7 +935,7 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_hist_kernel(const uint32_t
         const uint32_t i = base + r * GS_SORT_THREADS + threadIdx.x;
         if (i < n) {
             const uint32_t b = 2u * lo[r] + ((lo[r] < (uint32_t)NS && sp[lo[r]] == k[r]) ? 1u : 0u);
-            bucketId[i] = (typename SsBucketId<NS>::type)b;
+            bucketId[i] = (unsigned char)b;
             atomicAdd(&h[b], 1u);
         }
     }
@@ -1047,41 +945,16 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_hist_kernel(const uint32_t
     GS_PROBE_MARK(3072 + blockIdx.x, 2);
 }
 
-// Many sort tiles (BIG, more than GS_SMALL_SORT_BLOCKS): every scatter block summing the histogram rows of ALL the blocks
-// before it is quadratic in the tile count (245 rows at 1 M records, 489 at 2 M; round 3 measured binning 0.31 -> 0.52 ms
-// with it).  One small launch in between: block c turns the rows of its GS_SS_CHUNK tiles into exclusive prefixes inside
-// the chunk (in place) and writes the chunk's totals; a scatter block then sums the totals of the chunks before its own
-// -- 1/16 of the rows -- and adds its row.
-constexpr int GS_SS_CHUNK = 16;
-template <int NB>
-__global__ __launch_bounds__(256) void ss_colscan_kernel(int nb, uint32_t* __restrict__ histB, uint32_t* __restrict__ chunkTot)
-{
-    const int b0 = blockIdx.x * GS_SS_CHUNK;
-    const int d = blockIdx.y * 256 + threadIdx.x;
-    uint32_t v[GS_SS_CHUNK];
-#pragma unroll
-    for (int k = 0; k < GS_SS_CHUNK; k++) v[k] = b0 + k < nb ? histB[(size_t)(b0 + k) * NB + d] : 0u;
-    uint32_t run = 0;
-#pragma unroll
-    for (int k = 0; k < GS_SS_CHUNK; k++) {
-        if (b0 + k < nb) histB[(size_t)(b0 + k) * NB + d] = run;
-        run += v[k];
-    }
-    chunkTot[(size_t)blockIdx.x * NB + d] = run;
-}
-
 // radix_scatter_kernel<true, true, ITEMS> with the digit read from bucketId instead of cut out of the key
-template <int ITEMS, int NS, bool BIG>
+template <int ITEMS>
 __global__ __launch_bounds__(GS_SORT_THREADS) void ss_scatter_kernel(
-    const uint32_t* __restrict__ keysIn, const uint32_t* __restrict__ valsIn, const typename SsBucketId<NS>::type* __restrict__ bucketId,
+    const uint32_t* __restrict__ keysIn, const uint32_t* __restrict__ valsIn, const unsigned char* __restrict__ bucketId,
     uint32_t* __restrict__ keysOut, uint32_t* __restrict__ valsOut, uint32_t n, const uint32_t* __restrict__ histB,
-    const uint32_t* __restrict__ chunkTot, uint32_t* __restrict__ bucketStart, uint32_t* __restrict__ oob, ColourRider rider,
-    int ownBlocks)
+    uint32_t* __restrict__ bucketStart, uint32_t* __restrict__ oob, ColourRider rider, int ownBlocks)
 {
     if ((int)blockIdx.x >= ownBlocks) { colour_rider_block(rider, (int)blockIdx.x - ownBlocks); return; }   // gs_rider.h
-    constexpr int NB = 2 * (NS + 1), DPT = NB / GS_SORT_THREADS;       // buckets, buckets owned per thread (1 or 2)
+    constexpr int NB = GS_SS_BUCKETS;
     constexpr int TILE = GS_SORT_THREADS * ITEMS, PER_WAVE = TILE / 4;
-    typedef typename SsBucketId<NS>::type BId;
     __shared__ uint32_t digitBase[NB];
     __shared__ uint32_t blockStart[NB];
     __shared__ uint32_t waveRun[4][NB];
@@ -1089,7 +962,7 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_scatter_kernel(
     unsigned long long (*match)[NB] = reinterpret_cast<unsigned long long (*)[NB]>(keyS);
     static_assert(sizeof(unsigned long long) * 4 * NB <= sizeof(keyS), "match tables must fit in keyS");
     __shared__ uint32_t valS[TILE];
-    __shared__ BId digS[TILE];
+    __shared__ unsigned char digS[TILE];
     __shared__ uint32_t sm[8];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t tile = blockIdx.x, base = tile * TILE;
@@ -1111,34 +984,16 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_scatter_kernel(
         val[r] = valsIn[min(i, lastIdx)];
         dig[r] = bucketId[min(i, lastIdx)];
     }
-    // records of every bucket in all the sort tiles (total) and in the tiles before this one (before): rows of global
+    // records of this thread's bucket in all the sort tiles (total) and in the tiles before this one (before): rows of global
     // memory that are ready when the kernel starts -- summed HERE, under the latency of the key loads above and ahead of the
-    // ranking chain, not between the ranking and the stores (12.3 -> 10.x us per block alone on its CU)
-    uint32_t before[DPT], total[DPT];
-#pragma unroll
-    for (int j = 0; j < DPT; j++) { before[j] = 0; total[j] = 0; }
-    if (BIG) {
-        const int nc = (ownBlocks + GS_SS_CHUNK - 1) / GS_SS_CHUNK, myc = (int)tile / GS_SS_CHUNK;
-#pragma unroll 4
-        for (int cc = 0; cc < nc; cc++)
-#pragma unroll
-            for (int j = 0; j < DPT; j++) {
-                const uint32_t x = chunkTot[(size_t)cc * NB + tid * DPT + j];
-                total[j] += x;
-                before[j] += cc < myc ? x : 0u;
-            }
-#pragma unroll
-        for (int j = 0; j < DPT; j++) before[j] += histB[(size_t)tile * NB + tid * DPT + j];      // prefix inside the chunk
-    } else {
-        const int nb = ownBlocks;
+    // ranking chain, not between the ranking and the stores (12.3 -> 10.x us per block alone on its CU).  Every block sums the
+    // rows of ALL the blocks: quadratic in the tile count, which is why the form ends at GS_SMALL_SORT_BLOCKS tiles.
+    uint32_t before = 0, total = 0;
 #pragma unroll 16
-        for (int b = 0; b < nb; b++)
-#pragma unroll
-            for (int j = 0; j < DPT; j++) {
-                const uint32_t x = histB[(size_t)b * NB + tid * DPT + j];
-                total[j] += x;
-                before[j] += b < (int)tile ? x : 0u;
-            }
+    for (int b = 0; b < ownBlocks; b++) {
+        const uint32_t x = histB[(size_t)b * NB + tid];
+        total += x;
+        before += b < (int)tile ? x : 0u;
     }
 #pragma unroll
     for (int r = 0; r < ITEMS; r++) {
@@ -1157,36 +1012,16 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_scatter_kernel(
     }
     __syncthreads();
     GS_PROBE_MARK(3328 + blockIdx.x, 1);
-    {   // thread tid owns the DPT consecutive buckets from DPT tid on: block histogram, wave offsets, block and global bases
-        uint32_t c[DPT][4], cs[DPT], sum = 0;
-#pragma unroll
-        for (int j = 0; j < DPT; j++) {
-            const int d = tid * DPT + j;
-            c[j][0] = waveRun[0][d]; c[j][1] = waveRun[1][d]; c[j][2] = waveRun[2][d]; c[j][3] = waveRun[3][d];
-            cs[j] = c[j][0] + c[j][1] + c[j][2] + c[j][3];
-            sum += cs[j];
-        }
+    {   // thread tid owns bucket tid: block histogram, wave offsets, block and global bases
+        const uint32_t c0 = waveRun[0][tid], c1 = waveRun[1][tid], c2 = waveRun[2][tid], c3 = waveRun[3][tid];
         uint32_t tot;
-        uint32_t ls = block_excl_scan(sum, sm, &tot);
-#pragma unroll
-        for (int j = 0; j < DPT; j++) {
-            const int d = tid * DPT + j;
-            blockStart[d] = ls;
-            waveRun[0][d] = ls; waveRun[1][d] = ls + c[j][0]; waveRun[2][d] = ls + c[j][0] + c[j][1];
-            waveRun[3][d] = ls + c[j][0] + c[j][1] + c[j][2];
-            ls += cs[j];
-        }
-        uint32_t tsum = 0;
-#pragma unroll
-        for (int j = 0; j < DPT; j++) tsum += total[j];
-        uint32_t gs = block_excl_scan(tsum, sm, &tot);
-#pragma unroll
-        for (int j = 0; j < DPT; j++) {
-            const int d = tid * DPT + j;
-            digitBase[d] = gs + before[j];
-            if (tile == 0) bucketStart[d] = gs;     // first record of every bucket, for the local sorts behind this pass
-            gs += total[j];
-        }
+        const uint32_t ls = block_excl_scan(c0 + c1 + c2 + c3, sm, &tot);
+        blockStart[tid] = ls;
+        waveRun[0][tid] = ls; waveRun[1][tid] = ls + c0; waveRun[2][tid] = ls + c0 + c1;
+        waveRun[3][tid] = ls + c0 + c1 + c2;
+        const uint32_t gs = block_excl_scan(total, sm, &tot);
+        digitBase[tid] = gs + before;
+        if (tile == 0) bucketStart[tid] = gs;     // first record of every bucket, for the local sorts behind this pass
         if (tile == 0 && tid == GS_SORT_THREADS - 1) bucketStart[NB] = n;
     }
     __syncthreads();
@@ -1196,7 +1031,7 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_scatter_kernel(
         const uint32_t i = w * PER_WAVE + r * 64 + lane;
         if (i < cnt) {
             const uint32_t pos = waveRun[w][dig[r]] + rank[r];
-            keyS[pos] = key[r]; valS[pos] = val[r]; digS[pos] = (BId)dig[r];
+            keyS[pos] = key[r]; valS[pos] = val[r]; digS[pos] = (unsigned char)dig[r];
         }
     }
     __syncthreads();
@@ -1210,20 +1045,18 @@ __global__ __launch_bounds__(GS_SORT_THREADS) void ss_scatter_kernel(
     GS_PROBE_MARK(3328 + blockIdx.x, 3);
 }
 
-// workgroup size of the local sort: 512 threads keep up to 8192 records of a bucket in registers and LDS (73 KB), 1024
-// threads 16384 (144 KB; the 2 M-record sorts, whose buckets average 7.8 k)
-constexpr int GS_BUCKET_ITEMS = 16;
+// workgroup size of the local sort: 512 threads keep up to 8192 records of a bucket in registers and LDS (73 KB)
+constexpr int GS_BUCKET_THREADS = 512, GS_BUCKET_ITEMS = 16;
+constexpr int GS_BUCKET_NW = GS_BUCKET_THREADS / 64, GS_BUCKET_MAX = GS_BUCKET_THREADS * GS_BUCKET_ITEMS;
 
 // One stable LSD pass over the block's `n` records (wave w owns the contiguous records [w perWave, (w + 1) perWave), `rounds`
 // = perWave / 64 register slots per lane): ranks with the wave-private match tables of radix_scatter_kernel, then the
 // digit's first position and every wave's share of it.  Leaves in pos[] every record's position in block-sorted order,
 // in waveRun[0][d] the first position of digit d and in digitCount (thread d < 256) the block's count of digit d.
-template <int GS_BUCKET_THREADS>
 __device__ __forceinline__ void bucket_rank_pass(const uint32_t (&key)[GS_BUCKET_ITEMS], uint32_t n, uint32_t perWave, int rounds,
                                                  int shift, unsigned long long (*match)[256], uint32_t (*waveRun)[256],
                                                  uint32_t* sm, uint32_t (&pos)[GS_BUCKET_ITEMS], uint32_t& digitCount)
 {
-    constexpr int GS_BUCKET_NW = GS_BUCKET_THREADS / 64;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     for (int d = tid; d < GS_BUCKET_NW * 256; d += GS_BUCKET_THREADS) { (&waveRun[0][0])[d] = 0u; (&match[0][0])[d] = 0ull; }
     __syncthreads();
@@ -1274,22 +1107,21 @@ __device__ __forceinline__ void bucket_rank_pass(const uint32_t (&key)[GS_BUCKET
 // the splitters whose ranks fall into [s0, s0 + n), read from `sorted` (the bucket's records in order; LDS or global).
 // Splitter j = the key at rank ceil(j N / (NS + 1)) - 1 of this sort's result.
 // (One 64-bit division per splitter instead of two per record.)
-template <int NS, class Sorted>
+template <class Sorted>
 __device__ __forceinline__ void ss_emit_range(uint32_t* __restrict__ splitNext, uint32_t N, uint32_t s0, uint32_t n, Sorted sorted)
 {
+    constexpr int NS = GS_SS_SPLITTERS;
     for (uint32_t j = threadIdx.x + 1u; j <= (uint32_t)NS; j += blockDim.x) {
         const uint32_t r = (uint32_t)(((unsigned long long)j * N + (unsigned long long)NS) / (unsigned long long)(NS + 1)) - 1u;
         if (r >= s0 && r < s0 + n) splitNext[j - 1u] = sorted(r - s0);
     }
 }
 
-template <int GS_BUCKET_THREADS, int NS>
 __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t* __restrict__ keysA, uint32_t* __restrict__ valsA,
                                                                         uint32_t* __restrict__ keysB, uint32_t* __restrict__ valsB,
                                                                         const uint32_t* __restrict__ bucketStart,
                                                                         uint32_t* __restrict__ splitNext)
 {
-    constexpr int GS_BUCKET_NW = GS_BUCKET_THREADS / 64, GS_BUCKET_MAX = GS_BUCKET_THREADS * GS_BUCKET_ITEMS;
     __shared__ __attribute__((aligned(16))) uint32_t keyS[GS_BUCKET_MAX];              // doubles as the match tables
     __shared__ uint32_t valS[GS_BUCKET_MAX];
     __shared__ uint32_t waveRun[GS_BUCKET_NW][256];
@@ -1299,7 +1131,7 @@ __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t
     unsigned long long (*match)[256] = reinterpret_cast<unsigned long long (*)[256]>(keyS);
     static_assert(sizeof(unsigned long long) * GS_BUCKET_NW * 256 <= sizeof(keyS), "match tables must fit in keyS");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint32_t s0 = bucketStart[blockIdx.x], n = bucketStart[blockIdx.x + 1] - s0, N = bucketStart[2 * (NS + 1)];
+    const uint32_t s0 = bucketStart[blockIdx.x], n = bucketStart[blockIdx.x + 1] - s0, N = bucketStart[GS_SS_BUCKETS];
     if (n == 0u) return;                                         // (block-uniform)
     GS_PROBE_MARK(3584 + blockIdx.x, 0);
     GS_PROBE_VAL(3584 + blockIdx.x, 8, n);
@@ -1309,7 +1141,7 @@ __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t
         // every record of the bucket has the same key: the splitters whose ranks fall into it, without walking it (an
         // "equal" class can be most of the array: the Gaussians without a pair all carry the key 0xFFFFFFFF)
         const uint32_t k0 = keysA[s0];
-        ss_emit_range<NS>(splitNext, N, s0, n, [=](uint32_t) { return k0; });
+        ss_emit_range(splitNext, N, s0, n, [=](uint32_t) { return k0; });
         return;
     }
     if (tid == 0) { sBits[0] = 0xFFFFFFFFu; sBits[1] = 0u; }
@@ -1340,7 +1172,7 @@ __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t
             if (((varying >> shift) & 255u) == 0u) continue;       // block-uniform: the byte is the same in the whole bucket
             inLds = true;
             uint32_t dc;
-            bucket_rank_pass<GS_BUCKET_THREADS>(key, n, perWave, rounds, shift, match, waveRun, sm, pos, dc);
+            bucket_rank_pass(key, n, perWave, rounds, shift, match, waveRun, sm, pos, dc);
             __syncthreads();      // the match tables (in keyS) are dead
 #pragma unroll
             for (int r = 0; r < GS_BUCKET_ITEMS; r++) {
@@ -1364,7 +1196,7 @@ __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t
         GS_PROBE_MARK(3584 + blockIdx.x, 3);
         // (no pass ran: every key of the bucket is the same, sBits[0])
         const uint32_t kAll = sBits[0];
-        ss_emit_range<NS>(splitNext, N, s0, n, [=](uint32_t i) { return inLds ? keyS[i] : kAll; });
+        ss_emit_range(splitNext, N, s0, n, [=](uint32_t i) { return inLds ? keyS[i] : kAll; });
         GS_PROBE_MARK(3584 + blockIdx.x, 4);
         return;
     }
@@ -1409,7 +1241,7 @@ __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t
                 val[r] = vin[min(s0 + t0 + i, lastT)];
             }
             uint32_t dc;
-            bucket_rank_pass<GS_BUCKET_THREADS>(key, nt, perWaveT, GS_BUCKET_ITEMS, shift, match, waveRun, sm, pos, dc);
+            bucket_rank_pass(key, nt, perWaveT, GS_BUCKET_ITEMS, shift, match, waveRun, sm, pos, dc);
             // pos = position in tile-sorted order; the tile's records of digit d start at waveRun[0][d] there and go to
             // base[d] onwards in the bucket
 #pragma unroll
@@ -1431,41 +1263,36 @@ __global__ __launch_bounds__(GS_BUCKET_THREADS) void bucket_sort_kernel(uint32_t
     }
     if (kin != keysA)       // an odd number of passes: the result lies in B's stretch
         for (uint32_t i = tid; i < n; i += GS_BUCKET_THREADS) { keysA[s0 + i] = kin[s0 + i]; valsA[s0 + i] = vin[s0 + i]; }
-    ss_emit_range<NS>(splitNext, N, s0, n, [=](uint32_t i) { return kin[s0 + i]; });
+    ss_emit_range(splitNext, N, s0, n, [=](uint32_t i) { return kin[s0 + i]; });
 }
 
 // splitters for the next depth sort, read off a sorted key array (after the LSD passes of a context's first sort)
-__global__ void ss_refresh_kernel(const uint32_t* __restrict__ sortedKeys, uint32_t N, uint32_t* __restrict__ splitNext, int NS)
+__global__ void ss_refresh_kernel(const uint32_t* __restrict__ sortedKeys, uint32_t N, uint32_t* __restrict__ splitNext)
 {
+    constexpr int NS = GS_SS_SPLITTERS;
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x + 1u;       // splitter j = 1 .. NS at rank ceil(j N / (NS + 1))
     if (j > (uint32_t)NS) return;
     const uint32_t rank = (uint32_t)(((unsigned long long)j * N + (unsigned long long)NS) / (unsigned long long)(NS + 1)) - 1u;      // as ss_emit_range
     splitNext[j - 1u] = sortedKeys[min(rank, N - 1u)];
 }
 
-// true if the depth sort of N records is going to take the splitter buckets (radix_sort below): the kernels the colour
-// riders travel with (projection.hip decides on it before the binning is queued)
-// splitters / buckets of the depth sort of N records: 127 / 256 up to GS_SMALL_SORT_BLOCKS sort tiles, 255 / 512 above
-static inline int ss_splitters_for(int N) { return gs_small_depth_sort((long long)N) ? 127 : 255; }
-constexpr int GS_SPLIT_MAX_TILES = 1024;        // sort tiles (4 M records) up to which the splitter sort is taken (ssChunk's size)
-
+// Which form the depth sort of N records takes is decided here and in depth_sort() below, from N alone:
+//   N <= GS_RANK_SORT_MAX                          rank_sort_kernel
+//   up to GS_SMALL_SORT_BLOCKS sort tiles (655 k)  the splitter buckets; without splitters (a context's first sort, or
+//                                                  GS_TUNE_SPLITTER_DEPTH_SORT = 0) the two-launch LSD passes
+//   beyond                                         the three-launch LSD passes, sixteen waves per tile while the tiles are
+//                                                  no more than the CUs, four beyond that
+// ss_fits: may the depth sort of N records take the splitter buckets once it has splitters?  (the block-major histogram of
+// its sort tiles lies in c->hist: [256][nbCap])
 static bool ss_fits(const gs_ctx* c, int N)
 {
-    // Above GS_SMALL_SORT_BLOCKS sort tiles (655 k records) the 512-bucket form below is bit-exact and SLOWER than the twelve
-    // launches of the LSD passes it replaces (MI355X, round 4: 2 M records 184 us against 115 -- the local sort of 256
-    // buckets of 7.8 k records by 1024-thread workgroups alone takes 132 us --; 1 M records: binning 0.395 against 0.361 ms;
-    // and at these sizes the sort kernels fill the chip, so colour riders only stretch them: EXPERIMENTS.md).  It is kept
-    // behind GS_TUNE_SPLITTER_DEPTH_SORT = 2 for the tests and for A/B runs; 1 (default) takes splitters up to 655 k.
-    if (!gs_small_depth_sort((long long)N) && c->splitterSort < 2) return false;
-    const int nbSmall = gs_div_up(N, GS_SORT_THREADS * GS_SMALL_SORT_ITEMS);
-    const int NB = 2 * (ss_splitters_for(N) + 1);
-    return N > GS_TINY_SORT_MAX && nbSmall <= GS_SPLIT_MAX_TILES && (long long)nbSmall * NB <= 256LL * c->nbCap && c->splitterSort;
+    return c->splitterSort && N > GS_RANK_SORT_MAX && gs_small_depth_sort((long long)N) &&
+           gs_div_up(N, GS_SORT_THREADS * GS_SMALL_SORT_ITEMS) <= c->nbCap;
 }
 
-bool depth_sort_takes_splitters(const gs_ctx* c, int N)
-{
-    return ss_fits(c, N) && c->haveSplitters && c->splitterNS == ss_splitters_for(N);
-}
+// true if the depth sort of N records is going to take the splitter buckets: the kernels the colour riders travel with
+// (projection.hip decides on it before the binning is queued)
+bool depth_sort_takes_splitters(const gs_ctx* c, int N) { return ss_fits(c, N) && c->haveSplitters; }
 
 // A host kernel's share of the forward's outstanding colour units (gs_rider.h): `permille` of all of them, as rider
 // workgroups of `threads` threads behind the kernel's own.
@@ -1484,116 +1311,104 @@ static ColourRider rider_take(gs_ctx* c, int slot, int threads, int* blocks, int
     return a;
 }
 
-// sorts key[0] (and val[0] if hasVals) over key bits [bitLo, bitHi); *resultBuf = index (0/1) of the result buffers
-static int radix_sort(gs_ctx* c, uint32_t* key[2], uint32_t* val[2], bool hasVals, const uint32_t* nPtr, uint32_t nMax,
-                      int bitLo, int bitHi, int* resultBuf)
+// one 8-bit pass of the three-launch LSD sort over n = *nPtr records (nMax where nPtr is null): histogram per sort tile, row
+// scan, and the stable scatter `scatter` (an instantiation of radix_scatter_kernel<*, false, ...> of `threads` threads)
+template <class Scatter>
+static void lsd_pass(gs_ctx* c, Scatter scatter, int threads, const uint32_t* keyIn, const uint32_t* valIn, uint32_t* keyOut,
+                     uint32_t* valOut, const uint32_t* nPtr, uint32_t nMax, int shift)
 {
-    int src = 0;
     const int nbAll = gs_div_up(nMax, GS_SORT_TILE);
-    if (nbAll == 0) { *resultBuf = 0; return GS_OK; }
-    // count known on the host and few tiles (the depth sort of the Gaussians): two launches per pass, constant bytes skipped
-    const int nbSmall = gs_div_up(nMax, GS_SORT_THREADS * GS_SMALL_SORT_ITEMS);
-    if (!nPtr && hasVals && bitLo == 0 && bitHi == 32 && nMax <= (uint32_t)GS_TINY_SORT_MAX) {
-        if (c->rankSort)
-            hipLaunchKernelGGL(rank_sort_kernel, dim3(gs_div_up(nMax, 64)), dim3(GS_RANK_THREADS), 0, c->stream, key[0], val[0], key[1], val[1], nMax);
-        else
-            hipLaunchKernelGGL(radix_sort_tiny_kernel, dim3(1), dim3(GS_TINY_THREADS), 0, c->stream, key[0], val[0], key[1], val[1], nMax);
+    const int nb = nbAll < GS_SORT_MAX_GRID ? nbAll : GS_SORT_MAX_GRID;     // the kernels walk the tiles beyond the grid
+    hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(GS_SORT_THREADS), 0, c->stream, keyIn, nPtr, nMax, shift, c->nbCap, c->hist);
+    hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(256), 0, c->stream, nPtr, nMax, c->nbCap, c->hist, c->rowTotal);
+    hipLaunchKernelGGL(scatter, dim3(nb), dim3(threads), 0, c->stream, keyIn, valIn, keyOut, valOut, nPtr, nMax, shift, c->nbCap,
+                       c->hist, c->rowTotal, nullptr, 0, c->counters + GS_CNT_OVERFLOW);
+}
+
+// The depth sort: the N (depth key, Gaussian index) records of c->depthKey[0] / c->depthVal[0] by the whole key, stable; N is
+// known on the host.  *resultBuf = index (0/1) of the buffers that hold the result.
+static int depth_sort(gs_ctx* c, int N, int* resultBuf)
+{
+    uint32_t** key = c->depthKey;
+    uint32_t** val = c->depthVal;
+    const uint32_t n = (uint32_t)N;
+    if (N <= GS_RANK_SORT_MAX) {
+        hipLaunchKernelGGL(rank_sort_kernel, dim3(gs_div_up(N, 64)), dim3(GS_RANK_THREADS), 0, c->stream, key[0], val[0], key[1], val[1], n);
         GS_HIP_CHECK(c, hipGetLastError());
         *resultBuf = 1;
         return GS_OK;
     }
-    const bool depthSort = !nPtr && hasVals && bitLo == 0 && bitHi == 32;
-    const bool depthSmall = depthSort && gs_small_depth_sort((long long)nMax) && nbSmall <= c->nbCap;
-    if (depthSort && depth_sort_takes_splitters(c, (int)nMax)) {
+    const int nbSmall = gs_div_up(N, GS_SORT_THREADS * GS_SMALL_SORT_ITEMS);
+    if (depth_sort_takes_splitters(c, N)) {
         const uint32_t* split = c->sortSplit[c->splitCur];
         uint32_t* splitNext = c->sortSplit[c->splitCur ^ 1];
-        const bool big = !gs_small_depth_sort((long long)nMax);
         int rb = 0;
         ColourRider ra = rider_take(c, GS_RIDE_SS_HIST, GS_SORT_THREADS, &rb);
-        if (!big) {
-            hipLaunchKernelGGL((ss_hist_kernel<GS_SMALL_SORT_ITEMS, 127>), dim3(nbSmall + rb), dim3(GS_SORT_THREADS), 0, c->stream, key[0], nMax, split,
-                               reinterpret_cast<unsigned char*>(c->bucketId), c->hist, ra, nbSmall);
-            ra = rider_take(c, GS_RIDE_SS_SCATTER, GS_SORT_THREADS, &rb);
-            hipLaunchKernelGGL((ss_scatter_kernel<GS_SMALL_SORT_ITEMS, 127, false>), dim3(nbSmall + rb), dim3(GS_SORT_THREADS), 0, c->stream, key[0], val[0],
-                               reinterpret_cast<const unsigned char*>(c->bucketId), key[1], val[1], nMax, c->hist, nullptr, c->bucketStart,
-                               c->counters + GS_CNT_OVERFLOW, ra, nbSmall);
-            hipLaunchKernelGGL((bucket_sort_kernel<512, 127>), dim3(255), dim3(512), 0, c->stream, key[1], val[1], key[0], val[0],
-                               c->bucketStart, splitNext);
-        } else {
-            // more than GS_SMALL_SORT_BLOCKS sort tiles: 512 buckets, and a chunk scan of the histogram rows between the two
-            // passes (four launches; the LSD passes of this size are twelve)
-            hipLaunchKernelGGL((ss_hist_kernel<GS_SMALL_SORT_ITEMS, 255>), dim3(nbSmall + rb), dim3(GS_SORT_THREADS), 0, c->stream, key[0], nMax, split,
-                               reinterpret_cast<unsigned short*>(c->bucketId), c->hist, ra, nbSmall);
-            hipLaunchKernelGGL((ss_colscan_kernel<512>), dim3(gs_div_up(nbSmall, GS_SS_CHUNK), 2), dim3(256), 0, c->stream, nbSmall, c->hist, c->ssChunk);
-            ra = rider_take(c, GS_RIDE_SS_SCATTER, GS_SORT_THREADS, &rb);
-            hipLaunchKernelGGL((ss_scatter_kernel<GS_SMALL_SORT_ITEMS, 255, true>), dim3(nbSmall + rb), dim3(GS_SORT_THREADS), 0, c->stream, key[0], val[0],
-                               reinterpret_cast<const unsigned short*>(c->bucketId), key[1], val[1], nMax, c->hist, c->ssChunk, c->bucketStart,
-                               c->counters + GS_CNT_OVERFLOW, ra, nbSmall);
-            if (nMax <= 1400000u)        // buckets of ~N / 256 records: 8192 hold them with room up to 1.4 M, 16384 beyond
-                hipLaunchKernelGGL((bucket_sort_kernel<512, 255>), dim3(511), dim3(512), 0, c->stream, key[1], val[1], key[0], val[0],
-                                   c->bucketStart, splitNext);
-            else
-                hipLaunchKernelGGL((bucket_sort_kernel<1024, 255>), dim3(511), dim3(1024), 0, c->stream, key[1], val[1], key[0], val[0],
-                                   c->bucketStart, splitNext);
-        }
+        hipLaunchKernelGGL(ss_hist_kernel<GS_SMALL_SORT_ITEMS>, dim3(nbSmall + rb), dim3(GS_SORT_THREADS), 0, c->stream, key[0], n, split,
+                           c->bucketId, c->hist, ra, nbSmall);
+        ra = rider_take(c, GS_RIDE_SS_SCATTER, GS_SORT_THREADS, &rb);
+        hipLaunchKernelGGL(ss_scatter_kernel<GS_SMALL_SORT_ITEMS>, dim3(nbSmall + rb), dim3(GS_SORT_THREADS), 0, c->stream, key[0], val[0],
+                           c->bucketId, key[1], val[1], n, c->hist, c->bucketStart, c->counters + GS_CNT_OVERFLOW, ra, nbSmall);
+        hipLaunchKernelGGL(bucket_sort_kernel, dim3(GS_SS_BUCKETS - 1), dim3(GS_BUCKET_THREADS), 0, c->stream, key[1], val[1], key[0],
+                           val[0], c->bucketStart, splitNext);
         GS_HIP_CHECK(c, hipGetLastError());
         c->splitCur ^= 1;
         *resultBuf = 1;
         return GS_OK;
     }
-    // no splitters yet (a context's first depth sort, or the record count has crossed the 127 / 255 boundary): the LSD
-    // passes, then the splitters for the sorts behind it read off the sorted keys
-    const bool wantSplitters = depthSort && ss_fits(c, (int)nMax);
-    if (!nPtr && hasVals && gs_small_depth_sort((long long)nMax) && nbSmall <= c->nbCap) {
-        for (int shift = bitLo; shift < bitHi; shift += 8) {
-            const bool first = shift == bitLo;
+    int src = 0;
+    if (gs_small_depth_sort((long long)N) && nbSmall <= c->nbCap) {
+        // few tiles: two launches per pass, bytes that are the same in every real key skipped
+        for (int shift = 0; shift < 32; shift += 8) {
+            const bool first = shift == 0;
             if (first)
                 hipLaunchKernelGGL((radix_hist_small_kernel<true, GS_SMALL_SORT_ITEMS>), dim3(nbSmall), dim3(GS_SORT_THREADS), 0,
-                                   c->stream, key[src], nMax, shift, c->hist, c->sortBits);
+                                   c->stream, key[src], n, shift, c->hist, c->sortBits);
             else
                 hipLaunchKernelGGL((radix_hist_small_kernel<false, GS_SMALL_SORT_ITEMS>), dim3(nbSmall), dim3(GS_SORT_THREADS), 0,
-                                   c->stream, key[src], nMax, shift, c->hist, c->sortBits);
+                                   c->stream, key[src], n, shift, c->hist, c->sortBits);
             hipLaunchKernelGGL((radix_scatter_kernel<true, true, GS_SMALL_SORT_ITEMS>), dim3(nbSmall), dim3(GS_SORT_THREADS), 0,
-                               c->stream, key[src], val[src], key[src ^ 1], val[src ^ 1], nullptr, nMax, shift, c->nbCap, c->hist,
+                               c->stream, key[src], val[src], key[src ^ 1], val[src ^ 1], nullptr, n, shift, c->nbCap, c->hist,
                                nullptr, c->sortBits, first ? 1 : 0, c->counters + GS_CNT_OVERFLOW);
             src ^= 1;
         }
-        if (depthSmall && wantSplitters) {
-            hipLaunchKernelGGL(ss_refresh_kernel, dim3(1), dim3(256), 0, c->stream, key[src], nMax, c->sortSplit[c->splitCur], 127);
+        if (ss_fits(c, N)) {      // no splitters yet: those of the sorts behind this one, read off the sorted keys
+            hipLaunchKernelGGL(ss_refresh_kernel, dim3(1), dim3(256), 0, c->stream, key[src], n, c->sortSplit[c->splitCur]);
             c->haveSplitters = true;
-            c->splitterNS = 127;
         }
-        GS_HIP_CHECK(c, hipGetLastError());
-        *resultBuf = src;
-        return GS_OK;
+    } else {
+        // sixteen waves per tile while there is at most one tile per CU (82 KB of LDS: one block per CU).  MI355X: 1 M records /
+        // 245 tiles 12.7 -> 10.7 us per pass, 2 M / 489 tiles 15.3 -> 18.6
+        const bool wide = gs_div_up(N, GS_SORT_TILE) <= c->numCUs;
+        for (int shift = 0; shift < 32; shift += 8) {
+            if (wide)
+                lsd_pass(c, radix_scatter_kernel<true, false, GS_SORT_ITEMS / 4, 1024>, 1024, key[src], val[src], key[src ^ 1], val[src ^ 1],
+                         nullptr, n, shift);
+            else
+                lsd_pass(c, radix_scatter_kernel<true, false, GS_SORT_ITEMS>, GS_SORT_THREADS, key[src], val[src], key[src ^ 1],
+                         val[src ^ 1], nullptr, n, shift);
+            src ^= 1;
+        }
     }
-    const int nb = nbAll < GS_SORT_MAX_GRID ? nbAll : GS_SORT_MAX_GRID;     // the kernels walk the tiles beyond the grid
-    // sixteen waves per tile while there is at most one tile per CU (82 KB of LDS: one block per CU).  MI355X: 1 M records /
-    // 245 tiles 12.7 -> 10.7 us per pass, 2 M / 489 tiles 15.3 -> 18.6
-    const bool wideLsd = depthSort && c->lsdThreads != 256 && (c->lsdThreads == 1024 || nbAll <= c->numCUs);
-    for (int shift = bitLo; shift < bitHi; shift += 8) {
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(GS_SORT_THREADS), 0, c->stream, key[src], nPtr, nMax,
-                           shift, c->nbCap, c->hist);
-        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(256), 0, c->stream, nPtr, nMax, c->nbCap, c->hist,
-                           c->rowTotal);
-        if (hasVals && wideLsd)
-            hipLaunchKernelGGL((radix_scatter_kernel<true, false, GS_SORT_ITEMS / 4, 1024>), dim3(nb), dim3(1024), 0, c->stream, key[src],
-                               val[src], key[src ^ 1], val[src ^ 1], nPtr, nMax, shift, c->nbCap, c->hist, c->rowTotal,
-                               nullptr, 0, c->counters + GS_CNT_OVERFLOW);
-        else if (hasVals)
-            hipLaunchKernelGGL((radix_scatter_kernel<true, false, GS_SORT_ITEMS>), dim3(nb), dim3(GS_SORT_THREADS), 0, c->stream, key[src],
-                               val[src], key[src ^ 1], val[src ^ 1], nPtr, nMax, shift, c->nbCap, c->hist, c->rowTotal,
-                               nullptr, 0, c->counters + GS_CNT_OVERFLOW);
+    GS_HIP_CHECK(c, hipGetLastError());
+    *resultBuf = src;
+    return GS_OK;
+}
+
+// The tile sort in 8-bit LSD passes (images of more than GS_WIDE_BINS tiles; GS_TUNE_WIDE_TILE_SORT = 0): the pairs of key[0]
+// (and val[0] unless they are packed words) by the tile id in the bits [idxBits, idxBits + tileBits), stable, over the
+// device-resident pair count.  *resultBuf = index (0/1) of the buffers that hold the result.
+static int tile_sort_lsd(gs_ctx* c, uint32_t* key[2], uint32_t* val[2], bool packed, int* resultBuf)
+{
+    int src = 0;
+    for (int shift = c->idxBits; c->capM > 0 && shift < c->idxBits + c->tileBits; shift += 8) {
+        if (packed)
+            lsd_pass(c, radix_scatter_kernel<false, false, GS_SORT_ITEMS>, GS_SORT_THREADS, key[src], nullptr, key[src ^ 1], nullptr,
+                     c->counters + GS_CNT_M, (uint32_t)c->capM, shift);
         else
-            hipLaunchKernelGGL((radix_scatter_kernel<false, false, GS_SORT_ITEMS>), dim3(nb), dim3(GS_SORT_THREADS), 0, c->stream, key[src],
-                               nullptr, key[src ^ 1], nullptr, nPtr, nMax, shift, c->nbCap, c->hist, c->rowTotal, nullptr, 0,
-                               c->counters + GS_CNT_OVERFLOW);
+            lsd_pass(c, radix_scatter_kernel<true, false, GS_SORT_ITEMS>, GS_SORT_THREADS, key[src], val[src], key[src ^ 1], val[src ^ 1],
+                     c->counters + GS_CNT_M, (uint32_t)c->capM, shift);
         src ^= 1;
-    }
-    if (wantSplitters) {
-        hipLaunchKernelGGL(ss_refresh_kernel, dim3(1), dim3(256), 0, c->stream, key[src], nMax, c->sortSplit[c->splitCur], 255);
-        c->haveSplitters = true;
-        c->splitterNS = 255;
     }
     GS_HIP_CHECK(c, hipGetLastError());
     *resultBuf = src;
@@ -1758,12 +1573,12 @@ __device__ __forceinline__ void local_rank_pass(const uint32_t (&key)[GS_SORT_TI
     }
 }
 
-// THREADS: 256 (sixteen elements per thread) or 1024 (four).  The ranking rounds of a wave are a dependent chain through its
+// THREADS: 512 (eight elements per thread) or 1024 (four).  The ranking rounds of a wave are a dependent chain through its
 // LDS tables -- ~0.3 us each for a wave that has its SIMD to itself (tools/probe_read.py: 4.4 + 5.1 us for the two ranking steps of
-// a 256-thread block, of its 20) --, so the same sort tile on sixteen waves ranks in four rounds instead of sixteen and
-// gathers its runs' bases in one batch instead of four.
+// a 256-thread block, of its 20) --, so the same sort tile on sixteen waves ranks in four rounds instead of the sixteen of
+// four waves and gathers its runs' bases in one batch instead of four.
 template <bool HAS_VALS, int THREADS>
-__global__ __launch_bounds__(THREADS, HAS_VALS ? 1 : THREADS == 1024 ? 8 : THREADS == 512 ? 6 : 1) void wide_scatter_kernel(
+__global__ __launch_bounds__(THREADS, HAS_VALS ? 1 : THREADS == 1024 ? 8 : 6) void wide_scatter_kernel(
     const uint32_t* __restrict__ keysIn, const uint32_t* __restrict__ valsIn, uint32_t* __restrict__ keysOut,
     uint32_t* __restrict__ valsOut, const uint32_t* __restrict__ nPtr, uint32_t nMax, int shift,
     const uint16_t* __restrict__ cnt, const uint32_t* __restrict__ chunkSum, const uint32_t* __restrict__ tileTotal,
@@ -2013,9 +1828,9 @@ int launch_binning(gs_ctx* c, int N, bool wantPlain)
     c->sortedIdx = c->pairVal[0];
     c->sortedPlainValid = !packed;
     if (N == 0) { c->sortedPlainValid = true; return GS_OK; }
-    // 1. depth sort over N (n known on the host: nPtr == nullptr means n = nMax)
+    // 1. depth sort over N
     int res = 0;
-    int rc = radix_sort(c, c->depthKey, c->depthVal, true, nullptr, (uint32_t)N, 0, 32, &res);
+    int rc = depth_sort(c, N, &res);
     if (rc) return rc;
     const uint32_t* sortedG = c->depthVal[res];
     // 2. scan
@@ -2040,7 +1855,7 @@ int launch_binning(gs_ctx* c, int N, bool wantPlain)
                        : (pieces ? expand_kernel<false, true> : expand_kernel<false, false>);
     const int superW = cut_super_width(c);
     const uint32_t* superCut = nullptr;
-    if (cuts && c->superCut && c->cutSuper) {
+    if (cuts) {
         if (!c->superCutReady) { const int src = launch_cut_super(c, cuts); if (src) return src; }     // (the fused projection has it already)
         superCut = c->superCut;
     }
@@ -2094,7 +1909,7 @@ int launch_binning(gs_ctx* c, int N, bool wantPlain)
             // per CU).  MI355X, kernel trace: 10 k Gaussians / 176 sort tiles 21.4 (four waves) -> 14.8 (eight) -> 12.5 us
             // (sixteen); 300 k / 1751 tiles 54.4 -> 48.7 -> 57.0; 1 M / 5200 tiles 92.1 -> 83.3 -> 104.4.  The tile count is on
             // the device; the Gaussian count stands in for it.
-            const int st = c->scatterThreads ? c->scatterThreads : N <= 65536 ? 1024 : 512;
+            const int st = N <= 65536 ? 1024 : 512;
             auto launch_scatter = [&](auto kern, int threads, const uint32_t* vIn, uint32_t* vOut) {
                 hipLaunchKernelGGL(kern, dim3(scatterGrid), dim3(threads), 0, c->stream, pk[0], vIn, pk[1], vOut, mPtr, (uint32_t)c->capM,
                                    shift, c->wideCnt, c->wideChunk, c->wideTotal, c->tileRanges, c->T, seg, withSeg,
@@ -2102,20 +1917,17 @@ int launch_binning(gs_ctx* c, int N, bool wantPlain)
             };
             if (packed) {
                 if (st == 1024) launch_scatter(wide_scatter_kernel<false, 1024>, 1024, nullptr, nullptr);
-                else if (st == 512) launch_scatter(wide_scatter_kernel<false, 512>, 512, nullptr, nullptr);
-                else launch_scatter(wide_scatter_kernel<false, 256>, 256, nullptr, nullptr);
+                else launch_scatter(wide_scatter_kernel<false, 512>, 512, nullptr, nullptr);
             } else {
                 if (st == 1024) launch_scatter(wide_scatter_kernel<true, 1024>, 1024, pv[0], pv[1]);
-                else if (st == 512) launch_scatter(wide_scatter_kernel<true, 512>, 512, pv[0], pv[1]);
-                else launch_scatter(wide_scatter_kernel<true, 256>, 256, pv[0], pv[1]);
+                else launch_scatter(wide_scatter_kernel<true, 512>, 512, pv[0], pv[1]);
             }
         }
         GS_HIP_CHECK(c, hipGetLastError());
         c->sortedRaw = packed ? pk[1] : pv[1];
         if (!packed) c->sortedIdx = pv[1];
     } else {
-        rc = radix_sort(c, pk, pv, !packed, c->counters + GS_CNT_M, (uint32_t)c->capM, c->idxBits,
-                        c->idxBits + c->tileBits, &res);
+        rc = tile_sort_lsd(c, pk, pv, packed, &res);
         if (rc) return rc;
         c->sortedRaw = packed ? pk[res] : pv[res];
         if (!packed) c->sortedIdx = pv[res];

@@ -1287,7 +1287,7 @@ void fill_seg_base(gs_ctx* c, SegBaseArgs& a)
     a.nBlocks = c->numPixBlocks; a.blocksX = c->blocksX; a.tileW = c->tileW; a.tileH = c->tileH; a.gridW = c->gridW;
     a.tileRanges = c->tileRanges; a.tileTotal = nullptr;
     a.segBase = c->segBase; a.blockWork = c->blockWork; a.counters = c->counters; a.workHint = c->workHint;
-    a.blockOrder = c->blockOrder; a.queueStart = (uint32_t)blend_forward_v2_grid(c); a.fwdQueue = c->fwdQueue; a.nq = c->fwdQueues; a.spatial = c->fwdSpatial;
+    a.blockOrder = c->blockOrder; a.queueStart = (uint32_t)blend_forward_v2_grid(c); a.fwdQueue = c->fwdQueue;
 }
 
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha)
@@ -1394,7 +1394,7 @@ int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const floa
                         : (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, false> : blend_bwd_v2_kernel<SEGLEN, false, false>);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, c->stream, c->W, c->H, c->tileW, c->tileH,
                        c->gridW, blocksX, c->fwd.bg, reinterpret_cast<const float4*>(c->packed12), c->sortedRaw,
-                       c->idxMask, c->tileRanges, c->itemRow, reinterpret_cast<const uint4*>(c->segSlot), c->fwd.qslotCap, c->fwd.statePlanes, c->fwd.blockWork, c->itemBlock, c->counters, c->bwdQueue, (uint32_t)c->bwdQueues, cotColor,
+                       c->idxMask, c->tileRanges, c->itemRow, reinterpret_cast<const uint4*>(c->segSlot), c->fwd.qslotCap, c->fwd.statePlanes, c->fwd.blockWork, c->itemBlock, c->counters, c->bwdQueue, 8u, cotColor,
                        cotDepth, cotAlpha, outColor, outDepth, outAlpha, c->lastContrib, c->finalT, c->segState,
                        c->gradAcc16, c->virt);
     GS_HIP_CHECK(c, hipGetLastError());

@@ -147,30 +147,27 @@ struct SegBaseArgs {
     uint32_t* blockOrder;
     uint32_t queueStart;
     uint32_t* fwdQueue;             // [8][32]: the fused forward's eight work-queue heads, one per XCD (a cache line each)
-    int nq;                         // queues in use (GS_TUNE_FWD_QUEUES)
-    int spatial;                    // 1: queue x gets the x-th stripe of the image; 0: the blocks dealt to the queues in launch order
 };
 
 // Launch order of the forward's items, round 4: position p of the order belongs to queue / XCD p mod nq (blend_v2.hip).
-// Default (spatial = 0): ONE list of all blocks, deepest first, dealt to the queues round-robin -- every XCD gets the same mix
-// of deep and shallow blocks.  spatial = 1: queue x is given the blocks of the x-th STRIPE of the image -- the blocks
-// [x per, (x + 1) per) in row-major order, per = ceil(nBlocks / nq) --, deepest first inside the stripe: neighbouring blocks
-// share most of their records, and a stripe's Gaussians stay in its XCD's L2 (FETCH_SIZE of the forward 53 -> 18 MB per
-// launch on the bench scene) -- but stripes of equal block count are not stripes of equal work, and stealing only starts when
-// a whole XCD has run dry: same time on the bench scene, +25 % on the grown one (blend forward 0.90 -> 1.13 ms).  Kept for A/B.
-// Positions a short last stripe leaves over hold 0xFFFFFFFF (no block).
-// lds: 16 + 8 * 256 + 2 words
-constexpr int GS_SEGBASE_LDS = 16 + 8 * 256 + 2;
+// ONE list of all blocks, deepest first, dealt to the queues round-robin -- every XCD gets the same mix of deep and shallow
+// blocks.  (A stripe of the image per queue keeps a stripe's Gaussians in its XCD's L2 -- FETCH_SIZE of the forward 53 -> 18 MB
+// per launch on the bench scene -- but stripes of equal block count are not stripes of equal work, and stealing only starts
+// when a whole XCD has run dry: +25 % on the grown scene, EXPERIMENTS.md.)
+// Positions behind the last block hold 0xFFFFFFFF (no block).
+// lds: 16 + 256 + 2 words
+constexpr int GS_SEGBASE_LDS = 16 + 256 + 2;
 template <int SEG>
 __device__ __forceinline__ void seg_base_body(const SegBaseArgs& a, uint32_t* lds)
 {
     uint32_t* sm = lds;
     uint32_t* bucket = lds + 16;              // [nq][256]
-    uint32_t& carry = lds[16 + 8 * 256];
-    uint32_t& wmax = lds[16 + 8 * 256 + 1];
+    uint32_t& carry = lds[16 + 256];
+    uint32_t& wmax = lds[16 + 256 + 1];
     const int nT = (int)blockDim.x, nW = nT >> 6;
-    // (not spatial: ONE stripe, sorted deepest first, whose positions go to the queues round-robin -- position p to queue p mod nq)
-    const int nq = a.spatial ? a.nq : 1, per = (a.nBlocks + nq - 1) / nq;
+    // The order is built per stripe of `per` blocks, nq stripes interleaved; there is ONE stripe, sorted deepest first, whose
+    // positions go to the queues round-robin (position p to queue p mod the forward's queue count)
+    const int nq = 1, per = a.nBlocks;
     // every persistent wave's first item is fixed by its blockIdx.x (no pop: thousands of simultaneous pops on one counter
     // take ~6 ns each to resolve); the queues proper start behind those
     if (threadIdx.x == 0) { carry = 0; a.counters[GS_CNT_QUEUE_FWD] = a.queueStart; wmax = 0; }

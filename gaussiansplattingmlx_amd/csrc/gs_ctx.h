@@ -118,7 +118,7 @@ __device__ __forceinline__ void gs_block_pixels(const GsVirtGeom& g, int bx, int
 }
 constexpr int GS_F3D_CAM_FLOATS = 16;  // floats per camera of the 3-D filter's table (filter3d.hip)
 constexpr int GS_CUT_SUPER = 4;      // tiles per side of a super-tile of the coarse cuts
-// coarse depth cuts handed to the fused projection (binning.hip, cut_super_kernel): null superCut = none
+// coarse depth cuts handed to the fused projection (binning.hip, cut_super_kernel): null superCut = a forward without cuts
 struct GsCutCoarse {
     const uint32_t* superCut = nullptr;
     int superW = 0;
@@ -177,22 +177,18 @@ struct gs_ctx {
     uint32_t* sortSplit[2] = {nullptr, nullptr};   // [256] each
     int splitCur = 0;
     bool haveSplitters = false;
-    int splitterNS = 0;                            // how many splitters sortSplit holds: 127 (256 buckets) or 255 (512 buckets)
-    unsigned short* bucketId = nullptr;            // [capN] (read as bytes by the 256-bucket kernels)
-    uint32_t* bucketStart = nullptr;               // [520]: first record of every bucket, [buckets] = n
-    uint32_t* ssChunk = nullptr;                   // [65][512] bucket totals per chunk of 16 sort tiles (sorts of > 160 tiles)
+    unsigned char* bucketId = nullptr;             // [capN]
+    uint32_t* bucketStart = nullptr;               // [520]: first record of every bucket, [256] = n
     int colourRiders = 1;          // 1: K = 25 forwards compute their SH colours as riders of the binning kernels (GS_TUNE_COLOUR_RIDERS)
     GsRiderState rider;
     int riderShare[GS_RIDE_HOSTS] = {200, 500, 300};   // permille of a forward's colour units per host kernel
-    int splitterSort = 1;          // 1: depth sorts of 16385 .. 655 k records take the splitter buckets (three launches); 0: LSD passes;
-                                   // 2: larger sorts too (512 buckets, four launches: measured slower than their LSD passes)
+    int splitterSort = 1;          // 1: depth sorts of 16385 .. 655 k records take the splitter buckets (three launches); 0: LSD passes
     int nbCap = 0;
     // per-tile
     bool superCutReady = false;      // cut_super_kernel has run for the forward being built (the fused projection uses it first)
     uint32_t* dropPerBlock = nullptr; // [capN / 128 + 1] candidate pairs of the Gaussians each projection block dropped whole under the super-cuts
     int dropBlocks = 0;              // how many of them the current forward wrote (0: none -- no cuts, or an op-level binning)
     uint32_t* superCut = nullptr;    // [ceil(gridW / 4) * ceil(gridH / 4)] the deepest cut of every 4 x 4 tiles (binning.hip, cut_super_kernel)
-    int cutSuper = 1;                // 0 (GSPLAT_CUT_SUPER=0): the cut expansion enumerates every Gaussian's rect (A/B)
     uint32_t* tileRanges = nullptr;  // [T,2]
     uint32_t* tileCounts = nullptr;  // [T]
     // per 16x16 pixel block: work estimate and heaviest-first launch order (fast path)
@@ -200,8 +196,7 @@ struct gs_ctx {
     uint32_t* blockWorkOwn = nullptr;
     uint32_t* blockOrder = nullptr;  // [numPixBlocks]
     uint32_t* fwdQueue = nullptr;    // [8][32] work-queue heads of the fused blend forward, one per XCD
-    uint32_t* bwdQueue = nullptr;    // [8][32] ... and of the fused blend backward
-    int bwdQueues = 8;               // 8 = one per XCD (a stripe of the item list each), 1 = one for the chip (A/B)
+    uint32_t* bwdQueue = nullptr;    // [8][32] ... and of the fused blend backward (a stripe of the item list each)
     // depth cuts (binning.hip): per tile, 0xFFFFFFFF - (largest depth key still binned); 0 = no cut.  Lives in the
     // caller's per-view hint buffer behind the block-work words (gs_set_view_hints); written by the backward's item
     // kernel, read by the next forward of that view.
@@ -290,8 +285,6 @@ struct gs_ctx {
     int fwdQuadrants = 1;            // GS_TUNE_FWD_QUADRANTS: the forward's items are always 8x8 quadrants (the 16x8 variant it once
                                      // selected is gone); 0 still forces the one-wave kernel over the pair and four-wave kernels
                                      // (blend_forward_v2_wide, blend_forward_v2_pair_decide)
-    int scatterThreads = 0;          // threads per sort tile of the one-pass tile sort: 256 / 512 / 1024, 0 = by the Gaussian count (binning.hip)
-    int lsdThreads = 0;              // threads per tile of the LSD depth passes' scatter: 256 / 1024, 0 = by the tile count (binning.hip)
     int fwdWide = -1;                // blend forward with four waves per quadrant: 1 / 0, -1 = where the image has fewer quadrants than wave slots (blend_v2.hip)
     float fwdFoldScale = 1.0f;       // test knob (GS_TUNE_FWD_FOLD_TEST_SCALE): factor on the composed T in the four-wave fold's
                                      // "did the pixel cross 1e-4 inside this part" test; below 1 forces second takes that come back live
@@ -306,10 +299,6 @@ struct gs_ctx {
     bool rowGroups = true;           // GS_TUNE_TRIM_RECTS = 2 (default) / 1: trimmed rects cut further into four row groups, or the box alone
     int renderOnly = 0;              // GS_TUNE_RENDER_ONLY: fused forwards keep no checkpoints (statePlanes 0) and can have no backward
     int poisonCheckpoints = 0;       // test knob (GS_TUNE_POISON_CHECKPOINTS): the checkpoint arena is NaN-filled in front of every fused forward
-    int rankSort = 1;                // depth sorts of <= 16384 records by rank on the whole chip (0: the one-workgroup radix sort; binning.hip)
-    int fwdSpatial = 0;              // 0 (default): the blocks are dealt to the forward's queues round-robin in launch order (deepest first
-                                     // over the whole image); 1: queue x gets the x-th stripe of the image (a third of the fabric
-                                     // traffic, but equal block counts are not equal work: +25 % on the grown scene; GSPLAT_FWD_SPATIAL)
     int fwdQueues = 8;               // work queues of the fused forward: 8 = one per XCD (blend_v2.hip), 1 = one for the chip (A/B)
     int opFwdPpl = 1, opBwdPpl = 1;  // pixels per lane of the op-level blend kernels (blend.hip)
     bool segBaseWanted = false;      // gs_render_forward (16x16-block path): the binning may do the blend forward's
@@ -409,7 +398,7 @@ struct gs_ctx {
     } while (0)
 
 static inline int gs_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
-// does the depth sort of n records take the two-launch passes (binning.hip, radix_sort)?
+// does the depth sort of n records take the splitter buckets or the two-launch passes (binning.hip, depth_sort)?
 static inline bool gs_small_depth_sort(long long n) { return gs_div_up(n, GS_SORT_THREADS * GS_SMALL_SORT_ITEMS) <= GS_SMALL_SORT_BLOCKS; }
 
 // RAII stage timer: records a start/stop event pair around a launch sequence when profiling is on

@@ -1112,7 +1112,7 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
     // all of theirs (block lists and 16 x 16 tiles alike: the context's grid is the grid the cuts are kept on)
     GsCutCoarse cc;
     c->dropBlocks = 0;
-    if (c->fwd.cutsActive && c->fwd.cutStore && c->cutSuper && c->superCut && c->dropPerBlock) {
+    if (c->fwd.cutsActive && c->fwd.cutStore && c->dropPerBlock) {
         const int src = launch_cut_super(c, c->fwd.cutStore);
         if (src) return src;
         cc.superCut = c->superCut; cc.superW = cut_super_width(c); cc.dropPerBlock = c->dropPerBlock;

@@ -187,8 +187,7 @@ class GaussianRenderer:
         the geometry half only."""
         if K != 25 or self.getTuning("colour_riders") != 1 or ((self.TILE_SIZE.w % 16 or self.TILE_SIZE.h % 16) and not self.blockLists):
             return False
-        split = self.getTuning("splitter_depth_sort")
-        return bool(split) and N > 16384 and (N <= 160 * 4096 or (split >= 2 and N <= 1024 * 4096))
+        return bool(self.getTuning("splitter_depth_sort")) and 16384 < N <= 160 * 4096
 
     def stats(self):
         s = (C.c_uint32 * 8)()

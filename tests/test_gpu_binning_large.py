@@ -2,7 +2,7 @@
 
 With N >= 2^20 Gaussians and 12-13 tile bits a (tile, index) pair no longer fits one 32-bit word
 (binning.hip launch_binning: idxBits + tileBits > 32), so these inputs take the TWO-WORD pair path
-(expand_kernel with idxBits == 0, wide_scatter_kernel<true> or the key + value radix_sort and tile_ranges_kernel), the
+(expand_kernel with idxBits == 0, wide_scatter_kernel<true> or the key + value tile_sort_lsd and tile_ranges_kernel), the
 separate block-prefix launches above GS_FUSED_SCAN_MAX = 2048 scan blocks (bigScan) and the 8-slice expansion of blocks
 with >= 32768 positions -- none of which the small bit-exact cases of test_gpu_parity.py reach.  The rects are synthetic
 (as in test_tile_bin_equal_depth_ties_and_empty), so the oracle's cost is one stable sort of M pairs.
@@ -88,7 +88,7 @@ CASES = {
     # 1024x1024 = exactly 4096 tiles (12 bits) + 2^21 index bits = 33: two words; one-pass tile sort (wide = 1) or two
     # 8-bit passes (wide = 0); 4297 scan blocks > 2048: bigScan; near Gaussians: sliced blocks
     "1.1M_4096tiles": dict(W=1024, H=1024, N=1_100_000, wides=(1, 0)),
-    # 4160 tiles (13 bits) + 20 index bits = 33: two words through the key + value radix_sort and tile_ranges_kernel
+    # 4160 tiles (13 bits) + 20 index bits = 33: two words through the key + value tile_sort_lsd and tile_ranges_kernel
     "600k_4160tiles": dict(W=1040, H=1024, N=600_000, wides=(1,)),
     # the C5 shape itself: 2 M Gaussians, 1237x822 (78 x 52 = 4056 tiles, partial edge tiles)
     "c5_2M_1237x822": dict(W=1237, H=822, N=2_000_000, wides=(1,)),
@@ -179,13 +179,14 @@ def test_splitter_depth_sort_agrees_with_the_oracle(oracle32, N, ties):
     """The depth sort of more than 16384 records.  A context's FIRST sort takes the four LSD passes and leaves 127
     splitters; every later one buckets the records between the previous sort's splitters, scatters them stably and sorts
     every bucket locally (GS_TUNE_SPLITTER_DEPTH_SORT = 1, default; = 0: LSD passes always).  Above 655 360 records
-    (160 sort tiles; round 4, GS_TUNE_SPLITTER_DEPTH_SORT = 2 -- bit-exact but slower than the LSD passes of those sizes,
-    so not the default) there are 255 splitters / 512 buckets, a chunk scan of the histogram rows between the two
-    passes, and from 1.4 M records on the local sort with 16384 records per workgroup: the sizes of the grown bench
+    (160 sort tiles) every sort takes the three-launch LSD passes, whatever the knob says -- sixteen waves per sort tile
+    while the tiles are no more than the CUs (1.1 M records), four beyond (1.4 M, 2 M): the sizes of the grown bench
     scene (1 M) and of BASELINE's config 5 (2 M), and both sides of each boundary.  The order must be the
     oracle's stable sort whatever the splitters are: fresh ones (the same input again), STALE ones (other depths: one
     bucket then holds most of the records and is streamed through global memory by a single workgroup), depths that
-    differ in their low bits only, all-equal depths, and 30 % / 90 % ties (whole "equal to splitter" classes)."""
+    differ in their low bits only, all-equal depths, and 30 % / 90 % ties (whole "equal to splitter" classes).
+    GS_TUNE_SPLITTER_DEPTH_SORT = 2 once selected a second splitter form from 655 361 records on and now means 1: at that
+    size a caller who still sets it gets the same lists and no error."""
     W, H = 640, 360
     rectMin, rectMax, radii, depths = synthetic_rects(41 + N % 7, N, W, H, near=200, near_span=80.0, far_span=6.0, p_tied=ties)
     bn = oracle32.tile_bin(rectMin, rectMax, radii, depths, W, H, 16, 16)
@@ -196,7 +197,7 @@ def test_splitter_depth_sort_agrees_with_the_oracle(oracle32, N, ties):
     d4 = (depths * np.float32(37.0) + np.float32(0.05)).astype(np.float32)             # another range altogether
     bn4 = oracle32.tile_bin(rectMin, rectMax, radii, d4, W, H, 16, 16)
     r = _renderer(W, H)
-    on = 2 if N > 655_360 else 1        # (the 512-bucket form is not the default: slower than the LSD passes it replaces)
+    on = 1
     r.setTuning(splitter_depth_sort=on)
     bin_ = lambda d: r.buildGlobalTileSliceInfo((rectMin, rectMax), radii, d)
     _assert_same_lists(bin_(depths), bn, "first sort: LSD passes + splitters")
@@ -213,4 +214,7 @@ def test_splitter_depth_sort_agrees_with_the_oracle(oracle32, N, ties):
     r.setTuning(splitter_depth_sort=on)
     _assert_same_lists(bin_(d4), bn4, "knob back on: LSD + splitters")
     _assert_same_lists(bin_(d4), bn4, "splitters")
+    if N == 655_361:
+        r.setTuning(splitter_depth_sort=2)
+        _assert_same_lists(bin_(d4), bn4, "knob value 2 means 1")
     r.close()

@@ -255,7 +255,7 @@ def test_projection_appendix_c_through_abi():
                                         (1040, 1024, (16, 16), 2000), (200, 152, (16, 16), 16384), (200, 152, (16, 16), 16385),
                                         (96, 64, (16, 16), 1), (96, 64, (16, 16), 1025)])
 def test_tile_bin_bit_exact(oracle32, W, H, tile, N, wide):
-    """Depth sort: up to 16384 records in one workgroup (radix_sort_tiny_kernel; 16384 is its last size, 16385 the first of
+    """Depth sort: up to 16384 records by rank (rank_sort_kernel; 16384 is its last size, 16385 the first of
     the two-launches-per-pass path), 40000 through that path.  wide = 1: the one-pass tile sort (up to 4096 tiles: 1024x1024 is exactly 4096, 1040x1024 one column more and falls
     back); wide = 0: the two 8-bit passes + range kernel.  Same lists, bit for bit."""
     p, cam = _scene(21, N, W, H, scale=0.04)
@@ -306,9 +306,7 @@ def test_tile_bin_small_depth_sorts_with_ties(oracle32, N):
     """The depth sort of up to 16384 records is a sort by rank on the whole chip (rank_sort_kernel: 64 records per workgroup, all
     keys in LDS, sixteen waves counting a sixteenth of the keys each), from 16385 on the splitter buckets / LSD passes: the
     lists at both sides of the boundary, at workgroup and wave boundaries, with 40 % of the depths tied (the tie-break is the
-    Gaussian index) and a fifth of the Gaussians invisible, against the oracle's -- and the same under the one-workgroup
-    radix sort the rank sort replaces (GSPLAT_RANK_SORT=0 is an environment switch of the library: not reachable from here,
-    so that form is covered by what it sorted in rounds 2-3)."""
+    Gaussian index) and a fifth of the Gaussians invisible, against the oracle's."""
     W, H = 96, 80
     rng = np.random.default_rng(100 + N)
     rectMin = rng.uniform(0, 70, (N, 2)).astype(np.float32)
