@@ -106,11 +106,7 @@ __global__ __launch_bounds__(CB_NT) void blend_contrib_kernel(
                 const float4 ea = sa[j + k], eb = sb[j + k];
                 float w = 0.0f;
                 if (!done) {
-                    const float dx = px - ea.x, dy = py - ea.y;
-                    const float dxdy = dx * dy;
-                    const float e = -0.5f * (dx * dx * ea.z + dy * dy * eb.y + dxdy * ea.w + dxdy * eb.x);
-                    const float raw = comp_exp(e) * eb.z;
-                    const float alpha = raw > 0.99f ? 0.99f : raw;
+                    const float alpha = splat_alpha<true>(px, py, ea, eb, eb.z).alpha;
                     w = T * alpha;
                     T = T * (1.0f - alpha);
                     if (T < 1e-4f) done = true;

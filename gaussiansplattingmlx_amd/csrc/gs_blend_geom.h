@@ -1,5 +1,5 @@
 // gs_blend_geom.h -- what the op-level blend kernels (blend.hip) and the contribution pass (contrib.hip) share: the
-// enumeration of the 16x16 pixel blocks and the forward's exponential
+// enumeration of the 16x16 pixel blocks, the forward's exponential and the alpha of a Gaussian on a pixel
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,6 +48,24 @@ __device__ __forceinline__ float comp_exp(float x)
     const float d = fmaf(x, L2E_TAIL_LN2, lo * LN2);
     const float g = __builtin_amdgcn_exp2f(hi);
     return fmaf(g, d, g);
+}
+
+// alpha of one Gaussian on one pixel (tileGlobalAlphaFromGaussian), with the terms the backward step needs again.
+// a: mx my c00 c01, b: c10 c11 .. of the record.  COMP: comp_exp (the forwards, the contribution pass) or __expf (the backward step).
+struct SplatAlpha {
+    float dx, dy, dxdy, ex, raw, alpha;
+};
+template <bool COMP>
+__device__ __forceinline__ SplatAlpha splat_alpha(float px, float py, const float4& a, const float4& b, float opacity)
+{
+    SplatAlpha s;
+    s.dx = px - a.x; s.dy = py - a.y;
+    s.dxdy = s.dx * s.dy;
+    const float e = -0.5f * (s.dx * s.dx * a.z + s.dy * s.dy * b.y + s.dxdy * a.w + s.dxdy * b.x);
+    s.ex = COMP ? comp_exp(e) : __expf(e);
+    s.raw = s.ex * opacity;
+    s.alpha = s.raw > 0.99f ? 0.99f : s.raw;
+    return s;
 }
 
 }  // namespace gs

@@ -388,8 +388,12 @@ def test_blend_appendix_c_through_abi():
     assert int(_np(r._saved["last"])[pix]) == b["nContrib"]
 
 
-def test_blend_deep_list_early_termination(oracle32):
-    # many opaque splats stacked on a few pixels: exercises multi-chunk lists, saturation and the wave-level exit
+@pytest.mark.parametrize("tile", [(16, 16), (32, 32), (24, 24)])
+def test_blend_deep_list_early_termination(oracle32, tile):
+    # many opaque splats stacked on a few pixels: exercises multi-chunk lists, saturation and the wave-level exit.
+    # Every tile lists all N splats at every size; the larger tiles take the cull kernels -- (32, 32) on the image-grid
+    # enumeration of the blocks, (24, 24) on the per-tile one with clipped 8-pixel blocks -- whose rounds mix kept and culled
+    # entries and keep more than one 64-entry batch
     W, H = 64, 48
     N = 3000
     rng = np.random.default_rng(4)
@@ -401,10 +405,10 @@ def test_blend_deep_list_early_termination(oracle32):
     rmin = np.zeros((N, 2), np.float32)
     rmax = np.tile(np.array([[W - 1, H - 1]], np.float32), (N, 1))
     radii = np.ones(N, np.float32)
-    bn = oracle32.tile_bin(rmin, rmax, radii, packed[:, 10], W, H, 16, 16)
-    col, dep, alp, last = oracle32.blend_forward(packed, bn.sortedIdx, bn.tileRanges, W, H, 16, 16, False)
+    bn = oracle32.tile_bin(rmin, rmax, radii, packed[:, 10], W, H, tile[0], tile[1])
+    col, dep, alp, last = oracle32.blend_forward(packed, bn.sortedIdx, bn.tileRanges, W, H, tile[0], tile[1], False)
     assert last.max() < N and last.min() > 5
-    r = _renderer(W, H)
+    r = _renderer(W, H, tile)
     for ppl in (1, 2, 4):
         r.setTuning(op_fwd_ppl=ppl, op_bwd_ppl=ppl)
         r.buildGlobalTileSliceInfo((rmin, rmax), radii, packed[:, 10])
@@ -416,8 +420,8 @@ def test_blend_deep_list_early_termination(oracle32):
                      last=torch.as_tensor(last.astype(np.int32), device=r.device))
         got = _np(r.globalTileCompositeVJP(cC, None, None, saved=saved))
         z = np.zeros(W * H, np.float32)
-        want = oracle32.blend_backward(packed, bn.sortedIdx, bn.tileRanges, W, H, 16, 16, False, cC, z, z, col, dep,
-                                       alp, last)
+        want = oracle32.blend_backward(packed, bn.sortedIdx, bn.tileRanges, W, H, tile[0], tile[1], False, cC, z, z, col,
+                                       dep, alp, last)
         assert _rel(got, want) <= GRAD_RTOL
     r.setTuning(op_fwd_ppl=1, op_bwd_ppl=1)
 
