@@ -478,7 +478,7 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     }
     if (const char* e = getenv("GSPLAT_COLOUR_RIDERS")) c->colourRiders = atoi(e);      // tuning experiments (tools/rider_ab.py)
     if (const char* e = getenv("GSPLAT_FWD_WIDE")) c->fwdWide = atoi(e) < 0 ? -1 : atoi(e) != 0;
-    if (const char* e = getenv("GSPLAT_FWD_QUEUES")) { const int q = atoi(e); if (q == 1 || q == 2 || q == 4 || q == 8) c->fwdQueues = q; }
+    if (const char* e = getenv("GSPLAT_FWD_QUEUES")) { const int q = atoi(e); if (q >= 1 && q <= (int)GS_QUEUES && !(q & (q - 1))) c->fwdQueues = q; }
     if (const char* e = getenv("GSPLAT_RIDER_SHARES")) {      // tuning experiments: permille of the colour units per host kernel
         // exactly GS_RIDE_HOSTS comma-separated values, in the enum's order (ss_hist, ss_scatter, wide_tile); anything else
         // is refused loudly -- a sweep that passes four values would measure other splits than the ones it prints
@@ -505,7 +505,7 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     c->numPixBlocks = c->blocksX * c->blocksY;
     c->opBlocks = c->real.fast16 ? c->numPixBlocks : c->real.T * gs_div_up(tile_w, 16) * gs_div_up(tile_h, 16);
     const size_t maxBlocks = (size_t)(c->opBlocks > c->numPixBlocks ? c->opBlocks : c->numPixBlocks);
-    if (dev_alloc(c, &c->blockWorkOwn, maxBlocks) || dev_alloc(c, &c->blockOrder, maxBlocks + 8) || dev_alloc(c, &c->fwdQueue, 8 * 32) || dev_alloc(c, &c->bwdQueue, 8 * 32) ||
+    if (dev_alloc(c, &c->blockWorkOwn, maxBlocks) || dev_alloc(c, &c->blockOrder, maxBlocks + 8) || dev_alloc(c, &c->fwdQueue, GS_QUEUES * GS_QUEUE_STRIDE) || dev_alloc(c, &c->bwdQueue, GS_QUEUES * GS_QUEUE_STRIDE) ||
         dev_alloc(c, &c->segBase, (size_t)c->numPixBlocks) || dev_alloc(c, &c->finalT, P))
         return bail(GS_ERR_HIP);
     c->blockWork = c->blockWorkOwn;
@@ -1812,7 +1812,7 @@ int gs_ctx_set_tuning(gs_ctx* c, int knob, long long value)
     case GS_TUNE_FWD_QUADRANTS:
         c->fwdQuadrants = value != 0; return GS_OK;
     case GS_TUNE_FWD_QUEUES:
-        if (value != 1 && value != 2 && value != 4 && value != 8) return fail(c, GS_ERR_INVALID_ARG, "gs_ctx_set_tuning: forward queues must be 1, 2, 4 or 8");
+        if (value < 1 || value > (long long)GS_QUEUES || (value & (value - 1))) return fail(c, GS_ERR_INVALID_ARG, "gs_ctx_set_tuning: forward queues must be 1, 2, 4 or 8");
         c->fwdQueues = (int)value; return GS_OK;
     case GS_TUNE_FWD_FOUR_WAVES:
         c->fwdWide = value < 0 ? -1 : (value != 0); return GS_OK;

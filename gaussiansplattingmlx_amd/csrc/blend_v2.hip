@@ -19,23 +19,19 @@
 //    dropped moves no rendered value by more than ~5e-8 per entry, and the image's distance to the oracle does not
 //    change in the third digit (measured for thresholds 2^-42 ... 2^-24.5; at 2^-20 it does).  Dropped entries cost
 //    no LDS broadcast and no VALU.
-//  * Forward (blend_fwd_v2q_kernel): one wavefront per 8x8 quadrant of a 16x16 block, one pixel per lane, four
-//    splats per trip (exponents and exps first, the short serial chain through T second), branch-free termination
-//    (a finished pixel keeps blending with alpha = 0), wave-uniform exit.  Persistent waves pull items from a
-//    device queue; the first item of a wave is its blockIdx.x (thousands of simultaneous pops on one counter take
-//    ~6 ns each to resolve: 15 % of the kernel).  With a per-view block-work buffer (gs_set_block_work_buffer) the
-//    queue is ordered deepest-first, which takes the slowest wave from 1.55x to 1.16x the mean.  Every SEG list
-//    positions the running state (T, C, D) is saved per pixel.  blend_fwd_v2p_kernel (a staging wave beside every
-//    sweeping wave, for deep lists) and blend_fwd_v2w_kernel (four waves per quadrant, for images with fewer quadrants
-//    than wave slots) are the same sweep on other schedules; the three share their pieces ("forward" below).
-//  * Backward (blend_bwd_v2_kernel): the saved states make a tile's list SEGMENT-parallel.  The work items are
-//    (pixel block, segment) pairs of at most SEG list positions, pulled from a device queue by persistent
-//    single-wave workgroups.  Inside an item the sweep runs FORWARD (T by multiplication, as the forward pass), with
-//    the cotangent of T in closed form,
+//  * Forward (blend_fwd_v2q_kernel; "forward" below): one wavefront per 8x8 quadrant of a 16x16 block, one pixel per lane,
+//    four splats per trip (exponents and exps first, the short serial chain through T second), branch-free termination
+//    (a finished pixel keeps blending with alpha = 0), wave-uniform exit.  Persistent waves: a static first item each, the
+//    rest from eight device queues, deepest blocks first.  Every SEG list positions the running state (T, C, D) is saved
+//    per pixel.  blend_fwd_v2p_kernel and blend_fwd_v2w_kernel are the same sweep on other schedules.
+//  * Backward (blend_bwd_v2_kernel; "backward" below): the saved states make a tile's list SEGMENT-parallel.  The work items
+//    are (pixel block, segment) pairs of at most SEG list positions, handed to persistent single-wave workgroups like the
+//    forward's.  Inside an item the sweep runs FORWARD (T by multiplication, as the forward pass), with the cotangent of T
+//    in closed form,
 //        c_i = (sum_{j>i} T_j a_j S_j + T_n cT_n) / T_{i+1},
 //    the sum being (final colour - running colour) . cotColour.  Each lane owns 4 pixels, so the per-splat wave
-//    reduction is paid once per 256 pixel-splats; it is a TRANSPOSED reduction (wave_sum10_transposed): lane swaps
-//    and bank-masked DPP adds halve the live registers level by level, 23 instructions instead of 60.
+//    reduction is paid once per 256 pixel-splats; it is a TRANSPOSED reduction (gs_wavesum.h): lane swaps and bank-masked
+//    DPP adds halve the live registers level by level, 23 instructions instead of 60.
 //  * The reference rebuilds T from the rounded output alpha (T_n' = 1 - outAlpha) and divides its way back;
 //    every T of a pixel is therefore off by the factor s = T_n' / T_n.  The same factor is applied here, so
 //    the gradients match the reference's arithmetic, not just the exact calculus.
@@ -50,12 +46,10 @@
 namespace gs {
 
 constexpr int BLK = 16;
-constexpr uint32_t CKPT_POOL_MAX = 8;   // checkpoint slots a forward wave takes from the arena's shared part per atomic (blend_fwd_v2*_kernel):
-                                        // this many when the arena is roomy, fewer when a part of it holds less than that per wave
-                                        // (ckpt_pool below) -- a tiny reserve (capM of a few hundred thousand pairs: an arena of ~10 k
-                                        // slots for 4 - 5 k persistent waves) was used up by the waves' unused remainders, every
-                                        // forward reported an arena overflow until the regrow (round 5: tools/dp_overflow_rehearsal.py
-                                        // one_view, never re-run after the four-wave forward had multiplied the waves by four)
+constexpr uint32_t CKPT_POOL_MAX = 8;   // checkpoint slots a forward wave takes from the arena's shared part per atomic: this many
+                                        // when the arena is roomy, fewer when a part of it holds less than that per wave (ckpt_pool)
+                                        // -- or the waves' unused remainders use up a tiny reserve (~10 k slots for 4 - 5 k waves) and
+                                        // every forward reports an arena overflow until the regrow (tools/dp_overflow_rehearsal.py)
 static inline uint32_t ckpt_pool(uint32_t partSlots, uint32_t waves)
 {
     const uint32_t perWave = partSlots / (waves / 8u + 1u);
@@ -109,13 +103,6 @@ __device__ __forceinline__ RecV gather_chunk(const float4* __restrict__ packed12
     return v;
 }
 
-// park a chunk in the wave's LDS slot; DS operations of one wave complete in order, so the broadcast reads
-// that follow need no barrier
-__device__ __forceinline__ void stage_chunk(f4* slot, const RecV& v, int lane)
-{
-    slot[lane * 3] = v.a; slot[lane * 3 + 1] = v.b; slot[lane * 3 + 2] = v.c;
-}
-
 __device__ __forceinline__ Rec unpack(const f4 a, const f4 b, const f4 c)
 {
     Rec r;
@@ -153,6 +140,50 @@ __device__ __forceinline__ float gauss_alpha_raw(float q, float op)
 }
 
 // (cull bound CULL_QMIN and rect_min_q: gs_cull.h)
+
+// ---------------------------------------------------------------------------------------------
+// what the forward and the backward kernels share besides the records
+// ---------------------------------------------------------------------------------------------
+// A word of a table a kernel only reads (blockOrder, tileRanges, segBase, the depth cuts, the item list, the sweep
+// lengths: written by the launches in front of it), through the constant address space: at a wave-uniform index it is a
+// scalar load.  Flat __restrict__ kernel arguments say as much; the members of a by-value argument struct carry no such
+// promise, and the forward item's dependent chain of three look-ups came out as vector loads + v_readfirstlane (blend forward
+// on the 300 k / 800x800 scene: 0.1658 -> 0.1676 ms, one-wave kernel).
+__device__ __forceinline__ uint32_t table_word(const uint32_t* table, uint32_t i)
+{
+    return ((const __attribute__((address_space(4))) uint32_t*)table)[i];
+}
+
+// kept entries in the lanes below this one, from the ballot of the keepers (v_mbcnt: written as popc(m & ((1 << lane) - 1)),
+// the 64-bit lane mask became a loop invariant of the item loop that the four-wave forward, at its register budget, kept in
+// scratch)
+__device__ __forceinline__ uint32_t rank_below(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// One pop from the work queues, called by a whole wave: the nq queues are tried from the taker's own XCD's on, the ones
+// found empty (`dead`) skipped.  Lane 0 takes a ticket k from queue y and the wave reads it back; take(y, k) maps it to an
+// item and says whether there was one -- if not, queue y is empty, and since tickets only grow it stays so.  False: every
+// queue is empty.
+// (No look before the pop: a load of the line the pops hammer queues behind them -- measured, forward, one queue: 0.19 ->
+// 0.49 ms with a relaxed load in front of every atomicAdd.  And popping the next item ahead of time was measured slower in
+// the backward: vector-memory results return in order, so the current item's first record load waits behind the atomic.)
+template <class Take>
+__device__ __forceinline__ bool queue_pop(uint32_t* queues, uint32_t nq, uint32_t xcd, uint32_t& dead, int lane, Take take)
+{
+    bool got = false;
+    for (uint32_t t = 0; t < nq && !got; t++) {
+        const uint32_t y = (xcd + t) % nq;
+        if ((dead >> y) & 1u) continue;
+        uint32_t k = 0;
+        if (lane == 0) k = atomicAdd(&queues[y * GS_QUEUE_STRIDE], 1u);
+        k = __builtin_amdgcn_readfirstlane(k);
+        got = take(y, k);
+        if (!got) dead |= 1u << y;
+    }
+    return got;
+}
 
 // ---------------------------------------------------------------------------------------------
 // segment bookkeeping
@@ -193,9 +224,7 @@ __global__ __launch_bounds__(1024) void bwd_items_kernel(BwdPrepArgs prep, int c
 }
 
 // ---------------------------------------------------------------------------------------------
-// forward: one wavefront per 8x8 quadrant (h, k) of a 16x16 block, one pixel per lane, scalar f32.  (Rounds 1-2 also
-// kept a 16x8 variant, two pixels per lane in packed f32: the same instruction slots -- v_pk_* has no throughput
-// advantage -- but twice the per-splat dependent chain and a cull over 128 pixels instead of 64; 25 % slower, retired.)
+// forward: one wavefront per 8x8 quadrant (h, k) of a 16x16 block, one pixel per lane, scalar f32.
 //
 // Three kernels serve it (launch_blend_forward_v2 picks one per forward): blend_fwd_v2q_kernel, one wave per quadrant (the
 // default); blend_fwd_v2p_kernel, a staging wave beside every sweeping wave (deep lists); blend_fwd_v2w_kernel, four waves
@@ -206,12 +235,11 @@ __global__ __launch_bounds__(1024) void bwd_items_kernel(BwdPrepArgs prep, int c
 // kernel's bits.
 //
 // Checkpoints.  Every SEG list entries a quadrant that still has a live pixel saves its running state (T, R, G, B[, D])
-// for the segment-parallel backward.  Round 2 addressed the slots by list position (slot = first slot of the block +
-// segment), which sizes the arena for every list being swept to its end: 1.97 GB at the bench reserve, of which 0.1 GB
-// was ever touched.  Now a slot is ALLOCATED when it is written: every persistent wave keeps a private pool of
-// a few quadrant slots (one atomicAdd per CKPT_POOL_MAX boundaries, ckpt_pool), the slot's id goes to a small table indexed by
-// (block's first segment + segment, quadrant) -- 16 B per 64 list entries -- and the backward's item kernel copies the
-// four ids of a (block, segment) item into the item list, so the backward itself does no table look-up.  Stale table
+// for the segment-parallel backward.  A slot is ALLOCATED when it is written (slots addressed by list position size the
+// arena for every list being swept to its end: 1.97 GB at the bench reserve, of which 0.1 GB was ever touched): every
+// persistent wave keeps a private pool of a few quadrant slots (one atomicAdd per CKPT_POOL_MAX boundaries, ckpt_pool), the
+// slot's id goes to a small table indexed by (block's first segment + segment, quadrant) -- 16 B per 64 list entries --
+// and the backward's item kernel puts the table row of every (block, segment) item into the item list.  Stale table
 // entries are never read: the backward loads a quadrant's state only for pixels that were live at the boundary, and
 // then this forward wrote the entry.  An arena that runs out raises the overflow word like a pair reserve that does
 // (the render itself is complete; the step is gated, the host regrows: gs_ctx_reserve).
@@ -275,20 +303,12 @@ __device__ __forceinline__ void fwd_pop(const BlendFwdArgs& a, FwdQueue& q, bool
 {
     pos = 0xFFFFFFFFu; quad = 0;
     if (first && (q.slot >> 2) < q.staticRows) { pos = a.nq * (q.slot >> 2) + q.xcd; quad = q.slot & 3u; }
-    else if (mayPop) {
-        for (uint32_t t = 0; t < a.nq && pos == 0xFFFFFFFFu; t++) {
-            const uint32_t y = (q.xcd + t) % a.nq;
-            if ((q.dead >> y) & 1u) continue;
-            // (no look before the pop: a load of the line the pops hammer queues behind them -- measured, one queue:
-            // blend forward 0.19 -> 0.49 ms with a relaxed load in front of every atomicAdd)
-            uint32_t k = 0;
-            if (lane == 0) k = atomicAdd(&a.fwdQueue[y * 32u], 1u);
-            k = __builtin_amdgcn_readfirstlane(k);
+    else if (mayPop)
+        queue_pop(a.fwdQueue, a.nq, q.xcd, q.dead, lane, [&](uint32_t y, uint32_t k) {
             const uint32_t p = a.nq * (q.staticRows + (k >> 2)) + y;
             if (p < q.nPos) { pos = p; quad = k & 3u; }
-            else q.dead |= 1u << y;
-        }
-    }
+            return p < q.nPos;
+        });
 }
 
 // an item, decoded: the block, its quadrant, its list, this lane's pixel
@@ -301,19 +321,10 @@ struct FwdItem {
     float px, py;
     float qx0, qx1, qy0, qy1;          // the quadrant's pixel-centre rectangle, for the lane-private reach test at staging time
 };
-// A word of a table the forward only reads (blockOrder, tileRanges, segBase, the depth cuts: written by the launches in front
-// of it), through the constant address space: at a wave-uniform index it is a scalar load.  The kernels' flat __restrict__
-// arguments used to say as much; the members of a by-value struct carry no such promise, and the item's dependent chain of
-// three look-ups came out as vector loads + v_readfirstlane (blend forward on the 300 k / 800x800 scene: 0.1658 -> 0.1676 ms,
-// one-wave kernel).
-__device__ __forceinline__ uint32_t fwd_table_word(const uint32_t* table, uint32_t i)
-{
-    return ((const __attribute__((address_space(4))) uint32_t*)table)[i];
-}
 // false: a position a short last stripe leaves over (an empty list, no pixel in the image)
 __device__ __forceinline__ bool fwd_decode(const BlendFwdArgs& a, uint32_t pos, uint32_t quad, int lane, FwdItem& it)
 {
-    const uint32_t bRaw = __builtin_amdgcn_readfirstlane(fwd_table_word(a.blockOrder, pos));
+    const uint32_t bRaw = __builtin_amdgcn_readfirstlane(table_word(a.blockOrder, pos));
     const bool valid = bRaw != 0xFFFFFFFFu;
     it.b = (int)bRaw;
     it.h = (int)((quad >> 1) & 1u); it.k = (int)(quad & 1u);
@@ -322,10 +333,10 @@ __device__ __forceinline__ bool fwd_decode(const BlendFwdArgs& a, uint32_t pos, 
     if (valid) {
         const int by = it.b / a.blocksX, bx = it.b - by * a.blocksX;
         it.tile = ((by * BLK) / a.tileH) * a.gridW + (bx * BLK) / a.tileW;
-        it.start = __builtin_amdgcn_readfirstlane(fwd_table_word(a.tileRanges, 2 * it.tile));
-        const uint32_t end = __builtin_amdgcn_readfirstlane(fwd_table_word(a.tileRanges, 2 * it.tile + 1));
+        it.start = __builtin_amdgcn_readfirstlane(table_word(a.tileRanges, 2 * it.tile));
+        const uint32_t end = __builtin_amdgcn_readfirstlane(table_word(a.tileRanges, 2 * it.tile + 1));
         it.count = end > it.start ? end - it.start : 0u;
-        it.sbase = __builtin_amdgcn_readfirstlane(fwd_table_word(a.segBase, it.b));
+        it.sbase = __builtin_amdgcn_readfirstlane(table_word(a.segBase, it.b));
         gs_block_pixels(a.vg, bx, by, a.W, a.H, it.X0, it.Y0, it.XL, it.YL);
     }
     it.x = it.X0 + it.k * 8 + (lane & 7); it.y = it.Y0 + it.h * 8 + (lane >> 3);
@@ -346,9 +357,7 @@ __device__ __forceinline__ uint32_t fwd_stage_compact(f4* slot, const RecV& v, u
     const float qmin = rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, it.qx0 - v.a.x, it.qx1 - v.a.x, it.qy0 - v.a.y, it.qy1 - v.a.y);
     const bool keep = (c0 + lane < it.count) && !(qmin > CULL_QMIN);
     const unsigned long long m = __ballot(keep);
-    // kept entries in the lanes below this one (v_mbcnt: written as popc(m & ((1 << lane) - 1)), the 64-bit lane mask became a
-    // loop invariant of the item loop that the four-wave kernel, at its register budget, kept in scratch)
-    const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const uint32_t pos = rank_below(m);
     if (keep) {
         slot[pos * 3] = v.a; slot[pos * 3 + 1] = v.b;
         slot[pos * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(c0 + (uint32_t)lane + 1u)};
@@ -518,7 +527,7 @@ __device__ __forceinline__ void fwd_finish(const BlendFwdArgs& a, const FwdItem&
 {
     // depth cuts: live pixels at the end of a list that was cut short -- this forward has to be repeated without
     // cuts (pixels outside the image carry T = 0).  The flag word lives in host memory.
-    if (a.cutStore && fwd_any_live(T) && lane == 0 && fwd_table_word(a.cutStore, it.tile) != 0u) a.hostWords[0] = 1u;
+    if (a.cutStore && fwd_any_live(T) && lane == 0 && table_word(a.cutStore, it.tile) != 0u) a.hostWords[0] = 1u;
     const int x = it.X0 + it.k * 8 + (lane & 7), y = it.Y0 + it.h * 8 + (lane >> 3);
     const bool in = x < it.XL && y < it.YL;
     if (in) {
@@ -922,9 +931,95 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(BlendFwd
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward
+// backward: persistent single-wave workgroups, one (block, segment) item at a time.  The kernel is a short loop over the
+// pieces in front of it, in the order it uses them: the argument struct, the pop of the next item, its decode, the per-pixel
+// state load, the staging, the per-entry step (pair_exponent_bwd / pair_bwd / the transposed wave sum of gs_wavesum.h) and
+// the flush.
 // ---------------------------------------------------------------------------------------------
-// (wave_sum10_transposed: gs_wavesum.h)
+// what the kernel is launched with: one struct by value, filled once by launch_blend_backward_v2
+struct BlendBwdArgs {
+    int W, H, tileW, tileH, gridW, blocksX;
+    GsBackground bgc;                                       // the background the forward composited over
+    const float4* rec12;
+    const uint32_t* sortedIdx;
+    uint32_t idxMask;
+    const uint32_t *tileRanges, *blockWork;                 // per tile: its list; per block: how far the forward swept it
+    const uint32_t *itemBlock, *itemRow, *counters;         // the item list and its length (bwd_items_scan, counters[GS_CNT_ITEMS])
+    const uint32_t* segSlot;                                // [rows][4]: per item row, the four quadrants' checkpoint slots
+    const float* segState;                                  // the checkpoint arena, statePlanes x 64 floats per slot
+    uint32_t qslotCap;
+    int statePlanes;
+    uint32_t *bwdQueue, nq;
+    const float *cotColor, *cotDepth, *cotAlpha;            // the cotangents (cotDepth: DEPTH kernels only; cotAlpha may be null)
+    const float *outColor, *outDepth, *outAlpha, *finalT;   // the forward's images
+    const uint32_t* lastContrib;
+    float* gradAcc16;                                       // [N][16], cleared by the item kernel: the one thing written
+    GsVirtGeom vg;
+};
+
+// Work distribution, as in the forward: nq queues, one per XCD.  The item list is in block order, a block's segments next
+// to each other; queue x hands out the x-th nq-th of it (by item count), i.e. a horizontal stripe of the image with about
+// the same work as the others.  All the segments of a block -- which re-read the block's per-pixel cotangents and state,
+// 9 KB per item -- and the blocks next to it -- which share most of their records -- then run on one XCD and find those
+// bytes in its L2.  A wave whose own stripe is done takes from the others'.
+struct BwdQueue {
+    uint32_t xcd, slot;                   // this wave's XCD and its slot there
+    uint32_t nItems, perQ, staticPerQ;    // the list's length, a stripe's, and how much of each stripe the waves' first items cover
+    uint32_t dead;                        // queues found empty
+};
+__device__ __forceinline__ BwdQueue bwd_queue(const BlendBwdArgs& a)
+{
+    BwdQueue q;
+    q.nItems = __builtin_amdgcn_readfirstlane(table_word(a.counters, GS_CNT_ITEMS));
+    q.xcd = blockIdx.x % a.nq; q.slot = blockIdx.x / a.nq;
+    q.perQ = (q.nItems + a.nq - 1u) / a.nq;
+    q.staticPerQ = min(gridDim.x / a.nq, q.perQ);
+    q.dead = 0;
+    return q;
+}
+// the wave's next item: its static one first, then the queues.  >= nItems: none -- every queue is empty, and since they only
+// grow every wave gets there; for a first item: the wave lies beyond the static share or its stripe is short, and asks again
+__device__ __forceinline__ uint32_t bwd_pop(const BlendBwdArgs& a, BwdQueue& q, bool first, int lane)
+{
+    uint32_t item = 0xFFFFFFFFu;
+    if (first && q.slot < q.staticPerQ) item = q.xcd * q.perQ + q.slot;
+    else
+        queue_pop(a.bwdQueue, a.nq, q.xcd, q.dead, lane, [&](uint32_t y, uint32_t k) {
+            const uint32_t idx = q.staticPerQ + k;
+            const bool has = idx < q.perQ && y * q.perQ + idx < q.nItems;
+            if (has) item = y * q.perQ + idx;
+            return has;
+        });
+    return item;
+}
+
+// an item, decoded
+struct BwdItem {
+    uint32_t seg, start;               // the segment; the first entry of the tile's list
+    uint32_t i0, i1;                   // the segment's list positions, cut at the forward's sweep length
+    uint32_t qslot[4];                 // the four quadrants' checkpoint slots in front of the segment (unused for segment 0)
+    int X0, Y0, XL, YL;                // the block's pixel origin and limits (block lists: blocks are enumerated per tile)
+};
+template <int SEG>
+__device__ __forceinline__ BwdItem bwd_decode(const BlendBwdArgs& a, uint32_t item)
+{
+    BwdItem it;
+    const uint32_t packed = __builtin_amdgcn_readfirstlane(table_word(a.itemBlock, item));
+    const uint32_t row = __builtin_amdgcn_readfirstlane(table_word(a.itemRow, item));
+    const int b = (int)(packed >> 10);
+    it.seg = packed & 1023u;
+    const int by = b / a.blocksX, bx = b - by * a.blocksX;
+    const int tile = ((by * BLK) / a.tileH) * a.gridW + (bx * BLK) / a.tileW;
+    it.start = __builtin_amdgcn_readfirstlane(table_word(a.tileRanges, 2 * tile));
+    const uint32_t work = __builtin_amdgcn_readfirstlane(table_word(a.blockWork, b));
+    it.i0 = it.seg * SEG; it.i1 = min(it.i0 + SEG, work);
+    it.qslot[0] = it.qslot[1] = it.qslot[2] = it.qslot[3] = 0;
+    if (it.seg != 0)
+#pragma unroll
+        for (int k = 0; k < 4; k++) it.qslot[k] = __builtin_amdgcn_readfirstlane(table_word(a.segSlot, 4 * row + k));
+    gs_block_pixels(a.vg, bx, by, a.W, a.H, it.X0, it.Y0, it.XL, it.YL);
+    return it;
+}
 
 // packed-f32 helpers.  The f32 VALU of gfx950 retires one wave64 instruction per 4 cycles per SIMD (measured:
 // both blend kernels ran at >90 % of that issue rate while "using" 25 % of the 157 TFLOP/s headline, which
@@ -933,23 +1028,109 @@ __global__ __launch_bounds__(256, GS_V2W_WGS) void blend_fwd_v2w_kernel(BlendFwd
 __device__ __forceinline__ f2 splat2(float v) { return (f2){v, v}; }
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
+// per-pixel-pair state of the backward sweep.  With T the running transmittance, R_i = sum_{j<=i} T_j a_j S_j
+// (S_j = cot . sample_j), K = cot . final (colour, depth) + T_n cT_n and sc the reference's T-anchor scale
+// (T' = 1 - outAlpha = sc T_n), the sweep carries the three products it actually uses:
+//   Ts = sc T,   Q = sc (K - R)   (what the rest of the list and the background still owe, times sc).
+struct PairState {
+    f2 px, Ts, Q;
+    f2 cCx, cCy, cCz, cD;                // cotangents of colour / depth
+    float py;
+    uint32_t nc0, nc1;
+};
+// The lane's two pixel pairs, (x, x + 8) on rows y and y + 8 of the block, at the segment's start, from the image planes and
+// the checkpoint in front of the segment.  A pixel outside the image, or one the forward had finished before the segment
+// (nContrib <= i0), stays at nContrib 0 and takes no part.  hm: the sweep length of each 16x8 half (max nContrib over its
+// pixels): past it the half is dead, like one out of reach.
+template <bool DEPTH>
+__device__ __forceinline__ void bwd_load_pixels(const BlendBwdArgs& a, const BwdItem& it, int lane, PairState (&ps)[2], uint32_t (&hm)[2])
+{
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        PairState& p = ps[h];
+        const int y = it.Y0 + h * 8 + (lane >> 3);
+        p.py = (float)y;
+        p.Ts = p.Q = p.cCx = p.cCy = p.cCz = p.cD = splat2(0.f);
+        uint32_t ncs[2] = {0, 0};
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int x = it.X0 + k * 8 + (lane & 7);
+            p.px[k] = (float)x;
+            if (x < it.XL && y < it.YL) {
+                const size_t pix = (size_t)y * a.W + x;
+                const uint32_t n = a.lastContrib[pix];
+                if (n > it.i0) {
+                    ncs[k] = n;
+                    const float gx = a.cotColor[3 * pix], gy = a.cotColor[3 * pix + 1], gz = a.cotColor[3 * pix + 2];
+                    const float gd = DEPTH ? a.cotDepth[pix] : 0.0f;
+                    p.cCx[k] = gx; p.cCy[k] = gy; p.cCz[k] = gz; p.cD[k] = gd;
+                    const float cA = a.cotAlpha ? a.cotAlpha[pix] : 0.0f;
+                    const float Tn = a.finalT[pix];
+                    float bg0, bg1, bg2;      // T_n b_c: the products the forward added (gs_bg_terms)
+                    gs_bg_terms(a.bgc, Tn, bg0, bg1, bg2);
+                    const float cTn = -cA + gs_bg_cot(a.bgc, gx, gy, gz);
+                    // What the rest of the list still owes: cot . (final sums - the sums in front of the segment).  The
+                    // DIFFERENCE per channel first, then the dot product -- deep in a list both are of the size of the total
+                    // and their difference small, and cot . final - cot . checkpoint would carry two dot products' roundings at
+                    // the size of the total; the forward keeps its sums so that the difference itself is good (FwdPixel)
+                    const float sc = (1.0f - a.outAlpha[pix]) / Tn;     // the reference's T = 1 - outAlpha anchor
+                    float T0 = 1.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;      // state in front of the segment
+                    const uint32_t phys = it.qslot[h * 2 + k];
+                    if (it.seg != 0 && phys < a.qslotCap) {
+                        const float* st = a.segState + (size_t)phys * (a.statePlanes * 64) + lane;
+                        T0 = st[0]; s0 = st[64]; s1 = st[128]; s2 = st[192];
+                        if (DEPTH) s3 = st[256];
+                    }
+                    const float d0 = (a.outColor[3 * pix] - bg0) - s0, d1 = (a.outColor[3 * pix + 1] - bg1) - s1, d2 = (a.outColor[3 * pix + 2] - bg2) - s2;
+                    const float owedC = fmaf(gx, d0, fmaf(gy, d1, fmaf(gz, d2, DEPTH ? gd * (a.outDepth[pix] - s3) : 0.0f)));
+                    p.Ts[k] = sc * T0;
+                    p.Q[k] = sc * (owedC + Tn * cTn);
+                }
+            }
+        }
+        p.nc0 = ncs[0]; p.nc1 = ncs[1];
+        hm[h] = max(ncs[0], ncs[1]);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        hm[0] = max(hm[0], (uint32_t)__shfl_xor((int)hm[0], d, 64));
+        hm[1] = max(hm[1], (uint32_t)__shfl_xor((int)hm[1], d, 64));
+    }
+}
+
 // A list entry as the backward keeps it in LDS: the conic pre-multiplied by C = -1/(2 ln 2), so that the exponent of
 // 2^e comes out of two fused multiply-adds, e = dx^2 A + dxdy B + dy^2 Dq (A = c00 C, B = (c01 + c10) C, Dq = c11 C).
 // The FORWARD has to evaluate the quadratic form in the reference's operation order to stay within 1e-4 of it
-// (pair_exponent, gauss_alpha_raw); the backward only needs alpha to ~1e-6 (gradients are held to 1e-3), and this
+// (fwd_pre, gauss_alpha_raw); the backward only needs alpha to ~1e-6 (gradients are held to 1e-3), and this
 // form is four instructions per 16x8 half and splat shorter.
 struct RecB {
     float mx, my, A, B, Dq, r, g, b, op, depth;
 };
-__device__ __forceinline__ RecB unpack_b(const f4 a, const f4 b, const f4 c)
-{
-    RecB r;
-    r.mx = a.x; r.my = a.y; r.A = a.z; r.B = a.w;
-    r.Dq = b.x; r.r = b.z; r.g = b.w;
-    r.b = c.x; r.op = c.y; r.depth = c.z;
-    return r;
-}
 constexpr float EXP_INV_C1 = -1.3862943611198906f;     // 1 / C = -2 ln 2: gives the conic back at the flush
+// Staging compacts the 64-entry chunk at c0, as in the forward: lane j tests list entry c0 + j against the two 16x8 halves
+// of the block (rect_min_q) and parks it only if it can reach one of them, as a RecB (mx, my, A, B | Dq, -, r, g | b, op,
+// depth, tag) tagged with its position in the segment and the halves it does NOT reach (256, 512).  Entries out of reach cost
+// nothing afterwards.  Returns the entries parked.
+__device__ __forceinline__ uint32_t bwd_stage(const BlendBwdArgs& a, const BwdItem& it, const uint32_t (&hm)[2],
+                                              const uint32_t* __restrict__ idx, uint32_t c0, int lane, f4* sg)
+{
+    const float bx0 = (float)it.X0, bx1 = bx0 + 15.0f, by0 = (float)it.Y0;
+    const RecV v = load_chunk(a.rec12, idx, a.idxMask, c0, it.i1, lane);
+    const float X0 = bx0 - v.a.x, X1 = bx1 - v.a.x, Yt = by0 - v.a.y;
+    const uint32_t li = c0 + (uint32_t)lane;
+    const bool far0 = li >= hm[0] || rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, X0, X1, Yt, Yt + 7.0f) > CULL_QMIN;
+    const bool far1 = li >= hm[1] || rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, X0, X1, Yt + 8.0f, Yt + 15.0f) > CULL_QMIN;
+    const bool keep = (c0 + lane < it.i1) && !(far0 && far1);
+    const unsigned long long m = __ballot(keep);
+    const uint32_t pos = rank_below(m);
+    if (keep) {
+        const uint32_t tag = (c0 - it.i0 + (uint32_t)lane) | (far0 ? 256u : 0u) | (far1 ? 512u : 0u);
+        sg[pos * 3] = (f4){v.a.x, v.a.y, v.a.z * EXP_C1, (v.a.w + v.b.x) * EXP_C1};
+        sg[pos * 3 + 1] = (f4){v.b.y * EXP_C1, 0.0f, v.b.z, v.b.w};
+        sg[pos * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(tag)};
+    }
+    return (uint32_t)__popcll(m);
+}
 
 struct PairB {
     f2 dx, dxdy, dx2, e2;
@@ -964,17 +1145,6 @@ __device__ __forceinline__ void pair_exponent_bwd(const RecB& s, f2 px, float py
     o.dy2 = o.dy * o.dy;
     o.e2 = fma2(o.dxdy, splat2(s.B), fma2(o.dx2, splat2(s.A), splat2(o.dy2 * s.Dq)));
 }
-
-// per-pixel-pair state of the backward sweep.  With T the running transmittance, R_i = sum_{j<=i} T_j a_j S_j
-// (S_j = cot . sample_j), K = cot . final (colour, depth) + T_n cT_n and sc the reference's T-anchor scale
-// (T' = 1 - outAlpha = sc T_n), the sweep carries the three products it actually uses:
-//   Ts = sc T,   Q = sc (K - R)   (what the rest of the list and the background still owe, times sc).
-struct PairState {
-    f2 px, Ts, Q;
-    f2 cCx, cCy, cCz, cD;                // cotangents of colour / depth
-    float py;
-    uint32_t nc0, nc1;
-};
 
 // One splat against one pixel pair; adds the pair's contributions to the packed accumulators
 //   acc: 0 sum h dx   1 sum h dy   2 sum h dx^2   3 sum h dxdy   4 sum h dy^2   5 dop   6 dr   7 dg   8 db   9 ddepth
@@ -1033,210 +1203,99 @@ __device__ __forceinline__ void pair_bwd(const RecB& s, uint32_t i, const PairB&
     p.Ts = p.Ts * oma;
 }
 
-// 10 sums per splat: dmx dmy dc00 dc01(=dc10) dc11 dop dr dg db ddepth; flushed into the reference's packed
-// row order (dmx dmy dc00 dc01 dc10 dc11 dr dg db dop ddepth) of gradAcc16
-// DEPTH = false: no depth cotangent (the default training case): nine sums per splat
-// ABSGRAD: the two absolute sums of pair_bwd on top, reduced by wave_sum12_transposed into slots 12 and 14 of the splat's row
-// and flushed, times 1/|C|, into columns 12 and 13 of its gradAcc16 row (Ax, Ay in pixel units; bwd_items_kernel clears whole
-// rows, no kernel of the backward reads the row's fourth quarter)
-template <int SEG, bool DEPTH, bool ABSGRAD>
-__global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
-    int W, int H, int tileW, int tileH, int gridW, int blocksX, GsBackground bgc, const float4* __restrict__ rec12,
-    const uint32_t* __restrict__ sortedIdx, uint32_t idxMask, const uint32_t* __restrict__ tileRanges,
-    const uint32_t* __restrict__ itemRow, const uint4* __restrict__ segSlot, uint32_t qslotCap, int statePlanes,
-    const uint32_t* __restrict__ blockWork,
-    const uint32_t* __restrict__ itemBlock, uint32_t* __restrict__ counters, uint32_t* __restrict__ bwdQueue, uint32_t nq,
-    const float* __restrict__ cotColor,
-    const float* __restrict__ cotDepth, const float* __restrict__ cotAlpha, const float* __restrict__ outColor,
-    const float* __restrict__ outDepth, const float* __restrict__ outAlpha, const uint32_t* __restrict__ lastContrib,
-    const float* __restrict__ finalT, const float* __restrict__ segState, float* __restrict__ gradAcc16, GsVirtGeom vg)
+// One parked entry against the block: the two halves it reaches, the transposed wave sum of the 10 (12) per-lane sums, and
+// the park of the result in the entry's row of `part` -- a PartRow (gs_wavesum.h): every fourth lane holds one slot, and
+// three slots the reduction leaves idle take the conic terms the flush needs for the mean gradient.
+template <bool DEPTH, bool ABSGRAD>
+__device__ __forceinline__ void bwd_entry(const f4* sg, uint32_t jl, uint32_t i0, PairState (&ps)[2], int lane, float (*part)[16])
 {
-    __shared__ float part[SEG][16];   // per splat: the ten sums at wave_sum10_transposed's lanes, conic terms in the gaps
-    __shared__ f4 sg[192];
+    const f4 ra = sg[jl * 3], rb = sg[jl * 3 + 1], rc = sg[jl * 3 + 2];
+    const uint32_t tag = __builtin_amdgcn_readfirstlane(__float_as_uint(rc.w));
+    const uint32_t i = i0 + (tag & 255u);
+    const RecB s = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.z, rb.w, rc.x, rc.y, rc.z};
+    PairB e0, e1;
+    const bool k0 = (tag & 256u) != 0, k1 = (tag & 512u) != 0;     // wave-uniform: half out of reach
+    if (!k0) pair_exponent_bwd(s, ps[0].px, ps[0].py, e0);
+    if (!k1) pair_exponent_bwd(s, ps[1].px, ps[1].py, e1);
+    constexpr int NACC = ABSGRAD ? 12 : 10;
+    f2 acc2[NACC];
+#pragma unroll
+    for (int q = 0; q < NACC; q++) acc2[q] = splat2(0.0f);
+    if (!k0) pair_bwd<DEPTH, ABSGRAD, NACC>(s, i, e0, ps[0], acc2);
+    if (!k1) pair_bwd<DEPTH, ABSGRAD, NACC>(s, i, e1, ps[1], acc2);
+    float acc[NACC];
+#pragma unroll
+    for (int q = 0; q < NACC; q++) acc[q] = acc2[q].x + acc2[q].y;
+    float w;
+    if constexpr (ABSGRAD) w = wave_sum12_transposed<!DEPTH>(acc);
+    else w = wave_sum10_transposed<!DEPTH>(acc);
+    if (lane == PartRow::lane(PartRow::c00)) w = s.A * EXP_INV_C1;
+    if (lane == PartRow::lane(PartRow::c11)) w = s.Dq * EXP_INV_C1;
+    if (lane == PartRow::lane(PartRow::c01c10)) w = s.B * EXP_INV_C1;
+    if ((lane & 3) == 0) part[i - i0][lane >> 2] = w;
+}
+
+// The segment's n rows of `part` into gradAcc16, in the reference's packed column order (dmx dmy dc00 dc01 dc10 dc11 dr dg
+// db dop ddepth; PartRow says which slot a column reads).  The factor -1/2 of the exponent's derivative, the conic factors
+// of the mean gradient and the sign are applied here, once per splat.  Without a depth cotangent the depth column is not
+// written; ABSGRAD: the two absolute sums, times 1/|C|, go to columns 12 and 13 of the row (Ax, Ay in pixel units; column 11
+// is left alone, the item kernel clears whole rows, no kernel of the backward reads the row's fourth quarter).
+template <bool DEPTH, bool ABSGRAD>
+__device__ __forceinline__ void bwd_flush(const BlendBwdArgs& a, const uint32_t* __restrict__ idx, uint32_t n, int lane,
+                                          const float (*part)[16])
+{
+    constexpr uint32_t NCOL = ABSGRAD ? 13u : 11u;
+    constexpr int A1 = PartRow::sumSlot[0], A2 = PartRow::sumSlot[1];
+    for (uint32_t e = lane; e < n * NCOL; e += 64) {
+        const uint32_t j = e / NCOL, q = e - j * NCOL;
+        float v;
+        if (ABSGRAD && q >= 11) {
+            v = part[j][PartRow::slotOfColumn(q)] * -EXP_INV_C1;
+        } else if (q < 2) {
+            // d mean = -(2 c00 A1 + (c01 + c10) A2,  2 c11 A2 + (c01 + c10) A1),  A = -1/2 of the stored sums
+            const float a1 = -0.5f * part[j][A1], a2 = -0.5f * part[j][A2], cs = part[j][PartRow::c01c10];
+            v = q == 0 ? -(2.0f * part[j][PartRow::c00] * a1 + cs * a2) : -(2.0f * part[j][PartRow::c11] * a2 + cs * a1);
+        } else {
+            v = (DEPTH || q != 10) ? part[j][PartRow::slotOfColumn(q)] : 0.0f;
+            if (q < 6) v *= -0.5f;                                            // the four conic columns
+        }
+        if (v != 0.0f) atomicAdd(&a.gradAcc16[(size_t)(idx[j] & a.idxMask) * 16 + (ABSGRAD && q >= 11 ? q + 1 : q)], v);
+    }
+}
+
+// SEG list positions per item at most; DEPTH = false: no depth cotangent (the default training case): nine sums per splat;
+// ABSGRAD: the two absolute sums of pair_bwd on top.
+// Four waves per SIMD, no more: the default grid (16 waves per CU, gs_ctx::bwdWavesPerCu) is one wave per slot of the chip at
+// that occupancy, and the instantiations without a depth cotangent need few enough registers for a fifth wave, with which
+// the dispatcher is free to fill some CUs with 20 workgroups and leave others 12.
+template <int SEG, bool DEPTH, bool ABSGRAD>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void blend_bwd_v2_kernel(BlendBwdArgs a)
+{
+    __shared__ float part[SEG][16];   // per entry of the segment: a PartRow
+    __shared__ f4 sg[192];            // the staged chunk: three f4 per parked entry
     const int lane = threadIdx.x;
-    const uint32_t nItems = __builtin_amdgcn_readfirstlane(counters[GS_CNT_ITEMS]);
-    // (popping the next item ahead of time was measured slower: vector-memory results return in order, so the first
-    // record load of the current item then waits behind the contended atomic)
-    // Work distribution (round 4), as in the forward: nq queues, one per XCD.  The item list is in block order, a block's
-    // segments next to each other; queue x hands out the x-th nq-th of it (by item count), i.e. a horizontal stripe of the
-    // image with about the same work as the others.  All the segments of a block -- which re-read the block's per-pixel
-    // cotangents and state, 9 KB per item -- and the blocks next to it -- which share most of their records -- then run on
-    // one XCD and find those bytes in its L2.  A wave whose own stripe is done takes from the others'.
-    const uint32_t xcd = blockIdx.x % nq, slot = blockIdx.x / nq;
-    const uint32_t perQ = (nItems + nq - 1u) / nq;
-    const uint32_t staticPerQ = min(gridDim.x / nq, perQ);      // items of each stripe covered by the waves' first items
-    uint32_t dead = 0;
+    BwdQueue q = bwd_queue(a);
     for (bool first = true;; first = false) {
-        uint32_t item = 0xFFFFFFFFu;
-        if (first && slot < staticPerQ) item = xcd * perQ + slot;
-        else {
-            for (uint32_t t = 0; t < nq && item == 0xFFFFFFFFu; t++) {
-                const uint32_t y = (xcd + t) % nq;
-                if ((dead >> y) & 1u) continue;
-                uint32_t k = 0;
-                if (lane == 0) k = atomicAdd(&bwdQueue[y * 32u], 1u);
-                k = __builtin_amdgcn_readfirstlane(k);
-                const uint32_t idx = staticPerQ + k;
-                if (idx < perQ && y * perQ + idx < nItems) item = y * perQ + idx;
-                else dead |= 1u << y;
-            }
+        const uint32_t item = bwd_pop(a, q, first, lane);
+        if (item >= q.nItems) {
+            if (first) continue;
+            break;
         }
-        if (item == 0xFFFFFFFFu || item >= nItems) {
-            if (first) continue;       // (a wave beyond the static share: try the queues)
-            break;                     // every queue is empty; they only grow: every wave reaches this exit
-        }
-        const uint32_t packed = __builtin_amdgcn_readfirstlane(itemBlock[item]);
-        const uint32_t row = __builtin_amdgcn_readfirstlane(itemRow[item]);
-        const int b = (int)(packed >> 10);
-        const uint32_t seg = packed & 1023u;
-        const int by = b / blocksX, bx = b - by * blocksX;
-        const int tile = ((by * BLK) / tileH) * gridW + (bx * BLK) / tileW;
-        const uint32_t start = __builtin_amdgcn_readfirstlane(tileRanges[2 * tile]);
-        const uint32_t work = __builtin_amdgcn_readfirstlane(blockWork[b]);
-        const uint32_t i0 = seg * SEG, i1 = min(i0 + SEG, work);
-        // the four quadrants' checkpoint slots in front of this segment (unused for segment 0)
-        uint32_t qslot[4] = {0, 0, 0, 0};
-        if (seg != 0) {
-            const uint4 q4 = segSlot[row];
-            qslot[0] = __builtin_amdgcn_readfirstlane(q4.x); qslot[1] = __builtin_amdgcn_readfirstlane(q4.y);
-            qslot[2] = __builtin_amdgcn_readfirstlane(q4.z); qslot[3] = __builtin_amdgcn_readfirstlane(q4.w);
-        }
-
-        int BX0, BY0, BXL, BYL;     // the block's pixel origin and limits (block lists: blocks are enumerated per tile)
-        gs_block_pixels(vg, bx, by, W, H, BX0, BY0, BXL, BYL);
+        const BwdItem it = bwd_decode<SEG>(a, item);
         PairState ps[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            PairState& p = ps[h];
-            const int y = BY0 + h * 8 + (lane >> 3);
-            p.py = (float)y;
-            p.Ts = p.Q = p.cCx = p.cCy = p.cCz = p.cD = splat2(0.f);
-            uint32_t ncs[2] = {0, 0};
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const int x = BX0 + k * 8 + (lane & 7);
-                p.px[k] = (float)x;
-                if (x < BXL && y < BYL) {
-                    const size_t pix = (size_t)y * W + x;
-                    const uint32_t n = lastContrib[pix];
-                    if (n > i0) {
-                        ncs[k] = n;
-                        const float gx = cotColor[3 * pix], gy = cotColor[3 * pix + 1], gz = cotColor[3 * pix + 2];
-                        const float gd = DEPTH ? cotDepth[pix] : 0.0f;
-                        p.cCx[k] = gx; p.cCy[k] = gy; p.cCz[k] = gz; p.cD[k] = gd;
-                        const float cA = cotAlpha ? cotAlpha[pix] : 0.0f;
-                        const float Tn = finalT[pix];
-                        float bg0, bg1, bg2;      // T_n b_c: the products the forward added (gs_bg_terms)
-                        gs_bg_terms(bgc, Tn, bg0, bg1, bg2);
-                        const float cTn = -cA + gs_bg_cot(bgc, gx, gy, gz);
-                        // What the rest of the list still owes: cot . (final sums - the sums in front of the segment).  Round 6:
-                        // the DIFFERENCE per channel first, then the dot product -- deep in a list both are of the size of the
-                        // total and their difference small, and cot . final - cot . checkpoint (rounds 2-5) carried two dot
-                        // products' roundings at the size of the total; the forward keeps its sums so that the difference
-                        // itself is good (blend_fwd_v2q_kernel: base + chunk)
-                        const float sc = (1.0f - outAlpha[pix]) / Tn;     // the reference's T = 1 - outAlpha anchor
-                        float T0 = 1.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;      // state in front of the segment
-                        const uint32_t phys = qslot[h * 2 + k];
-                        if (seg != 0 && phys < qslotCap) {
-                            const float* st = segState + (size_t)phys * (statePlanes * 64) + lane;
-                            T0 = st[0]; s0 = st[64]; s1 = st[128]; s2 = st[192];
-                            if (DEPTH) s3 = st[256];
-                        }
-                        const float d0 = (outColor[3 * pix] - bg0) - s0, d1 = (outColor[3 * pix + 1] - bg1) - s1, d2 = (outColor[3 * pix + 2] - bg2) - s2;
-                        const float owedC = fmaf(gx, d0, fmaf(gy, d1, fmaf(gz, d2, DEPTH ? gd * (outDepth[pix] - s3) : 0.0f)));
-                        p.Ts[k] = sc * T0;
-                        p.Q[k] = sc * (owedC + Tn * cTn);
-                    }
-                }
-            }
-            p.nc0 = ncs[0]; p.nc1 = ncs[1];
-        }
-
-        // sweep length of each half (max nContrib over its pixels): past it the half is dead, like one out of reach
-        uint32_t hm0 = max(ps[0].nc0, ps[0].nc1), hm1 = max(ps[1].nc0, ps[1].nc1);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            hm0 = max(hm0, (uint32_t)__shfl_xor((int)hm0, d, 64));
-            hm1 = max(hm1, (uint32_t)__shfl_xor((int)hm1, d, 64));
-        }
-        const uint32_t* __restrict__ idx = sortedIdx + start;
-        const uint32_t n = i1 - i0;
+        uint32_t hm[2];
+        bwd_load_pixels<DEPTH>(a, it, lane, ps, hm);
+        const uint32_t* __restrict__ idx = a.sortedIdx + it.start;
+        const uint32_t n = it.i1 - it.i0;
         // rows of splats that turn out culled are never written: start from zeros
         for (uint32_t r = lane; r < n * 4; r += 64) reinterpret_cast<f4*>(&part[0][0])[r] = (f4){0.f, 0.f, 0.f, 0.f};
-        // Each 64-entry chunk is compacted at staging time, as in the forward: lane j tests list entry c0 + j against
-        // the two 16x8 halves of the block (rect_min_q) and parks it only if it can reach one of them, tagged with its
-        // list position and the halves it reaches.  Entries out of reach cost nothing below.
-        const float bx0 = (float)BX0, bx1 = bx0 + 15.0f, by0 = (float)BY0;
-        for (uint32_t c0 = i0; c0 < i1; c0 += 64) {
-            uint32_t nEff;
-            {
-                const RecV v = load_chunk(rec12, idx, idxMask, c0, i1, lane);
-                const float X0 = bx0 - v.a.x, X1 = bx1 - v.a.x, Yt = by0 - v.a.y;
-                const uint32_t li = c0 + (uint32_t)lane;
-                const bool far0 = li >= hm0 || rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, X0, X1, Yt, Yt + 7.0f) > CULL_QMIN;
-                const bool far1 = li >= hm1 || rect_min_q(v.a.z, v.a.w, v.b.x, v.b.y, X0, X1, Yt + 8.0f, Yt + 15.0f) > CULL_QMIN;
-                const bool keep = (c0 + lane < i1) && !(far0 && far1);
-                const unsigned long long m = __ballot(keep);
-                const uint32_t pos = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (keep) {
-                    const uint32_t tag = (c0 - i0 + (uint32_t)lane) | (far0 ? 256u : 0u) | (far1 ? 512u : 0u);
-                    // RecB: the conic goes in pre-multiplied (mx, my, A, B | Dq, -, r, g | b, op, depth, tag)
-                    sg[pos * 3] = (f4){v.a.x, v.a.y, v.a.z * EXP_C1, (v.a.w + v.b.x) * EXP_C1};
-                    sg[pos * 3 + 1] = (f4){v.b.y * EXP_C1, 0.0f, v.b.z, v.b.w};
-                    sg[pos * 3 + 2] = (f4){v.c.x, v.c.y, v.c.z, __uint_as_float(tag)};
-                }
-                nEff = (uint32_t)__popcll(m);
-            }
-          for (uint32_t jl = 0; jl < nEff; jl++) {
-            const f4 rc = sg[jl * 3 + 2];
-            const uint32_t tag = __builtin_amdgcn_readfirstlane(__float_as_uint(rc.w));
-            const uint32_t i = i0 + (tag & 255u);
-            const RecB s = unpack_b(sg[jl * 3], sg[jl * 3 + 1], rc);
-            PairB e0, e1;
-            const bool k0 = (tag & 256u) != 0, k1 = (tag & 512u) != 0;     // wave-uniform: half out of reach
-            if (!k0) pair_exponent_bwd(s, ps[0].px, ps[0].py, e0);
-            if (!k1) pair_exponent_bwd(s, ps[1].px, ps[1].py, e1);
-            constexpr int NACC = ABSGRAD ? 12 : 10;
-            f2 acc2[NACC];
-#pragma unroll
-            for (int q = 0; q < NACC; q++) acc2[q] = splat2(0.0f);
-            if (!k0) pair_bwd<DEPTH, ABSGRAD, NACC>(s, i, e0, ps[0], acc2);
-            if (!k1) pair_bwd<DEPTH, ABSGRAD, NACC>(s, i, e1, ps[1], acc2);
-            float acc[NACC];
-#pragma unroll
-            for (int q = 0; q < NACC; q++) acc[q] = acc2[q].x + acc2[q].y;
-            float w;
-            if constexpr (ABSGRAD) w = wave_sum12_transposed<!DEPTH>(acc);     // slots 12 (sum |h u|) and 14 (sum |h v|) on top
-            else w = wave_sum10_transposed<!DEPTH>(acc);
-            // slot 4 r + q of the splat's row: 0 a1 (sum h dx), 2 a2 (sum h dy), 1 dc00, 3 dc01, 8 dc11, 10 dop, 9 dr,
-            // 11 dg, 4 db, 6 ddepth; idle quads park the conic terms the flush needs for the mean gradient:
-            // 5 c00, 7 c11, 13 c01 + c10
-            if (lane == 20) w = s.A * EXP_INV_C1;        // c00
-            if (lane == 28) w = s.Dq * EXP_INV_C1;       // c11
-            if (lane == 52) w = s.B * EXP_INV_C1;        // c01 + c10
-            if ((lane & 3) == 0) part[i - i0][lane >> 2] = w;
-          }
+        for (uint32_t c0 = it.i0; c0 < it.i1; c0 += 64) {
+            const uint32_t nEff = bwd_stage(a, it, hm, idx, c0, lane, sg);
+            for (uint32_t jl = 0; jl < nEff; jl++) bwd_entry<DEPTH, ABSGRAD>(sg, jl, it.i0, ps, lane, part);
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the LDS writes have landed (single wave)
         __builtin_amdgcn_wave_barrier();
-        constexpr uint32_t NCOL = ABSGRAD ? 13u : 11u;
-        for (uint32_t e = lane; e < n * NCOL; e += 64) {
-            const uint32_t j = e / NCOL, q = e - j * NCOL;
-            // packed column q (dmx dmy dc00 dc01 dc10 dc11 dr dg db dop ddepth) <- slot
-            float v;
-            if (ABSGRAD && q >= 11) {
-                v = part[j][q == 11 ? 12 : 14] * -EXP_INV_C1;                     // Ax, Ay: columns 12 and 13 (11 is left alone)
-            } else if (q < 2) {
-                // d mean = -(2 c00 A1 + (c01 + c10) A2,  2 c11 A2 + (c01 + c10) A1),  A = -1/2 of the stored sums
-                const float a1 = -0.5f * part[j][0], a2 = -0.5f * part[j][2], cs = part[j][13];
-                v = q == 0 ? -(2.0f * part[j][5] * a1 + cs * a2) : -(2.0f * part[j][7] * a2 + cs * a1);
-            } else {
-                const uint32_t src = (0x6a4b98331ull >> ((q - 2) * 4)) & 15u;     // 1 3 3 8 9 11 4 10 6
-                v = (DEPTH || q != 10) ? part[j][src] : 0.0f;
-                if (q < 6) v *= -0.5f;                                            // the four conic columns
-            }
-            if (v != 0.0f) atomicAdd(&gradAcc16[(size_t)(idx[i0 + j] & idxMask) * 16 + (ABSGRAD && q >= 11 ? q + 1 : q)], v);
-        }
+        bwd_flush<DEPTH, ABSGRAD>(a, idx + it.i0, n, lane, part);
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
     }
@@ -1246,7 +1305,6 @@ __global__ __launch_bounds__(64) void blend_bwd_v2_kernel(
 // launchers
 // ---------------------------------------------------------------------------------------------
 constexpr int SEGLEN = GS_SEG_LEN;
-// the grid the fused forward is launched with (its queue starts behind the waves' static first items)
 // four waves per quadrant (blend_fwd_v2w_kernel) where the image has fewer quadrants than the chip has wave slots
 // (gs_ctx::fwdWide: 1 / 0 force, -1 by that rule; the trace buffer and GS_TUNE_FWD_QUADRANTS 0 keep the one-wave kernel)
 bool blend_forward_v2_wide(const gs_ctx* c)
@@ -1259,7 +1317,8 @@ bool blend_forward_v2_wide(const gs_ctx* c)
 // mapped host memory: read without a wait, a forward late) per pixel block.  Measured (MI355X, blend forward, one-wave / pair):
 // c3 grown to 1 M Gaussians, 8400 pairs per block: 0.890 -> 0.805 ms; c3 at 200 x 200 tiles, 5070: 0.237 / 0.238; c3, 3160:
 // 0.175 / 0.176; c2 0.174 / 0.174; the 2 M garden scene under its depth cuts, 740: 0.311 -> 0.320.  The decision is taken ONCE
-// per forward (gs_render_forward, fwdPairNow): the binning's bookkeeping and the launch must see the same grid.
+// per forward (gs_render_forward, fwdPairNow): the word it reads changes while the forward is being enqueued, and the grid,
+// the checkpoint pools sized by it and the kernel launched must follow from one reading.
 bool blend_forward_v2_pair_decide(const gs_ctx* c)
 {
     if (c->fwdTrace || !c->fwdQuadrants || blend_forward_v2_wide(c)) return false;
@@ -1269,15 +1328,12 @@ bool blend_forward_v2_pair_decide(const gs_ctx* c)
     // forward still 5 % ahead, 0.868 -> 0.825 ms; 200 x 200 tiles on block lists, 5070: level either way)
     return c->numPixBlocks > 0 && lastM / (unsigned long long)c->numPixBlocks >= 4500ull;
 }
-bool blend_forward_v2_pair(const gs_ctx* c)
-{
-    return c->fwdPairNow;
-}
-int blend_forward_v2_grid(const gs_ctx* c)
+// the grid the fused forward is launched with, in takers (waves of the one-wave kernel, workgroups of the other two)
+static int blend_forward_v2_grid(const gs_ctx* c)
 {
     const int fwdItems = c->numPixBlocks * 4;
     const int fwdGrid = blend_forward_v2_wide(c) ? c->numCUs * GS_V2W_WGS
-                        : blend_forward_v2_pair(c) ? c->numCUs * (c->fwdPair > 1 ? c->fwdPair : GS_V2P_WGS)
+                        : c->fwdPairNow ? c->numCUs * (c->fwdPair > 1 ? c->fwdPair : GS_V2P_WGS)
                                                    : c->numCUs * 4 * c->fwdWavesPerSimd;
     return fwdGrid > fwdItems ? fwdItems : fwdGrid;
 }
@@ -1287,7 +1343,7 @@ void fill_seg_base(gs_ctx* c, SegBaseArgs& a)
     a.nBlocks = c->numPixBlocks; a.blocksX = c->blocksX; a.tileW = c->tileW; a.tileH = c->tileH; a.gridW = c->gridW;
     a.tileRanges = c->tileRanges; a.tileTotal = nullptr;
     a.segBase = c->segBase; a.blockWork = c->blockWork; a.counters = c->counters; a.workHint = c->workHint;
-    a.blockOrder = c->blockOrder; a.queueStart = (uint32_t)blend_forward_v2_grid(c); a.fwdQueue = c->fwdQueue;
+    a.blockOrder = c->blockOrder; a.fwdQueue = c->fwdQueue;
 }
 
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha)
@@ -1303,7 +1359,7 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
         fill_seg_base(c, sa);
         hipLaunchKernelGGL(seg_base_kernel<SEGLEN>, dim3(1), dim3(1024), 0, c->stream, sa);
     }
-    const bool wide = blend_forward_v2_wide(c), pair = !wide && blend_forward_v2_pair(c);
+    const bool wide = blend_forward_v2_wide(c), pair = !wide && c->fwdPairNow;
     // capacity in slots of THIS forward's planes (the arena is sized for five)
     const uint32_t qcap = (uint32_t)(c->qslotCap * 5 / c->fwd.statePlanes);
     c->fwd.qslotCap = qcap;
@@ -1344,7 +1400,7 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
     return GS_OK;
 }
 
-void fill_bwd_prep(gs_ctx* c, int N, uint32_t queueStart, BwdPrepArgs& p)
+void fill_bwd_prep(gs_ctx* c, int N, BwdPrepArgs& p)
 {
     p.nBlocks = c->numPixBlocks;
     p.blockWork = c->fwd.blockWork;
@@ -1353,7 +1409,6 @@ void fill_bwd_prep(gs_ctx* c, int N, uint32_t queueStart, BwdPrepArgs& p)
     p.segBase = c->segBase;
     p.itemCap = (uint32_t)c->itemCap;
     p.counters = c->counters;
-    p.queueStart = queueStart;
     p.bwdQueue = c->bwdQueue;
     p.clearBuf = reinterpret_cast<float4*>(c->gradAcc16);
     p.clearCount = (size_t)N * 4;
@@ -1366,37 +1421,38 @@ void fill_bwd_prep(gs_ctx* c, int N, uint32_t queueStart, BwdPrepArgs& p)
     p.rec12 = c->packed12;
 }
 
-// the grid the fused backward will be launched with (its queue starts behind the waves' static first items)
-int blend_backward_v2_grid(const gs_ctx* c)
-{
-    int grid = c->numCUs * c->bwdWavesPerCu;
-    if ((long long)grid > c->itemCap) grid = (int)c->itemCap;
-    return grid < 1 ? 1 : grid;
-}
-
 int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
                              const float* outColor, const float* outDepth, const float* outAlpha, bool absgrad)
 {
-    const int blocksX = c->blocksX, nBlocks = c->numPixBlocks;
-    const int grid = blend_backward_v2_grid(c);
+    int grid = c->numCUs * c->bwdWavesPerCu;           // single-wave workgroups
+    if ((long long)grid > c->itemCap) grid = (int)c->itemCap;
+    if (grid < 1) grid = 1;
     BwdPrepArgs prep;
-    fill_bwd_prep(c, N, (uint32_t)grid, prep);
+    fill_bwd_prep(c, N, prep);
     // gs_loss_forward_backward has carried all of this along with its own kernel (ssim.hip) when the loss of this
     // forward went through the library
-    const bool prepared = c->fwd.bwdPrepared && c->fwd.preparedQueueStart == (uint32_t)grid && c->fwd.preparedN == N;
+    const bool prepared = c->fwd.bwdPrepared && c->fwd.preparedN == N;
     c->fwd.bwdPrepared = false;          // consumed: a second backward of the same forward prepares for itself
     if (!prepared) {
-        const int cutBlocks = prep.cutStore ? gs_div_up(nBlocks, 1024) : 0;
+        const int cutBlocks = prep.cutStore ? gs_div_up(c->numPixBlocks, 1024) : 0;
         const int clearBlocks = (int)((prep.clearCount + 8191) / 8192 < 1024 ? (prep.clearCount + 8191) / 8192 : 1024);
         hipLaunchKernelGGL(bwd_items_kernel<SEGLEN>, dim3(GS_ITEM_PARTS + cutBlocks + clearBlocks), dim3(1024), 0, c->stream, prep, cutBlocks);
     }
+    BlendBwdArgs a;
+    a.W = c->W; a.H = c->H; a.tileW = c->tileW; a.tileH = c->tileH; a.gridW = c->gridW; a.blocksX = c->blocksX;
+    a.bgc = c->fwd.bg;
+    a.rec12 = reinterpret_cast<const float4*>(c->packed12); a.sortedIdx = c->sortedRaw; a.idxMask = c->idxMask;
+    a.tileRanges = c->tileRanges; a.blockWork = c->fwd.blockWork;
+    a.itemBlock = c->itemBlock; a.itemRow = c->itemRow; a.counters = c->counters;
+    a.segSlot = c->segSlot; a.segState = c->segState;
+    a.qslotCap = c->fwd.qslotCap; a.statePlanes = c->fwd.statePlanes;
+    a.bwdQueue = c->bwdQueue; a.nq = GS_QUEUES;
+    a.cotColor = cotColor; a.cotDepth = cotDepth; a.cotAlpha = cotAlpha;
+    a.outColor = outColor; a.outDepth = outDepth; a.outAlpha = outAlpha; a.finalT = c->finalT;
+    a.lastContrib = c->lastContrib; a.gradAcc16 = c->gradAcc16; a.vg = c->virt;
     auto kern = absgrad ? (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, true> : blend_bwd_v2_kernel<SEGLEN, false, true>)
                         : (cotDepth ? blend_bwd_v2_kernel<SEGLEN, true, false> : blend_bwd_v2_kernel<SEGLEN, false, false>);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, c->stream, c->W, c->H, c->tileW, c->tileH,
-                       c->gridW, blocksX, c->fwd.bg, reinterpret_cast<const float4*>(c->packed12), c->sortedRaw,
-                       c->idxMask, c->tileRanges, c->itemRow, reinterpret_cast<const uint4*>(c->segSlot), c->fwd.qslotCap, c->fwd.statePlanes, c->fwd.blockWork, c->itemBlock, c->counters, c->bwdQueue, 8u, cotColor,
-                       cotDepth, cotAlpha, outColor, outDepth, outAlpha, c->lastContrib, c->finalT, c->segState,
-                       c->gradAcc16, c->virt);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, c->stream, a);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }

@@ -1,5 +1,5 @@
 // gs_bwd_prep.h -- what the fused blend backward needs before its first wave starts: the (block, segment) work-item
-// list from the forward's per-block sweep lengths, the queue head, and a cleared accumulator.  Shared by the stand-alone
+// list from the forward's per-block sweep lengths, the queue heads, and a cleared accumulator.  Shared by the stand-alone
 // bwd_items_kernel (blend_v2.hip) and by loss_fused_kernel (ssim.hip), which carries the same work along as extra
 // blocks when the loss of a fused forward is taken through the library: the serial item scan (one block, ~12 us) and the
 // clear then run UNDER the loss kernel instead of between it and the backward.
@@ -14,14 +14,13 @@ namespace gs {
 
 struct BwdPrepArgs {
     int nBlocks;
+    uint32_t itemCap;
     const uint32_t* blockWork;
     uint32_t* itemBlock;
     uint32_t* itemRow;       // per item: its row of the checkpoint-slot table (segBase[block] + segment - 1)
     const uint32_t* segBase;
-    uint32_t itemCap;
     uint32_t* counters;
-    uint32_t queueStart;
-    uint32_t* bwdQueue;      // [8][32]: the fused backward's work-queue heads, one per XCD (a cache line each)
+    uint32_t* bwdQueue;      // [GS_QUEUES][GS_QUEUE_STRIDE]: the fused backward's work-queue heads, one per XCD (a cache line each)
     float4* clearBuf;        // gradAcc16 as float4s
     size_t clearCount;
     // renewal of the view's depth cuts (binning.hip), one tile per thread; cutStore == nullptr: none kept
@@ -118,11 +117,8 @@ __device__ __forceinline__ void bwd_items_scan(const BwdPrepArgs& a, uint32_t* s
         if (threadIdx.x == 0) carry = c + tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0 && part == 0) {
-        a.counters[GS_CNT_ITEMS] = carry < a.itemCap ? carry : a.itemCap;
-        a.counters[GS_CNT_QUEUE] = a.queueStart;      // (rounds 1-3: the one queue behind the waves' first items)
-    }
-    if (part == 0 && threadIdx.x < 8) a.bwdQueue[threadIdx.x * 32] = 0u;      // blend_bwd_v2_kernel: pops count from the static share on
+    if (threadIdx.x == 0 && part == 0) a.counters[GS_CNT_ITEMS] = carry < a.itemCap ? carry : a.itemCap;
+    if (part == 0 && threadIdx.x < GS_QUEUES) a.bwdQueue[threadIdx.x * GS_QUEUE_STRIDE] = 0u;      // blend_bwd_v2_kernel: pops count from the static share on
 }
 
 // workgroup `part` of `parts`: its share of the accumulator clear
@@ -145,8 +141,7 @@ struct SegBaseArgs {
     uint32_t* counters;
     const uint32_t* workHint;
     uint32_t* blockOrder;
-    uint32_t queueStart;
-    uint32_t* fwdQueue;             // [8][32]: the fused forward's eight work-queue heads, one per XCD (a cache line each)
+    uint32_t* fwdQueue;             // [GS_QUEUES][GS_QUEUE_STRIDE]: the fused forward's work-queue heads, one per XCD (a cache line each)
 };
 
 // Launch order of the forward's items, round 4: position p of the order belongs to queue / XCD p mod nq (blend_v2.hip).
@@ -168,10 +163,9 @@ __device__ __forceinline__ void seg_base_body(const SegBaseArgs& a, uint32_t* ld
     // The order is built per stripe of `per` blocks, nq stripes interleaved; there is ONE stripe, sorted deepest first, whose
     // positions go to the queues round-robin (position p to queue p mod the forward's queue count)
     const int nq = 1, per = a.nBlocks;
-    // every persistent wave's first item is fixed by its blockIdx.x (no pop: thousands of simultaneous pops on one counter
-    // take ~6 ns each to resolve); the queues proper start behind those
-    if (threadIdx.x == 0) { carry = 0; a.counters[GS_CNT_QUEUE_FWD] = a.queueStart; wmax = 0; }
-    if (threadIdx.x < 8) a.fwdQueue[threadIdx.x * 32] = 0u;         // (blend_fwd_v2q_kernel: pops count from the static rows on)
+    if (threadIdx.x == 0) { carry = 0; wmax = 0; }
+    // (every persistent wave's first item is fixed by its blockIdx.x; the queues' pops count from behind those static rows on)
+    if (threadIdx.x < GS_QUEUES) a.fwdQueue[threadIdx.x * GS_QUEUE_STRIDE] = 0u;
     for (int i = threadIdx.x; i < nq * 256; i += nT) bucket[i] = 0;
     for (int i = threadIdx.x; i < a.nBlocks + 8; i += nT) a.blockOrder[i] = 0xFFFFFFFFu;
     __syncthreads();
@@ -253,6 +247,6 @@ __device__ __forceinline__ void seg_base_body(const SegBaseArgs& a, uint32_t* ld
 
 // blend_v2.hip
 void fill_seg_base(gs_ctx* c, SegBaseArgs& a);
-void fill_bwd_prep(gs_ctx* c, int N, uint32_t queueStart, BwdPrepArgs& p);
+void fill_bwd_prep(gs_ctx* c, int N, BwdPrepArgs& p);
 
 }  // namespace gs

@@ -19,13 +19,15 @@ enum {
     GS_CNT_CONTRIB_LO = 5,
     GS_CNT_CONTRIB_HI = 6,
     GS_CNT_ITEMS = 9,     // backward work items (block, segment)
-    GS_CNT_QUEUE = 10,    // backward work-queue head
-    GS_CNT_QUEUE_FWD = 11,  // forward work-queue head
     GS_CNT_CUT_DROPPED = 12,  // statistics: candidate pairs the depth cuts left out (low 32 bits)
     GS_CNT_QSLOTS = 16,   // ... + 8: checkpoint slots (one 8x8 quadrant each) the fused forward's waves have drawn from the
                           // shared part of the arena, one counter per eighth of it (blend_v2.hip)
     GS_CNT_COUNT = 24
 };
+
+// work queues of the fused blend kernels (blend_v2.hip): one head per XCD, each on a 128-byte line of its own
+constexpr uint32_t GS_QUEUES = 8;
+constexpr uint32_t GS_QUEUE_STRIDE = 32;    // words from one queue's head to the next
 
 constexpr int GS_SORT_THREADS = 256;
 constexpr int GS_SORT_ITEMS = 16;
@@ -195,8 +197,8 @@ struct gs_ctx {
     uint32_t* blockWork = nullptr;   // [numPixBlocks] active buffer: blockWorkOwn, or the caller's (gs_set_block_work_buffer)
     uint32_t* blockWorkOwn = nullptr;
     uint32_t* blockOrder = nullptr;  // [numPixBlocks]
-    uint32_t* fwdQueue = nullptr;    // [8][32] work-queue heads of the fused blend forward, one per XCD
-    uint32_t* bwdQueue = nullptr;    // [8][32] ... and of the fused blend backward (a stripe of the item list each)
+    uint32_t* fwdQueue = nullptr;    // [GS_QUEUES][GS_QUEUE_STRIDE] work-queue heads of the fused blend forward, one per XCD
+    uint32_t* bwdQueue = nullptr;    // ... and of the fused blend backward (a stripe of the item list each)
     // depth cuts (binning.hip): per tile, 0xFFFFFFFF - (largest depth key still binned); 0 = no cut.  Lives in the
     // caller's per-view hint buffer behind the block-work words (gs_set_view_hints); written by the backward's item
     // kernel, read by the next forward of that view.
@@ -378,7 +380,6 @@ struct gs_ctx {
         bool cutsActive = false;     // this forward binned under depth cuts
         bool missChecked = true;     // ... and gs_forward_missed has been asked since
         bool bwdPrepared = false;    // the loss kernel has built the backward's item list and cleared its accumulator
-        uint32_t preparedQueueStart = 0;
         int preparedN = 0;
         int statePlanes = 5;         // planes per checkpoint slot this forward wrote (5 with the depth sum, 4 without)
         uint32_t qslotCap = 0;       // ... and how many such slots the arena held for it
@@ -530,8 +531,6 @@ int launch_contrib_actions(gs_ctx* c, int N, const float* score, float threshold
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha);
 int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,
                              const float* outColor, const float* outDepth, const float* outAlpha, bool absgrad = false);
-int blend_backward_v2_grid(const gs_ctx* c);
-int blend_forward_v2_grid(const gs_ctx* c);
 bool blend_forward_v2_pair_decide(const gs_ctx* c);
 
 // ssim.hip

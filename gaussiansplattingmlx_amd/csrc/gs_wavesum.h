@@ -157,5 +157,19 @@ __device__ __forceinline__ float wave_sum12_transposed(const float (&v)[12])
     return d;
 }
 
+// The two tables above as data, and what the fused blend backward (blend_v2.hip) makes of them.  Slot s of a splat's
+// 16-float row is what lane 4 s holds after the reduction (row s / 4, quad s % 4); the backward parks the row in LDS, fills
+// three idle slots with the conic terms its flush needs, and the flush reads the packed gradAcc16 columns back out of it.
+struct PartRow {
+    static constexpr int sumSlot[12] = {0, 2, 1, 3, 8, 10, 9, 11, 4, 6, 12, 14};    // v[k] -> slot (v8 .. v11: their first copy)
+    static constexpr int c00 = 5, c11 = 7, c01c10 = 13;                             // idle slots (second copies): the splat's conic terms
+    // packed column -> the sum it is made of: dmx dmy (with the conic terms) dc00 dc01 dc10 dc11 dr dg db dop ddepth, then the
+    // two absolute sums (flushed one column further on: 12 and 13)
+    static constexpr int columnSum[13] = {0, 1, 2, 3, 3, 4, 6, 7, 8, 5, 9, 10, 11};
+    static constexpr int lane(int slot) { return 4 * slot; }
+    // column -> slot, a nibble per column: a shift and a mask in the flush's loop, no table in memory
+    static constexpr unsigned long long columnSlots(int q = 12) { return q < 0 ? 0ull : columnSlots(q - 1) | (unsigned long long)sumSlot[columnSum[q]] << (4 * q); }
+    static __device__ __forceinline__ uint32_t slotOfColumn(uint32_t q) { return (uint32_t)(columnSlots() >> (q * 4u)) & 15u; }
+};
 
 }  // namespace gs

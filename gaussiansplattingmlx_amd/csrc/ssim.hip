@@ -577,13 +577,11 @@ int launch_loss(gs_ctx* c, const float* render, const float* target, const float
     int prepBlocks = 0, cutBlocks = 0;
     if (c->fast16 && c->fwd.valid && !c->fwd.consumed && !c->fwd.blendBackwardDone && c->fwd.N > 0 && c->itemBlock &&
         c->fwd.statePlanes != 0) {         // (a render-only forward has no backward to prepare)
-        const uint32_t qs = (uint32_t)blend_backward_v2_grid(c);
-        fill_bwd_prep(c, c->fwd.N, qs, prep);
+        fill_bwd_prep(c, c->fwd.N, prep);
         const size_t parts = (prep.clearCount + 4095) / 4096;
         cutBlocks = prep.cutStore ? gs_div_up(prep.nBlocks, LNT) : 0;
         prepBlocks = (int)(((GS_ITEM_PARTS + cutBlocks + (parts < 496 ? parts : 496)) + 7) / 8 * 8);
         c->fwd.bwdPrepared = true;
-        c->fwd.preparedQueueStart = qs;
         c->fwd.preparedN = c->fwd.N;
     }
     constexpr size_t lds5 = sizeof(float) * ((size_t)2 * (LTY + 20) * (LTX + 20) + (size_t)5 * (LTY + 20) * (LTX + 10));

@@ -910,6 +910,102 @@ def test_forward_queue_count_leaves_the_same_bits():
         _renderer(W, H).setTuning(fwd_queues=3)
 
 
+def _two_block_scene(W, H, N=640, seed=41):
+    """A few hundred small splats in front of a W x H image of at most two 16 x 16 blocks: most of them spread over the image
+    and a margin around it (lists several 64-entry segments deep, translucent enough for some pixel to see them all), a tenth
+    dots in a band at the top edge, a fifth thin needles -- half of them at any angle, half lying along the top and bottom
+    edges a few pixels outside (their bounding squares reach blocks and halves the ellipses do not)."""
+    from gaussiansplattingmlx_amd.camera import Camera, look_at_c2w
+    rng = np.random.default_rng(seed)
+    cam = Camera(W, H, 40.0, 40.0, look_at_c2w([0.0, -4.0, 0.0]))
+    hx, hz = 0.5 * W / 40.0 * 4.0, 0.5 * H / 40.0 * 4.0           # the image's half extent in the plane y = 0
+    i = np.arange(N)
+    needles, along, dots = i % 5 == 0, i % 10 == 0, i % 10 == 1
+    xyz = np.stack([rng.uniform(-2 * hx, 2 * hx, N), rng.uniform(-0.3, 0.3, N), rng.uniform(-2 * hz, 2 * hz, N)], 1)
+    xyz[dots, 2] = rng.uniform(0.8 * hz, hz, int(dots.sum()))      # (the camera's y points down: +z of the world is the top)
+    xyz[along, 2] = rng.choice([-1.0, 1.0], int(along.sum())) * rng.uniform(1.3, 1.9, int(along.sum())) * hz
+    scales = rng.normal(np.log(0.02), 0.3, (N, 3))
+    scales[needles] = np.log([0.12, 0.004, 0.004])
+    scales[dots] = np.log(0.008)
+    rotation = rng.normal(0, 1, (N, 4))
+    rotation[along] = [1.0, 0.0, 0.0, 0.0] + rng.normal(0, 0.05, (int(along.sum()), 4))      # the long axis along x
+    p = dict(xyz=xyz, features_dc=rng.normal(0, 1, (N, 1, 3)), features_rest=rng.normal(0, 0.08, (N, 24, 3)), scales=scales,
+             rotation=rotation, opacity=rng.normal(-2.0, 0.5, N))
+    return {k: np.ascontiguousarray(v, np.float32) for k, v in p.items()}, cam
+
+
+def _rect_min_q(conic, dx0, dx1, dy0, dy1):
+    """gs_cull.h's rect_min_q in float64: the minimum of a positive definite conic's quadratic form over a rectangle given
+    relative to the mean."""
+    c00, b, c11 = conic[0, 0], 0.5 * (conic[0, 1] + conic[1, 0]), conic[1, 1]
+    if dx0 <= 0 <= dx1 and dy0 <= 0 <= dy1:
+        return 0.0
+    q = lambda x, y: c00 * x * x + 2 * b * x * y + c11 * y * y
+    return min(min(q(X, min(max(-b / c11 * X, dy0), dy1)) for X in (dx0, dx1)),
+               min(q(min(max(-b / c00 * Y, dx0), dx1), Y) for Y in (dy0, dy1)))
+
+
+def _assert_two_block_scene_reaches_every_piece(W, H, proj, idx, rng_, work, last):
+    """The scene's lists (the reference's: trim_rects 0) against what the backward does with them.  Per block, of the entries
+    in front of the sweep length `work`: some block sweeps past its second segment boundary; some entry reaches one 16 x 8
+    half only; some entry reaches neither and is dropped at staging.  Reach as blend_bwd_v2_kernel's staging takes it: in
+    front of the half's own sweep length (the largest nContrib of its pixels) and rect_min_q <= 40 over the half -- here in
+    float64 with a margin of 10 % either way, so that no entry counted hangs on a rounding."""
+    last = np.asarray(last).reshape(H, W)
+    one_half = neither = 0
+    for b in range((W + 15) // 16):
+        X0 = 16 * b
+        hm = [int(last[8 * h:8 * h + 8, X0:X0 + 16].max(initial=0)) for h in (0, 1)]
+        assert int(work[b]) == max(hm), (b, int(work[b]), hm)
+        for li in range(int(work[b])):
+            g = idx[rng_[b, 0] + li]
+            mx, my = proj["means2d"][g].astype(np.float64)
+            qs = [_rect_min_q(proj["conic"][g].astype(np.float64), X0 - mx, X0 + 15 - mx, 8 * h - my, 8 * h + 7 - my) for h in (0, 1)]
+            near = [li < hm[h] and qs[h] < 36.0 for h in (0, 1)]
+            far = [li >= hm[h] or qs[h] > 44.0 for h in (0, 1)]
+            one_half += (near[0] and far[1]) or (near[1] and far[0])
+            neither += far[0] and far[1]
+    assert int(np.max(work)) > 128, work
+    assert one_half > 0 and neither > 0, (one_half, neither)
+    return int(one_half), int(neither)
+
+
+@pytest.mark.parametrize("depth,absgrad", [(False, False), (True, False), (False, True), (True, True)])
+@pytest.mark.parametrize("W,H", [(16, 16), (29, 13)])
+def test_backward_wave_count_leaves_the_same_bits(oracle32, W, H, depth, absgrad):
+    """test_forward_queue_count_leaves_the_same_bits' counterpart for blend_bwd_v2_kernel: which wave takes which (block,
+    segment) item, and when, changes no bit of the gradients.  Every gradAcc16 entry starts from zero and takes one atomicAdd
+    per item its Gaussian is listed in; on an image of at most two blocks that is at most two addends, and 0 + a + b = 0 + b + a
+    exactly -- so no reference is needed: the same forward's backward under GS_TUNE_BWD_WAVES_PER_CU 1 and 16, twice each,
+    for each of the kernel's four instantiations (depth cotangent x absgrad).  One full block, and two blocks clipped in x
+    and y; the lists are the reference's (trim_rects 0), several segments deep, with entries that reach one half of a block
+    only and entries that reach none (_assert_two_block_scene_reaches_every_piece).  (At these sizes every item is some
+    wave's static first item under either setting: the queues are popped and found empty; what they hand out on larger
+    images is held to the oracle by the parity tests, where float atomics reorder sums.)"""
+    p, cam = _two_block_scene(W, H)
+    rng = np.random.default_rng(8)
+    cC, cD = rng.normal(size=(H, W, 3)).astype(np.float32), rng.normal(size=H * W).astype(np.float32)
+    r = _renderer(W, H)
+    r.setTuning(trim_rects=0)
+    r.setAbsgrad(absgrad)
+    res = r.renderForward({k: torch.as_tensor(v, device=r.device) for k, v in p.items()}, cam, wantDepth=depth)
+    _, idx, rng_, _ = _fused_lists(r, W, H)
+    proj = oracle32.render_forward(p, cam.as_dict(), W, H, 16, 16, 4)["proj"]
+    _assert_two_block_scene_reaches_every_piece(W, H, proj, idx, rng_, _np(r.blockWork()), _np(r.lastContrib()))
+    out = []
+    for waves in (1, 16, 1, 16):
+        r.setTuning(bwd_waves_per_cu=waves)
+        g = r.renderBackward(cC, cD) if depth else r.renderBackward(cC)
+        out.append({k: v.clone() for k, v in g.items()})
+        if absgrad:
+            out[-1]["absgrad"] = r.absgrad().clone()
+    r.close()
+    assert all(float(out[0][k].abs().max()) > 0 for k in out[0])
+    for o in out[1:]:
+        for k in out[0]:
+            assert torch.equal(o[k], out[0][k]), k
+
+
 @pytest.mark.parametrize("W,H,N,scale", [(200, 152, 6000, 0.05), (640, 600, 20000, 0.03), (400, 400, 10000, 0.12)])
 def test_staging_wave_forward_leaves_the_same_bits(W, H, N, scale):
     """GS_TUNE_FWD_PAIR (round 6: blend_fwd_v2p_kernel -- a second wave per quadrant loads, culls and compacts chunk c + 1 into
