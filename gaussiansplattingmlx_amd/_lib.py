@@ -52,6 +52,10 @@ class gs_lens(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
 
 
+class gs_fisheye_lens(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "k4", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
+
+
 class gs_adc_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("grad_threshold", "percent_dense", "min_opacity", "max_screen_size", "prune_world",
                                          "scene_extent")]
@@ -162,6 +166,8 @@ _SIGS = {
     "gs_set_bilateral_grid": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float]),
     "gs_apply_bilateral_grid": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
+    "gs_set_camera_model": (C.c_int, [_vp, C.c_int]),
+    "gs_get_camera_model": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "gs_set_background": (C.c_int, [_vp, _vp]),
     "gs_get_background": (C.c_int, [_vp, _vp]),
     "gs_composite_target": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp, _vp]),
@@ -181,6 +187,7 @@ _SIGS = {
     "gs_set_filter3d": (C.c_int, [_vp, _vp]),
     "gs_filter3d_bake": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_undistort": (C.c_int, [_vp, C.POINTER(gs_lens)] + [C.c_int] * 6 + [_vp, _vp, _vp]),
+    "gs_undistort_fisheye": (C.c_int, [_vp, C.POINTER(gs_fisheye_lens)] + [C.c_int] * 6 + [_vp, _vp, _vp]),
     "gs_set_mcmc": (C.c_int, [_vp, _vp]),
     "gs_mcmc_regularizer_grad": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_mcmc_inject_noise": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [C.c_float, _vp]),

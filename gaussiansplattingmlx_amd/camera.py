@@ -49,12 +49,22 @@ def getProjectionMatrix(znear: float, zfar: float, fovX: float, fovY: float, off
     return P
 
 
+CAMERA_MODELS = {"pinhole": 0, "fisheye": 1}      # GS_CAMERA_PINHOLE, GS_CAMERA_FISHEYE (include/gsplat.h)
+
+
 class Camera:
     def __init__(self, width: int, height: int, focalX: float, focalY: float, c2w, znear: float = 0.1,
-                 zfar: float = 100.0, cx: float | None = None, cy: float | None = None):
-        """cx, cy: the principal point in pixels (pixel i covers [i, i + 1)); None is the image centre W / 2, H / 2, and then
+                 zfar: float = 100.0, cx: float | None = None, cy: float | None = None, model: str = "pinhole"):
+        """model: "pinhole" (the default: every field is what it is without the argument) or "fisheye", the ideal equidistant
+        camera (include/gsplat.h gs_set_camera_model): focalX, focalY, cx, cy and the pose mean what they
+        mean for a pinhole, a point at angle theta off the axis lands focal * theta from the principal point, and FoVx / FoVy
+        and the rest of the projection matrix are not read by the renderer.
+        cx, cy: the principal point in pixels (pixel i covers [i, i + 1)); None is the image centre W / 2, H / 2, and then
         every field is the reference's.  FoVx / FoVy stay 2 atan(pixels / (2 focal)): they feed the EWA clamp's symmetric
         limX / limY, which the principal point does not enter."""
+        if model not in CAMERA_MODELS:
+            raise ValueError(f"Camera: model is one of {sorted(CAMERA_MODELS)}")
+        self.model = model
         c2w = np.asarray(c2w, dtype=np.float64).reshape(4, 4)
         self.imageWidth, self.imageHeight = int(width), int(height)
         self.focalX, self.focalY = np.float32(focalX), np.float32(focalY)
@@ -73,9 +83,12 @@ class Camera:
         self.c2w = c2w.copy()
 
     def as_dict(self):
-        return dict(view=self.worldViewTransform, proj=self.projectionMatrix, fovX=float(self.FoVx),
-                    fovY=float(self.FoVy), focalX=float(self.focalX), focalY=float(self.focalY),
-                    camCenter=self.cameraCenter.astype(np.float32), principalX=self.principalX, principalY=self.principalY)
+        d = dict(view=self.worldViewTransform, proj=self.projectionMatrix, fovX=float(self.FoVx),
+                 fovY=float(self.FoVy), focalX=float(self.focalX), focalY=float(self.focalY),
+                 camCenter=self.cameraCenter.astype(np.float32), principalX=self.principalX, principalY=self.principalY)
+        if self.model != "pinhole":
+            d["model"] = self.model
+        return d
 
 
 def look_at_c2w(eye, target=(0.0, 0.0, 0.0), up=(0.0, 0.0, 1.0)) -> np.ndarray:
@@ -130,7 +143,7 @@ def apply_pose_correction(camera: Camera, delta) -> Camera:
     if c2w is None:
         c2w = np.linalg.inv(np.asarray(camera.worldViewTransform, np.float64).T)
     out = Camera(camera.imageWidth, camera.imageHeight, camera.focalX, camera.focalY, np.asarray(c2w, np.float64) @ pose_delta_matrix(delta),
-                 cx=getattr(camera, "principalX", None), cy=getattr(camera, "principalY", None))
+                 cx=getattr(camera, "principalX", None), cy=getattr(camera, "principalY", None), model=getattr(camera, "model", "pinhole"))
     out.projectionMatrix = camera.projectionMatrix.copy()
     return out
 
@@ -138,10 +151,13 @@ def apply_pose_correction(camera: Camera, delta) -> Camera:
 def cameras_from_train_data(trainData, principal_point: bool = True, znear: float = 0.1, zfar: float = 100.0):
     """[Camera] of a loader's TrainData (Hs, Ws, intrinsicArray, c2wArray): focal lengths and, with principal_point, cx, cy from
     each view's intrinsics -- the camera model pointcloud.getRaysFromImages back-projects with.  principal_point=False gives
-    the reference's centred cameras."""
+    the reference's centred cameras.  A view marked "fisheye" in trainData.cameraModelArray (the loaders' fisheye="equidistant")
+    becomes a Camera(model="fisheye")."""
     Hs, Ws, intr, c2ws = trainData.getCameraParams()
+    models = getattr(trainData, "cameraModelArray", None)
     cams = []
-    for H, W, K, c2w in zip(Hs, Ws, np.asarray(intr, np.float64), np.asarray(c2ws, np.float64)):
+    for i, (H, W, K, c2w) in enumerate(zip(Hs, Ws, np.asarray(intr, np.float64), np.asarray(c2ws, np.float64))):
         cx, cy = (float(K[0, 2]), float(K[1, 2])) if principal_point else (None, None)
-        cams.append(Camera(int(W), int(H), K[0, 0], K[1, 1], c2w, znear, zfar, cx=cx, cy=cy))
+        cams.append(Camera(int(W), int(H), K[0, 0], K[1, 1], c2w, znear, zfar, cx=cx, cy=cy,
+                           model="pinhole" if models is None else str(models[i])))
     return cams

@@ -424,6 +424,12 @@ int refuse_filter3d(gs_ctx* c, const char* who)
     return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a 3-D filter is set (single-device steps only)");
 }
 
+int refuse_fisheye(gs_ctx* c, const char* who)
+{
+    if (!c->fisheye && !(c->fwd.valid && c->fwd.fisheye)) return GS_OK;
+    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": the fisheye camera model is set (gs_set_camera_model; pinhole cameras only)");
+}
+
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena)
 {
     const int N = c->fwd.N, K = c->fwd.K;
@@ -896,6 +902,10 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     if (!out_color || !out_alpha) return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: null output");
     if (N > 0 && (!xyz || !features_dc || (K > 1 && !features_rest) || !scales || !rotation || !opacity))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: null parameter tensor");
+    if (c->fisheye && c->poseDelta)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: the fisheye camera model has no pose refinement (gs_set_pose_correction is set)");
+    if (c->fisheye && c->filter3d)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: the fisheye camera model has no 3-D filter (gs_set_filter3d is set)");
     c->fwd.valid = false;
     c->visN = -1;
     const bool keepRadii = c->sparseAdam || c->adcGradSum != nullptr;      // (the ADC statistic reads the radii in the backward)
@@ -972,6 +982,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.poseDelta = c->poseDelta;
     c->fwd.poseGrad = c->poseGrad;
     c->fwd.antialias = c->antialias;
+    c->fwd.fisheye = c->fisheye;
     c->fwd.bg = c->bg;
     c->fwd.filter3d = c->filter3d;
     c->fwd.radii = keepRadii ? radii : nullptr;      // (a caller's buffer is remembered only where a backward will read it)
@@ -1119,6 +1130,24 @@ int gs_set_antialiasing(gs_ctx* c, int enable)
     return GS_OK;
 }
 
+// ---- camera model (include/gsplat.h gs_set_camera_model; gs_math.h fisheye_map) ---------------------------------------------
+int gs_set_camera_model(gs_ctx* c, int model)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (model != GS_CAMERA_PINHOLE && model != GS_CAMERA_FISHEYE)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_set_camera_model: model is GS_CAMERA_PINHOLE or GS_CAMERA_FISHEYE");
+    c->fisheye = model == GS_CAMERA_FISHEYE;
+    return GS_OK;
+}
+
+int gs_get_camera_model(gs_ctx* c, int* model)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!model) return fail(c, GS_ERR_INVALID_ARG, "gs_get_camera_model: null pointer");
+    *model = c->fisheye ? GS_CAMERA_FISHEYE : GS_CAMERA_PINHOLE;
+    return GS_OK;
+}
+
 // ---- background colour (include/gsplat.h gs_set_background; gs_ctx.h GsBackground, background.hip) -------------------------
 int gs_set_background(gs_ctx* c, const float* rgb)
 {
@@ -1156,6 +1185,7 @@ int gs_set_filter3d_cameras(gs_ctx* c, int V, const gs_camera* cams)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (V < 0 || (V > 0 && !cams)) return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d_cameras: V >= 0 and V cameras");
+    if (V > 0) { if (const int rc = refuse_fisheye(c, "gs_set_filter3d_cameras")) return rc; }
     GS_HIP_CHECK(c, hipSetDevice(c->device));
     if (V == 0) {
         GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a width kernel may still be reading the table)
@@ -1376,6 +1406,26 @@ int gs_undistort(gs_ctx* c, const gs_lens* lens, int src_w, int src_h, int dst_w
     return launch_undistort(c, *lens, src_w, src_h, dst_w, dst_h, channels, mode, src, dst, valid);
 }
 
+int gs_undistort_fisheye(gs_ctx* c, const gs_fisheye_lens* lens, int src_w, int src_h, int dst_w, int dst_h, int channels, int mode,
+                         const void* src, void* dst, unsigned char* valid)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!lens || !src || !dst) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: null pointer");
+    if (mode < 0 || mode > 2) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: mode is 0 (colour), 1 (mask) or 2 (depth)");
+    if (channels < 1 || channels > 4) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: channels in 1 .. 4");
+    if (mode != 0 && channels != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: mask and depth images have one channel");
+    if (src_w < 1 || src_h < 1 || dst_w < 1 || dst_h < 1) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: sizes are positive");
+    if (dst_h > 4 * 65535) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: at most 262140 destination rows");
+    const float focal[4] = {lens->fx, lens->fy, lens->dst_fx, lens->dst_fy};
+    for (float f : focal)
+        if (!(f > 0.0f) || !isfinite(f)) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: focal lengths are finite and > 0");
+    const float rest[8] = {lens->cx, lens->cy, lens->k1, lens->k2, lens->k3, lens->k4, lens->dst_cx, lens->dst_cy};
+    for (float f : rest)
+        if (!isfinite(f)) return fail(c, GS_ERR_INVALID_ARG, "gs_undistort_fisheye: principal points and coefficients are finite");
+    GS_HIP_CHECK(c, hipSetDevice(c->device));
+    return launch_undistort_fisheye(c, *lens, src_w, src_h, dst_w, dst_h, channels, mode, src, dst, valid);
+}
+
 int gs_set_bilateral_grid(gs_ctx* c, const float* grid, float* grad, int grid_w, int grid_h, int grid_l, float tv_weight)
 {
     if (!c) return GS_ERR_INVALID_ARG;
@@ -1482,6 +1532,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_begin")) return rc;
+    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_begin")) return rc;
     if (const int rc = refuse_adc_stats(c, "gs_render_backward_dp_begin")) return rc;
@@ -1499,6 +1550,7 @@ int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales,
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish")) return rc;
+    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_finish")) return rc;
     if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_finish")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish: no gs_render_backward_dp_begin on this context");
@@ -1516,6 +1568,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish_geom")) return rc;
+    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_finish_geom")) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish_geom: no gs_render_backward_dp_begin on this context");
@@ -1533,6 +1586,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_geom")) return rc;
+    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_geom")) return rc;
     if (const int rc = refuse_adc_stats(c, "gs_render_backward_dp_geom")) return rc;

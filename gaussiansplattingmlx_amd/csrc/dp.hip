@@ -378,6 +378,7 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
     GsDp* d = c->dp;
     if (const int rc = gs::refuse_pose_correction(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_filter3d(c, "gs_dp_step")) return rc;
+    if (const int rc = gs::refuse_fisheye(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_absgrad(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_adc_stats(c, "gs_dp_step")) return rc;
     if (const int rc = gs::refuse_sparse_adam(c, "gs_dp_step")) return rc;

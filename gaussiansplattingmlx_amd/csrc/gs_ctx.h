@@ -238,6 +238,7 @@ struct gs_ctx {
     float* bgPartials = nullptr;
     long long bgPartialsCap = 0;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
+    bool fisheye = false;                // gs_set_camera_model: GS_CAMERA_FISHEYE for the following forwards and the op-level projection
     bool absgrad = false;                // gs_set_absgrad: the fused backward also sums |g_x|, |g_y| per Gaussian
     int absgradN = -1;                   // N of the last backward that left (Ax, Ay) in gradAcc16's columns 12, 13; -1: none to read
     // sparse Adam (gs_set_sparse_adam): while on, every fused forward leaves radius > 0 of its N Gaussians
@@ -373,6 +374,7 @@ struct gs_ctx {
         const float* poseDelta = nullptr;  // the correction this forward was composed with (nullptr: none) ...
         float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
         bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
+        bool fisheye = false;              // the camera model this forward ran in (its backward's model)
         GsBackground bg;                   // the background this forward composited over (its backward's)
         const float* filter3d = nullptr;   // the 3-D filter widths this forward ran with (its backward's; nullptr: none)
         const float* radii = nullptr;      // where this forward's projection wrote its radii (nullptr: nowhere)
@@ -433,6 +435,7 @@ namespace gs {
 
 // api.hip: refusals that api.hip and dp.hip share (host code; `who` is the entry point's name, in front of the message)
 int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_ARG while a pose correction is bound
+int refuse_fisheye(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while the fisheye model is set (or the forward ran in it)
 int refuse_filter3d(gs_ctx* c, const char* who);             // GS_ERR_INVALID_ARG while a 3-D filter is set (or the forward ran with one)
 int refuse_absgrad(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while absgrad is on (gs_set_absgrad)
 int refuse_sparse_adam(gs_ctx* c, const char* who);          // GS_ERR_INVALID_ARG while sparse Adam is on (gs_set_sparse_adam)
@@ -487,6 +490,8 @@ int launch_filter3d_width(gs_ctx* c, int N, const float* xyz, float* filter);
 int launch_filter3d_bake(gs_ctx* c, int N, const float* scalesRaw, const float* opacityRaw, const float* filter, float* outScales,
                          float* outOpacity);
 int launch_undistort(gs_ctx* c, const gs_lens& lens, int srcW, int srcH, int dstW, int dstH, int channels, int mode, const void* src,
+                     void* dst, unsigned char* valid);
+int launch_undistort_fisheye(gs_ctx* c, const gs_fisheye_lens& lens, int srcW, int srcH, int dstW, int dstH, int channels, int mode, const void* src,
                      void* dst, unsigned char* valid);      // lens.hip
 int launch_colour_rest(gs_ctx* c);      // gs_rider.h: the colour units the binning kernels have not taken along
 int launch_color_cot(gs_ctx* c, int N, float* out);

@@ -137,14 +137,91 @@ __device__ __forceinline__ void build_cov3d(const float s[3], const float rq[4],
         for (int k = 0; k < 3; k++) rc.r[3 * i + k] = R[i][k];
 }
 
+// ---- equidistant fisheye camera (gs_set_camera_model) -----------------------------------------------------
+// A view-space point t = (x, y, z) lands at (fx x s + cx - 0.5, fy y s + cy - 0.5), s = theta / r, theta = atan2(r, z),
+// r^2 = x^2 + y^2 = rho.  The Jacobian of (x s, y s) is ((s + x^2 g, x y g, -x h), (x y g, s + y^2 g, -y h)) with
+// h = 1 / (rho + z^2) and g = 2 ds/drho = (z h - s) / rho; its VJP needs dg/drho = -(z h^2 + 3 g / 2) / rho and dg/dz = 2 h^2.
+// Both quotients cancel near the axis (z h - s -> -2 rho / (3 z^3)), so below w = rho / z^2 = GS_FISHEYE_SERIES_W they are their
+// series in w; s itself never cancels: up to 45 degrees it is A(w) / z, A(w) = atan(sqrt w) / sqrt w a polynomial on [0, 1]
+// whose constant term is exactly 1 (so r = 0 gives s = 1 / z, g = -2 / (3 z^3): the pinhole's Jacobian), beyond it theta comes
+// from the same polynomial of the reciprocal ratio.  Only mul, add, div and sqrt: with -ffp-contract=off the means and rects are
+// the bits an IEEE float32 evaluation on the host gives (tests/fisheye_numpy.py), as the pinhole's are.
+#define GS_FISHEYE_SERIES_W 0.04f
+
+struct FishMap {
+    float s, g, h, grho;        // grho = dg/drho
+};
+
+// atan(sqrt w) / sqrt w on 0 <= w <= 1 (|error| < 1.6e-8 before rounding, 9e-8 in float32)
+__device__ __forceinline__ float fisheye_atan_ratio(float w)
+{
+    float a = 0.0028340641874819994f;
+    a = a * w + -0.016005029901862144f;
+    a = a * w + 0.042587608098983765f;
+    a = a * w + -0.07495445758104324f;
+    a = a * w + 0.10636754333972931f;
+    a = a * w + -0.14202570915222168f;
+    a = a * w + 0.19992484152317047f;
+    a = a * w + -0.3333306610584259f;
+    a = a * w + 1.0f;
+    return a;
+}
+
+__device__ __forceinline__ void fisheye_map(float x, float y, float z, FishMap& f)
+{
+    const float rho = x * x + y * y, z2 = z * z;
+    const float h = 1.0f / (rho + z2);
+    const float w = rho / z2;
+    float s;
+    if (z > 0.0f && w <= 1.0f) s = fisheye_atan_ratio(w) / z;
+    else {      // beyond 45 degrees (and behind the camera, where nothing is visible but the values stay defined for r > 0)
+        const float r = sqrtf(rho), az = fabsf(z);
+        const bool steep = az < r;
+        const float lo = steep ? az : r, hi = steep ? r : az;
+        const float a = lo / hi;
+        float th = a * fisheye_atan_ratio(a * a);
+        if (steep) th = 1.5707963267948966f - th;
+        if (z < 0.0f) th = 3.141592653589793f - th;
+        s = th / r;
+    }
+    float g, grho;
+    if (z > 0.0f && w < GS_FISHEYE_SERIES_W) {
+        // g z^3 = sum_{k >= 1} (-1)^k 2 k / (2 k + 1) w^(k - 1), dg/drho z^5 = its derivative in w; six terms each (the first
+        // omitted ones are under 4e-9 and 3e-8 of the leading term at the threshold)
+        float G = 12.0f / 13.0f;
+        G = G * w + -10.0f / 11.0f;
+        G = G * w + 8.0f / 9.0f;
+        G = G * w + -6.0f / 7.0f;
+        G = G * w + 4.0f / 5.0f;
+        G = G * w + -2.0f / 3.0f;
+        float D = -84.0f / 15.0f;
+        D = D * w + 60.0f / 13.0f;
+        D = D * w + -40.0f / 11.0f;
+        D = D * w + 24.0f / 9.0f;
+        D = D * w + -12.0f / 7.0f;
+        D = D * w + 4.0f / 5.0f;
+        const float iz = 1.0f / z, iz3 = iz * iz * iz;
+        g = G * iz3;
+        grho = D * iz3 * iz * iz;
+    } else {
+        g = (z * h - s) / rho;
+        grho = -(z * h * h + 1.5f * g) / rho;
+    }
+    f.s = s; f.g = g; f.h = h; f.grho = grho;
+}
+
 // ---- EWA 2-D covariance (shared.slang:170-243), z-clamp quirk included ------
 struct Cov2Ctx {
     float t0, t1, t2, clipX, clipY, tx, ty;
     float b[6];
     float t[6];
     float u[4];             // the entries before the + 0.3 blur (the anti-aliased mode's det Sigma, aa_opacity_scale)
+    FishMap fm;             // FISHEYE: the map's s, g, h, dg/drho and
+    float fj[6];            // its full 2 x 3 Jacobian, rows (x, y, z) of the two screen coordinates
 };
 
+// FISHEYE: J is the equidistant map's full 2 x 3 Jacobian (fisheye_map) instead; no depth clamp, limX / limY unread.
+template <bool FISHEYE = false>
 __device__ __forceinline__ void build_cov2d(const float m[3], const float c[9], const CamParams& cam, float out[4],
                                             Cov2Ctx& cc)
 {
@@ -156,19 +233,40 @@ __device__ __forceinline__ void build_cov2d(const float m[3], const float c[9], 
 #pragma unroll
     for (int a = 0; a < 3; a++) pv[a] = m[0] * V[a] + m[1] * V[4 + a] + m[2] * V[8 + a] + V[12 + a];
     const float depth = pv[2];
-    const float zLimX = depth < -cam.limX ? -cam.limX : (depth > cam.limX ? cam.limX : depth);
-    const float zLimY = depth < -cam.limY ? -cam.limY : (depth > cam.limY ? cam.limY : depth);
-    const float xs = pv[0] / zLimX * depth;
-    const float ys = pv[1] / zLimY * depth;
-    const float jxx = cam.focalX / depth;
-    const float jxz = -xs * cam.focalX / (depth * depth);
-    const float jyy = cam.focalY / depth;
-    const float jyz = -ys * cam.focalY / (depth * depth);
     float JW[2][3];         // J W: row 0 from (jxx, 0, jxz), row 1 from (0, jyy, jyz)
+    float zLimX = depth, zLimY = depth, xs = pv[0], ys = pv[1];
+    if constexpr (FISHEYE) {
+        fisheye_map(pv[0], pv[1], depth, cc.fm);
+        const float xy = pv[0] * pv[1] * cc.fm.g;
+        cc.fj[0] = cam.focalX * (cc.fm.s + pv[0] * pv[0] * cc.fm.g);
+        cc.fj[1] = cam.focalX * xy;
+        cc.fj[2] = -(cam.focalX * pv[0] * cc.fm.h);
+        cc.fj[3] = cam.focalY * xy;
+        cc.fj[4] = cam.focalY * (cc.fm.s + pv[1] * pv[1] * cc.fm.g);
+        cc.fj[5] = -(cam.focalY * pv[1] * cc.fm.h);
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        JW[0][k] = jxx * V[4 * k] + jxz * V[4 * k + 2];
-        JW[1][k] = jyy * V[4 * k + 1] + jyz * V[4 * k + 2];
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                float acc = cc.fj[3 * r] * V[4 * k];
+                acc = acc + cc.fj[3 * r + 1] * V[4 * k + 1];
+                acc = acc + cc.fj[3 * r + 2] * V[4 * k + 2];
+                JW[r][k] = acc;
+            }
+    } else {
+        zLimX = depth < -cam.limX ? -cam.limX : (depth > cam.limX ? cam.limX : depth);
+        zLimY = depth < -cam.limY ? -cam.limY : (depth > cam.limY ? cam.limY : depth);
+        xs = pv[0] / zLimX * depth;
+        ys = pv[1] / zLimY * depth;
+        const float jxx = cam.focalX / depth;
+        const float jxz = -xs * cam.focalX / (depth * depth);
+        const float jyy = cam.focalY / depth;
+        const float jyz = -ys * cam.focalY / (depth * depth);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            JW[0][k] = jxx * V[4 * k] + jxz * V[4 * k + 2];
+            JW[1][k] = jyy * V[4 * k + 1] + jyz * V[4 * k + 2];
+        }
     }
     float M[2][3];          // (J W) Sigma
 #pragma unroll
@@ -204,6 +302,9 @@ struct ProjOut {
 };
 
 // Everything of the forward except colour (kernels.slang:47-63, 91-172).
+// FISHEYE: the mean through the equidistant map, cx - 0.5 = ((proj[8] + 1) W - 1) / 2 as the pinhole's NDC step places it
+// (DESIGN.md section 23); the rest of proj is unread.
+template <bool FISHEYE = false>
 __device__ __forceinline__ void project_geometry(const float m[3], const float s[3], const float rq[4],
                                                  const CamParams& cam, ProjOut& o)
 {
@@ -226,7 +327,11 @@ __device__ __forceinline__ void project_geometry(const float m[3], const float s
     RotCtx rc;
     build_cov3d(s, rq, c3, rc);
     Cov2Ctx cc;
-    build_cov2d(m, c3, cam, o.cov2d, cc);
+    build_cov2d<FISHEYE>(m, c3, cam, o.cov2d, cc);
+    if constexpr (FISHEYE) {
+        o.sx = cam.focalX * pv0 * cc.fm.s + ((P[8] + 1.0f) * cam.W - 1.0f) * 0.5f;
+        o.sy = cam.focalY * pv1 * cc.fm.s + ((P[9] + 1.0f) * cam.H - 1.0f) * 0.5f;
+    }
 #pragma unroll
     for (int k = 0; k < 4; k++) o.cov2dRaw[k] = cc.u[k];
     const float det = o.cov2d[0] * o.cov2d[3] - o.cov2d[1] * o.cov2d[2];
@@ -403,20 +508,22 @@ struct GeomGrads {
 // (means, depth, J) and through W = V[:3, :3] in J W.
 // AA (anti-aliased mode): aaCot = dL/d(packed opacity) sigma(o); the VJP of rho (aa_opacity_scale) joins the covariance
 // cotangent ahead of everything downstream of it (the pose share included), and *aaRho receives rho.
-template <bool POSE = false, bool AA = false>
+// FISHEYE (never with POSE): the equidistant map's VJP -- J^T of the mean's cotangent and the second derivatives of the map
+// under the cotangent of J (fisheye_map's g, h, dg/drho) -- in place of the perspective one; no clamp, proj unread.
+template <bool POSE = false, bool AA = false, bool FISHEYE = false>
 __device__ __forceinline__ void project_geometry_bwd(const float m[3], const float s[3], const float rq[4],
                                                      const CamParams& cam, const float cotM2d[2], float cotDepth,
                                                      const float cotCov[4], const float cotCon[4], GeomGrads& g,
                                                      float* dV = nullptr, float aaCot = 0.0f, float* aaRho = nullptr)
 {
     const float* V = cam.V;
-    const float* P = cam.P;
     float c3[9];
     RotCtx rc;
     build_cov3d(s, rq, c3, rc);
     float c2[4];
     Cov2Ctx cc;
-    build_cov2d(m, c3, cam, c2, cc);
+    static_assert(!(POSE && FISHEYE), "no pose refinement through the fisheye model");
+    build_cov2d<FISHEYE>(m, c3, cam, c2, cc);
 
     // inverse 2x2 (four independent entries)
     const float det = c2[0] * c2[3] - c2[1] * c2[2];
@@ -451,67 +558,97 @@ __device__ __forceinline__ void project_geometry_bwd(const float m[3], const flo
         db[l] += dt[0] * c3[l * 3 + 0] + dt[1] * c3[l * 3 + 1] + dt[2] * c3[l * 3 + 2];
         db[3 + l] += dt[3] * c3[l * 3 + 0] + dt[4] * c3[l * 3 + 1] + dt[5] * c3[l * 3 + 2];
     }
-    float dj00 = 0.f, dj02 = 0.f, dj11 = 0.f, dj12 = 0.f;
+    if constexpr (FISHEYE) {
+        float dj[6];
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        dj00 += db[k] * V[k * 4 + 0];
-        dj02 += db[k] * V[k * 4 + 2];
-        dj11 += db[3 + k] * V[k * 4 + 1];
-        dj12 += db[3 + k] * V[k * 4 + 2];
-    }
-    const float tz = cc.t2, tz2 = tz * tz;
-    float dtz = -cam.focalX / tz2 * dj00 - cam.focalY / tz2 * dj11;
-    const float dtx = -cam.focalX / tz2 * dj02;
-    const float dty = -cam.focalY / tz2 * dj12;
-    const float dtz2 = cc.tx * cam.focalX / (tz2 * tz2) * dj02 + cc.ty * cam.focalY / (tz2 * tz2) * dj12;
-    dtz += 2.0f * tz * dtz2;
-    const float ux = cc.t0 / cc.clipX, uy = cc.t1 / cc.clipY;
-    float dt2 = dtz + ux * dtx + uy * dty;
-    const float dux = cc.t2 * dtx, duy = cc.t2 * dty;
-    const float dt0 = dux / cc.clipX, dt1 = duy / cc.clipY;
-    const float dclipX = -cc.t0 / (cc.clipX * cc.clipX) * dux;
-    const float dclipY = -cc.t1 / (cc.clipY * cc.clipY) * duy;
-    if (cc.t2 >= -cam.limX && cc.t2 <= cam.limX) dt2 += dclipX;
-    if (cc.t2 >= -cam.limY && cc.t2 <= cam.limY) dt2 += dclipY;
+        for (int r = 0; r < 2; r++)
 #pragma unroll
-    for (int a = 0; a < 3; a++) g.dm[a] = V[a * 4 + 0] * dt0 + V[a * 4 + 1] * dt1 + V[a * 4 + 2] * dt2;
-
-    // screen -> ndc -> clip -> view -> point
-    const float pv0 = m[0] * V[0] + m[1] * V[4] + m[2] * V[8] + V[12];
-    const float pv1 = m[0] * V[1] + m[1] * V[5] + m[2] * V[9] + V[13];
-    const float pv2 = m[0] * V[2] + m[1] * V[6] + m[2] * V[10] + V[14];
-    const float pv3 = m[0] * V[3] + m[1] * V[7] + m[2] * V[11] + V[15];
-    const float pc0 = pv0 * P[0] + pv1 * P[4] + pv2 * P[8] + pv3 * P[12];
-    const float pc1 = pv0 * P[1] + pv1 * P[5] + pv2 * P[9] + pv3 * P[13];
-    const float pc3 = pv0 * P[3] + pv1 * P[7] + pv2 * P[11] + pv3 * P[15];
-    const float wInv = 1.0f / (pc3 + 0.000001f);
-    const float dndcX = cotM2d[0] * 0.5f * cam.W, dndcY = cotM2d[1] * 0.5f * cam.H;
-    const float dpc0 = dndcX * wInv, dpc1 = dndcY * wInv;
-    const float dwInv = pc0 * dndcX + pc1 * dndcY;
-    const float dpc3 = -dwInv * wInv * wInv;
-    float dpv[4];
+            for (int a = 0; a < 3; a++)
+                dj[3 * r + a] = db[3 * r] * V[a] + db[3 * r + 1] * V[4 + a] + db[3 * r + 2] * V[8 + a];
+        // L = A s + B g - C h with the cotangents folded: A on s, B on g, C on -h
+        const float x = cc.t0, y = cc.t1, z = cc.t2;
+        const FishMap& f = cc.fm;
+        const float a00 = cam.focalX * dj[0], a01 = cam.focalX * dj[1], a02 = cam.focalX * dj[2];
+        const float a10 = cam.focalY * dj[3], a11 = cam.focalY * dj[4], a12 = cam.focalY * dj[5];
+        const float A = a00 + a11, ax = a01 + a10;
+        const float B = a00 * x * x + ax * x * y + a11 * y * y;
+        const float C = a02 * x + a12 * y;
+        const float h2 = f.h * f.h;
+        // ds = (x g, y g, -h), dg = (2 x grho, 2 y grho, 2 h^2), dh = -2 h^2 (x, y, z)
+        const float common = A * f.g + 2.0f * B * f.grho + 2.0f * C * h2;
+        float dt0 = x * common + f.g * (2.0f * a00 * x + ax * y) - a02 * f.h;
+        float dt1 = y * common + f.g * (2.0f * a11 * y + ax * x) - a12 * f.h;
+        float dt2 = -(A * f.h) + 2.0f * B * h2 + 2.0f * C * z * h2;
+        // the mean: J^T of its cotangent; the depth is view z
+        dt0 += cc.fj[0] * cotM2d[0] + cc.fj[3] * cotM2d[1];
+        dt1 += cc.fj[1] * cotM2d[0] + cc.fj[4] * cotM2d[1];
+        dt2 += cc.fj[2] * cotM2d[0] + cc.fj[5] * cotM2d[1] + cotDepth;
 #pragma unroll
-    for (int i = 0; i < 4; i++) dpv[i] = P[i * 4 + 0] * dpc0 + P[i * 4 + 1] * dpc1 + P[i * 4 + 3] * dpc3;
-    dpv[2] += cotDepth;
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-        g.dm[a] += V[a * 4 + 0] * dpv[0] + V[a * 4 + 1] * dpv[1] + V[a * 4 + 2] * dpv[2] + V[a * 4 + 3] * dpv[3];
-    if constexpr (POSE) {
-        // p_view[a] = sum_k [m, 1][k] V[k][a]: the total cotangent of the view-space point is (dt0 + dpv0, dt1 + dpv1, dt2 + dpv2)
-        const float dp[3] = {dt0 + dpv[0], dt1 + dpv[1], dt2 + dpv[2]};
-        const float mh[4] = {m[0], m[1], m[2], 1.0f};
-        // J W with J = ((jxx, 0, jxz), (0, jyy, jyz)): b[k] = jxx V[k][0] + jxz V[k][2], b[3 + k] = jyy V[k][1] + jyz V[k][2]
-        const float jxx = cam.focalX / tz, jyy = cam.focalY / tz;
-        const float jxz = -cc.tx * cam.focalX / tz2, jyz = -cc.ty * cam.focalY / tz2;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int a = 0; a < 3; a++) dV[3 * k + a] = mh[k] * dp[a];
+        for (int a = 0; a < 3; a++) g.dm[a] = V[a * 4 + 0] * dt0 + V[a * 4 + 1] * dt1 + V[a * 4 + 2] * dt2;
+    } else {
+        float dj00 = 0.f, dj02 = 0.f, dj11 = 0.f, dj12 = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            dV[3 * k + 0] += db[k] * jxx;
-            dV[3 * k + 1] += db[3 + k] * jyy;
-            dV[3 * k + 2] += db[k] * jxz + db[3 + k] * jyz;
+            dj00 += db[k] * V[k * 4 + 0];
+            dj02 += db[k] * V[k * 4 + 2];
+            dj11 += db[3 + k] * V[k * 4 + 1];
+            dj12 += db[3 + k] * V[k * 4 + 2];
+        }
+        const float tz = cc.t2, tz2 = tz * tz;
+        float dtz = -cam.focalX / tz2 * dj00 - cam.focalY / tz2 * dj11;
+        const float dtx = -cam.focalX / tz2 * dj02;
+        const float dty = -cam.focalY / tz2 * dj12;
+        const float dtz2 = cc.tx * cam.focalX / (tz2 * tz2) * dj02 + cc.ty * cam.focalY / (tz2 * tz2) * dj12;
+        dtz += 2.0f * tz * dtz2;
+        const float ux = cc.t0 / cc.clipX, uy = cc.t1 / cc.clipY;
+        float dt2 = dtz + ux * dtx + uy * dty;
+        const float dux = cc.t2 * dtx, duy = cc.t2 * dty;
+        const float dt0 = dux / cc.clipX, dt1 = duy / cc.clipY;
+        const float dclipX = -cc.t0 / (cc.clipX * cc.clipX) * dux;
+        const float dclipY = -cc.t1 / (cc.clipY * cc.clipY) * duy;
+        if (cc.t2 >= -cam.limX && cc.t2 <= cam.limX) dt2 += dclipX;
+        if (cc.t2 >= -cam.limY && cc.t2 <= cam.limY) dt2 += dclipY;
+#pragma unroll
+        for (int a = 0; a < 3; a++) g.dm[a] = V[a * 4 + 0] * dt0 + V[a * 4 + 1] * dt1 + V[a * 4 + 2] * dt2;
+
+        // screen -> ndc -> clip -> view -> point
+        const float* P = cam.P;
+        const float pv0 = m[0] * V[0] + m[1] * V[4] + m[2] * V[8] + V[12];
+        const float pv1 = m[0] * V[1] + m[1] * V[5] + m[2] * V[9] + V[13];
+        const float pv2 = m[0] * V[2] + m[1] * V[6] + m[2] * V[10] + V[14];
+        const float pv3 = m[0] * V[3] + m[1] * V[7] + m[2] * V[11] + V[15];
+        const float pc0 = pv0 * P[0] + pv1 * P[4] + pv2 * P[8] + pv3 * P[12];
+        const float pc1 = pv0 * P[1] + pv1 * P[5] + pv2 * P[9] + pv3 * P[13];
+        const float pc3 = pv0 * P[3] + pv1 * P[7] + pv2 * P[11] + pv3 * P[15];
+        const float wInv = 1.0f / (pc3 + 0.000001f);
+        const float dndcX = cotM2d[0] * 0.5f * cam.W, dndcY = cotM2d[1] * 0.5f * cam.H;
+        const float dpc0 = dndcX * wInv, dpc1 = dndcY * wInv;
+        const float dwInv = pc0 * dndcX + pc1 * dndcY;
+        const float dpc3 = -dwInv * wInv * wInv;
+        float dpv[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) dpv[i] = P[i * 4 + 0] * dpc0 + P[i * 4 + 1] * dpc1 + P[i * 4 + 3] * dpc3;
+        dpv[2] += cotDepth;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+            g.dm[a] += V[a * 4 + 0] * dpv[0] + V[a * 4 + 1] * dpv[1] + V[a * 4 + 2] * dpv[2] + V[a * 4 + 3] * dpv[3];
+        if constexpr (POSE) {
+            // p_view[a] = sum_k [m, 1][k] V[k][a]: the total cotangent of the view-space point is (dt0 + dpv0, dt1 + dpv1, dt2 + dpv2)
+            const float dp[3] = {dt0 + dpv[0], dt1 + dpv[1], dt2 + dpv[2]};
+            const float mh[4] = {m[0], m[1], m[2], 1.0f};
+            // J W with J = ((jxx, 0, jxz), (0, jyy, jyz)): b[k] = jxx V[k][0] + jxz V[k][2], b[3 + k] = jyy V[k][1] + jyz V[k][2]
+            const float jxx = cam.focalX / tz, jyy = cam.focalY / tz;
+            const float jxz = -cc.tx * cam.focalX / tz2, jyz = -cc.ty * cam.focalY / tz2;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int a = 0; a < 3; a++) dV[3 * k + a] = mh[k] * dp[a];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                dV[3 * k + 0] += db[k] * jxx;
+                dV[3 * k + 1] += db[3 + k] * jyy;
+                dV[3 * k + 2] += db[k] * jxz + db[3 + k] * jyz;
+            }
         }
     }
 

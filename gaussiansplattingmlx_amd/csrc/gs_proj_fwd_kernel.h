@@ -5,13 +5,15 @@
 // AA: the anti-aliased mode (gs_set_antialiasing): the packed opacity is sigma(o) rho (aa_opacity_scale, gs_math.h).
 // F3D: the 3-D smoothing filter (gs_set_filter3d): the scales are sqrt(s^2 + f^2), f = filter3d[p], and the opacity gains kappa
 // (filter3d_activate, gs_math.h).  The other instantiations never read filter3d, the argument before dcam.
-// The forms that exist: {riders' geometry, SELF, one kernel in one or two phases, the same posed} x AA x F3D (24)
-constexpr bool proj_fwd_form_exists(bool TWO_PHASE, bool COLOUR, bool SELF, bool POSE)
+// FISHEYE: the equidistant camera model (gs_set_camera_model; project_geometry's FISHEYE, gs_math.h); never with POSE or F3D.
+// The forms that exist: {riders' geometry, SELF, one kernel in one or two phases, the same posed} x AA x F3D (24);
+// fisheye: {riders' geometry, SELF, one kernel in one or two phases} x AA (8)
+constexpr bool proj_fwd_form_exists(bool TWO_PHASE, bool COLOUR, bool SELF, bool POSE, bool F3D = false, bool FISHEYE = false)
 {
-    return COLOUR ? !SELF : (TWO_PHASE && !POSE);
+    return (COLOUR ? !SELF : (TWO_PHASE && !POSE)) && (!FISHEYE || (!POSE && !F3D));
 }
 
-template <bool TWO_PHASE, bool COLOUR, bool SELF, bool AA, bool F3D, bool POSE>
+template <bool TWO_PHASE, bool COLOUR, bool SELF, bool AA, bool F3D, bool POSE, bool FISHEYE = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_fwd_fused_kernel(
     int N, int K, int degree, CamParams hostCam, int tileW, int tileH, int gridW, int gridH,
     const float* __restrict__ xyz, const float* __restrict__ fdc, const float* __restrict__ frest,
@@ -22,7 +24,7 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_fwd_fused_kernel(
     GsVirtGeom vg, GsCutCoarse cc, uint4* __restrict__ tilePieces, const float* __restrict__ filter3d,
     const CamParams* __restrict__ dcam)
 {
-    static_assert(proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE), "no such form of the fused projection forward");
+    static_assert(proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE, F3D, FISHEYE), "no such form of the fused projection forward");
     CamParams posed;
     if constexpr (POSE) posed = *dcam;
     const CamParams& cam = POSE ? posed : hostCam;
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_fwd_fused_kernel(
             opacity *= filter3d_activate(s, filter3d[p], se);
             project_geometry(m, se, q, cam, o);
         } else
-        project_geometry(m, s, q, cam, o);
+        project_geometry<FISHEYE>(m, s, q, cam, o);
         // A 2-D covariance whose float32 determinant is not positive -- the true one always is (the +0.3 blur), so this is
         // cancellation: a needle tens of thousands of pixels long, cov2d = (4.2e7, -3.8e7; -3.8e7, 3.5e7) -- has a conic that is not
         // positive definite: q < 0 without bound, "weights" above 1, a 0.99-alpha blob over its whole 3-sigma square.  The reference's

@@ -36,8 +36,10 @@ CamParams make_cam(const gs_camera* cam, int W, int H)
 // ---------------------------------------------------------------------------------------------
 // op-level forward
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PROJ_THREADS) void proj_fwd_op_kernel(
-    int N, int K, int degree, CamParams cam, const float* __restrict__ scales, const float* __restrict__ rot,
+// FISHEYE: the camera model (gs_set_camera_model).  The pinhole kernel keeps its name and its code; the fisheye one stands beside it.
+template <bool FISHEYE>
+__device__ __forceinline__ void proj_fwd_op_body(
+    int N, int K, int degree, const CamParams& cam, const float* __restrict__ scales, const float* __restrict__ rot,
     const float* __restrict__ means3d, const float* __restrict__ shs, float* __restrict__ means2d,
     float* __restrict__ depths, float* __restrict__ color, float* __restrict__ cov2d, float* __restrict__ conic,
     float* __restrict__ radii, float* __restrict__ rectMin, float* __restrict__ rectMax)
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(PROJ_THREADS) void proj_fwd_op_kernel(
     const float s[3] = {scales[3 * p], scales[3 * p + 1], scales[3 * p + 2]};
     const float q[4] = {rot[4 * p], rot[4 * p + 1], rot[4 * p + 2], rot[4 * p + 3]};
     ProjOut o;
-    project_geometry(m, s, q, cam, o);
+    project_geometry<FISHEYE>(m, s, q, cam, o);
 
     const float x = m[0] - cam.cam[0], y = m[1] - cam.cam[1], z = m[2] - cam.cam[2];
     const float* sh = shs + (size_t)p * K * 3;
@@ -69,6 +71,25 @@ __global__ __launch_bounds__(PROJ_THREADS) void proj_fwd_op_kernel(
     radii[p] = o.radius;
     rectMin[2 * p] = o.rect[0]; rectMin[2 * p + 1] = o.rect[1];
     rectMax[2 * p] = o.rect[2]; rectMax[2 * p + 1] = o.rect[3];
+}
+
+// (two plain kernels over the body rather than one templated kernel: as a template instance the pinhole kernel compiled to 809
+// instructions where the parent has 841 -- this way it keeps the parent's)
+__global__ __launch_bounds__(PROJ_THREADS) void proj_fwd_op_kernel(
+    int N, int K, int degree, CamParams cam, const float* __restrict__ scales, const float* __restrict__ rot,
+    const float* __restrict__ means3d, const float* __restrict__ shs, float* __restrict__ means2d,
+    float* __restrict__ depths, float* __restrict__ color, float* __restrict__ cov2d, float* __restrict__ conic,
+    float* __restrict__ radii, float* __restrict__ rectMin, float* __restrict__ rectMax)
+{
+    proj_fwd_op_body<false>(N, K, degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii, rectMin, rectMax);
+}
+__global__ __launch_bounds__(PROJ_THREADS) void proj_fwd_op_fisheye_kernel(
+    int N, int K, int degree, CamParams cam, const float* __restrict__ scales, const float* __restrict__ rot,
+    const float* __restrict__ means3d, const float* __restrict__ shs, float* __restrict__ means2d,
+    float* __restrict__ depths, float* __restrict__ color, float* __restrict__ cov2d, float* __restrict__ conic,
+    float* __restrict__ radii, float* __restrict__ rectMin, float* __restrict__ rectMax)
+{
+    proj_fwd_op_body<true>(N, K, degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii, rectMin, rectMax);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -108,8 +129,9 @@ __device__ __forceinline__ void color_backward(int degree, int K, float x, float
 // ---------------------------------------------------------------------------------------------
 // op-level backward
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PROJ_THREADS) void proj_bwd_op_kernel(
-    int N, int K, int degree, CamParams cam, const float* __restrict__ scales, const float* __restrict__ rot,
+template <bool FISHEYE>
+__device__ __forceinline__ void proj_bwd_op_body(
+    int N, int K, int degree, const CamParams& cam, const float* __restrict__ scales, const float* __restrict__ rot,
     const float* __restrict__ means3d, const float* __restrict__ shs, const float* __restrict__ cotDepths,
     const float* __restrict__ cotMeans2d, const float* __restrict__ cotCov2d, const float* __restrict__ cotColor,
     const float* __restrict__ cotConic, float* __restrict__ gScales, float* __restrict__ gRot,
@@ -124,7 +146,7 @@ __global__ __launch_bounds__(PROJ_THREADS) void proj_bwd_op_kernel(
     const float ccov[4] = {cotCov2d[4 * p], cotCov2d[4 * p + 1], cotCov2d[4 * p + 2], cotCov2d[4 * p + 3]};
     const float ccon[4] = {cotConic[4 * p], cotConic[4 * p + 1], cotConic[4 * p + 2], cotConic[4 * p + 3]};
     GeomGrads g;
-    project_geometry_bwd(m, s, q, cam, cm, cotDepths[p], ccov, ccon, g);
+    project_geometry_bwd<false, false, FISHEYE>(m, s, q, cam, cm, cotDepths[p], ccov, ccon, g);
 
     const float x = m[0] - cam.cam[0], y = m[1] - cam.cam[1], z = m[2] - cam.cam[2];
     const float* sh = shs + (size_t)p * K * 3;
@@ -141,6 +163,27 @@ __global__ __launch_bounds__(PROJ_THREADS) void proj_bwd_op_kernel(
     }
 #pragma unroll
     for (int a = 0; a < 4; a++) gRot[4 * p + a] = g.dq[a];
+}
+
+__global__ __launch_bounds__(PROJ_THREADS) void proj_bwd_op_kernel(
+    int N, int K, int degree, CamParams cam, const float* __restrict__ scales, const float* __restrict__ rot,
+    const float* __restrict__ means3d, const float* __restrict__ shs, const float* __restrict__ cotDepths,
+    const float* __restrict__ cotMeans2d, const float* __restrict__ cotCov2d, const float* __restrict__ cotColor,
+    const float* __restrict__ cotConic, float* __restrict__ gScales, float* __restrict__ gRot,
+    float* __restrict__ gMeans, float* __restrict__ gShs, float* __restrict__ gCam)
+{
+    proj_bwd_op_body<false>(N, K, degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor, cotConic, gScales,
+                            gRot, gMeans, gShs, gCam);
+}
+__global__ __launch_bounds__(PROJ_THREADS) void proj_bwd_op_fisheye_kernel(
+    int N, int K, int degree, CamParams cam, const float* __restrict__ scales, const float* __restrict__ rot,
+    const float* __restrict__ means3d, const float* __restrict__ shs, const float* __restrict__ cotDepths,
+    const float* __restrict__ cotMeans2d, const float* __restrict__ cotCov2d, const float* __restrict__ cotColor,
+    const float* __restrict__ cotConic, float* __restrict__ gScales, float* __restrict__ gRot,
+    float* __restrict__ gMeans, float* __restrict__ gShs, float* __restrict__ gCam)
+{
+    proj_bwd_op_body<true>(N, K, degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor, cotConic, gScales,
+                           gRot, gMeans, gShs, gCam);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -469,7 +512,8 @@ __device__ __forceinline__ float wave_sum_xor(float v)
 // > 0.  A wave whose 64 rows are all invisible returns before it has staged, loaded or stored anything (under POSE it writes
 // its zero partials); in a mixed wave the invisible lanes store none of their 14 small elements and adam_rows / adam_rows_kept
 // skip their rows.  An invisible row's cotangent is all zero, so it adds nothing to gradNormAccum or to the pose sums either way.
-template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false, bool SPARSE = false>
+// FISHEYE (the equidistant camera model, gs_set_camera_model; never with POSE or F3D): project_geometry_bwd's FISHEYE.
+template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false, bool SPARSE = false, bool FISHEYE = false>
 __device__ __forceinline__ void proj_bwd_fused_body(
     int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
@@ -548,7 +592,7 @@ __device__ __forceinline__ void proj_bwd_fused_body(
         project_geometry_bwd<POSE, AA>(m, se, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr, cotOpacity * aaSg * f3dKappa,
                                        &aaRho);
     } else
-    project_geometry_bwd<POSE, AA>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr, cotOpacity * aaSg, &aaRho);
+    project_geometry_bwd<POSE, AA, FISHEYE>(m, s, q, cam, cm, cotDepth, ccov, ccon, g, POSE ? pose : nullptr, cotOpacity * aaSg, &aaRho);
     // A Gaussian no pixel blended (not visible, or off every tile) arrives with an all-zero cotangent row and its
     // gradient is exactly zero.  The reference's arithmetic evaluates J^T 0 term by term, which is 0 * inf = NaN when
     // the point sits within ~1e-3 of the camera plane (1 / t_z^2 overflows); one such NaN poisons Adam for good.
@@ -711,10 +755,12 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     }
 }
 
-// The forms that exist: MODE 2 {plain, F3D, MCMC, SPARSE} x POSE x AA, MODE 0 {plain, F3D} x POSE x AA, MODE 1 plain x AA (26)
-constexpr bool proj_bwd_form_exists(int MODE, bool POSE, bool MCMC, bool F3D, bool SPARSE)
+// The forms that exist: MODE 2 {plain, F3D, MCMC, SPARSE} x POSE x AA, MODE 0 {plain, F3D} x POSE x AA, MODE 1 plain x AA (26);
+// fisheye: MODE 2 {plain, MCMC, SPARSE} x AA, MODE 0 plain x AA (8)
+constexpr bool proj_bwd_form_exists(int MODE, bool POSE, bool MCMC, bool F3D, bool SPARSE, bool FISHEYE = false)
 {
     return (MODE == 0 || MODE == 1 || MODE == 2) &&
+           (!FISHEYE || (!POSE && !F3D && MODE != 1)) &&    // the fisheye model: no pose refinement, no 3-D filter, no data-parallel form
            (!POSE || MODE != 1) &&                          // no pose refinement in the data-parallel form
            (!MCMC || MODE == 2) &&                          // the MCMC step is fused into the Adam form only
            (!SPARSE || (MODE == 2 && !MCMC && !F3D)) &&     // sparse Adam: the plain fused Adam form only
@@ -739,13 +785,13 @@ struct ProjBwdArgs {
     const CamParams* dcam;         // POSE: the camera pose_camera_kernel composed on the device
 };
 
-template <int MODE, bool POSE, bool AA, bool MCMC, bool F3D, bool SPARSE>
+template <int MODE, bool POSE, bool AA, bool MCMC, bool F3D, bool SPARSE, bool FISHEYE = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(ProjBwdArgs a)
 {
-    static_assert(proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE), "no such form of the fused projection backward");
+    static_assert(proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE, FISHEYE), "no such form of the fused projection backward");
     CamParams posed;
     if constexpr (POSE) posed = *a.dcam;
-    proj_bwd_fused_body<MODE, POSE, AA, MCMC, F3D, SPARSE>(a.N, a.K, a.degree, POSE ? posed : a.cam, a.xyz, a.fdc, a.frest, a.scalesRaw,
+    proj_bwd_fused_body<MODE, POSE, AA, MCMC, F3D, SPARSE, FISHEYE>(a.N, a.K, a.degree, POSE ? posed : a.cam, a.xyz, a.fdc, a.frest, a.scalesRaw,
                                                            a.rotRaw, a.opacityRaw, a.gradAcc16, a.gXyz, a.gFdc, a.gFrest, a.gScales,
                                                            a.gRot, a.gOpacity, a.gradNormAccum, a.adam, a.posePartials, a.mc, a.filter3d,
                                                            a.visMask);
@@ -1056,6 +1102,11 @@ int launch_projection_forward(gs_ctx* c, int N, int K, const float* scales, cons
                               float* cov2d, float* conic, float* radii, float* rectMin, float* rectMax)
 {
     if (N == 0) return GS_OK;
+    if (c->fisheye)
+        hipLaunchKernelGGL(proj_fwd_op_fisheye_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
+                           c->degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii,
+                           rectMin, rectMax);
+    else
     hipLaunchKernelGGL(proj_fwd_op_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
                        c->degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii,
                        rectMin, rectMax);
@@ -1070,6 +1121,11 @@ int launch_projection_backward(gs_ctx* c, int N, int K, const float* scales, con
                                float* gCam)
 {
     if (N == 0) return GS_OK;
+    if (c->fisheye)
+        hipLaunchKernelGGL(proj_bwd_op_fisheye_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
+                           c->degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor,
+                           cotConic, gScales, gRot, gMeans, gShs, gCam);
+    else
     hipLaunchKernelGGL(proj_bwd_op_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
                        c->degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor,
                        cotConic, gScales, gRot, gMeans, gShs, gCam);
@@ -1139,21 +1195,22 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
     const bool colour = !c->rider.on && !selfColour;
     const size_t dynLds = c->rider.on ? 0 : colour ? lds : sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * GS_RIDER_ROW;
     const int rc = with_flags(
-        [&](auto TWO_PHASE, auto COLOUR, auto SELF, auto AA, auto F3D, auto POSE) {
-            if constexpr (proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE)) {
-                hipLaunchKernelGGL((proj_fwd_fused_kernel<TWO_PHASE, COLOUR, SELF, AA, F3D, POSE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
+        [&](auto TWO_PHASE, auto COLOUR, auto SELF, auto AA, auto F3D, auto POSE, auto FISHEYE) {
+            if constexpr (proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE, F3D, FISHEYE)) {
+                hipLaunchKernelGGL((proj_fwd_fused_kernel<TWO_PHASE, COLOUR, SELF, AA, F3D, POSE, FISHEYE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
                                    dim3(PROJ_FUSED_THREADS), dynLds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH,
                                    c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
                                    c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc,
                                    pieces, c->filter3d, c->poseCam);
                 return GS_OK;
-            } else {      // unreachable: rider.on and selfColour each imply !posed and exclude one another, so the form exists;
+            } else {      // unreachable: rider.on and selfColour each imply !posed and exclude one another, and api.hip refuses a
+                          // fisheye forward under a pose correction or a 3-D filter, so the form exists;
                           // the branch is here for the lambda to compile for the combinations that have no kernel
                 c->err = "fused projection forward: no kernel for this combination of settings";
                 return GS_ERR_INVALID_ARG;
             }
         },
-        !colour || twoPhase, colour, selfColour, c->antialias, c->filter3d != nullptr, posed);
+        !colour || twoPhase, colour, selfColour, c->antialias, c->filter3d != nullptr, posed, c->fisheye);
     if (rc) return rc;
     c->visBlocks = gs_div_up(N, PROJ_FUSED_THREADS);
     GS_HIP_CHECK(c, hipGetLastError());
@@ -1217,19 +1274,20 @@ static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, con
     a.visMask = c->visMask;
     const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
     const int rc = with_flags(
-        [&](auto ADAM, auto EMIT_MG, auto POSE, auto AA, auto MCMC, auto F3D, auto SPARSE) {
+        [&](auto ADAM, auto EMIT_MG, auto POSE, auto AA, auto MCMC, auto F3D, auto SPARSE, auto FISHEYE) {
             constexpr int MODE = ADAM ? 2 : EMIT_MG ? 1 : 0;
-            if constexpr (!(ADAM && EMIT_MG) && proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE)) {
-                hipLaunchKernelGGL((proj_bwd_fused_kernel<MODE, POSE, AA, MCMC, F3D, SPARSE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
+            if constexpr (!(ADAM && EMIT_MG) && proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE, FISHEYE)) {
+                hipLaunchKernelGGL((proj_bwd_fused_kernel<MODE, POSE, AA, MCMC, F3D, SPARSE, FISHEYE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
                                    dim3(PROJ_FUSED_THREADS), lds, c->stream, a);
                 return GS_OK;
             } else {      // unreachable: f3d, mcmc and sparse are derived above to exclude one another and, like pose, mode 1;
+                          // a fisheye forward ran without pose correction and filter (api.hip);
                           // the branch is here for the lambda to compile for the combinations that have no kernel
                 c->err = "fused projection backward: no kernel for this combination of settings";
                 return GS_ERR_INVALID_ARG;
             }
         },
-        mode == 2, mode == 1, pose, c->fwd.antialias, mcmc, f3d, sparse);
+        mode == 2, mode == 1, pose, c->fwd.antialias, mcmc, f3d, sparse, c->fwd.fisheye);
     if (rc) return rc;
     GS_HIP_CHECK(c, hipGetLastError());
     return pose ? launch_pose_grad(c, N) : GS_OK;

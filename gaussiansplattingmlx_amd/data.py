@@ -14,6 +14,7 @@ import json
 import os
 import struct
 from collections import namedtuple
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
@@ -34,9 +35,21 @@ class TrainData:
     depthArray: np.ndarray | None = None
     maskArray: np.ndarray | None = None       # uint8 [n, H, W] loss masks (255 keeps a pixel), None when no view has one
     depthAlign: np.ndarray | None = None      # float32 [n, 2]: (scale, offset) to apply to depthArray's view (trainStep's depthAlign)
+    # str [n]: "pinhole" or "fisheye" per view (camera.Camera's model), None: all pinhole.  Set by the loaders' fisheye="equidistant"
+    # after construction -- an attribute, not a dataclass field: code that walks dataclasses.fields(TrainData) takes every field for
+    # a per-view array that is there.  copy.copy / copy.deepcopy keep it; dataclasses.replace() builds a new object from the fields
+    # alone and would drop it -- a fisheye view would then train as a pinhole with a fisheye's focal length: use replace() below.
+    cameraModelArray = None
 
     def getCameraParams(self):
         return self.Hs, self.Ws, self.intrinsicArray, self.c2wArray
+
+    def replace(self, **changes):
+        """dataclasses.replace that keeps cameraModelArray (or takes a new one: replace(cameraModelArray=...))."""
+        models = changes.pop("cameraModelArray", self.cameraModelArray)
+        out = dataclasses.replace(self, **changes)
+        out.cameraModelArray = models
+        return out
 
 
 # ---- images ---------------------------------------------------------------------------------------------------
@@ -129,7 +142,8 @@ def _undistort_views(lenses, frames, masks, depths, undistorter=None):
     undistortImage (the kernel)."""
     if undistorter is None:
         from .lens import undistort_image as undistorter
-    todo = [i for i, L in enumerate(lenses) if L is not None and not L.is_pinhole]
+    # (a lens.FisheyeLensModel goes into the ideal equidistant camera with the same K: the loaders' fisheye="equidistant")
+    todo = [i for i, L in enumerate(lenses) if L is not None and not getattr(L, "is_equidistant", getattr(L, "is_pinhole", False))]
     if not todo:
         return frames, masks, depths
     frames = list(frames)
@@ -163,6 +177,35 @@ COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL
                  9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 # the models lens.LensModel inverts (k1, k2, p1, p2); the others load as pinholes and raise under undistort=True
 UNDISTORTABLE = {"SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", None}
+# the models lens.FisheyeLensModel resamples into the ideal equidistant camera under fisheye="equidistant" (DESIGN.md section 29):
+# name -> where k1 .. k4 stand in the model's parameters (the missing ones are 0)
+FISHEYE_MODELS = {"OPENCV_FISHEYE": (4, 4), "SIMPLE_RADIAL_FISHEYE": (3, 1), "RADIAL_FISHEYE": (3, 2)}
+
+
+def _check_fisheye(fisheye, undistort, who):
+    if fisheye not in (None, "equidistant"):
+        raise ValueError(f'{who}: fisheye is None or "equidistant"')
+    if fisheye is not None and not undistort:
+        raise ValueError(f'{who}: fisheye="equidistant" goes with undistort=True (the views are resampled into the ideal camera)')
+
+
+def colmapReadFisheyeCoefficients(binRoot):
+    """{camera id: (k1, k2, k3, k4)} of the cameras.bin cameras whose model (COLMAP's own table) is one of FISHEYE_MODELS."""
+    out = {}
+    with open(os.path.join(binRoot, "cameras.bin"), "rb") as f:
+        rd = lambda fmt: struct.unpack("<" + fmt, f.read(struct.calcsize("<" + fmt)))
+        (n,) = rd("Q")
+        for _ in range(n):
+            camId, model = rd("Ii")
+            rd("QQ")
+            if model not in COLMAP_MODELS:
+                raise ValueError(f"cameras.bin: camera {camId} has the unknown model id {model}")
+            name, count = COLMAP_MODELS[model]
+            p = rd("d" * count)
+            if name in FISHEYE_MODELS:
+                first, nk = FISHEYE_MODELS[name]
+                out[camId] = tuple(p[first:first + nk]) + (0.0,) * (4 - nk)
+    return out
 
 
 def _colmapCamera(camId, model, width, height, p):
@@ -268,7 +311,7 @@ def colmapReadPointSet(points3DPath):
 
 class ColmapDataLoader:
     def __init__(self, binRoot, imageRoot, maskRoot=None, depthRoot=None, depthParams=None, cameraModels: str = "reference",
-                 undistort: bool = False):
+                 undistort: bool = False, fisheye=None):
         """cameraModels: "reference" reads cameras.bin with the reference app's model table, "colmap" with COLMAP's own
         (colmapReadCamerasAndPoses); a real COLMAP reconstruction needs "colmap".
 
@@ -276,6 +319,12 @@ class ColmapDataLoader:
         load time (_undistort_views; the principal point is kept, camera.cameras_from_train_data renders it) and fold the
         validity of the resampling into TrainData.maskArray, so that the border the lens leaves empty is ignored by the loss.
         A camera model the lens module does not invert (fisheye, FULL_OPENCV, FOV) raises a ValueError in load().
+
+        fisheye: None (the default: everything above, the ValueError for a fisheye camera included) or "equidistant", with
+        cameraModels="colmap" and undistort=True: a view whose camera is OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE or RADIAL_FISHEYE
+        is resampled into the ideal equidistant camera with the same K (lens.FisheyeLensModel; validity folded into maskArray
+        as above) and marked "fisheye" in TrainData.cameraModelArray, so that camera.cameras_from_train_data hands the trainer
+        a Camera(model="fisheye").  THIN_PRISM_FISHEYE, FOV and FULL_OPENCV still raise.
 
         maskRoot: a directory of per-view loss masks (TrainData.maskArray).  A view's mask is <maskRoot>/<image file
         name>.png (COLMAP's own convention: "frame.jpg.png") or, failing that, <maskRoot>/<image file name without its
@@ -287,9 +336,12 @@ class ColmapDataLoader:
         or a path to it): a view's "scale" and "offset" go to TrainData.depthAlign, (1, 0) for a view without an entry."""
         self.binRoot, self.imageRoot, self.maskRoot = binRoot, imageRoot, maskRoot
         self.depthRoot, self.depthParams = depthRoot, readDepthParams(depthParams)
-        self.cameraModels, self.undistort = cameraModels, bool(undistort)
+        self.cameraModels, self.undistort, self.fisheye = cameraModels, bool(undistort), fisheye
         if cameraModels not in ("reference", "colmap"):
             raise ValueError('cameraModels is "reference" or "colmap"')
+        _check_fisheye(fisheye, undistort, "ColmapDataLoader")
+        if fisheye is not None and cameraModels != "colmap":
+            raise ValueError('ColmapDataLoader: fisheye="equidistant" goes with cameraModels="colmap" (the reference table has no fisheye model)')
         if depthRoot is None and depthParams is not None:
             raise ValueError("depthParams go with a depthRoot")
 
@@ -332,11 +384,18 @@ class ColmapDataLoader:
         Hs, Ws = [f[2] for f in frames], [f[3] for f in frames]
         masks = None if self.maskRoot is None else _stack_masks([self._maskPath(p.filePath) for p in poses], Hs, Ws, resizeFactor)
         depths, align = (None, None) if self.depthRoot is None else self._depths(poses, Hs, Ws, resizeFactor)
+        models = None
         if self.undistort:
-            from .lens import LensModel
+            from .lens import FisheyeLensModel, LensModel
             lenses = []
+            fish = colmapReadFisheyeCoefficients(self.binRoot) if self.fisheye == "equidistant" else {}
+            if fish:
+                models = np.array(["fisheye" if p.cameraId in fish else "pinhole" for p in poses])
             for p, K in zip(poses, intr):
                 cam = camMap[p.cameraId]
+                if p.cameraId in fish:
+                    lenses.append(FisheyeLensModel(K[0, 0], K[1, 1], K[0, 2], K[1, 2], *fish[p.cameraId]))
+                    continue
                 if cam.model not in UNDISTORTABLE:
                     raise ValueError(f"undistort=True: camera {cam.id} has the model {cam.model}, which is not inverted here "
                                      "(SIMPLE_RADIAL, RADIAL and OPENCV are)")
@@ -346,8 +405,9 @@ class ColmapDataLoader:
         pts, cols = colmapReadPointSet(os.path.join(self.binRoot, "points3D.bin"))
         ch = cols.astype(np.float32) / np.float32(255.0)
         pcd = PointCloud(pts.astype(np.float32), dict(R=ch[:, 0], G=ch[:, 1], B=ch[:, 2]))
-        return (TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, depths, masks, align), pcd,
-                TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
+        td = TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, depths, masks, align)
+        td.cameraModelArray = models
+        return td, pcd, TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4)
 
 
 # ---- OpenGL -> OpenCV -------------------------------------------------------------------------------------------
@@ -387,10 +447,14 @@ def parsePLY(path):
 
 
 class NerfStudioDataLoader:
-    def __init__(self, directory, undistort: bool = False):
+    def __init__(self, directory, undistort: bool = False, fisheye=None):
         """undistort: as ColmapDataLoader's, from the frame's k1, k2, p1, p2 or, when the frame has none of them, the file
-        header's; a "camera_model" other than OPENCV or PINHOLE (or none) raises a ValueError in load()."""
-        self.directory, self.undistort = directory, bool(undistort)
+        header's; a "camera_model" other than OPENCV or PINHOLE (or none) raises a ValueError in load().
+        fisheye: None (the default: exactly the above) or "equidistant", with undistort=True: a frame whose "camera_model" is
+        OPENCV_FISHEYE (or SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE) is resampled from its k1 .. k4 (missing ones 0) into the ideal
+        equidistant camera and marked "fisheye" in TrainData.cameraModelArray, as ColmapDataLoader's."""
+        self.directory, self.undistort, self.fisheye = directory, bool(undistort), fisheye
+        _check_fisheye(fisheye, undistort, "NerfStudioDataLoader")
 
     def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA, undistorter=None):
         """loadTrainDataAndPointCloud (:385-416): transforms.json + its ply_file_path.  A frame's "mask_path" (relative to the
@@ -404,14 +468,16 @@ class NerfStudioDataLoader:
         def intrinsic(d):
             return _intrinsics3(d["fl_x"], d["fl_y"], d["cx"], d["cy"]) if all(k in d for k in ("fl_x", "fl_y", "cx", "cy")) else None
         COEFFS = ("k1", "k2", "p1", "p2")
-        intr, c2ws, frames, maskPaths, coeffs = [], [], [], [], []
+        intr, c2ws, frames, maskPaths, coeffs, fish = [], [], [], [], [], []
         for fr in meta["frames"]:
             if self.undistort:
                 model = fr.get("camera_model", meta.get("camera_model"))
-                if model not in (None, "OPENCV", "PINHOLE"):
+                fish.append(self.fisheye == "equidistant" and model in FISHEYE_MODELS)
+                if model not in (None, "OPENCV", "PINHOLE") and not fish[-1]:
                     raise ValueError(f'undistort=True: camera_model "{model}" is not inverted here (OPENCV and PINHOLE are)')
-                src = fr if any(k in fr for k in COEFFS) else meta
-                coeffs.append([float(src.get(k, 0.0)) for k in COEFFS])
+                names = ("k1", "k2", "k3", "k4") if fish[-1] else COEFFS
+                src = fr if any(k in fr for k in names) else meta
+                coeffs.append([float(src.get(k, 0.0)) for k in names])
             maskPaths.append(os.path.join(self.directory, fr["mask_path"]) if fr.get("mask_path") else None)
             K = intrinsic(fr)
             K = intrinsic(meta) if K is None else K
@@ -424,13 +490,17 @@ class NerfStudioDataLoader:
             # the reference reads transform_matrix as Float before widening (:359)
             c2ws.append(opengl_c2w_to_opencv(np.asarray(fr["transform_matrix"], np.float32).astype(np.float64)).astype(np.float32))
         masks = _stack_masks(maskPaths, [f[2] for f in frames], [f[3] for f in frames], resizeFactor)
+        models = None
         if self.undistort:
-            from .lens import LensModel
-            lenses = [LensModel(K[0, 0], K[1, 1], K[0, 2], K[1, 2], *c) for K, c in zip(intr, coeffs)]
+            from .lens import FisheyeLensModel, LensModel
+            lenses = [(FisheyeLensModel if f else LensModel)(K[0, 0], K[1, 1], K[0, 2], K[1, 2], *c) for K, c, f in zip(intr, coeffs, fish)]
             frames, masks, _ = _undistort_views(lenses, frames, masks, None, undistorter)
+            if any(fish):
+                models = np.array(["fisheye" if f else "pinhole" for f in fish])
         Hs, Ws, rgbs, alphas = _stack_frames(frames, whiteBackground)
-        return (TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None, masks), pcd,
-                TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4))
+        td = TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None, masks)
+        td.cameraModelArray = models
+        return td, pcd, TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4)
 
 
 # ---- Blender demo set (BlenderDataLoader.swift) --------------------------------------------------------------------

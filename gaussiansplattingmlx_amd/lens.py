@@ -14,6 +14,9 @@ radial-tangential lens, resampled into a pinhole camera once when a dataset is l
     mask         the same blend of the uint8 levels, then floor(v + 0.5)
     depth        sum w_i d_i / sum w_i over the taps with d_i > 0 (0 = hole), 0 when the weights' sum is 0
 
+FisheyeLensModel / undistort_fisheye_image (gs_undistort_fisheye) are the same resampling for OpenCV's
+fisheye lens (k1 .. k4) into the ideal equidistant camera: taps, modes and validity as above, the lens map stated in the class.
+
 These are the host-side statements of what csrc/lens.hip computes in float32, for tests, and the loaders' own undistorter on a
 machine without a GPU (data.py).  dtype=np.float32 evaluates the kernel's own arithmetic, operation for operation, as
 filter3d.filter_scales(dtype=) does.  The principal point is kept, not recentred: the camera renders it (camera.py)."""
@@ -69,6 +72,111 @@ class LensModel:
         return xd, yd
 
 
+FISHEYE_COORD_ROUNDINGS = 38    # FisheyeLensModel: roundings on the longest path to su / sv (coord_delta)
+FISHEYE_FOLD_ROUNDINGS = 33     # ... and to the derivative d theta_d / d theta
+
+
+class FisheyeLensModel:
+    """OpenCV's / COLMAP's fisheye lens (OPENCV_FISHEYE; SIMPLE_RADIAL_FISHEYE and RADIAL_FISHEYE with k3 = k4 = 0; include/gsplat.h
+    gs_undistort_fisheye): a ray at angle theta off the axis lands at
+    theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) focal lengths from the principal point.  The
+    destination of its resampling is the IDEAL EQUIDISTANT camera (theta_d = theta) that Camera(model="fisheye") renders, not a
+    pinhole: a destination pixel's normalised (x, y) is theta (cos phi, sin phi), so the lens is the radial polynomial in
+    t2 = x^2 + y^2 = theta^2 and needs no inversion.  Valid: the four taps inside the source, d theta_d / d theta > 0, and theta
+    below the first root of that derivative (beyond it the derivative may turn positive again)."""
+
+    def __init__(self, fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, k4=0.0):
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self.k1, self.k2, self.k3, self.k4 = (float(v or 0.0) for v in (k1, k2, k3, k4))
+        if not (self.fx > 0.0 and self.fy > 0.0):
+            raise ValueError("FisheyeLensModel: focal lengths are > 0")
+
+    @property
+    def K(self):
+        return self.fx, self.fy, self.cx, self.cy
+
+    @property
+    def coefficients(self):
+        return self.k1, self.k2, self.k3, self.k4
+
+    @property
+    def is_equidistant(self) -> bool:
+        return not any(self.coefficients)
+
+    def as_float32(self) -> "FisheyeLensModel":
+        return FisheyeLensModel(*(float(np.float32(v)) for v in (*self.K, *self.coefficients)))
+
+    def distort(self, x, y, dtype=np.float64):
+        """(xd, yd) = (x, y) theta_d / theta, in `dtype` and in the kernel's order of operations."""
+        T = np.dtype(dtype).type
+        x, y = np.asarray(x, dtype), np.asarray(y, dtype)
+        k1, k2, k3, k4 = (T(v) for v in self.coefficients)
+        t2 = x * x + y * y
+        radial = (((k4 * t2 + k3) * t2 + k2) * t2 + k1) * t2 + T(1)
+        return x * radial, y * radial
+
+    def first_fold(self, tMax=None) -> float:
+        """theta^2 at the first root of D(t) = d theta_d / d theta = 1 + 3 k1 t + 5 k2 t^2 + 7 k3 t^3 + 9 k4 t^4, inf without one.
+        tMax=None: over all t > 0, the smallest positive real root numpy.roots finds.  tMax given (the largest t of a destination
+        image, dst_t_max): csrc/lens.hip's own search, step for step in float64 -- [0, tMax] in 4096 steps for the first sign
+        change, then 100 bisections -- which is what the resampling uses on both sides, so that host and kernel cut at the same
+        limit.  The scan steps over a root D only touches and over a pair of roots closer than a step; `D > 0` still decides
+        every pixel there, on both sides alike."""
+        if tMax is not None:
+            k1, k2, k3, k4 = self.coefficients
+            D = lambda t: (((9.0 * k4 * t + 7.0 * k3) * t + 5.0 * k2) * t + 3.0 * k1) * t + 1.0      # noqa: E731
+            lo = 0.0
+            for step in range(1, 4097):
+                hi = tMax * step / 4096
+                if not D(hi) > 0.0:
+                    a, b = lo, hi
+                    for _ in range(100):
+                        m = 0.5 * (a + b)
+                        if D(m) > 0.0:
+                            a = m
+                        else:
+                            b = m
+                    return b
+                lo = hi
+            return float("inf")
+        c = [9.0 * self.k4, 7.0 * self.k3, 5.0 * self.k2, 3.0 * self.k1, 1.0]
+        while len(c) > 1 and c[0] == 0.0:
+            c = c[1:]
+        if len(c) == 1:
+            return float("inf")
+        roots = np.roots(c)
+        real = roots[np.abs(roots.imag) <= 1e-12 * np.maximum(1.0, np.abs(roots.real))].real
+        real = real[real > 0.0]
+        return float(real.min()) if real.size else float("inf")
+
+    def fold(self, x, y, dtype=np.float64, tMax=None):
+        """The derivative d theta_d / d theta at (x, y), negated in magnitude beyond the first fold (first_fold(tMax)): valid iff > 0."""
+        T = np.dtype(dtype).type
+        x, y = np.asarray(x, dtype), np.asarray(y, dtype)
+        k1, k2, k3, k4 = (T(v) for v in self.coefficients)
+        t2 = x * x + y * y
+        d = ((((T(9) * k4) * t2 + T(7) * k3) * t2 + T(5) * k2) * t2 + T(3) * k1) * t2 + T(1)
+        lim = self.first_fold(tMax)
+        limit = T(min(lim, float(np.finfo(np.float32).max))) if T is np.float32 else T(lim)
+        return np.where(t2 < limit, d, -np.abs(d)).astype(dtype)
+
+
+def dst_t_max(dstK, dstW, dstH) -> float:
+    """The largest t = x^2 + y^2 over the destination image's corners (pixel edges 0 .. W, 0 .. H), as csrc/lens.hip forms it
+    from the float32 destination intrinsics."""
+    nfx, nfy, ncx, ncy = (float(np.float32(v)) for v in dstK)
+    return max(((cx - ncx) / nfx) ** 2 + ((cy - ncy) / nfy) ** 2 for cx in (0.0, float(dstW)) for cy in (0.0, float(dstH)))
+
+
+def undistort_fisheye_image(img, lens: FisheyeLensModel, dstK=None, dstSize=None, mode: str = "color", dtype=np.float64):
+    """undistort_image for a FisheyeLensModel: (out, valid uint8 [H, W]), the view resampled into the ideal equidistant camera
+    dstK = (fx, fy, cx, cy) of size dstSize (None: the lens's own intrinsics and the source's size).  float64 states it, float32
+    evaluates csrc/lens.hip's arithmetic operation for operation."""
+    if not isinstance(lens, FisheyeLensModel):
+        raise ValueError("undistort_fisheye_image takes a FisheyeLensModel")
+    return undistort_image(img, lens, dstK, dstSize, mode, dtype)
+
+
 def _dst(lens, dstK, dstSize, srcShape):
     nfx, nfy, ncx, ncy = (float(v) for v in (lens.K if dstK is None else dstK))
     if not (nfx > 0.0 and nfy > 0.0):
@@ -98,6 +206,8 @@ def source_coords(lens, dstK, dstW, dstH, dtype=np.float64):
     fx, fy, cx, cy = (T(v) for v in lens.K)
     su = (fx * xd + cx) - T(0.5)
     sv = (fy * yd + cy) - T(0.5)
+    if isinstance(lens, FisheyeLensModel):
+        return su, sv, lens.fold(x, y, dtype, dst_t_max(dstK, dstW, dstH))
     r2 = x * x + y * y
     fold = (T(1) + (T(3) * T(lens.k1)) * r2) + (T(5) * T(lens.k2)) * (r2 * r2)
     return su, sv, fold
@@ -176,6 +286,15 @@ def coord_delta(lens, dstK, dstW, dstH):
     x, y = _normalised(dstK, dstW, dstH, np.float64)
     ax, ay = np.abs(x), np.abs(y)
     r2 = x * x + y * y
+    if isinstance(lens, FisheyeLensModel):
+        # x: 2; x x: 5; t2: 6; k4 t2: 7; + k3: 8; t2: 15; + k2: 16; t2: 23; + k1: 24; t2: 31; + 1: 32; x radial: 35; fx: 36;
+        # + cx: 37; - 0.5: 38 roundings of M = f |x| (1 + |k1| t2 + .. + |k4| t2^4) + |c| + 0.5.  The derivative: 9 k4: 1; t2: 8;
+        # + 7 k3: 9 (its own product inside); t2: 16; 17; 24; 25; 32; + 1: 33 roundings of 1 + 3 |k1| t2 + .. + 9 |k4| t2^4
+        k1, k2, k3, k4 = (abs(v) for v in lens.coefficients)
+        rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * (k3 + r2 * k4)))
+        Mu, Mv = lens.fx * ax * rad + abs(lens.cx) + 0.5, lens.fy * ay * rad + abs(lens.cy) + 0.5
+        der = 1.0 + r2 * (3.0 * k1 + r2 * (5.0 * k2 + r2 * (7.0 * k3 + r2 * 9.0 * k4)))
+        return FISHEYE_COORD_ROUNDINGS * U32 * np.maximum(Mu, Mv), FISHEYE_FOLD_ROUNDINGS * U32 * der
     r4 = r2 * r2
     k1, k2, p1, p2 = (abs(v) for v in lens.coefficients)
     rad = 1.0 + k1 * r2 + k2 * r4

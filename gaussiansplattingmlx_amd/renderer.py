@@ -109,6 +109,7 @@ class GaussianRenderer:
         self._target_cache = OrderedDict()
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
         self._antialiased = False
+        self._camera_model = "pinhole"
         self._absgrad = False
         self._sparse_adam = False
         self._background = None
@@ -412,6 +413,9 @@ class GaussianRenderer:
         cam = camera if isinstance(camera, _lib.gs_camera) else self._camera(
             camera.worldViewTransform, camera.projectionMatrix, camera.cameraCenter, camera.FoVx, camera.FoVy,
             camera.focalX, camera.focalY)
+        model = getattr(camera, "model", "pinhole")      # (the camera's model: views of both kinds share a renderer)
+        if model != self._camera_model:
+            self.setCameraModel(model)
         p = {k: (v if isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
                  else self._t(v)) for k, v in params.items()}
         N = p["xyz"].shape[0]
@@ -595,11 +599,22 @@ class GaussianRenderer:
         W, H = (srcW, srcH) if dstSize is None else (int(dstSize[0]), int(dstSize[1]))
         if W < 1 or H < 1:
             raise ValueError("undistortImage: dstSize = (width, height), both positive")
-        L = _lib.gs_lens(*lens.K, *lens.coefficients, nfx, nfy, ncx, ncy)
+        fisheye = isinstance(lens, _lens.FisheyeLensModel)      # (k1 .. k4 into the equidistant camera: gs_undistort_fisheye)
+        L = (_lib.gs_fisheye_lens if fisheye else _lib.gs_lens)(*lens.K, *lens.coefficients, nfx, nfy, ncx, ncy)
         out = torch.empty((H, W) + tuple(src.shape[2:]), dtype=dtype, device=self.device)
         valid = torch.empty((H, W), dtype=torch.uint8, device=self.device) if wantValid else None
-        self._check(self.lib.gs_undistort(self.ctx, C.byref(L), srcW, srcH, W, H, chans, _lens.MODES[mode], _p(src), _p(out), _p(valid)))
+        call = self.lib.gs_undistort_fisheye if fisheye else self.lib.gs_undistort
+        self._check(call(self.ctx, C.byref(L), srcW, srcH, W, H, chans, _lens.MODES[mode], _p(src), _p(out), _p(valid)))
         return out, valid
+
+    def undistortFisheyeImage(self, img, lens, dstK=None, dstSize=None, mode: str = "color", wantValid: bool = True):
+        """gs_undistort_fisheye: undistortImage for a lens.FisheyeLensModel -- the view resampled into the ideal equidistant
+        camera dstK = (fx, fy, cx, cy) that Camera(model="fisheye") renders (None: the lens's own intrinsics and the source's
+        size).  Modes, shapes and the validity output are undistortImage's; lens.undistort_fisheye_image states it in float64."""
+        from . import lens as _lens
+        if not isinstance(lens, _lens.FisheyeLensModel):
+            raise ValueError("undistortFisheyeImage takes a lens.FisheyeLensModel")
+        return self.undistortImage(img, lens, dstK, dstSize, mode, wantValid)
 
     @staticmethod
     def _grid_shape(shape, what):
@@ -675,6 +690,26 @@ class GaussianRenderer:
         up as a replica mismatch).  PLY snapshots do not record the mode: render a model in the mode it was trained in."""
         self._check(self.lib.gs_set_antialiasing(self.ctx, 1 if enable else 0))
         self._antialiased = bool(enable)
+
+    def setCameraModel(self, model: str = "pinhole"):
+        """gs_set_camera_model: "pinhole" (the default) or "fisheye", the ideal equidistant camera (include/gsplat.h, DESIGN.md
+        section 29), for the following forwards; every fused backward uses the model of its forward.  renderForward and
+        renderChecked set it from their camera (`camera.model`, "pinhole" for a camera without one), so a trainer follows its
+        cameras; projectionScreenFused* and forwardWithCameraParams* take plain matrices and use the setting in effect.
+        Not with a pose correction, a 3-D filter or the data-parallel entry points: those calls raise."""
+        from .camera import CAMERA_MODELS
+        if model not in CAMERA_MODELS:
+            raise ValueError(f"setCameraModel: model is one of {sorted(CAMERA_MODELS)}")
+        self._check(self.lib.gs_set_camera_model(self.ctx, CAMERA_MODELS[model]))
+        self._camera_model = model
+
+    @property
+    def cameraModel(self) -> str:
+        return self._camera_model
+
+    @cameraModel.setter
+    def cameraModel(self, model: str):
+        self.setCameraModel(model)
 
     @property
     def antialiased(self) -> bool:

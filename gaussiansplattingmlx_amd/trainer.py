@@ -1715,6 +1715,8 @@ class GaussianTrainer:
         loss[4].  stepCameras: the cameras of ALL ranks for this step in rank order (every rank derives them from the
         shared view permutation, see view_for), or just their centres [R,3]; required by the sh_compressed exchange.
         viewKey: identifies the training view (renderer.renderForward): enables the forward's deepest-first order.
+        camera: a Camera(model="fisheye") is rendered and differentiated through the equidistant model, view
+        by view beside pinhole ones; single-device steps with one view only, not with pose_opt or filter_3d.
 
         Reserved-capacity overflow: the step's calls raise GS_ERR_WORKSPACE_OVERFLOW as soon as the host sees the
         device's flag (at the latest at the checks below: the first visit of every view, every densify cadence); the
@@ -1740,6 +1742,16 @@ class GaussianTrainer:
         accumulated and expected modes, an inverse depth in the disparity mode.  depthMask: uint8 or bool [H, W], non-zero =
         the pixel takes part in the depth term; None means targetDepth > 0 (sensor holes are 0).  depthAlign = (scale, offset):
         the term compares with scale * targetDepth + offset (Inria's depth_params.json pair; TrainData.depthAlign)."""
+        if getattr(camera, "model", "pinhole") == "fisheye":
+            # (include/gsplat.h gs_set_camera_model: the fisheye model has no pose, filter or data-parallel kernels)
+            for on, name in ((self.pose_opt, "pose_opt"), (self.filter_3d, "filter_3d")):
+                if on:
+                    raise ValueError(f"trainStep: a fisheye camera does not go with {name} (pinhole cameras only)")
+            if self.pg is not None or self.exchange_impl == "native":
+                raise ValueError("trainStep: a fisheye camera takes single-device steps only (no process group, dp_bootstrap or "
+                                 "native exchange)")
+            if self.viewsPerRank != 1:
+                raise ValueError("trainStep: a fisheye camera takes one view per step only (views_per_rank > 1 is not supported)")
         if lossMask is not None:
             if self.viewsPerRank != 1:
                 raise ValueError("trainStep: lossMask takes one view per step only (views_per_rank > 1 is not supported)")

@@ -351,6 +351,28 @@ int gs_apply_bilateral_grid(gs_ctx* ctx, int W, int H, const float* grid /*DEVIC
  * record it: render a model in the mode it was trained in. */
 int gs_set_antialiasing(gs_ctx* ctx, int enable);
 
+/* Camera model (not in the reference; gsplat's camera_model="fisheye").  GS_CAMERA_PINHOLE (the default)
+ * is the reference's perspective projection, kernel for kernel.  Under GS_CAMERA_FISHEYE every following gs_render_forward and
+ * the op-level gs_projection_forward / gs_projection_backward project through the ideal equidistant model: a view-space point
+ * (x, y, z) with r = sqrt(x^2 + y^2), theta = atan2(r, z) lands at
+ *   means2d = (fx x theta / r + cx - 0.5,  fy y theta / r + cy - 0.5)        (r = 0: the principal point),
+ * and the 2-D covariance is (J W) Sigma (J W)^T + 0.3 I with J the full 2 x 3 Jacobian of that map (no frustum clamp).  Depth
+ * stays view z and visibility stays z >= 0.2, so the field of view is below 180 degrees.  Colour, radius, rect, conic, the
+ * degenerate-determinant rule and the anti-aliased mode are what they are for a pinhole.
+ * Read from the gs_camera: focal_x, focal_y (fx, fy), proj[8] and proj[9] (cx = (proj[8] + 1) W / 2, cy = (proj[9] + 1) H / 2,
+ * the principal point as DESIGN.md section 23 places it), view, cam_center, and the context's W, H.  Not read: fov_x, fov_y and
+ * the rest of proj.  The gs_camera's layout is unchanged.
+ * A per-context setting as gs_set_antialiasing is: it allocates nothing and may be changed before every forward, so views of
+ * both models can share a context; a fused backward (gs_render_backward, gs_render_backward_adam) uses the model its forward
+ * ran in.  Any other value of model returns GS_ERR_INVALID_ARG and leaves the setting as it was.
+ * Not served, each GS_ERR_INVALID_ARG with the reason in gs_last_error: a fisheye gs_render_forward while a pose correction
+ * (gs_set_pose_correction) or a 3-D filter (gs_set_filter3d) is set; gs_render_backward_dp*, gs_dp_step and
+ * gs_set_filter3d_cameras while the model is set or behind a forward made in it. */
+#define GS_CAMERA_PINHOLE 0
+#define GS_CAMERA_FISHEYE 1
+int gs_set_camera_model(gs_ctx* ctx, int model);
+int gs_get_camera_model(gs_ctx* ctx, int* model /*HOST*/);
+
 /* Background colour (not in the reference, which composites over black or white; Inria's
  * --random_background, gsplat's backgrounds=).  With a colour b set, every following blend forward writes, per pixel and channel,
  *   out_c = sums_c + T b_c        (T the final transmittance; alpha, depth and nContrib do not change),
@@ -492,6 +514,19 @@ int gs_filter3d_bake(gs_ctx* ctx, int N, const float* scales_raw /*[N,3]*/, cons
 typedef struct gs_lens { float fx, fy, cx, cy, k1, k2, p1, p2; float dst_fx, dst_fy, dst_cx, dst_cy; } gs_lens;
 int gs_undistort(gs_ctx* ctx, const gs_lens* lens /*HOST*/, int src_w, int src_h, int dst_w, int dst_h, int channels,
                  int mode, const void* src /*DEVICE*/, void* dst /*DEVICE*/, unsigned char* valid /*DEVICE [dst_h,dst_w] or NULL*/);
+
+/* The same resampling for OpenCV's / COLMAP's fisheye lens (OPENCV_FISHEYE: fx, fy, cx, cy, k1 .. k4; SIMPLE_RADIAL_FISHEYE and
+ * RADIAL_FISHEYE are the family with k3 = k4 = 0) into the IDEAL EQUIDISTANT camera (dst_fx, dst_fy, dst_cx, dst_cy) that
+ * GS_CAMERA_FISHEYE renders.  A destination pixel's normalised (x, y) is theta (cos phi, sin phi), and the
+ * lens maps theta forward to theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8): no inversion.  In float32
+ * and in this order (no contraction), x and y as above:
+ *   t2 = x x + y y,  radial = (((k4 t2 + k3) t2 + k2) t2 + k1) t2 + 1,  su = (fx (x radial) + cx) - 0.5,  sv = (fy (y radial) + cy) - 0.5.
+ * VALID iff the four taps lie inside the source, d theta_d / d theta = ((((9 k4) t2 + 7 k3) t2 + 5 k2) t2 + 3 k1) t2 + 1 > 0, and t2
+ * is below the first root of that derivative inside the destination image (found on the host in float64: a scan of 4096 steps
+ * and bisection).  Modes, taps, layouts, the validity output, the argument checks and the asynchrony are gs_undistort's. */
+typedef struct gs_fisheye_lens { float fx, fy, cx, cy, k1, k2, k3, k4; float dst_fx, dst_fy, dst_cx, dst_cy; } gs_fisheye_lens;
+int gs_undistort_fisheye(gs_ctx* ctx, const gs_fisheye_lens* lens /*HOST*/, int src_w, int src_h, int dst_w, int dst_h, int channels,
+                         int mode, const void* src /*DEVICE*/, void* dst /*DEVICE*/, unsigned char* valid /*DEVICE [dst_h,dst_w] or NULL*/);
 
 /* MCMC densification strategy (not in the reference; DESIGN.md "MCMC strategy"): "3D Gaussian Splatting as Markov Chain Monte
  * Carlo" (Kheradmand et al. 2024), gsplat's MCMCStrategy, with its defaults in brackets.  Notation: o = sigmoid(opacity_raw),
