@@ -168,6 +168,8 @@ _SIGS = {
     "gs_set_antialiasing": (C.c_int, [_vp, C.c_int]),
     "gs_set_camera_model": (C.c_int, [_vp, C.c_int]),
     "gs_get_camera_model": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "gs_set_sh_degree": (C.c_int, [_vp, C.c_int]),
+    "gs_get_sh_degree": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "gs_set_background": (C.c_int, [_vp, _vp]),
     "gs_get_background": (C.c_int, [_vp, _vp]),
     "gs_composite_target": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp, _vp]),
@@ -229,7 +231,7 @@ def load():
 # gs_tuning (include/gsplat.h)
 TUNE_FWD_WAVES_PER_SIMD, TUNE_BWD_WAVES_PER_CU, TUNE_FWD_QUADRANTS, TUNE_OP_FWD_PPL, TUNE_OP_BWD_PPL, \
     TUNE_FWD_TRACE_BUFFER, TUNE_DEPTH_GRADIENT, TUNE_WIDE_TILE_SORT, TUNE_HOST_OVERFLOW_ERRORS, TUNE_SPLITTER_DEPTH_SORT, \
-    TUNE_COLOUR_RIDERS, TUNE_FWD_QUEUES, TUNE_FWD_FOUR_WAVES, TUNE_FWD_FOLD_TEST_SCALE, TUNE_POISON_CHECKPOINTS, TUNE_RENDER_ONLY, TUNE_FWD_PAIR, TUNE_FWD_SLOW_SLOT, TUNE_TRIM_RECTS = range(19)
+    TUNE_COLOUR_RIDERS, TUNE_FWD_QUEUES, TUNE_FWD_FOUR_WAVES, TUNE_FWD_FOLD_TEST_SCALE, TUNE_POISON_CHECKPOINTS, TUNE_RENDER_ONLY, TUNE_FWD_PAIR, TUNE_FWD_SLOW_SLOT, TUNE_TRIM_RECTS, TUNE_SH_BAND_SKIP = range(20)
 
 
 def exported_symbols():

@@ -461,7 +461,7 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     c->W = W; c->H = H; c->tileW = tile_w; c->tileH = tile_h;
     c->gridW = (W + tile_w - 1) / tile_w; c->gridH = (H + tile_h - 1) / tile_h;
     c->T = c->gridW * c->gridH;
-    c->degree = sh_degree; c->whiteBg = white_bg ? 1 : 0;
+    c->degree = c->maxDegree = sh_degree; c->whiteBg = white_bg ? 1 : 0;
     c->bg.mode = c->whiteBg ? GS_BG_WHITE : GS_BG_BLACK;
     c->fast16 = (tile_w % 16 == 0) && (tile_h % 16 == 0);
     c->blocksX = gs_div_up(W, 16); c->blocksY = gs_div_up(H, 16);
@@ -983,6 +983,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.poseGrad = c->poseGrad;
     c->fwd.antialias = c->antialias;
     c->fwd.fisheye = c->fisheye;
+    c->fwd.degree = c->degree;
     c->fwd.bg = c->bg;
     c->fwd.filter3d = c->filter3d;
     c->fwd.radii = keepRadii ? radii : nullptr;      // (a caller's buffer is remembered only where a backward will read it)
@@ -1127,6 +1128,24 @@ int gs_set_antialiasing(gs_ctx* c, int enable)
     if (!c) return GS_ERR_INVALID_ARG;
     if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_antialiasing: enable is 0 or 1");
     c->antialias = enable == 1;
+    return GS_OK;
+}
+
+// ---- active SH degree (include/gsplat.h gs_set_sh_degree; projection.hip proj_bwd_fused_kernel's BANDS forms) -----------------
+int gs_set_sh_degree(gs_ctx* c, int degree)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (degree < 0 || degree > c->maxDegree)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_set_sh_degree: degree is 0 .. the sh_degree the context was created with");
+    c->degree = degree;
+    return GS_OK;
+}
+
+int gs_get_sh_degree(gs_ctx* c, int* degree)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!degree) return fail(c, GS_ERR_INVALID_ARG, "gs_get_sh_degree: null pointer");
+    *degree = c->degree;
     return GS_OK;
 }
 
@@ -1900,6 +1919,8 @@ int gs_ctx_set_tuning(gs_ctx* c, int knob, long long value)
     case GS_TUNE_TRIM_RECTS:
         if (value < 0 || value > 2) return fail(c, GS_ERR_INVALID_ARG, "gs_ctx_set_tuning: trim rects is 0 (the reference's squares), 1 (cut by the ellipse's box) or 2 (and into four row groups)");
         c->trimRects = value != 0; c->rowGroups = value == 2; return GS_OK;
+    case GS_TUNE_SH_BAND_SKIP:
+        c->shBandSkip = value != 0; return GS_OK;
     case GS_TUNE_FWD_TRACE_BUFFER:
         c->fwdTrace = reinterpret_cast<unsigned long long*>((uintptr_t)value); return GS_OK;
     default:

@@ -239,6 +239,8 @@ struct gs_ctx {
     long long bgPartialsCap = 0;
     bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
     bool fisheye = false;                // gs_set_camera_model: GS_CAMERA_FISHEYE for the following forwards and the op-level projection
+    int maxDegree = 0;                   // gs_ctx_create's sh_degree; `degree` is the active one (gs_set_sh_degree), 0 .. maxDegree
+    int shBandSkip = 1;                  // GS_TUNE_SH_BAND_SKIP: 1 = a lower-degree fused Adam step takes the BANDS form (projection.hip)
     bool absgrad = false;                // gs_set_absgrad: the fused backward also sums |g_x|, |g_y| per Gaussian
     int absgradN = -1;                   // N of the last backward that left (Ax, Ay) in gradAcc16's columns 12, 13; -1: none to read
     // sparse Adam (gs_set_sparse_adam): while on, every fused forward leaves radius > 0 of its N Gaussians
@@ -375,6 +377,7 @@ struct gs_ctx {
         float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
         bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
         bool fisheye = false;              // the camera model this forward ran in (its backward's model)
+        int degree = 0;                    // the active SH degree this forward ran with (its backward's)
         GsBackground bg;                   // the background this forward composited over (its backward's)
         const float* filter3d = nullptr;   // the 3-D filter widths this forward ran with (its backward's; nullptr: none)
         const float* radii = nullptr;      // where this forward's projection wrote its radii (nullptr: nowhere)

@@ -469,6 +469,117 @@ __device__ __forceinline__ void adam_rows_kept(const AdamFuse& adam, const float
     }
 }
 
+// BANDS (the band-limited forms of the fused Adam step, gs_set_sh_degree): of a row of L floats only the columns [0, Lact),
+// Lact = 3 ((degree + 1)^2 - 1) < L, are staged, differentiated and updated.  Where the full-row form may use 16-byte accesses
+// (L % 4 == 0 and an aligned span in all three arenas) a row's first A4 = ceil(Lact / 4) float4 are moved: item j = lane + 64 i of
+// the wave's rows x A4 items is float4 (j % A4) of row (j / A4), so i < A4 and the parameter values stay in A4 <= SH_BAND_MAX4
+// registers per lane for the update, as adam_rows_kept keeps them.  A float4 that straddles Lact (L = 72: columns 8..11 at degree
+// 1, 44..47 at degree 3) is loaded and stored back whole, its inactive elements as they came -- the rule SPARSE has for a
+// straddling float4; a float4 beyond it is neither loaded nor stored.  Other spans go element by element (sh_band_in, adam_band_rows).
+// The LDS pitch stays L + 1; nothing reads an LDS column >= Lact (color_backward is given (degree + 1)^2 for K and writes none).
+constexpr int SH_BAND_MAX4 = 12;      // K = 25 at degree 3: 48 of 72 columns
+
+__device__ __forceinline__ void sh_band_load4(const float* __restrict__ g, int totalA, int L4, int A4, int lane,
+                                              float4 (&regs)[SH_BAND_MAX4])
+{
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+#pragma unroll
+    for (int i = 0; i < SH_BAND_MAX4; i++) {
+        if (i < A4) {      // (wave-uniform)
+            const int j = min(lane + 64 * i, totalA - 1), r = j / A4;
+            regs[i] = g4[r * L4 + (j - r * A4)];
+        }
+    }
+}
+__device__ __forceinline__ void sh_band_to_lds4(float* __restrict__ lds, int totalA, int L, int A4, int lane,
+                                                const float4 (&regs)[SH_BAND_MAX4])
+{
+#pragma unroll
+    for (int i = 0; i < SH_BAND_MAX4; i++) {
+        const int j = lane + 64 * i;
+        if (i < A4 && j < totalA) {
+            const int r = j / A4;
+            float* d = lds + r * (L + 1) + 4 * (j - r * A4);
+            d[0] = regs[i].x; d[1] = regs[i].y; d[2] = regs[i].z; d[3] = regs[i].w;
+        }
+    }
+}
+__device__ __forceinline__ void sh_band_in(float* __restrict__ lds, const float* __restrict__ g, int rows, int L, int Lact, int lane)
+{
+    const int total = rows * Lact;
+    for (int e = lane; e < total; e += 64) {
+        const int r = e / Lact, c = e - r * Lact;
+        lds[r * (L + 1) + c] = g[r * L + c];
+    }
+}
+
+// Adam over the active float4 of one wave's rows, parameters from the kept registers; moments in batches of 3 float4
+__device__ __forceinline__ void adam_band_rows_kept(const AdamFuse& adam, const float* frest, int row0, int totalA, int L, int Lact,
+                                                    int A4, const float* myRows, int lane, float lr, float4 (&pp)[SH_BAND_MAX4])
+{
+    const size_t off0 = (size_t)(frest - adam.pBase) + (size_t)row0 * L;
+    float4* P4 = reinterpret_cast<float4*>(const_cast<float*>(adam.pBase) + off0);
+    float4* M4 = reinterpret_cast<float4*>(adam.mBase + off0);
+    float4* V4 = reinterpret_cast<float4*>(adam.vBase + off0);
+    const int L4 = L >> 2;
+    constexpr int B = 3, NB = SH_BAND_MAX4 / B;
+    static_assert(NB * B == SH_BAND_MAX4, "whole batches");
+    // (a batch of moments in flight ahead of the update, as adam_rows_kept has it, bought nothing here: measured)
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        if (k * B < A4) {      // (wave-uniform)
+            float4 mm[B], vv[B];
+#pragma unroll
+            for (int b = 0; b < B; b++) {      // unconditional, clamped: the batch's loads in flight at once
+                const int j = min(lane + 64 * (k * B + b), totalA - 1), r = j / A4, e = r * L4 + (j - r * A4);
+                mm[b] = M4[e]; vv[b] = V4[e];
+            }
+#pragma unroll
+            for (int b = 0; b < B; b++) {
+                const int j = lane + 64 * (k * B + b);
+                if (j < totalA) {
+                    const int r = j / A4, c4 = j - r * A4, e = r * L4 + c4, c = 4 * c4;
+                    const float* g = myRows + r * (L + 1) + c;
+                    float4& p = pp[k * B + b];
+                    adam_step(adam, g[0], lr, p.x, mm[b].x, vv[b].x);      // (c < Lact: A4 = ceil(Lact / 4))
+                    if (c + 1 < Lact) adam_step(adam, g[1], lr, p.y, mm[b].y, vv[b].y);
+                    if (c + 2 < Lact) adam_step(adam, g[2], lr, p.z, mm[b].z, vv[b].z);
+                    if (c + 3 < Lact) adam_step(adam, g[3], lr, p.w, mm[b].w, vv[b].w);
+                    P4[e] = p; M4[e] = mm[b]; V4[e] = vv[b];
+                }
+            }
+        }
+    }
+}
+// ... element by element (L % 4 != 0, or a span that is not 16-byte aligned), four elements' loads in flight at once
+__device__ __forceinline__ void adam_band_rows(const AdamFuse& adam, const float* frest, int row0, int rows, int L, int Lact,
+                                               const float* myRows, int lane, float lr)
+{
+    const size_t off0 = (size_t)(frest - adam.pBase) + (size_t)row0 * L;
+    float* P = const_cast<float*>(adam.pBase) + off0;
+    float* M = adam.mBase + off0;
+    float* V = adam.vBase + off0;
+    const int total = rows * Lact;
+    constexpr int B = 4;
+    for (int e0 = lane; e0 < total; e0 += 64 * B) {
+        float pp[B], mm[B], vv[B];
+#pragma unroll
+        for (int b = 0; b < B; b++) {
+            const int e = min(e0 + 64 * b, total - 1), r = e / Lact, o = r * L + (e - r * Lact);
+            pp[b] = P[o]; mm[b] = M[o]; vv[b] = V[o];
+        }
+#pragma unroll
+        for (int b = 0; b < B; b++) {
+            const int e = e0 + 64 * b;
+            if (e < total) {
+                const int r = e / Lact, c = e - r * Lact, o = r * L + c;
+                adam_step(adam, myRows[r * (L + 1) + c], lr, pp[b], mm[b], vv[b]);
+                P[o] = pp[b]; M[o] = mm[b]; V[o] = vv[b];
+            }
+        }
+    }
+}
+
 // A cotangent row that is not finite.  The blend backward gates a pixel's contribution to a splat branch-free (alpha and its
 // gradient times 0 past the pixel's nContrib or under the 0.99 clamp), which is exact while the splat's weight exp(-q/2) is finite.
 // A conic that is not positive definite -- float32 cancellation in the determinant of a needle tens of thousands of pixels long:
@@ -513,7 +624,11 @@ __device__ __forceinline__ float wave_sum_xor(float v)
 // its zero partials); in a mixed wave the invisible lanes store none of their 14 small elements and adam_rows / adam_rows_kept
 // skip their rows.  An invisible row's cotangent is all zero, so it adds nothing to gradNormAccum or to the pose sums either way.
 // FISHEYE (the equidistant camera model, gs_set_camera_model; never with POSE or F3D): project_geometry_bwd's FISHEYE.
-template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false, bool SPARSE = false, bool FISHEYE = false>
+// BANDS (an active degree below the one K allows, gs_set_sh_degree; MODE 2 only, never with POSE, MCMC, F3D or SPARSE): the f_rest
+// columns >= 3 ((degree + 1)^2 - 1) are not staged, not written in LDS and not updated (sh_band_load4 .. adam_band_rows above); at
+// degree 0 the kernel touches no f_rest byte and no LDS.  Everything else is the plain MODE 2 form's arithmetic in its order.
+template <int MODE, bool POSE, bool AA = false, bool MCMC = false, bool F3D = false, bool SPARSE = false, bool FISHEYE = false,
+          bool BANDS = false>
 __device__ __forceinline__ void proj_bwd_fused_body(
     int N, int K, int degree, const CamParams& cam, const float* xyz, const float* fdc,
     const float* frest, const float* scalesRaw, const float* rotRaw,
@@ -551,8 +666,20 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     // float4-addressable in all three arenas and fits the 18 registers (K <= 25)
     float4 keptRows[SH_ROWS_MAX4];
     const int total4 = (rows * L) >> 2;
-    const bool kept = ADAM && rows > 0 && L > 0 && (L & 3) == 0 && total4 <= 64 * SH_ROWS_MAX4 &&
-                      (((size_t)(frest - adam.pBase) + (size_t)row0 * L) & 3) == 0;
+    bool kept = ADAM && rows > 0 && L > 0 && (L & 3) == 0 && total4 <= 64 * SH_ROWS_MAX4 &&
+                (((size_t)(frest - adam.pBase) + (size_t)row0 * L) & 3) == 0;
+    // BANDS: the active columns alone; `kept` = the span takes 16-byte accesses and its active float4 fit the registers
+    const int Kact = (degree + 1) * (degree + 1), Lact = 3 * (Kact - 1), A4 = (Lact + 3) >> 2, totalA = rows * A4;
+    float4 bandRows[BANDS ? SH_BAND_MAX4 : 1];
+    if constexpr (BANDS) {
+        kept = kept && A4 <= SH_BAND_MAX4;
+        if (rows > 0 && Lact > 0) {
+            if (kept) {
+                sh_band_load4(frest + (size_t)row0 * L, totalA, L >> 2, A4, lane, bandRows);
+                sh_band_to_lds4(myRows, totalA, L, A4, lane, bandRows);
+            } else sh_band_in(myRows, frest + (size_t)row0 * L, rows, L, Lact, lane);
+        }
+    } else
     if (kept) {
         sh_rows_load4(frest + (size_t)row0 * L, total4, 0, lane, keptRows);
         sh_rows_to_lds4(myRows, total4, L, 0, lane, keptRows);
@@ -653,7 +780,7 @@ __device__ __forceinline__ void proj_bwd_fused_body(
                        [&](int, int, float) {}, d, gFdc ? gd0 : nullptr);
     else {
         float gdc[3] = {0.f, 0.f, 0.f};          // the DC gradient stays in registers for the fused Adam step
-        color_backward(degree, K, x, y, z, ccol,
+        color_backward(degree, BANDS ? Kact : K, x, y, z, ccol,
                        [&](int k, int ch) { return k == 0 ? d0[ch] : rest[(k - 1) * 3 + ch]; },
                        [&](int k, int ch, float v) {
                            if (k == 0) { if (ADAM) gdc[ch] = v; else gd0[ch] = v; }
@@ -740,6 +867,12 @@ __device__ __forceinline__ void proj_bwd_fused_body(
     }
     }
     if (MODE == 0 && rows > 0 && L > 0) sh_rows_out(myRows, gFrest + (size_t)row0 * L, rows, L, lane);
+    if constexpr (BANDS) {
+        if (!gateWord && rows > 0 && Lact > 0) {
+            if (kept) adam_band_rows_kept(adam, frest, row0, totalA, L, Lact, A4, myRows, lane, adam.lr[2], bandRows);
+            else adam_band_rows(adam, frest, row0, rows, L, Lact, myRows, lane, adam.lr[2]);
+        }
+    } else
     if (ADAM && !gateWord && rows > 0 && L > 0) {
         if (kept) adam_rows_kept<SPARSE>(adam, frest, row0, total4, L, myRows, lane, adam.lr[2], keptRows, visBits);
         else adam_rows<SPARSE>(adam, frest, row0, rows, L, myRows, lane, adam.lr[2], visBits);
@@ -756,10 +889,11 @@ __device__ __forceinline__ void proj_bwd_fused_body(
 }
 
 // The forms that exist: MODE 2 {plain, F3D, MCMC, SPARSE} x POSE x AA, MODE 0 {plain, F3D} x POSE x AA, MODE 1 plain x AA (26);
-// fisheye: MODE 2 {plain, MCMC, SPARSE} x AA, MODE 0 plain x AA (8)
-constexpr bool proj_bwd_form_exists(int MODE, bool POSE, bool MCMC, bool F3D, bool SPARSE, bool FISHEYE = false)
+// fisheye: MODE 2 {plain, MCMC, SPARSE} x AA, MODE 0 plain x AA (8); band-limited: MODE 2 plain x AA x {pinhole, fisheye} (4)
+constexpr bool proj_bwd_form_exists(int MODE, bool POSE, bool MCMC, bool F3D, bool SPARSE, bool FISHEYE = false, bool BANDS = false)
 {
     return (MODE == 0 || MODE == 1 || MODE == 2) &&
+           (!BANDS || (MODE == 2 && !POSE && !MCMC && !F3D && !SPARSE)) &&      // band-limited: the plain fused Adam form only
            (!FISHEYE || (!POSE && !F3D && MODE != 1)) &&    // the fisheye model: no pose refinement, no 3-D filter, no data-parallel form
            (!POSE || MODE != 1) &&                          // no pose refinement in the data-parallel form
            (!MCMC || MODE == 2) &&                          // the MCMC step is fused into the Adam form only
@@ -785,13 +919,13 @@ struct ProjBwdArgs {
     const CamParams* dcam;         // POSE: the camera pose_camera_kernel composed on the device
 };
 
-template <int MODE, bool POSE, bool AA, bool MCMC, bool F3D, bool SPARSE, bool FISHEYE = false>
+template <int MODE, bool POSE, bool AA, bool MCMC, bool F3D, bool SPARSE, bool FISHEYE = false, bool BANDS = false>
 __global__ __launch_bounds__(PROJ_FUSED_THREADS) void proj_bwd_fused_kernel(ProjBwdArgs a)
 {
-    static_assert(proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE, FISHEYE), "no such form of the fused projection backward");
+    static_assert(proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE, FISHEYE, BANDS), "no such form of the fused projection backward");
     CamParams posed;
     if constexpr (POSE) posed = *a.dcam;
-    proj_bwd_fused_body<MODE, POSE, AA, MCMC, F3D, SPARSE, FISHEYE>(a.N, a.K, a.degree, POSE ? posed : a.cam, a.xyz, a.fdc, a.frest, a.scalesRaw,
+    proj_bwd_fused_body<MODE, POSE, AA, MCMC, F3D, SPARSE, FISHEYE, BANDS>(a.N, a.K, a.degree, POSE ? posed : a.cam, a.xyz, a.fdc, a.frest, a.scalesRaw,
                                                            a.rotRaw, a.opacityRaw, a.gradAcc16, a.gXyz, a.gFdc, a.gFrest, a.gScales,
                                                            a.gRot, a.gOpacity, a.gradNormAccum, a.adam, a.posePartials, a.mc, a.filter3d,
                                                            a.visMask);
@@ -1261,7 +1395,7 @@ static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, con
     const bool mcmc = mode == 2 && !f3d && c->mcmcOn;
     const bool sparse = mode == 2 && !f3d && !mcmc && c->sparseAdam;      // (api.hip has checked that the forward left its mask)
     ProjBwdArgs a = {};
-    a.N = N; a.K = K; a.degree = c->degree;
+    a.N = N; a.K = K; a.degree = c->fwd.degree;      // (the degree this backward's forward ran with: gs_set_sh_degree)
     a.cam = c->fwd.cam; a.dcam = c->poseCam;
     a.xyz = c->fwd.xyz; a.fdc = c->fwd.fdc; a.frest = c->fwd.frest; a.scalesRaw = c->fwd.scales; a.rotRaw = c->fwd.rot;
     a.opacityRaw = c->fwd.opacity; a.gradAcc16 = c->gradAcc16;
@@ -1272,12 +1406,15 @@ static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, con
     if (mcmc) a.mc = mcmc_fuse(c->mcmc, N, adam.lr[0]);
     a.filter3d = c->fwd.filter3d;
     a.visMask = c->visMask;
-    const size_t lds = sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
+    // the band-limited form: a plain fused Adam step below the degree K allows (GS_TUNE_SH_BAND_SKIP 0: the full-row form, whose
+    // inactive columns meet exact zero gradients); at degree 0 it uses no LDS
+    const bool bands = mode == 2 && !pose && !mcmc && !f3d && !sparse && c->shBandSkip && (a.degree + 2) * (a.degree + 2) <= K;
+    const size_t lds = bands && a.degree == 0 ? 0 : sizeof(float) * (PROJ_FUSED_THREADS / 64) * 64 * ((K - 1) * 3 + 1);
     const int rc = with_flags(
-        [&](auto ADAM, auto EMIT_MG, auto POSE, auto AA, auto MCMC, auto F3D, auto SPARSE, auto FISHEYE) {
+        [&](auto ADAM, auto EMIT_MG, auto POSE, auto AA, auto MCMC, auto F3D, auto SPARSE, auto FISHEYE, auto BANDS) {
             constexpr int MODE = ADAM ? 2 : EMIT_MG ? 1 : 0;
-            if constexpr (!(ADAM && EMIT_MG) && proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE, FISHEYE)) {
-                hipLaunchKernelGGL((proj_bwd_fused_kernel<MODE, POSE, AA, MCMC, F3D, SPARSE, FISHEYE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
+            if constexpr (!(ADAM && EMIT_MG) && proj_bwd_form_exists(MODE, POSE, MCMC, F3D, SPARSE, FISHEYE, BANDS)) {
+                hipLaunchKernelGGL((proj_bwd_fused_kernel<MODE, POSE, AA, MCMC, F3D, SPARSE, FISHEYE, BANDS>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
                                    dim3(PROJ_FUSED_THREADS), lds, c->stream, a);
                 return GS_OK;
             } else {      // unreachable: f3d, mcmc and sparse are derived above to exclude one another and, like pose, mode 1;
@@ -1287,7 +1424,7 @@ static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, con
                 return GS_ERR_INVALID_ARG;
             }
         },
-        mode == 2, mode == 1, pose, c->fwd.antialias, mcmc, f3d, sparse, c->fwd.fisheye);
+        mode == 2, mode == 1, pose, c->fwd.antialias, mcmc, f3d, sparse, c->fwd.fisheye, bands);
     if (rc) return rc;
     GS_HIP_CHECK(c, hipGetLastError());
     return pose ? launch_pose_grad(c, N) : GS_OK;

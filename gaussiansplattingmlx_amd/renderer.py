@@ -110,6 +110,7 @@ class GaussianRenderer:
         self.targetStatsCacheBytes = 8 << 30      # cap of the per-view caches together (6 H W floats each); LRU beyond it
         self._antialiased = False
         self._camera_model = "pinhole"
+        self._sh_degree = self.active_sh_degree      # (the library's default: the maximum)
         self._absgrad = False
         self._sparse_adam = False
         self._background = None
@@ -165,10 +166,11 @@ class GaussianRenderer:
                    colour_riders=_lib.TUNE_COLOUR_RIDERS, fwd_queues=_lib.TUNE_FWD_QUEUES, fwd_four_waves=_lib.TUNE_FWD_FOUR_WAVES,
                    fwd_fold_test_scale=_lib.TUNE_FWD_FOLD_TEST_SCALE, poison_checkpoints=_lib.TUNE_POISON_CHECKPOINTS,
                    render_only=_lib.TUNE_RENDER_ONLY, fwd_pair=_lib.TUNE_FWD_PAIR, fwd_slow_slot=_lib.TUNE_FWD_SLOW_SLOT,
-                   trim_rects=_lib.TUNE_TRIM_RECTS)
+                   trim_rects=_lib.TUNE_TRIM_RECTS, sh_band_skip=_lib.TUNE_SH_BAND_SKIP)
     _TUNING_DEFAULTS = dict(fwd_waves_per_simd=4, bwd_waves_per_cu=16, fwd_quadrants=1, op_fwd_ppl=1, op_bwd_ppl=1,
                             fwd_trace_buffer=0, depth_gradient=1, wide_tile_sort=1, host_overflow_errors=1, splitter_depth_sort=1,
-                            colour_riders=1, fwd_queues=8, fwd_four_waves=-1, fwd_fold_test_scale=1000, poison_checkpoints=0, render_only=0, fwd_pair=-1, fwd_slow_slot=3, trim_rects=2)
+                            colour_riders=1, fwd_queues=8, fwd_four_waves=-1, fwd_fold_test_scale=1000, poison_checkpoints=0, render_only=0, fwd_pair=-1, fwd_slow_slot=3, trim_rects=2,
+                            sh_band_skip=1)
 
     def setTuning(self, **knobs):
         """Launch tuning of THIS renderer's context (gs_ctx_set_tuning); results never depend on it (fwd_four_waves: within
@@ -702,6 +704,28 @@ class GaussianRenderer:
             raise ValueError(f"setCameraModel: model is one of {sorted(CAMERA_MODELS)}")
         self._check(self.lib.gs_set_camera_model(self.ctx, CAMERA_MODELS[model]))
         self._camera_model = model
+
+    def setSHDegree(self, degree: int):
+        """gs_set_sh_degree: the active SH degree, 0 .. maxSHDegree, of the following forwards (include/gsplat.h, DESIGN.md section
+        30); the default is the maximum, the degree the renderer was built with.  K of the model stays the row stride: only the
+        bands k < (degree + 1)^2 are evaluated, and the gradient of every other coefficient is an exact zero.  Every fused
+        backward uses the degree of its forward.  active_sh_degree stays what the constructor got (callers size K from it)."""
+        if isinstance(degree, bool) or int(degree) != degree:
+            raise ValueError("setSHDegree: degree is an integer")
+        self._check(self.lib.gs_set_sh_degree(self.ctx, int(degree)))
+        self._sh_degree = int(degree)
+
+    @property
+    def shDegree(self) -> int:
+        return self._sh_degree
+
+    @shDegree.setter
+    def shDegree(self, degree: int):
+        self.setSHDegree(degree)
+
+    @property
+    def maxSHDegree(self) -> int:
+        return self.active_sh_degree
 
     @property
     def cameraModel(self) -> str:

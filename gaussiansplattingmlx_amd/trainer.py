@@ -477,7 +477,7 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None):
+                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None, sh_schedule=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -620,7 +620,28 @@ class GaussianTrainer:
         sums are what is accumulated and absgrad.threshold replaces grad_threshold (gsplat's DefaultStrategy(absgrad=True)).
         Composes with pose_opt, exposure_opt, bilateral_grid, background, depth, lossMask, an anti-aliased renderer and
         fuse_adam on or off; single-device steps with one view only, not with filter_3d, contrib_prune, sparse_adam or
-        referenceParamReload."""
+        referenceParamReload.
+
+        sh_schedule: a progressive SH degree (sh_schedule.SHDegreeSchedule, include/gsplat.h gs_set_sh_degree, DESIGN.md section
+        30; Inria's oneupSHdegree, gsplat's sh_degree_interval).  Before step t the trainer sets the renderer's active degree to
+        sh_schedule.degree_at(t), capped at the renderer's maximum, when it differs; the degree only ever rises during a run,
+        and lastSHDegree holds the running step's.  The model keeps its K: the bands above the active degree are not evaluated,
+        their gradients are exact zeros, and the plain fused step (fuse_adam with none of pose_opt, strategy='mcmc', filter_3d
+        and sparse_adam) leaves their bytes in the parameter and both moment arenas untouched and unread.  Every other form runs
+        its full-row update on those zeros, which moves nothing: a band that has never been active has zero moments, and every
+        event carries zeros as zeros.  evaluate, contribution scoring and the ADC and MCMC events render at the current degree;
+        snapshots are written whole, the inactive bands as the model holds them.  Composes with every single-device feature and
+        strategy through the form that feature already selects; single-device steps with one view only.  None (the default): no
+        call, kernel or result differs."""
+        self.sh_schedule = None
+        self.lastSHDegree = None
+        if sh_schedule is not None:
+            from .sh_schedule import SHDegreeSchedule
+            if not isinstance(sh_schedule, SHDegreeSchedule):
+                raise ValueError("sh_schedule must be an SHDegreeSchedule")
+            sh_schedule.validate()
+            _require_single_device("sh_schedule", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            self.sh_schedule = sh_schedule
         self.depth = None
         self._depthStep = None          # the running step's depth inputs (trainStep sets and clears it)
         if depth is not None:
@@ -1448,7 +1469,10 @@ class GaussianTrainer:
 
         restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
         filter_was, bg_was, pose_was = r.filter3D, getattr(r, "_background", None), getattr(r, "_pose", (None, None))
+        degree_was = r.shDegree if self.sh_schedule is not None else None
         try:
+            if self.sh_schedule is not None:
+                r.setSHDegree(self._scheduledSHDegree())      # (the degree the next step trains at)
             if self.filter_3d:
                 r.setFilter3D(self._filter)
             if bg is not None:
@@ -1465,6 +1489,8 @@ class GaussianTrainer:
             return EvalResult.from_sums(sums.cpu().numpy(), None if ccSums is None else ccSums.cpu().numpy())
         finally:
             r.setTuning(**restore)
+            if degree_was is not None:
+                r.setSHDegree(degree_was)
             if self.filter_3d:
                 r.setFilter3D(filter_was)
             if bg is not None:
@@ -1968,8 +1994,17 @@ class GaussianTrainer:
         r._cuts_renewed()
         r._check(r.lib.gs_dp_step(r.ctx, mode, C.byref(a)))
 
+    def _scheduledSHDegree(self):
+        """The active degree of the step about to run: the schedule's, never below a degree this run has already trained at."""
+        d = self.sh_schedule.degree_at(self.iteration, self.gaussRender.maxSHDegree)
+        return d if self.lastSHDegree is None else max(d, self.lastSHDegree)
+
     def _beginIteration(self):
         r, m = self.gaussRender, self.model
+        if self.sh_schedule is not None:
+            self.lastSHDegree = self._scheduledSHDegree()
+            if r.shDegree != self.lastSHDegree:
+                r.setSHDegree(self.lastSHDegree)
         if self.referenceParamReload and self._committed_params is None:
             self._committed_params = m.arena.clone()      # what the reference's model holds: the tensors before any step
         if self.densify:

@@ -373,6 +373,25 @@ int gs_set_antialiasing(gs_ctx* ctx, int enable);
 int gs_set_camera_model(gs_ctx* ctx, int model);
 int gs_get_camera_model(gs_ctx* ctx, int* model /*HOST*/);
 
+/* Active SH degree (not in the reference, whose degree is fixed; Inria's oneupSHdegree, gsplat's
+ * sh_degree_interval).  gs_ctx_create's sh_degree is the context's MAXIMUM and the default; the active degree d, 0 <= d <= maximum,
+ * is what the following gs_render_forward calls evaluate: the bands k < (d + 1)^2 of a row of K coefficients, K only the row
+ * stride.  A fused backward (gs_render_backward, gs_render_backward_adam, gs_render_backward_dp*) uses the degree its forward ran
+ * with; gs_projection_forward / gs_projection_backward and gs_sh_grad_from_views* use the value at the time of the call, and every
+ * "K smaller than (degree+1)^2" check is made against the active degree.  The gradient of a coefficient k >= (d + 1)^2 is an
+ * exact 0.0.  Any other value returns GS_ERR_INVALID_ARG with the reason in gs_last_error and leaves the setting as it was.
+ * A per-context setting as gs_set_antialiasing is: it allocates nothing and may be changed before every forward.  With the
+ * setter never called every launch, argument and result is what it was without it.
+ * gs_render_backward_adam below the degree K allows -- (d + 2)^2 <= K -- with no pose correction, MCMC step, 3-D filter or
+ * sparse Adam set takes a band-limited form: the elements of features_rest in the columns >= 3 ((d + 1)^2 - 1) of a row keep
+ * their bits in the parameter and both moment arenas, whatever they hold, and 16-byte words that hold no active column are
+ * neither read nor written (at degree 0 no features_rest byte moves).  Every other form runs its full-row update, in which an
+ * inactive element meets an exact zero gradient: zero moments stay zero and the parameter stays put (lr 0 / (sqrt(0) + eps) = 0),
+ * while moments that are NOT zero decay and keep moving their parameter -- after lowering the degree by hand those forms and the
+ * band-limited one differ on the inactive columns, and on nothing else. */
+int gs_set_sh_degree(gs_ctx* ctx, int degree);
+int gs_get_sh_degree(gs_ctx* ctx, int* degree /*HOST*/);
+
 /* Background colour (not in the reference, which composites over black or white; Inria's
  * --random_background, gsplat's backgrounds=).  With a colour b set, every following blend forward writes, per pixel and channel,
  *   out_c = sums_c + T b_c        (T the final transmittance; alpha, depth and nContrib do not change),
@@ -1243,6 +1262,10 @@ typedef enum gs_tuning {
                                      * corners: 14 % fewer pairs again on the bench scene); 1 keeps the box.  0: the reference's lists,
                                      * position for position (tests that hold M and nContrib to the oracle run with 0).  The op-level
                                      * gs_tile_bin is always the reference's */
+    GS_TUNE_SH_BAND_SKIP = 19,      /* 1 (default): gs_render_backward_adam below the degree K allows takes the band-limited form of the
+                                     * fused projection backward + Adam (gs_set_sh_degree).  0: the full-row form at every degree (A/B,
+                                     * tests): the same active columns to the noise of the blend backward's float atomics; inactive
+                                     * columns with zero moments the same bits */
     GS_TUNE_POISON_CHECKPOINTS = 14, /* TEST knob: 1 = the checkpoint arena is filled with NaN in front of every fused forward, so a
                                      * backward that reads a checkpoint lane its forward did not write shows up as NaN gradients */
     GS_TUNE_DEPTH_GRADIENT = 6      /* 1 (default): gs_render_backward* may get a cot_depth.  0: the caller promises NULL (the
