@@ -1,0 +1,1 @@
+from .features import FeatureField  # noqa: F401

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPLAT_LIB", os.path.join(HERE, "libgsplat_hip.so"))   # override: kernel experiments
 
 GS_OK = 0
+MAX_FEATURE_CHANNELS = 256      # GS_MAX_FEATURE_CHANNELS
 STATUS = {1: "GS_ERR_INVALID_ARG", 2: "GS_ERR_SIZE_MISMATCH", 3: "GS_ERR_WORKSPACE_OVERFLOW", 4: "GS_ERR_HIP",
           5: "GS_ERR_NO_FORWARD", 6: "GS_ERR_NO_DEVICE", 7: "GS_ERR_IO", 8: "GS_ERR_COMM", 9: "GS_ERR_REPLICA_MISMATCH"}
 GS_ERR_REPLICA_MISMATCH = 9
@@ -101,6 +102,11 @@ _SIGS = {
     "gs_blend_contrib": (C.c_int, [_vp, C.c_int] + [_vp] * 3),
     "gs_render_contrib": (C.c_int, [_vp, _vp, _vp]),
     "gs_contrib_actions": (C.c_int, [_vp, C.c_int, _vp, C.c_float, _vp, _vp]),
+    "gs_blend_features": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 3),
+    "gs_blend_features_backward": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 3),
+    "gs_render_features": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "gs_render_features_backward": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "gs_feature_channel_group": (C.c_int, []),
     "gs_ssim_window": (C.c_int, [C.c_int, C.c_float, _vp]),
     "gs_ssim_forward": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp] * 9),
     "gs_ssim_backward": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp] * 11),

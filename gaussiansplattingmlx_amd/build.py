@@ -31,6 +31,7 @@ SOURCES = {
     "bilateral_grid.hip": ["-ffp-contract=off"],
     "filter3d.hip": ["-ffp-contract=off"],
     "contrib.hip": ["-ffp-contract=off"],
+    "features.hip": ["-ffp-contract=off"],
     "background.hip": ["-ffp-contract=off"],
     "depth_loss.hip": ["-ffp-contract=off"],
     "lens.hip": ["-ffp-contract=off"],

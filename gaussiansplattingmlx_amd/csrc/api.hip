@@ -845,6 +845,39 @@ int gs_blend_contrib(gs_ctx* c, int N, const float* packed, float* max_w, float*
     return launch_blend_contrib(c, max_w, sum_w);
 }
 
+// the op-level feature pair's preconditions: gs_blend_contrib's, and a channel count in range
+static int blend_features_preflight(gs_ctx* c, const char* who, int N, int C, const float* packed, const void* in, const void* out)
+{
+    if (!c->binValid) return fail(c, GS_ERR_NO_FORWARD, std::string(who) + ": call gs_tile_bin first");
+    if (c->binIsBlockLists) return fail(c, GS_ERR_NO_FORWARD, std::string(who) + ": the last binning on this context was a fused forward's block lists (tile size not a multiple of 16); call gs_tile_bin");
+    if (N != c->binN) return fail(c, GS_ERR_SIZE_MISMATCH, std::string(who) + ": N differs from the binned N");
+    if (C < 1 || C > GS_MAX_FEATURE_CHANNELS) return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": C must be in [1, GS_MAX_FEATURE_CHANNELS]");
+    if (!in || !out || (N > 0 && !packed)) return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    return GS_OK;
+}
+
+int gs_blend_features(gs_ctx* c, int N, int C, const float* packed, const float* features, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (const int prc = blend_features_preflight(c, "gs_blend_features", N, C, packed, features, out)) return prc;
+    RealGeomScope real(c);
+    c->fwd.valid = false; c->fwd.bwdPrepared = false;      // as gs_blend_forward: the ctx's packed records are overwritten
+    if (const int rc = launch_pack11_to_12(c, N, packed)) return rc;
+    return launch_blend_features(c, C, features, out);
+}
+
+int gs_blend_features_backward(gs_ctx* c, int N, int C, const float* packed, const float* cot, float* grad_features)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (const int prc = blend_features_preflight(c, "gs_blend_features_backward", N, C, packed, cot, grad_features)) return prc;
+    RealGeomScope real(c);
+    c->fwd.valid = false; c->fwd.bwdPrepared = false;
+    if (const int rc = launch_pack11_to_12(c, N, packed)) return rc;
+    return launch_blend_features_backward(c, C, cot, grad_features);
+}
+
+int gs_feature_channel_group(void) { return feature_channel_group(); }
+
 // ---- SSIM -----------------------------------------------------------------------------------------
 int gs_ssim_window(int K, float sigma, float* window)
 {
@@ -1515,6 +1548,25 @@ int gs_render_contrib(gs_ctx* c, float* max_w, float* sum_w)
     if (!max_w && !sum_w) return fail(c, GS_ERR_INVALID_ARG, "gs_render_contrib: null buffer (one of max_w, sum_w at least)");
     // reads the forward's records and lists, writes nothing of the context's: a backward may still follow
     return launch_blend_contrib(c, max_w, sum_w);
+}
+
+// reads the forward's records and lists, writes nothing of the context's: a backward and further feature calls may follow
+int gs_render_features(gs_ctx* c, int C, const float* features, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    { const int prc = backward_preflight(c, "gs_render_features", false); if (prc) return prc; }
+    if (C < 1 || C > GS_MAX_FEATURE_CHANNELS) return fail(c, GS_ERR_INVALID_ARG, "gs_render_features: C must be in [1, GS_MAX_FEATURE_CHANNELS]");
+    if (!features || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_render_features: null buffer");
+    return launch_blend_features(c, C, features, out);
+}
+
+int gs_render_features_backward(gs_ctx* c, int C, const float* cot, float* grad_features)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    { const int prc = backward_preflight(c, "gs_render_features_backward", false); if (prc) return prc; }
+    if (C < 1 || C > GS_MAX_FEATURE_CHANNELS) return fail(c, GS_ERR_INVALID_ARG, "gs_render_features_backward: C must be in [1, GS_MAX_FEATURE_CHANNELS]");
+    if (!cot || !grad_features) return fail(c, GS_ERR_INVALID_ARG, "gs_render_features_backward: null buffer");
+    return launch_blend_features_backward(c, C, cot, grad_features);
 }
 
 int gs_contrib_actions(gs_ctx* c, int N, const float* score, float threshold, int* actions, int* output_counts)

@@ -22,23 +22,6 @@ namespace gs {
 constexpr int CB_NT = 256;       // threads per block = pixels per block = list entries per chunk
 constexpr int CB_BATCH = 4;      // entries per wave reduction
 
-// The three ways the 16x16 blocks are enumerated: the op-level kernels' (block_rect: the image grid, or per tile for tile sizes
-// that are not multiples of 16), and the fused path's block lists (gs_block_pixels: every block has a list of its own).
-struct ContribGeom {
-    BlockGeom g;
-    GsVirtGeom virt;             // virt.nbx != 0: block lists (g.blocksX = g.gridW = blocks per row, g.tileW = g.tileH = 16)
-};
-
-__device__ __forceinline__ BlockRect contrib_rect(const ContribGeom& cg, int blk)
-{
-    if (cg.virt.nbx == 0) return block_rect(cg.g, blk);
-    BlockRect r;
-    const int by = blk / cg.g.blocksX, bx = blk - by * cg.g.blocksX;
-    gs_block_pixels(cg.virt, bx, by, cg.g.W, cg.g.H, r.x0, r.y0, r.xEnd, r.yEnd);
-    r.tile = by * cg.g.gridW + bx;
-    return r;
-}
-
 // wave64 sums of s0..s3 and maxima of m0..m3 (all eight >= 0); lane 63 holds the totals afterwards
 #define GS_CB_STEP(CTRL)                         \
     "v_add_f32_dpp %0, %0, %0 " CTRL "\n\t"      \
@@ -144,12 +127,7 @@ __global__ void contrib_actions_kernel(int N, const float* __restrict__ score, f
 int launch_blend_contrib(gs_ctx* c, float* maxW, float* sumW)
 {
     ContribGeom cg;
-    cg.g.W = c->W; cg.g.H = c->H; cg.g.tileW = c->tileW; cg.g.tileH = c->tileH; cg.g.gridW = c->gridW;
-    cg.g.blocksX = c->virt.nbx ? c->blocksX : gs_div_up(c->W, TILE);
-    cg.g.bptX = c->fast16 ? 0 : gs_div_up(c->tileW, TILE);
-    cg.g.bptY = c->fast16 ? 0 : gs_div_up(c->tileH, TILE);
-    cg.virt = c->virt;
-    const int nBlocks = c->virt.nbx ? c->numPixBlocks : c->opBlocks;
+    const int nBlocks = contrib_geom(c, cg);
     if (nBlocks <= 0 || c->binN <= 0) return GS_OK;
     const uint32_t* idx = c->sortedPlainValid ? c->sortedIdx : c->sortedRaw;
     const uint32_t mask = c->sortedPlainValid ? 0xFFFFFFFFu : c->idxMask;

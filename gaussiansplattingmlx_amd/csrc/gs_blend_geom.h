@@ -1,7 +1,8 @@
-// gs_blend_geom.h -- what the op-level blend kernels (blend.hip) and the contribution pass (contrib.hip) share: the
-// enumeration of the 16x16 pixel blocks, the forward's exponential and the alpha of a Gaussian on a pixel
+// gs_blend_geom.h -- what the op-level blend kernels (blend.hip), the contribution pass (contrib.hip) and the feature pass
+// (features.hip) share: the enumeration of the 16x16 pixel blocks, the forward's exponential and the alpha of a Gaussian on a pixel
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gs_ctx.h"
 
 namespace gs {
 
@@ -35,6 +36,36 @@ __device__ __forceinline__ BlockRect block_rect(const BlockGeom& g, int blk)
         r.xEnd = min(g.W, (tx + 1) * g.tileW); r.yEnd = min(g.H, (ty + 1) * g.tileH);
     }
     return r;
+}
+
+// The three ways the passes over the lists of the last binning (contrib.hip, features.hip) enumerate the 16x16 blocks: the
+// op-level kernels' (block_rect: the image grid, or per tile for tile sizes that are not multiples of 16), and the fused path's
+// block lists (gs_block_pixels: every block has a list of its own).
+struct ContribGeom {
+    BlockGeom g;
+    GsVirtGeom virt;             // virt.nbx != 0: block lists (g.blocksX = g.gridW = blocks per row, g.tileW = g.tileH = 16)
+};
+
+__device__ __forceinline__ BlockRect contrib_rect(const ContribGeom& cg, int blk)
+{
+    if (cg.virt.nbx == 0) return block_rect(cg.g, blk);
+    BlockRect r;
+    const int by = blk / cg.g.blocksX, bx = blk - by * cg.g.blocksX;
+    gs_block_pixels(cg.virt, bx, by, cg.g.W, cg.g.H, r.x0, r.y0, r.xEnd, r.yEnd);
+    r.tile = by * cg.g.gridW + bx;
+    return r;
+}
+
+// ... in the geometry the context describes at the time of the call (the caller's tile grid for the op-level form; the fused
+// path's own -- block lists included -- behind a fused forward); the number of blocks (0: nothing to sweep)
+inline int contrib_geom(const gs_ctx* c, ContribGeom& cg)
+{
+    cg.g.W = c->W; cg.g.H = c->H; cg.g.tileW = c->tileW; cg.g.tileH = c->tileH; cg.g.gridW = c->gridW;
+    cg.g.blocksX = c->virt.nbx ? c->blocksX : gs_div_up(c->W, TILE);
+    cg.g.bptX = c->fast16 ? 0 : gs_div_up(c->tileW, TILE);
+    cg.g.bptY = c->fast16 ? 0 : gs_div_up(c->tileH, TILE);
+    cg.virt = c->virt;
+    return c->virt.nbx ? c->numPixBlocks : c->opBlocks;
 }
 
 // exp(x), x <= 0, for the FORWARD kernels: v_exp_f32 on the rounded product x log2(e) is off by |x log2 e| 2^-24 relative

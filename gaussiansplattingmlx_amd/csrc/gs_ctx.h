@@ -535,6 +535,12 @@ int launch_gradacc_to_packed11(gs_ctx* c, int N, float* gradPacked11);
 int launch_blend_contrib(gs_ctx* c, float* maxW, float* sumW);
 int launch_contrib_actions(gs_ctx* c, int N, const float* score, float threshold, int* actions, int* outputCounts);
 
+// features.hip: C-channel feature images over the lists of the last binning (out [H, W, C] fully written) and their gradient
+// with respect to the features (grad [N, C] accumulates); the channels a sweep of the list carries
+int launch_blend_features(gs_ctx* c, int C, const float* features, float* out);
+int launch_blend_features_backward(gs_ctx* c, int C, const float* cot, float* grad);
+int feature_channel_group();
+
 // blend_v2.hip (fused fast path)
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha);
 int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const float* cotDepth, const float* cotAlpha,

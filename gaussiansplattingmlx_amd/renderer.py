@@ -354,6 +354,73 @@ class GaussianRenderer:
         self._check(self.lib.gs_contrib_actions(self.ctx, N, _p(score), C.c_float(threshold), _p(actions), _p(counts)))
         return actions, counts
 
+    # -- N-channel feature rendering (include/gsplat.h gs_blend_features) ---------------------
+    def _feature_arg(self, who, name, t, rows, C):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.numel() == rows * C):
+            raise ValueError(f"{who}: {name} must be a contiguous float32 device tensor of {rows} x {C} elements")
+
+    def _feature_channels(self, who, t, rows):
+        """C of a [rows, C] (or [H, W, C]) tensor: its last dimension."""
+        if not isinstance(t, torch.Tensor) or t.dim() < 2 or rows <= 0 or t.numel() % rows:
+            raise ValueError(f"{who}: a float32 device tensor with the channels as its last dimension")
+        C_ = int(t.shape[-1])
+        if not 1 <= C_ <= _lib.MAX_FEATURE_CHANNELS:
+            raise ValueError(f"{who}: 1 <= C <= {_lib.MAX_FEATURE_CHANNELS}, got {C_}")
+        return C_
+
+    def _features_forward(self, who, N, features, out, call):
+        C_ = self._feature_channels(who, features, N)
+        self._feature_arg(who, "features", features, N, C_)
+        if out is None:
+            out = self._empty(self.H, self.W, C_)
+        self._feature_arg(who, "out", out, self.H * self.W, C_)
+        self._check(call(C_, _p(features), _p(out)))
+        return out
+
+    def _features_backward(self, who, N, cot, grad, call):
+        C_ = self._feature_channels(who, cot, self.H * self.W)
+        self._feature_arg(who, "cot", cot, self.H * self.W, C_)
+        if grad is None:
+            grad = torch.zeros((N, C_), dtype=torch.float32, device=self.device)
+        self._feature_arg(who, "grad", grad, N, C_)
+        self._check(call(C_, _p(cot), _p(grad)))
+        return grad
+
+    def blendFeatures(self, packedGaussians, features, out=None):
+        """The feature image [H, W, C] of the view whose lists the last buildGlobalTileSliceInfo built: out[p] = sum over the
+        entries of p's list of w(p, g) features[g] with blendContrib's weights.  features: float32 device tensor [N, C],
+        1 <= C <= 256.  Every pixel of out is written (out=None allocates); the same bits on every run."""
+        packed = self._t(packedGaussians)
+        N = int(packed.shape[0])
+        return self._features_forward("blendFeatures", N, features, out,
+                                      lambda C_, f, o: self.lib.gs_blend_features(self.ctx, N, C_, _p(packed), f, o))
+
+    def blendFeaturesVJP(self, packedGaussians, cot, grad=None):
+        """The gradient of blendFeatures with respect to the features for the cotangent image cot [H, W, C]:
+        grad[g] += sum over the pixels of w(p, g) cot[p].  ACCUMULATES into grad [N, C] (grad=None: zeros are allocated)."""
+        packed = self._t(packedGaussians)
+        N = int(packed.shape[0])
+        return self._features_backward("blendFeaturesVJP", N, cot, grad,
+                                       lambda C_, ct, g: self.lib.gs_blend_features_backward(self.ctx, N, C_, _p(packed), ct, g))
+
+    def renderFeatures(self, features, out=None):
+        """blendFeatures for the view of the last renderForward / renderChecked, on that forward's own records and lists (its
+        anti-aliased opacity, 3-D filter and pose correction included).  Consumes nothing: a renderBackward may follow."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "renderFeatures: no renderForward on this renderer")
+        N = int(self._fused["params"]["xyz"].shape[0])
+        return self._features_forward("renderFeatures", N, features, out,
+                                      lambda C_, f, o: self.lib.gs_render_features(self.ctx, C_, f, o))
+
+    def renderFeaturesVJP(self, cot, grad=None):
+        """blendFeaturesVJP for the view of the last renderForward / renderChecked.  ACCUMULATES into grad [N, C]."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "renderFeaturesVJP: no renderForward on this renderer")
+        N = int(self._fused["params"]["xyz"].shape[0])
+        return self._features_backward("renderFeaturesVJP", N, cot, grad,
+                                       lambda C_, ct, g: self.lib.gs_render_features_backward(self.ctx, C_, ct, g))
+
     # -- render / forward (GaussianRenderer.swift:736-934) ---------------------------------------------------
     def render(self, imageWidth, imageHeight, means2d, cov2d, color, opacity, depths, radii, conic, rect,
                inputIsDepthSorted: bool = False):

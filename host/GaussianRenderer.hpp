@@ -148,6 +148,11 @@ public:
     // classifyGaussians: action 3 / count 0 where score < threshold, else 0 / 1.
     void blendContrib(int N, const float* packed, float* maxW, float* sumW) { check(gs_blend_contrib(ctx_, N, packed, maxW, sumW)); }
     void renderContrib(float* maxW, float* sumW) { check(gs_render_contrib(ctx_, maxW, sumW)); }
+    // N-channel feature rendering (include/gsplat.h gs_blend_features): out[H,W,C] is fully written, gradFeatures[N,C] accumulates
+    void blendFeatures(int N, int C, const float* packed, const float* features, float* out) { check(gs_blend_features(ctx_, N, C, packed, features, out)); }
+    void blendFeaturesVJP(int N, int C, const float* packed, const float* cot, float* gradFeatures) { check(gs_blend_features_backward(ctx_, N, C, packed, cot, gradFeatures)); }
+    void renderFeatures(int C, const float* features, float* out) { check(gs_render_features(ctx_, C, features, out)); }
+    void renderFeaturesVJP(int C, const float* cot, float* gradFeatures) { check(gs_render_features_backward(ctx_, C, cot, gradFeatures)); }
     void contribActions(int N, const float* score, float threshold, int* actions, int* outputCounts)
     {
         check(gs_contrib_actions(ctx_, N, score, threshold, actions, outputCounts));

@@ -202,6 +202,27 @@ int gs_blend_backward(gs_ctx* ctx, int N, const float* packed, const float* cot_
 int gs_blend_contrib(gs_ctx* ctx, int N, const float* packed /*[N,11]*/, float* max_w /*DEVICE [N] or NULL*/,
                      float* sum_w /*DEVICE [N] or NULL*/);
 
+/* N-channel per-Gaussian feature rendering (not in the reference): any per-Gaussian vector f[g, 0..C)
+ * -- semantic or language features, identities, normals, albedo -- blended over the same splats with gs_blend_contrib's
+ * weights w(p, g) = T alpha (its rule to the bit: clamp at 0.99, a pixel stops after the entry that brings T below 1e-4, no
+ * background term, the background setting is not seen):
+ *   forward    out[p, c]            = sum over the entries g of p's list of  w(p, g) features[g, c]
+ *   backward   grad_features[g, c] += sum over the pixels p of               w(p, g) cot[p, c]
+ * The geometry is frozen: there is no gradient into opacity, conic or mean.  One pass over the tile lists of the last
+ * gs_tile_bin / gs_tile_bin_cut per group of gs_feature_channel_group() channels.  out DEVICE [H, W, C] is written at every
+ * pixel (zeros where nothing blends; the caller does not clear) without atomics: the same bits on every run.  grad_features
+ * DEVICE [N, C] ACCUMULATES with float atomics (zero it once, call once per view); rows of Gaussians in no list or behind every
+ * pixel's stop are not touched.  cot must be finite.  1 <= C <= GS_MAX_FEATURE_CHANNELS, any C (rows need no alignment), else
+ * GS_ERR_INVALID_ARG, as for a NULL buffer.  Preconditions and codes otherwise as gs_blend_contrib; every tile size gs_ctx_create
+ * accepts is supported.  No sync, no allocation. */
+#define GS_MAX_FEATURE_CHANNELS 256
+int gs_blend_features(gs_ctx* ctx, int N, int C, const float* packed /*[N,11]*/, const float* features /*DEVICE [N,C]*/,
+                      float* out /*DEVICE [H,W,C]*/);
+int gs_blend_features_backward(gs_ctx* ctx, int N, int C, const float* packed /*[N,11]*/, const float* cot /*DEVICE [H,W,C]*/,
+                               float* grad_features /*DEVICE [N,C], accumulates*/);
+/* The number of channels one sweep of the lists carries (a build constant): C channels cost ceil(C / it) sweeps. */
+int gs_feature_channel_group(void);
+
 /* ---- a10: SSIM -------------------------------------------------------------------------------------- */
 
 /* gaussian(windowSize:sigma:) outer product (LossUtil.swift:47-54, GaussianTrainer.swift:308-314);
@@ -262,6 +283,16 @@ int gs_render_backward_adam(gs_ctx* ctx, const float* cot_color, const float* co
  * overflow.  After a forward under depth cuts ask gs_forward_missed first, as for any other use of its outputs.  Consumes
  * nothing: a backward may still follow, the render outputs and gs_last_stats are untouched.  No sync, no allocation. */
 int gs_render_contrib(gs_ctx* ctx, float* max_w /*DEVICE [N] or NULL*/, float* sum_w /*DEVICE [N] or NULL*/);
+
+/* gs_blend_features / gs_blend_features_backward for the last gs_render_forward's view, on that forward's own records and
+ * lists (its anti-aliased opacity, 3-D filter and pose correction included; trimmed rects and depth cuts as for
+ * gs_render_contrib).  features / grad_features are DEVICE [N of the forward, C], out / cot DEVICE [H, W, C].  Refuse what
+ * gs_render_contrib refuses, with the same codes; C outside [1, GS_MAX_FEATURE_CHANNELS] or a NULL buffer: GS_ERR_INVALID_ARG.
+ * Consume nothing: a backward and further feature calls on the same forward may follow, the render outputs and gs_last_stats
+ * are untouched.  No sync, no allocation. */
+int gs_render_features(gs_ctx* ctx, int C, const float* features /*DEVICE [N,C]*/, float* out /*DEVICE [H,W,C]*/);
+int gs_render_features_backward(gs_ctx* ctx, int C, const float* cot /*DEVICE [H,W,C]*/,
+                                float* grad_features /*DEVICE [N,C], accumulates*/);
 
 /* Per-view camera pose refinement (not in the reference; DESIGN.md "Pose refinement").  delta DEVICE [6] = (w, tau), float32,
  * a correction of the camera-to-world pose in the camera's own OpenCV frame (x right, y down, z forward):
