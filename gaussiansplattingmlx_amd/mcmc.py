@@ -72,7 +72,12 @@ def grown_count(N: int, cap_max: int, grow_rate: float) -> int:
 def relocation_formula(o, n, min_opacity: float = 0.005, n_max: int = 51):
     """The relocation's opacity and scale factor in float64 for sources of opacity o drawn n - 1 times (n clamped to n_max):
     o' = clamp(1 - (1 - o)^(1/n), min_opacity, 1 - 2^-23), and s'/s = o / sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k
-    o'^(k+1) / sqrt(k+1).  What csrc/mcmc.hip mcmc_formula_kernel computes, in the same order."""
+    o'^(k+1) / sqrt(k+1).  What csrc/mcmc.hip mcmc_formula_kernel computes, in the same order.
+
+    Accuracy: against the same expression at 60 decimal digits (tests/test_mcmc_cpu.py) both results are within 2.5e-10
+    relative for raw opacities in [-5.2, 30] and n up to 51 (the alternating sum's cancellation; 1e-9 up to raw 36.5).
+    Float64 loses it from raw >= 37 on, where o = sigmoid(raw) rounds to 1.0 and o' sits at its upper clamp: the sum's terms
+    then reach C(50, 25), and s'/s is off by 1.8e-7 at n = 35 and 1.3e-3 at n = 51."""
     o = np.asarray(o, np.float64)
     n = np.minimum(np.broadcast_to(np.asarray(n, np.int64), o.shape), int(n_max))
     on = np.clip(1.0 - np.power(1.0 - o, 1.0 / n), float(min_opacity), 1.0 - 2.0 ** -23)

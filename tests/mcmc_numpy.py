@@ -1,5 +1,6 @@
-"""A numpy restatement of the MCMC strategy's generator, per-step terms and event draws (include/gsplat.h gs_set_mcmc,
-gs_mcmc_random, gs_mcmc_relocate, gs_mcmc_grow), for tests/test_mcmc_cpu.py and tests/test_gpu_mcmc.py."""
+"""A numpy restatement of the MCMC strategy's generator, per-step terms, event draws and whole events (include/gsplat.h
+gs_set_mcmc, gs_mcmc_random, gs_mcmc_relocate, gs_mcmc_grow), for tests/test_mcmc_cpu.py, tests/test_gpu_mcmc.py and
+tests/test_gpu_mcmc_events.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -88,3 +89,72 @@ def draw(opacity_raw, mode: int, min_opacity: float, n: int, seed: int, t: int):
     target = u * cdf[-1]
     k = np.minimum(np.searchsorted(cdf, target, side="right"), len(rows) - 1)
     return rows[k], target, cdf, rows, dead
+
+
+def min_boundary_gap(cdf, target) -> float:
+    """The smallest |cdf[q] - target[j]| / cdf[-1] over all draws j and prefix entries q.  The device builds its prefix in
+    another summation order (a Hillis-Steele scan per block plus a serial carry), so its entries differ from numpy's cumsum by
+    up to about N 2^-53 of the total: a draw whose target is farther than that from every entry has one possible source."""
+    cdf, target = np.asarray(cdf, np.float64), np.asarray(target, np.float64).reshape(-1)
+    if cdf.size == 0 or target.size == 0:
+        return np.inf
+    k = np.searchsorted(cdf, target)
+    lo, hi = cdf[np.clip(k - 1, 0, cdf.size - 1)], cdf[np.clip(k, 0, cdf.size - 1)]
+    return float(np.minimum(np.abs(target - lo), np.abs(hi - target)).min() / cdf[-1])
+
+
+KEYS = ("xyz", "features_dc", "features_rest", "scales", "rotation", "opacity")
+
+
+def event(p, m, v, mode: int, cfg, t: int, seed: int, n_add=None):
+    """A whole event (include/gsplat.h gs_mcmc_relocate: mode 0, gs_mcmc_grow: mode 1) restated in float64 over the N rows of
+    the six float32 tensors p and their moments m, v (dicts keyed like KEYS), with cfg's min_opacity, n_max, cap_max and
+    grow_rate.  The destinations are the dead rows in index order (relocation) or the rows N + j (growth; n_add rows, by
+    default grown_count(N, cap_max, grow_rate) - N).  A source drawn c times gets the formula's opacity and scale for n =
+    min(c + 1, n_max), each rounded to float32 once; a destination is a copy of its source's modified row; the moments of
+    sources and destinations are zero; every other float is the input's, bit for bit.
+
+    Returns dict(p, m, v: the state after the event (N + n_add rows after a growth), N: its count, stats: dead / relocated /
+    live / N as gs_mcmc_relocate reports them (relocation), sources: [draws] the source of every draw, dests: [draws] its
+    destination, counts: [N] draws per row, cdf / target: the draws' prefix and targets (for min_boundary_gap))."""
+    from gaussiansplattingmlx_amd.mcmc import grown_count, relocation_formula
+    p = {k: np.array(p[k], np.float32, copy=True) for k in KEYS}
+    m = {k: np.array(m[k], np.float32, copy=True) for k in KEYS}
+    v = {k: np.array(v[k], np.float32, copy=True) for k in KEYS}
+    N = p["opacity"].shape[0]
+    raw = p["opacity"].reshape(N)
+    o = sigmoid(raw.astype(np.float64))
+    fin = np.isfinite(raw)
+    cand = fin & ((o > cfg.min_opacity) if mode == 0 else (o > 0))
+    n_dead, n_cand = (int((~cand).sum()) if mode == 0 else 0), int(cand.sum())
+    if mode == 0:
+        n_draw = n_dead
+    else:
+        n_draw = grown_count(N, cfg.cap_max, cfg.grow_rate) - N if n_add is None else int(n_add)
+    out = dict(p=p, m=m, v=v, N=N, stats=dict(dead=n_dead, relocated=0, live=n_cand, N=N) if mode == 0 else None,
+               sources=np.zeros(0, np.int64), dests=np.zeros(0, np.int64), counts=np.zeros(N, np.int64),
+               cdf=np.zeros(0), target=np.zeros(0))
+    if N == 0 or n_draw <= 0 or n_cand == 0:
+        return out
+    src, target, cdf, _, dead = draw(raw, mode, cfg.min_opacity, n_draw, seed, t)
+    dst = dead if mode == 0 else N + np.arange(n_draw)
+    cnt = np.bincount(src, minlength=N)
+    s_rows = np.nonzero(cnt)[0]
+    on, ratio = relocation_formula(o[s_rows], cnt[s_rows] + 1, cfg.min_opacity, cfg.n_max)
+    p["opacity"].reshape(N)[s_rows] = np.log(on / (1.0 - on)).astype(np.float32)
+    p["scales"][s_rows] = np.log(np.exp(p["scales"][s_rows].astype(np.float64)) * ratio[:, None]).astype(np.float32)
+    for k in KEYS:
+        m[k][s_rows] = 0
+        v[k][s_rows] = 0
+    if mode == 1:
+        grow = lambda a, fill: np.concatenate([a, fill((n_draw,) + a.shape[1:], np.float32)])       # noqa: E731
+        for k in KEYS:
+            p[k], m[k], v[k] = grow(p[k], np.empty), grow(m[k], np.zeros), grow(v[k], np.zeros)
+    for k in KEYS:
+        p[k][dst] = p[k][src]
+        m[k][dst] = 0
+        v[k][dst] = 0
+    out.update(N=N + (n_draw if mode == 1 else 0), sources=src, dests=np.asarray(dst, np.int64), counts=cnt, cdf=cdf, target=target)
+    if mode == 0:
+        out["stats"]["relocated"] = n_draw
+    return out

@@ -1,5 +1,6 @@
 """The MCMC strategy without a device: the float64 relocation formula, MCMCConfig's validation, the trainer's refusals and the
 generator's restatement (tests/mcmc_numpy.py)."""
+import decimal
 import importlib.util
 import math
 import os
@@ -54,6 +55,147 @@ def test_n_is_clamped_at_n_max():
 def test_clamp_bounds():
     on, _ = relocation_formula(np.array([1e-6, 1.0 - 1e-12]), 1, min_opacity=0.005)
     assert on[0] == 0.005 and on[1] == 1.0 - 2.0 ** -23
+
+
+def _formula_decimal(o: float, n: int, min_opacity: float, digits: int = 60):
+    """relocation_formula's expression for one float64 o at `digits` decimal digits: the n-th root through ln / exp."""
+    D = decimal.Decimal
+    with decimal.localcontext() as ctx:
+        ctx.prec = digits
+        o = D(o)                                                    # (a float converts exactly)
+        on = 1 - ((1 - o).ln() / n).exp()
+        on = min(max(on, D(min_opacity)), 1 - D(2) ** -23)
+        den = D(0)
+        for a in range(1, n + 1):
+            pw = on
+            for k in range(a):
+                term = math.comb(a - 1, k) * pw / D(k + 1).sqrt()
+                den += -term if k & 1 else term
+                pw *= on
+        return on, o / den
+
+
+RAW = np.concatenate([np.linspace(-5.2, 30.0, 45), [-5.0, -1.0, 0.0, 1.0, 8.0, 17.3, 29.9]]).astype(np.float32)
+
+
+@pytest.mark.parametrize("n", [2, 3, 5, 10, 20, 35, 51])
+def test_formula_against_60_digit_decimal(n):
+    """The float64 formula against the same expression at 60 digits, raw opacities in [-5.2, 30] (the lower
+    clamp of o' included): 1e-9 relative on both results, about five times what float64 reaches here (2.4e-10, n = 51).
+    The range ends below raw = 37, where sigmoid(raw) rounds to 1.0 in float64 (relocation_formula's docstring)."""
+    o = mn.sigmoid(RAW)
+    assert RAW.min() == np.float32(-5.2) and RAW.max() == 30.0 and (o < 1.0).all()
+    on, ratio = relocation_formula(o, n, 0.005, 51)
+    worst = 0.0
+    for i in range(o.size):
+        won, wr = _formula_decimal(float(o[i]), n, 0.005)
+        for got, want in ((on[i], won), (ratio[i], wr)):
+            worst = max(worst, float(abs(decimal.Decimal(float(got)) - want) / abs(want)))
+    print(f"n={n}: worst relative error {worst:.3e}")
+    assert worst <= 1e-9, worst
+
+
+def _three_rows(raw, K=2):
+    """Three hand-made rows of distinct floats (row i's values start at 100 i), their moments nonzero everywhere."""
+    N = len(raw)
+    shapes = dict(xyz=(3,), features_dc=(1, 3), features_rest=(K - 1, 3), scales=(3,), rotation=(4,), opacity=())
+    p, off = {}, 1.0
+    for k in mn.KEYS:
+        per = int(np.prod(shapes[k])) if shapes[k] else 1
+        p[k] = (off + 100.0 * np.arange(N)[:, None] + np.arange(per)[None, :]).reshape((N,) + shapes[k]).astype(np.float32)
+        off += per
+    p["scales"] = (p["scales"] * np.float32(1e-2) - 3).astype(np.float32)
+    p["opacity"] = np.asarray(raw, np.float32)
+    m = {k: (np.zeros_like(p[k]) + 0.25 + np.arange(N).reshape((N,) + (1,) * (p[k].ndim - 1))).astype(np.float32) for k in mn.KEYS}
+    v = {k: (m[k] + 7).astype(np.float32) for k in mn.KEYS}
+    return p, m, v
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def test_event_three_rows_one_dead():
+    """Rows 0 and 1 live (o = 0.5, 0.731), row 2 dead: one draw u, the source is row 0 iff u (o0 + o1) < o0; n = 2, whose
+    formula has the closed form o' = 1 - sqrt(1 - o), s'/s = o / (2 o' - o'^2 / sqrt 2)."""
+    cfg, t, seed = MCMCConfig(), 600, 12345
+    p, m, v = _three_rows([0.0, 1.0, -10.0])
+    e = mn.event(p, m, v, 0, cfg, t, seed)
+    o = mn.sigmoid(p["opacity"])
+    u = mn.uniforms(mn.philox([0], t, 1, seed))[0]
+    s = 0 if u * (o[0] + o[1]) < o[0] else 1
+    other = 1 - s
+    assert e["stats"] == dict(dead=1, relocated=1, live=2, N=3) and e["N"] == 3
+    assert e["sources"].tolist() == [s] and e["dests"].tolist() == [2] and e["counts"].tolist() == [1 - s, s, 0]
+    on = 1 - math.sqrt(1 - o[s])
+    ratio = o[s] / (2 * on - on * on / math.sqrt(2))
+    np.testing.assert_allclose(e["p"]["opacity"][s], math.log(on / (1 - on)), rtol=2e-7)
+    np.testing.assert_allclose(e["p"]["scales"][s], p["scales"][s].astype(np.float64) + math.log(ratio), rtol=2e-7)
+    for k in mn.KEYS:
+        assert e["p"][k].dtype == np.float32 and e["p"][k].shape == p[k].shape
+        assert np.array_equal(_bits(e["p"][k][2]), _bits(e["p"][k][s])), k                # the destination: the modified source
+        if k not in ("opacity", "scales"):
+            assert np.array_equal(_bits(e["p"][k][s]), _bits(p[k][s])), k                 # the source keeps everything else
+        assert np.array_equal(_bits(e["p"][k][other]), _bits(p[k][other])), k             # the row not drawn: untouched
+        for got, was in ((e["m"][k], m[k]), (e["v"][k], v[k])):
+            assert (got[[s, 2]] == 0).all() and np.array_equal(_bits(got[other]), _bits(was[other])), k
+    assert p["opacity"][2] == np.float32(-10.0) and (m["xyz"] != 0).all()                # the inputs are left alone
+
+
+@pytest.mark.parametrize("raw", [[-10.0, -9.0, -8.0], [np.nan, np.inf, -np.inf]])
+def test_event_every_row_dead(raw):
+    cfg = MCMCConfig(cap_max=100, grow_rate=1.0)
+    p, m, v = _three_rows(raw)
+    p["xyz"][1, 0] = np.array([0x7FC12345], np.uint32).view(np.float32)[0]               # a NaN payload survives
+    e = mn.event(p, m, v, 0, cfg, 600, 7)
+    assert e["stats"] == dict(dead=3, relocated=0, live=0, N=3) and e["sources"].size == 0
+    g = mn.event(p, m, v, 1, cfg, 600, 7)              # growth: finite rows keep their weight, non-finite ones have none
+    assert g["N"] == (6 if np.isfinite(raw).all() else 3)
+    for out in (e, g) if g["N"] == 3 else (e,):
+        for k in mn.KEYS:
+            for got, was in ((out["p"][k], p[k]), (out["m"][k], m[k]), (out["v"][k], v[k])):
+                assert np.array_equal(_bits(got), _bits(was)), k
+
+
+def test_event_no_row_dead():
+    cfg = MCMCConfig(cap_max=100)
+    p, m, v = _three_rows([0.0, 1.0, 2.0])
+    e = mn.event(p, m, v, 0, cfg, 600, 7)
+    assert e["stats"] == dict(dead=0, relocated=0, live=3, N=3)
+    for k in mn.KEYS:
+        for got, was in ((e["p"][k], p[k]), (e["m"][k], m[k]), (e["v"][k], v[k])):
+            assert np.array_equal(_bits(got), _bits(was)), k
+    assert mn.event(p, m, v, 1, cfg, 700, 7)["N"] == 3                 # floor(1.05 * 3) = 3: nothing to add
+    # growth by two rows: rows 3 and 4 are copies of their modified sources, n = draws + 1 on every source
+    g = mn.event(p, m, v, 1, cfg, 700, 7, n_add=2)
+    o = mn.sigmoid(p["opacity"])
+    u = mn.uniforms(mn.philox([0, 1], 700, 2, 7))
+    src = np.searchsorted(np.cumsum(o), u * o.sum(), side="right")
+    assert g["N"] == 5 and g["stats"] is None and g["sources"].tolist() == src.tolist() and g["dests"].tolist() == [3, 4]
+    cnt = np.bincount(src, minlength=3)
+    on, ratio = relocation_formula(o, cnt + 1, cfg.min_opacity, cfg.n_max)
+    for i in range(3):
+        if cnt[i]:
+            np.testing.assert_allclose(mn.sigmoid(g["p"]["opacity"][i]), on[i], rtol=1e-6)
+            np.testing.assert_allclose(np.exp(g["p"]["scales"][i].astype(np.float64)),
+                                       np.exp(p["scales"][i].astype(np.float64)) * ratio[i], rtol=1e-6)
+        else:
+            assert g["p"]["opacity"][i] == p["opacity"][i] and np.array_equal(g["p"]["scales"][i], p["scales"][i])
+    for k in mn.KEYS:
+        assert g["p"][k].shape == (5,) + p[k].shape[1:]
+        for j in range(2):
+            assert np.array_equal(_bits(g["p"][k][3 + j]), _bits(g["p"][k][src[j]])), k
+        for got, was in ((g["m"][k], m[k]), (g["v"][k], v[k])):
+            assert (got[3:] == 0).all() and (got[:3][cnt > 0] == 0).all()
+            assert np.array_equal(_bits(got[:3][cnt == 0]), _bits(was[cnt == 0])), k
+
+
+def test_min_boundary_gap():
+    cdf = np.array([1.0, 3.0, 4.0])
+    assert mn.min_boundary_gap(cdf, [0.5, 2.0]) == 0.125           # 0.5 from the entry 1.0, of a total of 4
+    assert mn.min_boundary_gap(cdf, [3.0 + 4e-9]) == pytest.approx(1e-9, rel=1e-6)
+    assert mn.min_boundary_gap(cdf, [3.9]) == pytest.approx(0.025)
+    assert mn.min_boundary_gap(cdf, []) == np.inf
 
 
 def test_grown_count():
