@@ -626,6 +626,11 @@ class GaussianRenderer:
         self._check(self.lib.gs_set_pose_correction(self.ctx, None if delta is None else _p(delta), None if grad is None else _p(grad)))
         self._pose = (delta, grad)        # (kept alive while the library holds their addresses)
 
+    @property
+    def poseCorrection(self):
+        """(delta, grad) as setPoseCorrection last bound them, (None, None) when off."""
+        return getattr(self, "_pose", (None, None))
+
     def setExposure(self, M=None, grad=None):
         """gs_set_exposure: M / grad float32 device tensors of 12 elements (M = [A | b] row-major 3 x 4), or both None (off, the
         default).  The following lossForwardBackward calls take the loss of A render + b, return dL/d render as the colour
@@ -826,6 +831,12 @@ class GaussianRenderer:
         self._background = b          # (what setBackground last set, as _sparse_adam is kept: a trainer puts it back behind its step)
 
     @property
+    def customBackground(self):
+        """What setBackground last set: float32 [3], or None for the renderer's own black or white (`background` is the colour
+        in effect either way)."""
+        return self._background
+
+    @property
     def background(self):
         """The colour in effect (gs_get_background), float32 [3]: the one set, or the renderer's black or white."""
         b = np.zeros(3, np.float32)
@@ -874,6 +885,11 @@ class GaussianRenderer:
         renderer whose tile size is served by the generic blend kernels.  None (the default): no kernel, buffer or result differs."""
         self._check(self.lib.gs_set_adc_stats(self.ctx, _p(gradSum), _p(count), _p(maxRadius)))
         self._adc_stats = None if gradSum is None else (gradSum, count, maxRadius)
+
+    @property
+    def adcStats(self):
+        """(gradSum, count, maxRadius) as setADCStats last set them, or None."""
+        return getattr(self, "_adc_stats", None)
 
     def adcAccumulate(self, rows16, radii, useAbs: bool, gradSum, count, maxRadius):
         """gs_adc_accumulate: the step's statistic kernel on the caller's rows [N, 16] and radii [N], in place."""
@@ -1017,6 +1033,12 @@ class GaussianRenderer:
         """gs_set_mcmc: the MCMC strategy's per-step part (regularisers, noise) in the following renderBackwardAdam calls, or
         None (off, the default)."""
         self._check(self.lib.gs_set_mcmc(self.ctx, None if params is None else C.byref(params)))
+        self._mcmc = params
+
+    @property
+    def mcmc(self):
+        """The gs_mcmc_params setMCMC last set, or None."""
+        return getattr(self, "_mcmc", None)
 
     def mcmcRegularizerGrad(self, scales, opacity, gradScales, gradOpacity, params):
         """gs_mcmc_regularizer_grad: gradOpacity / gradScales += the regularisers' gradients (in place)."""

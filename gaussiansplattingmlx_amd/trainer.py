@@ -23,6 +23,7 @@ from ._lib import GS_ERR_REPLICA_MISMATCH, GsplatError
 from .renderer import GaussianRenderer, _p
 
 GS_ERR_WORKSPACE_OVERFLOW = 3
+ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-15      # the project's Adam (no bias correction): every step of this file
 
 PARAM_ORDER = ("xyz", "features_dc", "features_rest", "scales", "rotation", "opacity")   # GaussianModel.swift:46-55
 # arena layout: the 11 geometry floats per Gaussian first (one contiguous all-reduce), the SH tensors behind them
@@ -410,6 +411,64 @@ class GaussModel:
         self._layout(int(N), self.capacity, pads=(), stride=self.stride)
 
 
+def _adamStep(r, fn: str, n, tensors, seg_end, lrs, scale, before=(), after=()):
+    """One of the library's Adam kernels (fn: gs_adam_step, gs_adam_step_add, gs_adam_step_visible) with the project's Adam:
+    beta (0.9, 0.999), eps 1e-15, no bias correction.  tensors = (parameters, gradients, m, v) over n floats; seg_end / lrs: the
+    segments' ends (a ctypes array as it is, or a sequence) and learning rates; scale: grad_scale.  before / after: what fn
+    takes in front of the constants (gs_adam_step_visible's row widths) and behind grad_scale."""
+    k = len(lrs)
+    ends = seg_end if isinstance(seg_end, C.Array) else (C.c_longlong * k)(*[int(x) for x in seg_end])
+    r._check(getattr(r.lib, fn)(r.ctx, n, *[_p(t) for t in tensors], k, ends, (C.c_float * k)(*lrs), *before,
+                                C.c_float(ADAM_BETA1), C.c_float(ADAM_BETA2), C.c_float(ADAM_EPS), C.c_float(scale), *after))
+
+
+def _set_adc_stats(r, stats):
+    # (a step sets the statistic in _beginIteration, and behind densify_until no step does: then nothing is put back either)
+    if r.adcStats is not stats:
+        r.setADCStats(*(stats or (None, None, None)))
+
+
+class _Borrowed:
+    """The caller's renderer, lent to the trainer for one call: `with _Borrowed(r, *keep) as lent` reads the settings named in
+    `keep` through the renderer's getters, lent.set(name=value, ...) reads a setting that is not held yet and then sets it, and
+    on the way out, whatever happened, everything held is put back in SETTINGS' order and the `unbind` per-view tables are
+    unbound (a step binds its view's rows itself; they are the trainer's, so there is nothing of the caller's to put back)."""
+    SETTINGS = {       # name: (read, write)
+        "depth_gradient": (lambda r: r.getTuning("depth_gradient"), lambda r, v: r.setTuning(depth_gradient=v)),
+        "host_overflow_errors": (lambda r: r.getTuning("host_overflow_errors"), lambda r, v: r.setTuning(host_overflow_errors=v)),
+        "mcmc": (lambda r: r.mcmc, lambda r, v: r.setMCMC(v)),
+        "sh_degree": (lambda r: r.shDegree, lambda r, v: r.setSHDegree(v)),
+        "filter_3d": (lambda r: r.filter3D, lambda r, v: r.setFilter3D(v)),
+        "sparse_adam": (lambda r: r.sparseAdam, lambda r, v: r.setSparseAdam(v)),
+        "adc_stats": (lambda r: r.adcStats, _set_adc_stats),
+        "background": (lambda r: r.customBackground, lambda r, v: r.setBackground(v)),
+        "loss_mask": (lambda r: r.lossMask, lambda r, v: r.setLossMask(v)),
+        "pose": (lambda r: r.poseCorrection, lambda r, v: r.setPoseCorrection(*v)),
+    }
+
+    def __init__(self, r, *keep, unbind=()):
+        self.r, self.unbind = r, unbind
+        self.was = {name: self.SETTINGS[name][0](r) for name in keep}
+
+    def set(self, **settings):
+        for name, value in settings.items():
+            read, write = self.SETTINGS[name]
+            if name not in self.was:
+                self.was[name] = read(self.r)
+            write(self.r, value)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for name, (_, write) in self.SETTINGS.items():
+            if name in self.was:
+                write(self.r, self.was[name])
+        for t in self.unbind:
+            t.unbind(self.r)
+        return False
+
+
 class _PerViewTable:
     """The trainable state of one per-view correction (pose_opt, exposure_opt, bilateral_grid): for each of n_views training
     views a row of `width` floats and its two Adam moments, the gradient the step writes, and how a row is bound to the renderer.
@@ -451,10 +510,8 @@ class _PerViewTable:
         """Adam on the view's row (gs_adam_step; the project's Adam: beta (0.9, 0.999), eps 1e-15, no bias correction): gated like
         the step's other optimizer kernels, so a step from a blank render moves no row either.  The other views' rows and moments
         are left alone."""
-        r, k = renderer, len(self.segments)
-        r._check(r.lib.gs_adam_step(r.ctx, self.width, _p(self.rows[row]), _p(self.gradRow(row)), _p(self.m[row]), _p(self.v[row]),
-                                    k, (C.c_longlong * k)(*self.segments), (C.c_float * k)(*self.rates(iteration, iterationCount)),
-                                    C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0)))
+        _adamStep(renderer, "gs_adam_step", self.width, (self.rows[row], self.gradRow(row), self.m[row], self.v[row]),
+                  self.segments, self.rates(iteration, iterationCount), 1.0)
 
 
 def _require_single_device(feature, views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views=1):
@@ -466,6 +523,55 @@ def _require_single_device(feature, views_per_rank, process_group, dp_bootstrap,
         raise ValueError(f"{feature}: single-device steps only (no process group, dp_bootstrap or native exchange)")
     if n_views is None or isinstance(n_views, bool) or int(n_views) != n_views or int(n_views) < 1:
         raise ValueError(f"{feature} needs n_views >= 1 (view keys 0 .. n_views - 1)")
+
+
+# The trainer's optional features in the order the constructor checks them (DESIGN.md section 32 has the table for readers):
+#   keyword: (its config class as (module, "a Class") -- None for a plain switch --, the label in front of its single-device
+#             messages, ((a switch it is refused with, the message), ...), are the refusals checked BEHIND the single-device
+#             requirement?)
+# Every enabled feature takes single-device steps with one view (_require_single_device).  The switches a refusal may name:
+# the keywords, "mcmc" / "adc" for the strategies and "no_densify" for densify=False under the reference strategy.
+_FEATURES = {
+    "sh_schedule": ((".sh_schedule", "an SHDegreeSchedule"), "sh_schedule", (), False),
+    "depth": ((".depth_loss", "a DepthConfig"), "depth", (), False),
+    "background": ((".background", "a BackgroundConfig"), "background", (), False),
+    "sparse_adam": (None, "sparse_adam", (
+        ("mcmc", "sparse_adam: the reference strategy only (strategy='mcmc' moves every Gaussian every step)"),
+        ("filter_3d", "sparse_adam: not with filter_3d=True")), False),
+    "adc": ((".adc", "an ADCConfig"), "strategy='adc'", (
+        ("filter_3d", "strategy='adc': not with filter_3d"), ("contrib_prune", "strategy='adc': not with contrib_prune"),
+        ("sparse_adam", "strategy='adc': not with sparse_adam")), True),
+    "contrib_prune": ((".contrib_prune", "a ContribPruneConfig"), "contrib_prune", (
+        ("mcmc", "contrib_prune: the reference strategy only (not with strategy='mcmc')"),), False),
+    "absgrad": ((".absgrad", "an AbsGradConfig"), "absgrad", (
+        ("mcmc", "absgrad: the reference strategy or strategy='adc' (not with strategy='mcmc')"),
+        ("no_densify", "absgrad changes the densification criterion: not with densify=False")), False),
+    "mcmc": ((".mcmc", "an MCMCConfig"), "strategy='mcmc'", (), False),
+    "filter_3d": (None, "filter_3d", (("mcmc", "filter_3d: the reference strategy only (not with strategy='mcmc')"),), False),
+    "pose_opt": (None, "pose_opt", (), False),
+    "exposure_opt": (None, "exposure_opt", (), False),
+    "bilateral_grid": (None, "bilateral_grid", (
+        ("exposure_opt", "bilateral_grid and exposure_opt are exclusive (a constant grid is an exposure)"),), False),
+}
+
+
+def _admit(feature, value, on, where, n_views=1):
+    """One enabled feature's checks from _FEATURES: its config's type and validate(), what it is refused with (on: switch ->
+    is it on), the single-device requirement (where: views_per_rank, process_group, dp_bootstrap, exchange_impl).  Returns
+    the value."""
+    config, label, refusals, late = _FEATURES[feature]
+    if config is not None:
+        import importlib
+        if not isinstance(value, getattr(importlib.import_module(config[0], __package__), config[1].split()[1])):
+            raise ValueError(f"{feature} must be {config[1]}")
+        value.validate()
+    refused = [message for switch, message in refusals if on[switch]]
+    if refused and not late:
+        raise ValueError(refused[0])
+    _require_single_device(label, *where, n_views)
+    if refused:
+        raise ValueError(refused[0])
+    return value
 
 
 class GaussianTrainer:
@@ -633,109 +739,53 @@ class GaussianTrainer:
         snapshots are written whole, the inactive bands as the model holds them.  Composes with every single-device feature and
         strategy through the form that feature already selects; single-device steps with one view only.  None (the default): no
         call, kernel or result differs."""
-        self.sh_schedule = None
+        # which switches are on, as _FEATURES' refusals name them
+        on = dict(mcmc=strategy == "mcmc", adc=strategy == "adc", filter_3d=bool(filter_3d), sparse_adam=bool(sparse_adam),
+                  contrib_prune=contrib_prune is not None, exposure_opt=bool(exposure_opt),
+                  no_densify=not densify and strategy != "adc")
+        where = (views_per_rank, process_group, dp_bootstrap, exchange_impl)
+
+        def admit(feature, value=None, n_views=1):
+            return None if value is None and _FEATURES[feature][0] else _admit(feature, value, on, where, n_views)
+
         self.lastSHDegree = None
-        if sh_schedule is not None:
-            from .sh_schedule import SHDegreeSchedule
-            if not isinstance(sh_schedule, SHDegreeSchedule):
-                raise ValueError("sh_schedule must be an SHDegreeSchedule")
-            sh_schedule.validate()
-            _require_single_device("sh_schedule", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            self.sh_schedule = sh_schedule
-        self.depth = None
         self._depthStep = None          # the running step's depth inputs (trainStep sets and clears it)
-        if depth is not None:
-            from .depth_loss import DepthConfig
-            if not isinstance(depth, DepthConfig):
-                raise ValueError("depth must be a DepthConfig")
-            depth.validate()
-            _require_single_device("depth", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            self.depth = depth
-        self.background = None
         self.lastBackground = None
         self._bgTarget = None
         self._bgSource = None
-        if background is not None:
-            from .background import BackgroundConfig
-            if not isinstance(background, BackgroundConfig):
-                raise ValueError("background must be a BackgroundConfig")
-            background.validate()
-            _require_single_device("background", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            self.background = background
+        self.sh_schedule, self.depth, self.background = admit("sh_schedule", sh_schedule), admit("depth", depth), admit("background", background)
         if not isinstance(sparse_adam, bool):
             raise ValueError("sparse_adam is True or False")
         self.sparse_adam = sparse_adam
         if sparse_adam:
-            if strategy == "mcmc":
-                raise ValueError("sparse_adam: the reference strategy only (strategy='mcmc' moves every Gaussian every step)")
-            if filter_3d:
-                raise ValueError("sparse_adam: not with filter_3d=True")
-            _require_single_device("sparse_adam", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            admit("sparse_adam")
         if strategy not in ("reference", "mcmc", "adc"):
             raise ValueError(f"unknown strategy {strategy!r} (\"reference\", \"mcmc\" or \"adc\")")
         self.strategy = strategy
-        self.adc = None
         self.lastADCStats = None
         self.adcSizePrune = False       # size pruning: on once the first opacity reset has happened
         self._adcAcc = None             # [3, N]: gradSum, count, maxRadius
-        if strategy == "adc":
-            from .adc import ADCConfig
-            if adc is None:
-                raise ValueError("strategy='adc' needs adc=ADCConfig(scene_extent=adc.scene_extent(cameras))")
-            if not isinstance(adc, ADCConfig):
-                raise ValueError("adc must be an ADCConfig")
-            adc.validate()
-            _require_single_device("strategy='adc'", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            for on, name in ((filter_3d, "filter_3d"), (contrib_prune is not None, "contrib_prune"), (sparse_adam, "sparse_adam")):
-                if on:
-                    raise ValueError(f"strategy='adc': not with {name}")
-            self.adc = adc
-            densify = False
-        elif adc is not None:
+        if strategy == "adc" and adc is None:
+            raise ValueError("strategy='adc' needs adc=ADCConfig(scene_extent=adc.scene_extent(cameras))")
+        if strategy != "adc" and adc is not None:
             raise ValueError("adc settings need strategy='adc'")
-        self.contribPrune = None
+        self.adc = admit("adc", adc)
         self.lastContribPruneStats = None
-        if contrib_prune is not None:
-            from .contrib_prune import ContribPruneConfig
-            if not isinstance(contrib_prune, ContribPruneConfig):
-                raise ValueError("contrib_prune must be a ContribPruneConfig")
-            contrib_prune.validate()
-            if strategy == "mcmc":
-                raise ValueError("contrib_prune: the reference strategy only (not with strategy='mcmc')")
-            _require_single_device("contrib_prune", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            self.contribPrune = contrib_prune
-        self.absgrad = None
-        if absgrad is not None:
-            from .absgrad import AbsGradConfig
-            if not isinstance(absgrad, AbsGradConfig):
-                raise ValueError("absgrad must be an AbsGradConfig")
-            absgrad.validate()
-            if strategy == "mcmc":
-                raise ValueError("absgrad: the reference strategy or strategy='adc' (not with strategy='mcmc')")
-            if not densify and strategy != "adc":
-                raise ValueError("absgrad changes the densification criterion: not with densify=False")
-            _require_single_device("absgrad", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            self.absgrad = absgrad
-        self.mcmc = None
+        self.contribPrune, self.absgrad = admit("contrib_prune", contrib_prune), admit("absgrad", absgrad)
         self.lastMCMCStats = None
-        if strategy == "mcmc":
-            from .mcmc import MCMCConfig
-            cfg = MCMCConfig() if mcmc is None else mcmc
-            if not isinstance(cfg, MCMCConfig):
-                raise ValueError("mcmc must be an MCMCConfig")
-            cfg.validate()
-            _require_single_device("strategy='mcmc'", views_per_rank, process_group, dp_bootstrap, exchange_impl)
-            if cfg.cap_max < model.N:
-                raise ValueError(f"strategy='mcmc': cap_max = {cfg.cap_max} is below the model's N = {model.N}")
-            self.mcmc = cfg
-            densify = False
-        elif mcmc is not None:
+        if strategy != "mcmc" and mcmc is not None:
             raise ValueError("mcmc settings need strategy='mcmc'")
+        if strategy == "mcmc" and mcmc is None:
+            from .mcmc import MCMCConfig
+            mcmc = MCMCConfig()
+        self.mcmc = admit("mcmc", mcmc)
+        if self.mcmc is not None and self.mcmc.cap_max < model.N:
+            raise ValueError(f"strategy='mcmc': cap_max = {self.mcmc.cap_max} is below the model's N = {model.N}")
+        if strategy != "reference":
+            densify = False             # (the strategy has its own events: the reference's are off)
         self.filter_3d = bool(filter_3d)
         if self.filter_3d:
-            if strategy == "mcmc":
-                raise ValueError("filter_3d: the reference strategy only (not with strategy='mcmc')")
-            _require_single_device("filter_3d", views_per_rank, process_group, dp_bootstrap, exchange_impl)
+            admit("filter_3d")
             if filter_cameras is None or len(filter_cameras) < 1:
                 raise ValueError("filter_3d needs filter_cameras (the training cameras)")
             if isinstance(filter_3d_interval, bool) or int(filter_3d_interval) != filter_3d_interval or int(filter_3d_interval) < 1:
@@ -744,12 +794,12 @@ class GaussianTrainer:
             raise ValueError("filter_cameras need filter_3d=True")
         self.pose_opt = bool(pose_opt)
         if self.pose_opt:
-            _require_single_device("pose_opt", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
+            admit("pose_opt", n_views=n_views)
             if len(pose_lr) != 2:
                 raise ValueError("pose_lr = (rotation rate, translation rate)")
         self.exposure_opt = bool(exposure_opt)
         if self.exposure_opt:
-            _require_single_device("exposure_opt", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
+            admit("exposure_opt", n_views=n_views)
             try:
                 elr = tuple(float(x) for x in exposure_lr)
             except (TypeError, ValueError):
@@ -758,9 +808,7 @@ class GaussianTrainer:
                 raise ValueError("exposure_lr = (initial rate, final rate), both positive and finite")
         self.bilateral_grid = bool(bilateral_grid)
         if self.bilateral_grid:
-            if self.exposure_opt:
-                raise ValueError("bilateral_grid and exposure_opt are exclusive (a constant grid is an exposure)")
-            _require_single_device("bilateral_grid", views_per_rank, process_group, dp_bootstrap, exchange_impl, n_views)
+            admit("bilateral_grid", n_views=n_views)
             bgs = GaussianRenderer._grid_shape(bilateral_grid_shape, "bilateral_grid_shape")
             try:
                 blr, btv = float(bilateral_grid_lr), float(bilateral_grid_tv)
@@ -808,7 +856,7 @@ class GaussianTrainer:
             self._cotDepth = r._empty(r.H, r.W)
             if self.depth.mode != "accumulated":      # (the accumulated depth has no cotangent into alpha)
                 self._cotAlpha = r._empty(r.H, r.W)
-        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in model.seg_end])
+        self._seg_end = self._segEnds()
         self.iteration = 0
         # densification (GaussianTrainer.swift:293-300, 304)
         self.gradientThreshold, self.minOpacity, self.maxScale = 0.0002, 0.005, 0.01
@@ -895,7 +943,7 @@ class GaussianTrainer:
         self._alloc_exchange_buffers()
         if self.mcmc is not None:
             model.restride(max(self.mcmc.cap_max, model.capacity))
-            self._seg_end = (C.c_longlong * 6)(*[int(x) for x in model.seg_end])
+            self._seg_end = self._segEnds()
         # the enabled per-view corrections, in the order a step binds them and runs their Adam: pose, exposure, grid
         self._perView = {}
         eye = torch.eye(3, 4, dtype=torch.float32).reshape(12)        # [I | 0]: an exposure, a grid's node
@@ -933,6 +981,10 @@ class GaussianTrainer:
             self.checkReplicas()
             if self._plans_events():      # ... likewise the plan check's side stream and its 16-word collective
                 self.checkPlans(dict(zip(PLAN_WORDS, (model.N, 0, model.N, model.N, 0, 0, 0, model.N))))
+
+    def _segEnds(self):
+        """The arena's six segment ends as the Adam kernels take them."""
+        return (C.c_longlong * 6)(*[int(x) for x in self.model.seg_end])
 
     @property
     def referenceParamReload(self):
@@ -976,10 +1028,9 @@ class GaussianTrainer:
         if N_new != N0:
             m.setCount(N_new)
         self.lastMCMCStats = dict(dead=st["dead"], relocated=st["relocated"], added=N_new - N0, N=N_new)
-        if st["relocated"] > 0 or N_new != N0:
-            r.dropDepthCuts()         # rows moved or were added: the views' depth cuts no longer describe the scene
-        if r.reserved is not None and N_new > r.reserved[0]:
-            r.reserve(N_new, int(r.reserved[1] * (N_new / max(r.reserved[0], 1)) * 1.1))
+        # rows moved or were added: the views' depth cuts no longer describe the scene.  No new layout: the rows were appended in
+        # place at the stride the constructor laid out, and nothing of what a committed event resets belongs to this strategy
+        self._afterCommit(N_new, grew=st["relocated"] > 0 or N_new != N0, layout=False, resetAccum=False)
         return self.lastMCMCStats
 
     # -- adaptive density control (adc.py, include/gsplat.h gs_set_adc_stats) --------------------------------
@@ -1027,15 +1078,9 @@ class GaussianTrainer:
         r.adcGatherMoments(mOld, gather, mode, actions, out=mNew)
         r.adcGatherMoments(vOld, gather, mode, actions, out=vNew)
         m.commitStaged(zero=False, moments=True)
-        self._committed = True
-        self._adcAcc = None
+        self._adcAcc = None                 # (the strategy's own statistic starts anew, not the reference's accumulator)
         self._adcAccumulators()
-        if st["split"] > 0 or st["clone"] > 0:
-            r.dropDepthCuts()               # (new Gaussians lengthen the sweeps: see split_and_prune)
-        if r.reserved is not None and total > r.reserved[0]:
-            r.reserve(total, int(r.reserved[1] * (total / max(r.reserved[0], 1)) * 1.1))
-        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in m.seg_end])
-        self._alloc_exchange_buffers()
+        self._afterCommit(total, grew=st["split"] > 0 or st["clone"] > 0, resetAccum=False)
         return st
 
     def _adcResetOpacity(self):
@@ -1189,6 +1234,35 @@ class GaussianTrainer:
     def _plans_events(self) -> bool:
         return bool(self.plannedDensify) and not self.referenceParamReload
 
+    def _afterCommit(self, N_new: int, grew: bool, regrow: bool = True, layout: bool = True, resetAccum: bool = True,
+                     keepForReload: bool = False):
+        """What every event does once the model holds its N_new rows.  grew: rows were added (or moved).  New Gaussians
+        lengthen the sweeps: a stale depth cut then costs a whole repeated forward, a fresh one 60 us of binning -- measured:
+        every view missed once after such an event --, so the cuts go.  An event that only PRUNED (every event of a scene at
+        the maxGaussians cap, GaussianTrainer.swift:300, 808) removes splats of opacity < 0.005: no sweep gets longer by more
+        than the cuts' margin (2 x the sweep + 128 entries), and the cuts are depth keys, not indices, so the compaction of
+        the arrays does not touch them.  They stay -- with 100 views and an event every 100 iterations every visit would
+        otherwise be an uncut one (the 2 M garden scene: 1.85 instead of 0.47 ms of binning per step).  A cut that does miss
+        is caught as ever (renderer.forwardMissed).
+        regrow: a pair reserve made for fewer Gaussians grows in proportion, plus a tenth.  layout: the arena was laid out anew
+        -- the event counts as committed, the segment ends and the exchange's buffers follow the new N.  resetAccum: the
+        reference strategy's densify statistic starts anew.  keepForReload: under referenceParamReload the committed
+        parameters are kept for the reload (the events that can run with it)."""
+        r, m = self.gaussRender, self.model
+        if layout:
+            self._committed = True
+        if keepForReload and self.referenceParamReload:
+            self._committed_params = m.arena.clone()
+        if grew:
+            r.dropDepthCuts()
+        if regrow and r.reserved is not None and N_new > r.reserved[0]:
+            r.reserve(N_new, int(r.reserved[1] * (N_new / max(r.reserved[0], 1)) * 1.1))
+        if layout:
+            self._seg_end = self._segEnds()
+            self._alloc_exchange_buffers()
+        if resetAccum:
+            self.resetGradientAccumulation()
+
     def _split_and_prune_planned(self, iteration: int, allowDensify: bool):
         """The event with the count left on the device (include/gsplat.h, gs_densify_plan; densify.hip).  Queued before the
         host waits for anything: classify, the scan and the plan, the output map and the gather for `capacity` slots into the
@@ -1241,14 +1315,7 @@ class GaussianTrainer:
             if not packed:
                 m._staged = (cap, cap, cap)
         m.commitStaged(N_new=N_new, zero=False)
-        self._committed = True
-        if plan["applies"] and (st["split"] > 0 or st["clone"] > 0):
-            r.dropDepthCuts()         # (new Gaussians lengthen the sweeps: see split_and_prune)
-        if r.reserved is not None and N_new > r.reserved[0]:
-            r.reserve(N_new, int(r.reserved[1] * (N_new / max(r.reserved[0], 1)) * 1.1))
-        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in m.seg_end])
-        self._alloc_exchange_buffers()
-        self.resetGradientAccumulation()
+        self._afterCommit(N_new, grew=plan["applies"] and (st["split"] > 0 or st["clone"] > 0))
         if self._exchange:
             self.checkReplicas(deferred=True)      # queued behind the gather; the verdict where the host next waits
         return st
@@ -1295,23 +1362,7 @@ class GaussianTrainer:
             noise = torch.randn(total, 3, generator=gen, device=r.device, dtype=torch.float32)
         r.densifyGather(p, gather, mode, noise, out=m.stagingViews(total))
         m.commitStaged()
-        self._committed = True
-        if self.referenceParamReload:
-            self._committed_params = m.arena.clone()
-        # The model changed.  New Gaussians (splits, clones) lengthen the sweeps: a stale cut then costs a whole repeated
-        # forward, a fresh one 60 us of binning -- measured: every view missed once after such an event --, so the cuts go.
-        # An event that only PRUNED (every event of a scene at the maxGaussians cap, GaussianTrainer.swift:300, 808) removes
-        # splats of opacity < 0.005: no sweep gets longer by more than the cuts' margin (2 x the sweep + 128 entries), and
-        # the cuts are depth keys, not indices, so the compaction of the arrays does not touch them.  They stay -- with 100
-        # views and an event every 100 iterations every visit would otherwise be an uncut one (the 2 M garden scene: 1.85
-        # instead of 0.47 ms of binning per step).  A cut that does miss is caught as ever (renderer.forwardMissed).
-        if st["split"] > 0 or st["clone"] > 0:
-            r.dropDepthCuts()
-        if r.reserved is not None and total > r.reserved[0]:
-            r.reserve(total, int(r.reserved[1] * (total / max(r.reserved[0], 1)) * 1.1))
-        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in m.seg_end])
-        self._alloc_exchange_buffers()
-        self.resetGradientAccumulation()
+        self._afterCommit(total, grew=st["split"] > 0 or st["clone"] > 0, keepForReload=True)
         if self._exchange:
             self.checkReplicas()       # before the next size-dependent collective
         return st
@@ -1326,21 +1377,15 @@ class GaussianTrainer:
             cams = [self.refinedCamera(i, c) for i, c in enumerate(cams)]
         for t in self._perView.values():
             t.unbind(r)               # (a step binds its view's rows again; the refined cameras above carry the poses)
-        if self.filter_3d:
-            r.setFilter3D(self._filter)
-        try:
-            for attempt in range(4):
-                try:
-                    scores = r.contributionScores(m.getParams(), cams)
-                    r.sync()
-                    return scores
-                except GsplatError as e:
-                    if e.code != GS_ERR_WORKSPACE_OVERFLOW or attempt == 3:
-                        raise
-                    self._recover_overflow()
-        finally:
+        def score():
+            scores = r.contributionScores(m.getParams(), cams)
+            r.sync()
+            return scores
+
+        with _Borrowed(r) as lent:
             if self.filter_3d:
-                r.setFilter3D(None)
+                lent.set(filter_3d=self._filter)
+            return self._retryOnOverflow(score)
 
     def _contribPruneEvent(self, cameras, threshold: float, score: str):
         """Scores the model over `cameras` and prunes what lies below the threshold through the densify event's machinery.
@@ -1372,13 +1417,8 @@ class GaussianTrainer:
             gather, mode = r.buildDensifyOutputMap(actions, offsets, N_new)
             r.densifyGather(p, gather, mode, None, out=m.stagingViews(N_new))
             m.commitStaged()
-        self._committed = True
-        if self.referenceParamReload:
-            self._committed_params = m.arena.clone()
-        # (the depth cuts stay, as after a densify event that only pruned: see split_and_prune)
-        self._seg_end = (C.c_longlong * 6)(*[int(x) for x in m.seg_end])
-        self._alloc_exchange_buffers()
-        self.resetGradientAccumulation()
+        # (nothing grew: the depth cuts stay, as after a densify event that only pruned, and no reserve is too small now)
+        self._afterCommit(N_new, grew=False, regrow=False, keepForReload=True)
         st.update(kept=int(N_new), pruned=int(N - N_new))
         return st
 
@@ -1467,36 +1507,20 @@ class GaussianTrainer:
                     # (the fit's p is the CLAMPED render: M is applied to that, and the metrics clamp M p again)
                     r.imageMetrics(r.applyExposure(img.clamp(0.0, 1.0), M), tgt, mask, out=ccSums[i])
 
-        restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
-        filter_was, bg_was, pose_was = r.filter3D, getattr(r, "_background", None), getattr(r, "_pose", (None, None))
-        degree_was = r.shDegree if self.sh_schedule is not None else None
-        try:
+        def measure():      # (a forward that overflowed the reserved pairs is blank: regrow, measure again)
+            views()
+            r.sync()
+
+        # (the two knobs are the caller's whatever a forward's repeat does to them; the pose is bound view by view above)
+        with _Borrowed(r, "depth_gradient", "host_overflow_errors", *(("pose",) if pose is not None else ())) as lent:
             if self.sh_schedule is not None:
-                r.setSHDegree(self._scheduledSHDegree())      # (the degree the next step trains at)
+                lent.set(sh_degree=self._scheduledSHDegree())      # (the degree the next step trains at)
             if self.filter_3d:
-                r.setFilter3D(self._filter)
+                lent.set(filter_3d=self._filter)
             if bg is not None:
-                r.setBackground(bg)
-            for attempt in range(4):
-                try:
-                    views()
-                    r.sync()
-                    break
-                except GsplatError as e:      # (a forward that overflowed the reserved pairs is blank: regrow, measure again)
-                    if e.code != GS_ERR_WORKSPACE_OVERFLOW or attempt == 3:
-                        raise
-                    self._recover_overflow()
+                lent.set(background=bg)
+            self._retryOnOverflow(measure)
             return EvalResult.from_sums(sums.cpu().numpy(), None if ccSums is None else ccSums.cpu().numpy())
-        finally:
-            r.setTuning(**restore)
-            if degree_was is not None:
-                r.setSHDegree(degree_was)
-            if self.filter_3d:
-                r.setFilter3D(filter_was)
-            if bg is not None:
-                r.setBackground(bg_was)
-            if pose is not None:
-                r.setPoseCorrection(*pose_was)
 
     def checkReplicas(self, deferred: bool = False):
         """Every rank of a data-parallel job calls this at the same point (after every committed densify event): one
@@ -1513,14 +1537,18 @@ class GaussianTrainer:
                 r._check(r.lib.gs_dp_check_replicas_begin(r.ctx, int(m.N), _p(m.arena), int(m.numel)))
                 self._replica_pending = True
                 return
-            rc = r.lib.gs_dp_check_replicas(r.ctx, int(m.N), _p(m.arena), int(m.numel))
-            if rc == GS_ERR_REPLICA_MISMATCH:
-                raise ReplicaMismatch(r.lib.gs_last_error(r.ctx).decode())
-            r._check(rc)
+            self._replicaVerdict(r.lib.gs_dp_check_replicas(r.ctx, int(m.N), _p(m.arena), int(m.numel)))
         elif deferred:
             self._replica_pending = check_replicas_begin(m.N, m.arena, self.pg)
         else:
             check_replicas(m.N, m.arena, self.pg)
+
+    def _replicaVerdict(self, rc):
+        """The return code of one of the library's replica checks: ReplicaMismatch with its message, or any other error."""
+        r = self.gaussRender
+        if rc == GS_ERR_REPLICA_MISMATCH:
+            raise ReplicaMismatch(r.lib.gs_last_error(r.ctx).decode())
+        r._check(rc)
 
     def _resolveReplicaCheck(self):
         """The verdict of a deferred checkReplicas, if one is outstanding (every rank reaches this at the same points)."""
@@ -1528,11 +1556,7 @@ class GaussianTrainer:
         if not pending:
             return
         if self._native:
-            r = self.gaussRender
-            rc = r.lib.gs_dp_check_replicas_end(r.ctx)
-            if rc == GS_ERR_REPLICA_MISMATCH:
-                raise ReplicaMismatch(r.lib.gs_last_error(r.ctx).decode())
-            r._check(rc)
+            self._replicaVerdict(self.gaussRender.lib.gs_dp_check_replicas_end(self.gaussRender.ctx))
         else:
             check_replicas_end(pending, self.pg, self.rank)
 
@@ -1541,11 +1565,7 @@ class GaussianTrainer:
         does not wait for this stream's queue; ReplicaMismatch on EVERY rank unless all planned the same event."""
         words = [int(plan[k]) for k in PLAN_WORDS]
         if self._native:
-            r = self.gaussRender
-            rc = r.lib.gs_dp_check_plan(r.ctx, (C.c_longlong * 8)(*words), 8)
-            if rc == GS_ERR_REPLICA_MISMATCH:
-                raise ReplicaMismatch(r.lib.gs_last_error(r.ctx).decode())
-            r._check(rc)
+            self._replicaVerdict(self.gaussRender.lib.gs_dp_check_plan(self.gaussRender.ctx, (C.c_longlong * 8)(*words), 8))
         else:
             if getattr(self, "_side", None) is None and self.gaussRender.device.type == "cuda":
                 self._side = torch.cuda.Stream(device=self.gaussRender.device)
@@ -1562,6 +1582,19 @@ class GaussianTrainer:
         capN = max(int(st["capN"]), self.model.capacity)
         r.reserve(capN, max(int(need * 1.5) + 65536, int(st["capM"] * 1.5)))
         self.overflowRecoveries += 1
+
+    def _retryOnOverflow(self, body, attempts: int = 4, recover: bool = True):
+        """body(), repeated behind a regrown reserve while it raises GS_ERR_WORKSPACE_OVERFLOW: every regrow is by half at
+        least, so a few rounds reach any need; the last attempt's error, and any other, is the caller's.  recover=False: no
+        repeat at all (a data-parallel step never raises it -- host_overflow_errors is off, see __init__ -- and no rank may
+        regrow on its own)."""
+        for attempt in range(attempts):
+            try:
+                return body()
+            except GsplatError as e:
+                if e.code != GS_ERR_WORKSPACE_OVERFLOW or not recover or attempt == attempts - 1:
+                    raise
+                self._recover_overflow()
 
     def _overflow_reported(self) -> bool:
         """Has the device raised an overflow report that nobody has taken delivery of?  No wait: the report lives in host
@@ -1798,64 +1831,43 @@ class GaussianTrainer:
                                                      or self.iteration == self.iterationCount - 1)
         step = self._profiledStep if profiled else (self._trainStepMulti if self.viewsPerRank > 1 else self._trainStep)
         r = self.gaussRender
-        # knobs of the caller's renderer that this step changes, put back whatever happens
-        restore = dict(depth_gradient=r.getTuning("depth_gradient"), host_overflow_errors=r.getTuning("host_overflow_errors"))
-        sparse_was = getattr(r, "_sparse_adam", False)
-        bg_was = mask_was = None
+        # what this step changes of the caller's renderer, put back whatever happens.  Held from the start: the two knobs, the
+        # background (the target is composited before anything is set) and, with strategy='adc', the statistic _beginIteration sets
+        keep = ["depth_gradient", "host_overflow_errors"]
+        if self.adc is not None:
+            keep.append("adc_stats")
         if self.background is not None:
             # the step's colour: the renderer's background for every forward of the step, and the target over it
             b = self.background.color_at(self.iteration)
-            bg_was = (getattr(r, "_background", None),)
+            keep.append("background")
             targetRGB = self._compositeTarget(targetRGB, targetAlpha, b)
         tables = list(self._perView.values())
         row = tables[0].row(viewKey) if tables else None       # (one n_views for all of them)
-        try:
-            if depth is not None:
-                self._depthStep = self._depthInputs(targetDepth, depthMask, depthAlign)
-            r.setTuning(depth_gradient=0 if depth is None else 1)
-            if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
-                r.setMCMC(self._mcmcParams())
-            if self.filter_3d:
-                r.setFilter3D(self._filter)
-            if self.sparse_adam and not sparse_was:
-                r.setSparseAdam(True)
-            if self.background is not None:
-                r.setBackground(b)
-                self.lastBackground = b
-            for t in tables:
-                t.bindRow(r, row)
-            if lossMask is not None:
-                was = r.lossMask
-                r.setLossMask(lossMask)
-                mask_was = (was,)
-            if self._exchange:
-                r.setTuning(host_overflow_errors=0)
-                if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
-                    self._collectiveOverflowCheck()
-            for attempt in range(4):
-                try:
-                    return step(camera, targetRGB, stepCameras, viewKey)
-                except GsplatError as e:
-                    if e.code != GS_ERR_WORKSPACE_OVERFLOW or self._exchange or attempt == 3:
-                        raise      # (data-parallel steps never raise it: host_overflow_errors is off, see __init__)
-                    self._recover_overflow()      # (every regrow is by half at least: a few rounds reach any need)
-        finally:
-            self._depthStep = None
-            r.setTuning(**restore)
-            if self.mcmc is not None:
-                r.setMCMC(None)
-            if self.filter_3d:
-                r.setFilter3D(None)
-            if self.sparse_adam and not sparse_was:
-                r.setSparseAdam(False)
-            if self.adc is not None and getattr(r, "_adc_stats", None) is not None:
-                r.setADCStats(None)       # (set by _beginIteration: the accumulators are this trainer's, the renderer the caller's)
-            if bg_was is not None:
-                r.setBackground(bg_was[0])
-            if mask_was is not None:
-                r.setLossMask(mask_was[0])
-            for t in tables:
-                t.unbind(r)
+        with _Borrowed(r, *keep, unbind=tables) as lent:
+            try:
+                if depth is not None:
+                    self._depthStep = self._depthInputs(targetDepth, depthMask, depthAlign)
+                lent.set(depth_gradient=0 if depth is None else 1)
+                if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
+                    lent.set(mcmc=self._mcmcParams())
+                if self.filter_3d:
+                    lent.set(filter_3d=self._filter)
+                if self.sparse_adam and not r.sparseAdam:       # (a caller's renderer that has it on keeps it on)
+                    lent.set(sparse_adam=True)
+                if self.background is not None:
+                    lent.set(background=b)
+                    self.lastBackground = b
+                for t in tables:
+                    t.bindRow(r, row)
+                if lossMask is not None:
+                    lent.set(loss_mask=lossMask)
+                if self._exchange:
+                    lent.set(host_overflow_errors=0)
+                    if self.iteration % self.overflowCheckInterval == 0 and self.iteration > 0:
+                        self._collectiveOverflowCheck()
+                return self._retryOnOverflow(lambda: step(camera, targetRGB, stepCameras, viewKey), recover=not self._exchange)
+            finally:
+                self._depthStep = None
 
     def _depthInputs(self, targetDepth, depthMask, depthAlign):
         """The step's depth target and mask on the device and its gs_depth_loss_params."""
@@ -1981,7 +1993,7 @@ class GaussianTrainer:
         a.n_arena, a.geom_numel, a.nseg = int(m.numel), int(m.geom_numel), 6
         for i, (e, lr) in enumerate(zip(m.seg_end, arenaLearningRates(self.iteration, self.iterationCount))):
             a.seg_end[i], a.seg_lr[i] = int(e), float(lr)
-        a.beta1, a.beta2, a.eps = 0.9, 0.999, 1e-15
+        a.beta1, a.beta2, a.eps = ADAM_BETA1, ADAM_BETA2, ADAM_EPS
         mode = _lib.GS_DP_ALLREDUCE
         if self.dp_exchange == "sh_compressed":
             if stepCameras is None or len(stepCameras) != self.world:
@@ -2052,10 +2064,38 @@ class GaussianTrainer:
         """Adam on the geometry slice after the all-reduce; the xyz segment's gradient = reduced + the view-direction terms the
         SH kernel rebuilt meanwhile (gs_adam_step_add)."""
         r, m = self.gaussRender, self.model
-        glr = (C.c_float * 4)(lr["xyz"], lr["scales"], lr["rotation"], lr["opacity"])
-        r._check(r.lib.gs_adam_step_add(r.ctx, m.geom_numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 4,
-                                        (C.c_longlong * 4)(*[int(x) for x in m.seg_end[:4]]), glr, C.c_float(0.9), C.c_float(0.999),
-                                        C.c_float(1e-15), C.c_float(scale), _p(self._xyz_add), 3 * m.N))
+        _adamStep(r, "gs_adam_step_add", m.geom_numel, (m.arena, m.grad, m.m, m.v), m.seg_end[:4],
+                  (lr["xyz"], lr["scales"], lr["rotation"], lr["opacity"]), scale, after=(_p(self._xyz_add), 3 * m.N))
+
+    def _arenaAdam(self, fn: str, scale: float, **kw):
+        """Adam over the whole arena, its six segments at the step's learning rates."""
+        m = self.model
+        _adamStep(self.gaussRender, fn, m.numel, (m.arena, m.grad, m.m, m.v), self._seg_end,
+                  arenaLearningRates(self.iteration, self.iterationCount), scale, **kw)
+
+    def _shCompressedUpdate(self, stepCameras, own, scale: float, gather, reduce, xt):
+        """The update of a step in the sh_compressed form, one view or several: wait for the gathered colour cotangents, rebuild
+        the SH gradients over the step's len(own) views (fuse_adam: with the SH tensors' Adam step in the same pass, on the old
+        xyz; own[q]: view q's xyz gradient without its view-direction term where this rank rendered q, else None), wait for the
+        geometry slice's all-reduce -- the rebuild ran under it --, then Adam on the geometry slice (fuse_adam) or on the whole
+        arena, all at grad_scale `scale`.  gather / reduce: the collectives' Work, None where nothing is to wait for."""
+        r, m = self.gaussRender, self.model
+        self._awaitGather(gather, xt)
+        centres = np.stack([np.asarray(getattr(c, "cameraCenter", c), np.float32).reshape(3) for c in stepCameras])
+        if self.fuse_adam:
+            lr = dict(zip(PARAM_ORDER, getLearningRates(self.iteration, self.iterationCount)))
+            r.shGradFromViewsAdamDir(m.getParams(), self._cc_all, centres, own, m.arena, m.m, m.v, lr["features_dc"],
+                                     lr["features_rest"], scale, self._xyz_add)
+        else:
+            r.shGradFromViews(m.getParams()["xyz"], self._cc_all, centres, m.K, out=m.getGrads())
+        if reduce is not None:
+            self._xt_mark(xt, "wr0")
+            reduce.wait()
+            self._xt_mark(xt, "wr1")
+        if self.fuse_adam:
+            self._geometryAdam(lr, scale)
+        else:
+            self._arenaAdam("gs_adam_step", scale)
 
     def _trainStepMulti(self, cameras, targets, stepCameras=None, viewKeys=None):
         """One iteration over viewsPerRank views of this rank (see __init__): cameras / targets / viewKeys are sequences of
@@ -2090,7 +2130,7 @@ class GaussianTrainer:
                 self.addGradientAccumulation()
         g_geom = m.grad[:m.geom_numel]
         torch.sum(self._geom_v, dim=0, out=g_geom)               # the rank's share of the all-reduce, summed by addressing
-        reduce = None
+        gather = reduce = None
         xt = self._xt_step() if self._exchange else None
         if self._exchange:
             import torch.distributed as dist
@@ -2098,28 +2138,12 @@ class GaussianTrainer:
             reduce = dist.all_reduce(g_geom, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
             if xt is not None:
                 xt["work"].update(reduce=reduce)
-            self._awaitGather(gather, xt)
-        centres = np.stack([np.asarray(getattr(c, "cameraCenter", c), np.float32).reshape(3) for c in stepCameras])
-        scale = 1.0 / total
+        own = None
         if self.fuse_adam:
-            lr = dict(zip(PARAM_ORDER, getLearningRates(self.iteration, self.iterationCount)))
             own = [None] * total
             for j in range(V):
                 own[self.rank * V + j] = self._xyz_own[j]
-            r.shGradFromViewsAdamDir(m.getParams(), self._cc_all, centres, own, m.arena, m.m, m.v, lr["features_dc"],
-                                     lr["features_rest"], scale, self._xyz_add)
-            if reduce is not None:
-                self._xt_mark(xt, "wr0")
-                reduce.wait()
-                self._xt_mark(xt, "wr1")
-            self._geometryAdam(lr, scale)
-        else:
-            r.shGradFromViews(m.getParams()["xyz"], self._cc_all, centres, m.K, out=m.getGrads())
-            if reduce is not None:
-                reduce.wait()
-            lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
-            r._check(r.lib.gs_adam_step(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
-                                        C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(scale)))
+        self._shCompressedUpdate(stepCameras, own, 1.0 / total, gather, reduce, xt)
         torch.mean(self._loss_v, dim=0, out=self._loss)          # this rank's views; the step's loss is the mean over all of them
         return self._finishIteration()
 
@@ -2142,14 +2166,10 @@ class GaussianTrainer:
         fused = False
         if self._native:
             self._nativeStep(stepCameras)
-            if self.densify:
-                self.addGradientAccumulation()
             fused = True
         elif not self._exchange and self.fuse_adam:
             r._measure("bwd.fused+train.optimizer.applySingle", lambda: r.renderBackwardAdam(
                 self._cot, m.arena, m.m, m.v, getLearningRates(self.iteration, self.iterationCount), **self._depthCots()))
-            if self.densify:
-                self.addGradientAccumulation()
             fused = True
         elif not self._exchange:
             r.renderBackward(self._cot, out=m.getGrads(), **self._depthCots())
@@ -2157,12 +2177,8 @@ class GaussianTrainer:
                 g = m.getGrads()
                 r.mcmcRegularizerGrad(m.getParams()["scales"], m.getParams()["opacity"], g["scales"], g["opacity"],
                                       self._mcmcParams())
-            if self.densify:
-                self.addGradientAccumulation()
         elif self.dp_exchange == "allreduce":
             r.renderBackward(self._cot, out=m.getGrads())          # adds this view's |grad xyz| before the sum below
-            if self.densify:
-                self.addGradientAccumulation()
             self._xt_mark(xt, "wr0")                     # (a blocking collective: all of it is exposed)
             allreduce_gradients(m._gbuf[:m.numel + 1], self.pg)      # the arena and, behind it, the step's gate word
             self._xt_mark(xt, "wr1")
@@ -2182,41 +2198,20 @@ class GaussianTrainer:
                 r.renderBackwardDPBegin(self._cot, colorCot=self._cc_local)      # + this rank's word of the gate at [3 N]
                 gather = self._gatherColourCotangents(xt, inline=False)          # (runs under the projection backward below)
                 r.renderBackwardDPFinish(out=g)
-            if self.densify:
-                self.addGradientAccumulation()
             reduce = dist.all_reduce(m.grad[:m.geom_numel], op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-            centres = np.stack([np.asarray(getattr(c, "cameraCenter", c), np.float32).reshape(3) for c in stepCameras])
             if xt is not None:
                 xt["work"].update(reduce=reduce)
-            self._awaitGather(gather, xt)
-            if self.fuse_adam:
-                # SH tensors: gradient rebuild + Adam in one pass (old xyz: the geometry step comes after); then the
-                # geometry slice alone goes through gs_adam_step
-                lr = dict(zip(PARAM_ORDER, getLearningRates(self.iteration, self.iterationCount)))
-                own = [self._xyz_own[0] if q == self.rank else None for q in range(self.world)]
-                r.shGradFromViewsAdamDir(m.getParams(), self._cc_all, centres, own, m.arena, m.m, m.v, lr["features_dc"],
-                                         lr["features_rest"], 1.0 / self.world, self._xyz_add)
-                self._xt_mark(xt, "wr0")
-                reduce.wait()
-                self._xt_mark(xt, "wr1")
-                self._geometryAdam(lr, 1.0 / self.world)
-                fused = True
-            else:
-                r.shGradFromViews(m.getParams()["xyz"], self._cc_all, centres, m.K, out=g)
-                self._xt_mark(xt, "wr0")
-                reduce.wait()
-                self._xt_mark(xt, "wr1")
+            own = [self._xyz_own[0] if q == self.rank else None for q in range(self.world)] if self.fuse_adam else None
+            self._shCompressedUpdate(stepCameras, own, 1.0 / self.world, gather, reduce, xt)
+            fused = True         # (the update is done, Adam included, with or without fuse_adam)
+        if self.densify:
+            self.addGradientAccumulation()        # (the statistic's denominator: the backward above has added this view's |grad xyz|)
         if not fused and self.sparse_adam:
             # the rows the step's forward saw, and only those (rows >= N of a strided layout and the pads are left alone too)
-            lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
             widths = (C.c_int * 6)(*[max(int(m._per[k]), 1) for k in ARENA_ORDER])      # (K = 1: an empty segment, any width)
-            r._check(r.lib.gs_adam_step_visible(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
-                                                widths, C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0),
-                                                m.N, None))
+            self._arenaAdam("gs_adam_step_visible", 1.0, before=(widths,), after=(m.N, None))
         elif not fused:
-            lrs = (C.c_float * 6)(*arenaLearningRates(self.iteration, self.iterationCount))
-            r._check(r.lib.gs_adam_step(r.ctx, m.numel, _p(m.arena), _p(m.grad), _p(m.m), _p(m.v), 6, self._seg_end, lrs,
-                                        C.c_float(0.9), C.c_float(0.999), C.c_float(1e-15), C.c_float(1.0 / self.world)))
+            self._arenaAdam("gs_adam_step", 1.0 / self.world)
             if self.mcmc is not None:
                 p = m.getParams()
                 r.mcmcInjectNoise(p["xyz"], p["scales"], p["rotation"], p["opacity"],
