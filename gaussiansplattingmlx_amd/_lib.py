@@ -57,6 +57,20 @@ class gs_fisheye_lens(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "k4", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
 
 
+class gs_tsdf_grid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("trunc", C.c_float)]
+
+
+class gs_tsdf_view(C.Structure):
+    _fields_ = [("Rt", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("width", C.c_int), ("height", C.c_int), ("depth", C.c_void_p), ("color", C.c_void_p)]
+
+
+GS_TSDF_MAX_VIEWS = 8
+TSDF_MAX_DIM, TSDF_MAX_POINTS = 1024, 1 << 28
+
+
 class gs_adc_params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("grad_threshold", "percent_dense", "min_opacity", "max_screen_size", "prune_world",
                                          "scene_extent")]
@@ -196,6 +210,10 @@ _SIGS = {
     "gs_filter3d_bake": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_undistort": (C.c_int, [_vp, C.POINTER(gs_lens)] + [C.c_int] * 6 + [_vp, _vp, _vp]),
     "gs_undistort_fisheye": (C.c_int, [_vp, C.POINTER(gs_fisheye_lens)] + [C.c_int] * 6 + [_vp, _vp, _vp]),
+    "gs_tsdf_integrate": (C.c_int, [_vp, C.POINTER(gs_tsdf_grid), C.c_int, C.POINTER(gs_tsdf_view)] + [_vp] * 4),
+    "gs_tsdf_mesh_workspace_bytes": (C.c_size_t, [C.POINTER(gs_tsdf_grid)]),
+    "gs_tsdf_mesh_plan": (C.c_int, [_vp, C.POINTER(gs_tsdf_grid), _vp, _vp, C.c_float, _vp, C.c_size_t, C.POINTER(C.c_longlong)]),
+    "gs_tsdf_mesh_emit": (C.c_int, [_vp, C.POINTER(gs_tsdf_grid), _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "gs_set_mcmc": (C.c_int, [_vp, _vp]),
     "gs_mcmc_regularizer_grad": (C.c_int, [_vp, C.c_int] + [_vp] * 5),
     "gs_mcmc_inject_noise": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [C.c_float, _vp]),

@@ -36,6 +36,7 @@ SOURCES = {
     "depth_loss.hip": ["-ffp-contract=off"],
     "lens.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
+    "tsdf.hip": ["-ffp-contract=off"],
 }
 # -fno-slp-vectorize: on gfx950 v_pk_*_f32 issues at half the rate of the scalar forms, so the SLP vectoriser's packed
 # math buys nothing and pays for its operand shuffles in v_mov (measured: blend backward 0.65 -> 0.55 ms without it)

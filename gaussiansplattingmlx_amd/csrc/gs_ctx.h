@@ -343,6 +343,13 @@ struct gs_ctx {
     hipEvent_t densifyDone = nullptr;
     bool densifyPlanned = false;
     float** densifyTable = nullptr;      // device: the six tensor starts of a packed planned gather (dn_packed_table_kernel)
+    // the last gs_tsdf_mesh_plan (tsdf.hip): what gs_tsdf_mesh_emit must be called with, and the counts it writes (ws null: none)
+    struct {
+        const void* ws = nullptr;
+        gs_tsdf_grid grid = {};
+        float minWeight = 0.0f;
+        long long V = 0, F = 0;
+    } tsdfPlan;
     // counters
     uint32_t* counters = nullptr;  // device [GS_CNT_COUNT]
     uint32_t* countersHost = nullptr;  // pinned host mirror

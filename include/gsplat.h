@@ -578,6 +578,77 @@ typedef struct gs_fisheye_lens { float fx, fy, cx, cy, k1, k2, k3, k4; float dst
 int gs_undistort_fisheye(gs_ctx* ctx, const gs_fisheye_lens* lens /*HOST*/, int src_w, int src_h, int dst_w, int dst_h, int channels,
                          int mode, const void* src /*DEVICE*/, void* dst /*DEVICE*/, unsigned char* valid /*DEVICE [dst_h,dst_w] or NULL*/);
 
+/* Mesh extraction (not in the reference; tests/tsdf_numpy.py restates both halves): depth images fused
+ * into a truncated signed distance volume, then marching tetrahedra.
+ *
+ * VOLUME.  Lattice point (i, j, k) lies at origin + voxel (i, j, k), in float32 one product and one sum per axis, and has linear
+ * index i + nx (j + ny k): x is fastest in memory.  The caller owns the device arrays tsdf [n], weight [n], rgb [n, 3],
+ * cweight [n] (float32, n = nx ny nz; zeros = nothing observed); rgb and cweight are both given or both NULL.  Every dimension
+ * is 2 .. 1024 and n <= 2^28 (7 n fits 31 bits); voxel and trunc are finite and > 0, the origin finite: otherwise
+ * GS_ERR_INVALID_ARG.
+ *
+ * gs_tsdf_integrate fuses 1 .. GS_TSDF_MAX_VIEWS pinhole views.  A view is the row-major 3 x 4 world-to-view [R | t] (OpenCV
+ * axes: x right, y down, z forward), fx, fy, cx, cy (pixel i covers [i, i + 1), camera.py's convention), the image size, a device
+ * depth image [height, width] of view-space z (0, negative or non-finite = hole) and an optional device colour image
+ * [height, width, 3].  For every lattice point p and every view in order, in float32 and in this order of operations (no
+ * contraction):
+ *   x = ((R00 px + R01 py) + R02 pz) + t0, y and z likewise from rows 1 and 2; skip unless z > 0 and finite;
+ *   u = fx (x / z) + cx, v = fy (y / z) + cy; the pixel is (floor u, floor v); skip unless 0 <= floor u <= width - 1 and
+ *     0 <= floor v <= height - 1, compared as floats before any conversion (a NaN fails every test);
+ *   d = depth[pixel]; skip unless d > 0 and finite;  s = d - z; skip if s < -trunc;  f = min(1, s / trunc);
+ *   tsdf = (tsdf w + f) / (w + 1), w = w + 1 (w the voxel's weight);
+ *   where s <= trunc, a colour image is given and rgb is not NULL: rgb_c = (rgb_c cw + colour_c) / (cw + 1) per channel, then
+ *     cw = cw + 1 (cw the voxel's cweight).
+ * One lane per lattice point, its state in registers across the views of the call: the volume is read once and written once (where
+ * a view touched it) per call, and a call of k views computes bit for bit what k one-view calls compute.  A voxel no view
+ * reaches keeps every bit.  n_views outside 1 .. GS_TSDF_MAX_VIEWS, a NULL depth image, non-positive sizes, non-finite or
+ * non-positive focal lengths or non-finite other numbers return GS_ERR_INVALID_ARG.  Asynchronous on the context's stream (the
+ * views are copied into the launch), allocates nothing.
+ *
+ * EXTRACTION is marching tetrahedra on the Kuhn (Freudenthal) split: every cell (i, j, k) .. (i + 1, j + 1, k + 1) is cut into
+ * the 6 tetrahedra that are the paths (0,0,0) -> (1,1,1) adding the axes in one of their 6 permutations, taken in lexicographic
+ * order (xyz, xzy, yxz, yzx, zxy, zyx); the split is translation invariant, so neighbouring cells agree on their shared face
+ * diagonals.  Inside is tsdf < 0.  A tetrahedron is emitted iff all four corners have weight >= min_weight.  A vertex lies on one
+ * lattice edge whose endpoints differ in being inside; every lattice point OWNS the 7 edges towards (1,0,0), (0,1,0), (0,0,1),
+ * (1,1,0), (1,0,1), (0,1,1), (1,1,1) (slots 0 .. 6), and with a the owner, b the other end, f the tsdf:
+ *   t = f_a / (f_a - f_b),  position_c = p_a_c + t (p_b_c - p_a_c) per axis, p as under VOLUME;
+ *   colour_c = rgb_a_c + t (rgb_b_c - rgb_a_c); an endpoint's own colour where the other has cweight 0, 0.5 where both have.
+ * A vertex is created once, whoever uses it; only referenced vertices exist.  Vertices ascend in (owner's linear index * 7 +
+ * slot), triangles in (cell's linear index, tetrahedron 0 .. 5, triangle 0 / 1).  Triangles are counter-clockwise seen from the
+ * tsdf >= 0 side, decided from the tetrahedron's parity (the permutation's sign) and its sign pattern alone, never from
+ * positions, so zero-area triangles (a lattice value of exactly 0) are wound like their neighbours.  With the path corners
+ * numbered 0 .. 3, for an even tetrahedron (an odd one takes the rule with inside and outside exchanged):
+ *   one corner i inside: the vertices on (i, a), (i, b), (i, c), where (i, a, b, c) is an even permutation of (0, 1, 2, 3) and a
+ *     the lowest of the three; one corner i outside: those in reverse, (i, c), (i, b), (i, a);
+ *   two inside p < q, two outside r < s: the quad pr, ps, qs, qr, walked the other way round from pr (pr, qr, qs, ps) when
+ *     (p, r, s, q) is an odd permutation, split along the diagonal from its first vertex: (c0, c1, c2), (c0, c2, c3).
+ *
+ * gs_tsdf_mesh_plan marks the used edges and counts the triangles per cell, scans both (tile sums, one block over the tiles with
+ * 64-bit totals, apply), copies counts = {vertices, triangles} to the HOST and waits [sync].  More than INT32_MAX of either:
+ * GS_ERR_INVALID_ARG.  workspace is a device buffer of at least gs_tsdf_mesh_workspace_bytes(grid) bytes (0 for a grid outside
+ * the limits), 256-byte aligned.  gs_tsdf_mesh_emit, asynchronous, writes the mesh the context's LAST plan counted into caller
+ * buffers of those sizes: vertices [V, 3] float32, colors [V, 3] float32 or NULL (needs rgb and cweight), faces [F, 3] int32.  It
+ * takes the plan's workspace, grid and min_weight and the same, unchanged, tsdf and weight (anything else: GS_ERR_INVALID_ARG, or
+ * GS_ERR_NO_FORWARD without a plan); a plan of 0 vertices and 0 triangles launches nothing and reads no buffer.  Neither call
+ * allocates.  No kernel of the three uses a float atomic or orders workgroups: the output is bit-reproducible. */
+#define GS_TSDF_MAX_VIEWS 8
+typedef struct gs_tsdf_grid { float origin[3]; float voxel; int nx, ny, nz; float trunc; } gs_tsdf_grid;
+typedef struct gs_tsdf_view {
+    float Rt[12];
+    float fx, fy, cx, cy;
+    int width, height;
+    const float* depth;   /* DEVICE [height, width] */
+    const float* color;   /* DEVICE [height, width, 3] or NULL */
+} gs_tsdf_view;
+int gs_tsdf_integrate(gs_ctx* ctx, const gs_tsdf_grid* grid /*HOST*/, int n_views, const gs_tsdf_view* views /*HOST [n_views]*/,
+                      float* tsdf /*[n]*/, float* weight /*[n]*/, float* rgb /*[n,3] or NULL*/, float* cweight /*[n] or NULL*/);
+size_t gs_tsdf_mesh_workspace_bytes(const gs_tsdf_grid* grid /*HOST*/);
+int gs_tsdf_mesh_plan(gs_ctx* ctx, const gs_tsdf_grid* grid /*HOST*/, const float* tsdf, const float* weight, float min_weight,
+                      void* workspace, size_t workspace_bytes, long long* counts /*HOST [2]*/);
+int gs_tsdf_mesh_emit(gs_ctx* ctx, const gs_tsdf_grid* grid /*HOST*/, const float* tsdf, const float* weight, const float* rgb,
+                      const float* cweight, float min_weight, void* workspace, float* vertices /*[V,3]*/, float* colors /*[V,3] or NULL*/,
+                      int32_t* faces /*[F,3]*/);
+
 /* MCMC densification strategy (not in the reference; DESIGN.md "MCMC strategy"): "3D Gaussian Splatting as Markov Chain Monte
  * Carlo" (Kheradmand et al. 2024), gsplat's MCMCStrategy, with its defaults in brackets.  Notation: o = sigmoid(opacity_raw),
  * s = exp(scales_raw), R the rotation of q / (|q| + 1e-8), Sigma = R diag(s^2) R^T, N the Gaussian count.
