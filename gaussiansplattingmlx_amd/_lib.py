@@ -49,6 +49,12 @@ class gs_depth_loss_params(C.Structure):
     _fields_ = [("mode", C.c_int), ("lambda_", C.c_float), ("alpha_min", C.c_float), ("scale", C.c_float), ("offset", C.c_float)]
 
 
+class gs_normal_loss_params(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")] + [("H", C.c_int), ("W", C.c_int)] + \
+        [(n, C.c_float) for n in ("lambda_l1", "lambda_cos", "lambda_smooth", "alpha_min", "max_jump", "edge_gamma")] + \
+        [("accumulate", C.c_int)]
+
+
 class gs_lens(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
 
@@ -169,6 +175,8 @@ _SIGS = {
     "gs_loss_forward_backward": (C.c_int, [_vp] + [_vp] * 5 + [C.c_float, C.c_float] + [_vp] * 3),
     "gs_depth_loss": (C.c_int, [_vp, C.POINTER(gs_depth_loss_params)] + [_vp] * 7),
     "gs_depth_normalize": (C.c_int, [_vp, C.c_longlong, _vp, _vp, C.c_float, _vp]),
+    "gs_normal_loss": (C.c_int, [_vp, C.POINTER(gs_normal_loss_params)] + [_vp] * 9),
+    "gs_depth_normals": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_float, _vp]),
     "gs_image_metrics": (C.c_int, [_vp, C.c_int, C.c_int] + [_vp] * 4),
     "gs_colour_moments": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4),
     "gs_adam_step": (C.c_int, [_vp, C.c_longlong] + [_vp] * 4 + [C.c_int, _vp, _vp] + [C.c_float] * 4),

@@ -34,6 +34,7 @@ SOURCES = {
     "features.hip": ["-ffp-contract=off"],
     "background.hip": ["-ffp-contract=off"],
     "depth_loss.hip": ["-ffp-contract=off"],
+    "normal_loss.hip": ["-ffp-contract=off"],
     "lens.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
     "tsdf.hip": ["-ffp-contract=off"],

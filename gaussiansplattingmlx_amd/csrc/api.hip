@@ -553,7 +553,7 @@ int gs_ctx_destroy(gs_ctx* c)
     free_pair_ws(c);
     dev_free(c->segState);
     dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk); dev_free(c->wideTotal); dev_free(c->rowTotal); dev_free(c->sortBits); dev_free(c->bucketStart); dev_free(c->sortSplit[0]); dev_free(c->sortSplit[1]); dev_free(c->tileRanges); dev_free(c->tileCounts); dev_free(c->superCut);
-    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->metricsWs); dev_free(c->windowDev);
+    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->normalWs); dev_free(c->normalPartials); dev_free(c->metricsWs); dev_free(c->windowDev);
     dev_free(c->counters); dev_free(c->blockWorkOwn); dev_free(c->blockOrder); dev_free(c->fwdQueue); dev_free(c->bwdQueue); dev_free(c->segBase); dev_free(c->finalT);
     for (auto& e : c->profPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (c->countersHost) (void)hipHostFree(c->countersHost);
@@ -1794,6 +1794,67 @@ int gs_depth_normalize(gs_ctx* c, long long n_pixels, const float* depth, const 
     if (!(alpha_min >= 0.0f) || !isfinite(alpha_min)) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: alpha_min is finite and >= 0");
     if (!depth || !alpha || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normalize: null pointer");
     return launch_depth_normalize(c, n_pixels, depth, alpha, alpha_min, out);
+}
+
+// ---- normal regularisation (include/gsplat.h gs_normal_loss / gs_depth_normals; normal_loss.hip) ---------------------------
+namespace {
+bool nonneg_finite(float x) { return x >= 0.0f && isfinite(x); }
+
+// what both entry points ask of the camera, the size and the two thresholds; NULL when all is well
+const char* normal_geometry_error(const gs_normal_loss_params& p)
+{
+    if (!(p.fx > 0.0f) || !(p.fy > 0.0f) || !isfinite(p.fx) || !isfinite(p.fy)) return "fx and fy are positive and finite";
+    if (!isfinite(p.cx) || !isfinite(p.cy)) return "cx and cy are finite";
+    if (p.H <= 0 || p.W <= 0) return "H and W are positive";
+    if (!nonneg_finite(p.alpha_min)) return "alpha_min is finite and >= 0";
+    if (!nonneg_finite(p.max_jump)) return "max_jump is finite and >= 0";
+    return nullptr;
+}
+}  // namespace
+
+int gs_depth_normals(gs_ctx* c, const float* intrinsics, int H, int W, const float* depth, const float* alpha, float alpha_min,
+                     float max_jump, float* out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!intrinsics || !depth || !alpha || !out) return fail(c, GS_ERR_INVALID_ARG, "gs_depth_normals: null pointer");
+    gs_normal_loss_params p = {};
+    p.fx = intrinsics[0]; p.fy = intrinsics[1]; p.cx = intrinsics[2]; p.cy = intrinsics[3];
+    p.H = H; p.W = W; p.alpha_min = alpha_min; p.max_jump = max_jump;
+    if (const char* why = normal_geometry_error(p)) return fail(c, GS_ERR_INVALID_ARG, std::string("gs_depth_normals: ") + why);
+    return launch_depth_normals(c, p, depth, alpha, out);
+}
+
+int gs_normal_loss(gs_ctx* c, const gs_normal_loss_params* p, const float* render_depth, const float* render_alpha,
+                   const float* target_normals, const unsigned char* mask, const float* edge_image, float* loss, float* normal_out,
+                   float* cot_depth, float* cot_alpha)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!p) return fail(c, GS_ERR_INVALID_ARG, "gs_normal_loss: null params");
+    if (const char* why = normal_geometry_error(*p)) return fail(c, GS_ERR_INVALID_ARG, std::string("gs_normal_loss: ") + why);
+    if (!nonneg_finite(p->lambda_l1) || !nonneg_finite(p->lambda_cos) || !nonneg_finite(p->lambda_smooth))
+        return fail(c, GS_ERR_INVALID_ARG, "gs_normal_loss: lambda_l1, lambda_cos and lambda_smooth are finite and >= 0");
+    if (!nonneg_finite(p->edge_gamma)) return fail(c, GS_ERR_INVALID_ARG, "gs_normal_loss: edge_gamma is finite and >= 0");
+    if (p->accumulate != 0 && p->accumulate != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_normal_loss: accumulate is 0 or 1");
+    if (!render_depth || !render_alpha || !loss || !normal_out || !cot_depth || !cot_alpha)
+        return fail(c, GS_ERR_INVALID_ARG, "gs_normal_loss: null buffer");
+    { const int orc = deferred_overflow(c); if (orc) return orc; }
+    const long long want = normal_loss_ws_floats((long long)p->H * p->W);
+    if (want > c->normalWsFloats || !c->normalPartials) {      // the first call, or a larger image: a step never allocates after it
+        GS_HIP_CHECK(c, hipSetDevice(c->device));
+        if (c->normalWs) {
+            GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a queued call still works in the old buffer)
+            c->ws_bytes -= (size_t)c->normalWsFloats * sizeof(float);
+            dev_free(c->normalWs);
+        }
+        c->normalWsFloats = 0;
+        if (const int rc = dev_alloc(c, &c->normalWs, (size_t)want)) return rc;
+        c->normalWsFloats = want;
+        if (!c->normalPartials)
+            if (const int rc = dev_alloc(c, &c->normalPartials, (size_t)normal_loss_ws_doubles())) return rc;
+    }
+    GsStageTimer t(c, GS_STAGE_LOSS);
+    return launch_normal_loss(c, *p, render_depth, render_alpha, target_normals, mask, edge_image, loss, normal_out, cot_depth,
+                              cot_alpha, c->normalWs, c->normalPartials);
 }
 
 // ---- held-out evaluation (include/gsplat.h gs_image_metrics / gs_colour_moments; metrics.hip) ------------------------------

@@ -330,6 +330,9 @@ struct gs_ctx {
     const unsigned char* lossMask = nullptr;   // gs_set_loss_mask: caller-owned [H][W] per-pixel loss weights v / 255, nullptr = off
     int lossPartialBlocks = 0;
     double* depthLossWs = nullptr;    // gs_depth_loss: [depth_loss_ws_doubles()] per-block (sum, count) partials + n, allocated at the first call
+    float* normalWs = nullptr;        // gs_normal_loss: [normalWsFloats] the normals and q, 7 floats per pixel, allocated at the first
+    long long normalWsFloats = 0;     //   call, regrown only for a larger image; normalPartials: [normal_loss_ws_doubles()]
+    double* normalPartials = nullptr;
     double* metricsWs = nullptr;      // gs_image_metrics / gs_colour_moments: [metricsWsDoubles] per-block partials, allocated at the
     long long metricsWsDoubles = 0;   //   first call, regrown only for a larger image (metrics.hip metrics_ws_doubles)
     float* windowDev = nullptr;       // [121] default SSIM window
@@ -492,6 +495,12 @@ int launch_depth_loss(gs_ctx* c, int mode, float lambda, float alphaMin, float s
                       const float* alpha, const float* target, const unsigned char* mask, float* loss, float* cotDepth,
                       float* cotAlpha);
 int launch_depth_normalize(gs_ctx* c, long long n, const float* depth, const float* alpha, float alphaMin, float* out);
+long long normal_loss_ws_floats(long long np);      // normal_loss.hip
+long long normal_loss_ws_doubles();
+int launch_depth_normals(gs_ctx* c, const gs_normal_loss_params& s, const float* depth, const float* alpha, float* out);
+int launch_normal_loss(gs_ctx* c, const gs_normal_loss_params& s, const float* depth, const float* alpha, const float* target,
+                       const unsigned char* mask, const float* edge, float* loss, float* normalOut, float* cotDepth,
+                       float* cotAlpha, float* ws, double* partials);
 long long metrics_ws_doubles(int H, int W);      // metrics.hip
 int launch_image_metrics(gs_ctx* c, int H, int W, const float* render, const float* target, const unsigned char* mask, double* out);
 int launch_colour_moments(gs_ctx* c, long long n, const float* render, const float* target, const unsigned char* mask, double* out);

@@ -40,15 +40,21 @@ class TrainData:
     # a per-view array that is there.  copy.copy / copy.deepcopy keep it; dataclasses.replace() builds a new object from the fields
     # alone and would drop it -- a fisheye view would then train as a pinhole with a fisheye's focal length: use replace() below.
     cameraModelArray = None
+    # float32 [n, H, W, 3]: per-view normal priors in camera space, OpenCV axes, facing the camera (trainStep's targetNormal;
+    # DESIGN.md section 34); a hole is the zero vector.  None: no view has one.  Set by the loaders' normalRoot= after
+    # construction -- an attribute beside the fields, for cameraModelArray's reason, and carried by replace() as it is.
+    normalArray = None
 
     def getCameraParams(self):
         return self.Hs, self.Ws, self.intrinsicArray, self.c2wArray
 
     def replace(self, **changes):
-        """dataclasses.replace that keeps cameraModelArray (or takes a new one: replace(cameraModelArray=...))."""
+        """dataclasses.replace that keeps cameraModelArray and normalArray (or takes new ones: replace(cameraModelArray=...))."""
         models = changes.pop("cameraModelArray", self.cameraModelArray)
+        normals = changes.pop("normalArray", self.normalArray)
         out = dataclasses.replace(self, **changes)
         out.cameraModelArray = models
+        out.normalArray = normals
         return out
 
 
@@ -90,6 +96,51 @@ def readInverseDepth(path, resizeFactor: float = 1.0):
         img = img.resize((int(img.size[0] * resizeFactor), int(img.size[1] * resizeFactor)), Image.BILINEAR)
         inv = np.array(img, np.float32)
     return inv
+
+
+NORMAL_CONVENTIONS = ("opencv", "opengl")
+
+
+def readNormalMap(path, resizeFactor: float = 1.0, convention: str = "opencv"):
+    """A view's normal prior (trainStep's targetNormal): an 8- or 16-bit RGB PNG whose value v in [0, 1] is the component
+    2 v - 1, float32 [H, W, 3] in camera space, under the images' own bilinear resize (taken on the float components; the
+    kernel normalises).  Eight bits of precision either way: PIL has no 16-bit RGB image and hands on a 16-bit file's high
+    bytes, so a component of such a file is up to 2 / 255 off -- under a degree, below any monocular estimator's own error.
+    convention: "opencv" (x right, y down, z forward: a surface facing the camera has z < 0) takes the file as it is;
+    "opengl" (x right, y up, z backward, what most monocular estimators write) flips y and z."""
+    from PIL import Image
+    if convention not in NORMAL_CONVENTIONS:
+        raise ValueError(f'normalConvention is one of {", ".join(NORMAL_CONVENTIONS)}')
+    raw = np.array(Image.open(path))
+    if raw.ndim != 3 or raw.shape[2] < 3 or raw.dtype != np.uint8:      # (what PIL makes of an RGB or RGBA file of either depth)
+        raise ValueError(f"normal map {path}: an 8- or 16-bit RGB PNG is expected")
+    n = np.float32(2.0) * (raw[..., :3].astype(np.float32) / np.float32(255.0)) - np.float32(1.0)
+    if resizeFactor != 1.0:
+        size = (int(raw.shape[1] * resizeFactor), int(raw.shape[0] * resizeFactor))
+        n = np.stack([np.array(Image.fromarray(np.ascontiguousarray(n[..., c])).resize(size, Image.BILINEAR), np.float32)
+                      for c in range(3)], -1)
+    if convention == "opengl":
+        n = n * np.array([1.0, -1.0, -1.0], np.float32)
+    return np.ascontiguousarray(n, np.float32)
+
+
+def _check_normals(normalRoot, normalConvention, undistort, who):
+    if normalConvention not in NORMAL_CONVENTIONS:
+        raise ValueError(f'{who}: normalConvention is one of {", ".join(NORMAL_CONVENTIONS)}')
+    if normalRoot is not None and undistort:
+        raise ValueError(f"{who}: normalRoot does not go with undistort=True (resampling a view bends its rays: its normal prior "
+                         "would have to be resampled and its directions rotated, which is not done here)")
+
+
+def _stack_normals(paths, Hs, Ws, resizeFactor: float, convention: str):
+    """normalArray of the views whose normal maps are `paths` (None or a missing file: the view is all holes)."""
+    out = []
+    for p, H, W in zip(paths, Hs, Ws):
+        n = readNormalMap(p, resizeFactor, convention) if p is not None and os.path.exists(p) else np.zeros((int(H), int(W), 3), np.float32)
+        if n.shape != (int(H), int(W), 3):
+            raise ValueError(f"normal map {p}: {n.shape[1]} x {n.shape[0]} after the resize, its image is {int(W)} x {int(H)}")
+        out.append(n)
+    return np.stack(out).astype(np.float32)
 
 
 def readDepthParams(depthParams) -> dict:
@@ -311,7 +362,7 @@ def colmapReadPointSet(points3DPath):
 
 class ColmapDataLoader:
     def __init__(self, binRoot, imageRoot, maskRoot=None, depthRoot=None, depthParams=None, cameraModels: str = "reference",
-                 undistort: bool = False, fisheye=None):
+                 undistort: bool = False, fisheye=None, normalRoot=None, normalConvention: str = "opencv"):
         """cameraModels: "reference" reads cameras.bin with the reference app's model table, "colmap" with COLMAP's own
         (colmapReadCamerasAndPoses); a real COLMAP reconstruction needs "colmap".
 
@@ -333,8 +384,14 @@ class ColmapDataLoader:
         depthRoot: a directory of per-view depth priors in Inria's layout, <depthRoot>/<image stem>.png, 16-bit, value / 65536
         the inverse depth (TrainData.depthArray, the target of DepthConfig(mode="disparity")); a view without a file gets
         zeros, which the depth term's default mask (target > 0) leaves out.  depthParams: Inria's depth_params.json (the dict
-        or a path to it): a view's "scale" and "offset" go to TrainData.depthAlign, (1, 0) for a view without an entry."""
+        or a path to it): a view's "scale" and "offset" go to TrainData.depthAlign, (1, 0) for a view without an entry.
+
+        normalRoot: a directory of per-view normal priors, <normalRoot>/<image stem>.png (readNormalMap: an 8- or 16-bit RGB
+        PNG, v -> 2 v - 1, in normalConvention's axes), into TrainData.normalArray (trainStep's targetNormal; DESIGN.md section
+        34); a view without a file is all holes.  Not with undistort=True."""
         self.binRoot, self.imageRoot, self.maskRoot = binRoot, imageRoot, maskRoot
+        self.normalRoot, self.normalConvention = normalRoot, normalConvention
+        _check_normals(normalRoot, normalConvention, undistort, "ColmapDataLoader")
         self.depthRoot, self.depthParams = depthRoot, readDepthParams(depthParams)
         self.cameraModels, self.undistort, self.fisheye = cameraModels, bool(undistort), fisheye
         if cameraModels not in ("reference", "colmap"):
@@ -407,6 +464,10 @@ class ColmapDataLoader:
         pcd = PointCloud(pts.astype(np.float32), dict(R=ch[:, 0], G=ch[:, 1], B=ch[:, 2]))
         td = TrainData(Hs, Ws, intr, c2ws, rgbs, alphas, depths, masks, align)
         td.cameraModelArray = models
+        if self.normalRoot is not None:
+            stems = [os.path.splitext(os.path.relpath(p.filePath, self.imageRoot))[0] for p in poses]
+            td.normalArray = _stack_normals([os.path.join(self.normalRoot, s + ".png") for s in stems], Hs, Ws, resizeFactor,
+                                            self.normalConvention)
         return td, pcd, TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4)
 
 
@@ -447,13 +508,17 @@ def parsePLY(path):
 
 
 class NerfStudioDataLoader:
-    def __init__(self, directory, undistort: bool = False, fisheye=None):
+    def __init__(self, directory, undistort: bool = False, fisheye=None, normalRoot=None, normalConvention: str = "opencv"):
         """undistort: as ColmapDataLoader's, from the frame's k1, k2, p1, p2 or, when the frame has none of them, the file
         header's; a "camera_model" other than OPENCV or PINHOLE (or none) raises a ValueError in load().
         fisheye: None (the default: exactly the above) or "equidistant", with undistort=True: a frame whose "camera_model" is
         OPENCV_FISHEYE (or SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE) is resampled from its k1 .. k4 (missing ones 0) into the ideal
-        equidistant camera and marked "fisheye" in TrainData.cameraModelArray, as ColmapDataLoader's."""
+        equidistant camera and marked "fisheye" in TrainData.cameraModelArray, as ColmapDataLoader's.
+        normalRoot, normalConvention: as ColmapDataLoader's; a frame's normal map is <normalRoot>/<the stem of its file_path's
+        name>.png."""
         self.directory, self.undistort, self.fisheye = directory, bool(undistort), fisheye
+        self.normalRoot, self.normalConvention = normalRoot, normalConvention
+        _check_normals(normalRoot, normalConvention, undistort, "NerfStudioDataLoader")
         _check_fisheye(fisheye, undistort, "NerfStudioDataLoader")
 
     def load(self, resizeFactor: float = 1.0, whiteBackground: bool = False, readImage=readImageRGBA, undistorter=None):
@@ -500,6 +565,10 @@ class NerfStudioDataLoader:
         Hs, Ws, rgbs, alphas = _stack_frames(frames, whiteBackground)
         td = TrainData(Hs, Ws, np.stack(intr), np.stack(c2ws), rgbs[..., :3], alphas, None, masks)
         td.cameraModelArray = models
+        if self.normalRoot is not None:
+            stems = [os.path.splitext(os.path.basename(fr["file_path"]))[0] for fr in meta["frames"]]
+            td.normalArray = _stack_normals([os.path.join(self.normalRoot, s + ".png") for s in stems], Hs, Ws, resizeFactor,
+                                            self.normalConvention)
         return td, pcd, TILE_SIZE_H_W(w=int(Ws[0]) // 4, h=int(Hs[0]) // 4)
 
 

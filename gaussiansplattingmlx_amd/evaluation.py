@@ -40,10 +40,12 @@ def split_train_data(trainData, test_every: int = 8, offset: int = 0):
     """(train, test): two TrainData with every per-view array sliced by split_views; a field that is None stays None."""
     tr, te = split_views(len(trainData.Hs), test_every, offset)
 
-    models = getattr(trainData, "cameraModelArray", None)       # (an attribute beside the fields: data.TrainData)
+    models = getattr(trainData, "cameraModelArray", None)       # (attributes beside the fields: data.TrainData)
+    normals = getattr(trainData, "normalArray", None)
 
     def take(idx):
         return trainData.replace(cameraModelArray=None if models is None else np.asarray(models)[idx],
+                                 normalArray=None if normals is None else np.asarray(normals)[idx],
                                  **{f.name: (None if getattr(trainData, f.name) is None else np.asarray(getattr(trainData, f.name))[idx])
                                     for f in dataclasses.fields(trainData)})
     return take(tr), take(te)

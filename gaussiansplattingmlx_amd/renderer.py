@@ -1418,6 +1418,101 @@ class GaussianRenderer:
         self._check(self.lib.gs_depth_normalize(self.ctx, d.numel(), _p(d), _p(a), C.c_float(alpha_min), _p(out)))
         return out
 
+    # -- normal regularisation (include/gsplat.h gs_normal_loss / gs_depth_normals; normal_loss.py) -------
+    def _pinhole(self, camera, who):
+        """(fx, fy, cx, cy) of a pinhole camera: a Camera, its as_dict(), a gs_camera (the principal point read back from its
+        projection matrix's offsets, camera.py) or a sequence of the four; a fisheye one is refused."""
+        if isinstance(camera, _lib.gs_camera):
+            model = "pinhole"
+            K = (camera.focal_x, camera.focal_y, (camera.proj[8] + 1.0) * self.W / 2.0, (camera.proj[9] + 1.0) * self.H / 2.0)
+        elif isinstance(camera, dict):
+            model = camera.get("model", "pinhole")
+            K = (camera["focalX"], camera["focalY"], camera.get("principalX", self.W / 2.0), camera.get("principalY", self.H / 2.0))
+        elif hasattr(camera, "focalX"):
+            model = getattr(camera, "model", "pinhole")
+            K = (camera.focalX, camera.focalY, getattr(camera, "principalX", self.W / 2.0), getattr(camera, "principalY", self.H / 2.0))
+        else:
+            model, K = "pinhole", tuple(camera)
+            if len(K) != 4:
+                raise ValueError(f"{who}: camera is a Camera, its as_dict() or (fx, fy, cx, cy)")
+        if model != "pinhole":
+            raise ValueError(f"{who}: a {model} camera is not served: the normals of a depth image are taken along pinhole rays "
+                             "(rx, ry, 1); DESIGN.md section 34")
+        return tuple(float(x) for x in K)
+
+    def depthNormals(self, res, camera, alpha_min: float = 0.05, max_jump: float = 0.0):
+        """gs_depth_normals: the normals of a render's expected depth image D / a in camera space (OpenCV axes, facing the
+        camera), [H, W, 3]; the zero vector where a pixel has none -- the image's border, a pixel that is not depth-valid
+        (a >= alpha_min, a > 0, D > 0) or has such a neighbour, and with max_jump > 0 a depth edge.  res: a RenderResult with
+        its depth image, or a (depth, alpha) pair of [H, W] images of any one size.  A fisheye camera is refused."""
+        depth, alpha = (res.depth, res.alpha) if hasattr(res, "depth") else res
+        if depth is None:
+            raise ValueError("depthNormals: the render has no depth image (renderForward(wantDepth=True))")
+        K = self._pinhole(camera, "depthNormals")
+        d, a = self._t(depth), self._t(alpha)
+        if d.dim() == 3 and d.shape[-1] == 1:
+            d, a = d.reshape(d.shape[:2]), a.reshape(d.shape[:2])
+        if d.dim() != 2 or d.numel() != a.numel():
+            raise ValueError("depthNormals: depth and alpha are [H, W] images of one size")
+        H, W = int(d.shape[0]), int(d.shape[1])
+        out = self._empty(H, W, 3)
+        self._check(self.lib.gs_depth_normals(self.ctx, (C.c_float * 4)(*K), H, W, _p(d), _p(a), C.c_float(alpha_min),
+                                              C.c_float(max_jump), _p(out)))
+        return out
+
+    def normalLossParams(self, camera, l1_weight: float = 0.0, cos_weight: float = 0.0, smooth_weight: float = 0.0,
+                         alpha_min: float = 0.05, max_jump: float = 0.0, edge_gamma: float = 0.0, accumulate: bool = False):
+        """gs_normal_loss_params for this renderer's H x W image under a pinhole camera (a Camera, its as_dict() or
+        (fx, fy, cx, cy)): the three weights (the header's lambda_l1, lambda_cos, lambda_smooth), alpha_min, max_jump,
+        edge_gamma and whether the cotangents are added to what the buffers hold."""
+        K = self._pinhole(camera, "normalLossParams")
+        return _lib.gs_normal_loss_params(*K, self.H, self.W, float(l1_weight), float(cos_weight), float(smooth_weight),
+                                          float(alpha_min), float(max_jump), float(edge_gamma), int(bool(accumulate)))
+
+    def normalLoss(self, renderDepth, renderAlpha, camera, targetNormal, mask, edgeImage, params, out=None):
+        """gs_normal_loss on a render's depth and alpha images ([H, W] or [H, W, 1]): returns (loss, terms, cotDepth, cotAlpha),
+        terms = (L_l1, L_cos, L_s) on the device and the cotangents [H, W] as the fused backwards take them.  targetNormal:
+        [H, W, 3] in camera space, OpenCV axes, facing the camera (normalised by the kernel; squared norm < 0.25 is a hole), or
+        None: the smoothness term alone.  mask: uint8 or bool, non-zero = the pixel takes part in the prior terms, or None = all.
+        edgeImage: [H, W, 3] or None.  params: normalLossParams(camera, ...) or a dict of its keyword arguments; the camera's
+        intrinsics are taken from `camera` either way.  out: dict(loss=, terms=, cotDepth=, cotAlpha=) of buffers to use; loss is
+        the float[4] a lossForwardBackward has written -- loss[0] gains the weighted terms -- and starts at zero without out; with
+        params.accumulate the cotangents are added to what out's buffers hold (a depthLoss queued before)."""
+        if isinstance(params, _lib.gs_normal_loss_params):
+            K = self._pinhole(camera, "normalLoss")
+            p = _lib.gs_normal_loss_params(*K, self.H, self.W, params.lambda_l1, params.lambda_cos, params.lambda_smooth,
+                                           params.alpha_min, params.max_jump, params.edge_gamma, params.accumulate)
+        else:
+            p = self.normalLossParams(camera, **params)
+        P = self.H * self.W
+        rd, ra = self._t(renderDepth), self._t(renderAlpha)
+        if rd.numel() != P or ra.numel() != P:
+            raise ValueError(f"normalLoss: render depth and render alpha are [H, W] = [{self.H}, {self.W}] images")
+        tn = None if targetNormal is None else self._t(targetNormal)
+        ei = None if edgeImage is None else self._t(edgeImage)
+        for name, t in (("targetNormal", tn), ("edgeImage", ei)):
+            if t is not None and t.numel() != 3 * P:
+                raise ValueError(f"normalLoss: {name} is [H, W, 3] = [{self.H}, {self.W}, 3], or None")
+        nm = None
+        if mask is not None:
+            nm = mask if torch.is_tensor(mask) else torch.as_tensor(np.ascontiguousarray(mask))
+            if nm.dtype not in (torch.uint8, torch.bool) or nm.numel() != P:
+                raise ValueError(f"normalLoss: mask is a uint8 or bool [H, W] = [{self.H}, {self.W}] image, or None")
+            nm = nm.to(device=self.device, dtype=torch.uint8).contiguous()
+        out = out or {}
+        if p.accumulate and not ("cotDepth" in out and "cotAlpha" in out):
+            raise ValueError("normalLoss: accumulate adds to out['cotDepth'] and out['cotAlpha']: pass both")
+        loss = out["loss"] if "loss" in out else torch.zeros(4, device=self.device)
+        terms = out["terms"] if "terms" in out else self._empty(3)
+        cotDepth = out["cotDepth"] if "cotDepth" in out else self._empty(self.H, self.W)
+        cotAlpha = out["cotAlpha"] if "cotAlpha" in out else self._empty(self.H, self.W)
+        for name, t, n in (("loss", loss, 4), ("terms", terms, 3), ("cotDepth", cotDepth, P), ("cotAlpha", cotAlpha, P)):
+            if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device or t.numel() != n:
+                raise ValueError(f"normalLoss: out[{name!r}] is a contiguous float32 device tensor of {n} elements")
+        self._check(self.lib.gs_normal_loss(self.ctx, C.byref(p), _p(rd), _p(ra), _p(tn), _p(nm), _p(ei), _p(loss), _p(terms),
+                                            _p(cotDepth), _p(cotAlpha)))
+        return loss, terms, cotDepth, cotAlpha
+
     # -- held-out evaluation (include/gsplat.h gs_image_metrics / gs_colour_moments, DESIGN.md section 24; evaluation.py) ------
     def _metric_mask(self, who, mask, H, W):
         """A uint8 or bool [H, W] mask, tensor or array, as the contiguous uint8 device tensor the kernels read (itself if it is one)."""

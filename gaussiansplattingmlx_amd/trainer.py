@@ -534,6 +534,7 @@ def _require_single_device(feature, views_per_rank, process_group, dp_bootstrap,
 _FEATURES = {
     "sh_schedule": ((".sh_schedule", "an SHDegreeSchedule"), "sh_schedule", (), False),
     "depth": ((".depth_loss", "a DepthConfig"), "depth", (), False),
+    "normal": ((".normal_loss", "a NormalConfig"), "normal", (), False),
     "background": ((".background", "a BackgroundConfig"), "background", (), False),
     "sparse_adam": (None, "sparse_adam", (
         ("mcmc", "sparse_adam: the reference strategy only (strategy='mcmc' moves every Gaussian every step)"),
@@ -583,7 +584,7 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None, sh_schedule=None):
+                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None, sh_schedule=None, normal=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -712,6 +713,19 @@ class GaussianTrainer:
         single-device steps with one view only.  Off (the default): no kernel, launch, buffer or result differs, and the step
         still renders without a depth image.
 
+        normal: normal regularisation from the rendered depth (normal_loss.NormalConfig, include/gsplat.h gs_normal_loss,
+        DESIGN.md section 34; the normal terms of DN-Splatter, MonoSDF and VCR-GauS, the smoothness the surface methods beside
+        mesh.extract_mesh train with).  From iteration normal.start on every step renders WITH the depth image under
+        depth_gradient = 1 (put back behind the step, also when it raises), runs the colour loss as always, the depth term where
+        depth= is set, and then gs_normal_loss on the render's depth and alpha: the L1 and cosine terms against trainStep's
+        targetNormal (under normalMask) and the smoothness term between neighbouring pixels, weighted on the step's target
+        colour by normal.edge_gamma.  A step without targetNormal runs the smoothness term alone.  The term's two cotangents go
+        to the backward beside the colour's -- added to the depth term's where there is one, which then always writes an alpha
+        cotangent, zeros in its accumulated mode --, a repeated forward repeats the term, loss[0] includes the weighted terms
+        and lastNormalTerms holds (L_l1, L_cos, L_s).  Pinhole cameras only.  It composes with what depth= composes with;
+        single-device steps with one view only.  Before normal.start, and with None (the default): no kernel, launch, buffer
+        or result differs.
+
         strategy="adc", adc: adaptive density control, the densification of the original 3DGS (adc.ADCConfig, include/gsplat.h
         gs_set_adc_stats; Inria's densify_and_prune and reset_opacity, gsplat's DefaultStrategy) with the
         settings `adc` -- required, for its scene_extent (adc.scene_extent(cameras)).  The trainer owns three [N] accumulators
@@ -750,10 +764,13 @@ class GaussianTrainer:
 
         self.lastSHDegree = None
         self._depthStep = None          # the running step's depth inputs (trainStep sets and clears it)
+        self._normalStep = None         # the running step's normal term, from iteration normal.start on (the same)
+        self._normalTerms = None        # (L_l1, L_cos, L_s) of the last step that ran the term, on the device
         self.lastBackground = None
         self._bgTarget = None
         self._bgSource = None
-        self.sh_schedule, self.depth, self.background = admit("sh_schedule", sh_schedule), admit("depth", depth), admit("background", background)
+        self.sh_schedule, self.depth, self.normal = admit("sh_schedule", sh_schedule), admit("depth", depth), admit("normal", normal)
+        self.background = admit("background", background)
         if not isinstance(sparse_adam, bool):
             raise ValueError("sparse_adam is True or False")
         self.sparse_adam = sparse_adam
@@ -1769,7 +1786,7 @@ class GaussianTrainer:
                                 counts, version, source, self.viewsPerRank)
 
     def trainStep(self, camera, targetRGB, stepCameras=None, viewKey=None, targetAlpha=None, lossMask=None, targetDepth=None,
-                  depthMask=None, depthAlign=(1.0, 0.0)):
+                  depthMask=None, depthAlign=(1.0, 0.0), targetNormal=None, normalMask=None):
         """One iteration: forward, loss, backward, (gradient exchange), Adam.  Asynchronous; returns the device
         loss[4].  stepCameras: the cameras of ALL ranks for this step in rank order (every rank derives them from the
         shared view permutation, see view_for), or just their centres [R,3]; required by the sh_compressed exchange.
@@ -1800,7 +1817,12 @@ class GaussianTrainer:
         targetDepth: the view's depth map, [H, W], with a trainer built with depth= (and only then): a metric depth in the
         accumulated and expected modes, an inverse depth in the disparity mode.  depthMask: uint8 or bool [H, W], non-zero =
         the pixel takes part in the depth term; None means targetDepth > 0 (sensor holes are 0).  depthAlign = (scale, offset):
-        the term compares with scale * targetDepth + offset (Inria's depth_params.json pair; TrainData.depthAlign)."""
+        the term compares with scale * targetDepth + offset (Inria's depth_params.json pair; TrainData.depthAlign).
+
+        targetNormal: the view's normal prior, [H, W, 3] in camera space (OpenCV axes, facing the camera; TrainData.normalArray),
+        with a trainer built with normal= (and only then); a pixel of squared norm < 0.25 is a hole.  None: the step runs the
+        smoothness term alone.  normalMask: uint8 or bool [H, W], non-zero = the pixel takes part in the prior terms; None = all.
+        The smoothness pairs are weighted on the step's target colour (normal.edge_gamma)."""
         if getattr(camera, "model", "pinhole") == "fisheye":
             # (include/gsplat.h gs_set_camera_model: the fisheye model has no pose, filter or data-parallel kernels)
             for on, name in ((self.pose_opt, "pose_opt"), (self.filter_3d, "filter_3d")):
@@ -1827,6 +1849,13 @@ class GaussianTrainer:
                              "trainStep: a trainer built with depth= needs targetDepth (the view's depth map, [H, W])")
         if depth is None and depthMask is not None:
             raise ValueError("trainStep: depthMask goes with a trainer built with depth=DepthConfig(...)")
+        normal = self.normal
+        if normal is None and (targetNormal is not None or normalMask is not None):
+            raise ValueError("trainStep: targetNormal and normalMask go with a trainer built with normal=NormalConfig(...)")
+        if normal is not None and getattr(camera, "model", "pinhole") != "pinhole":
+            raise ValueError("trainStep: normal= takes pinhole cameras only (the normals of a depth image are taken along "
+                             "pinhole rays; a fisheye camera is not served)")
+        normalOn = normal is not None and self.iteration >= normal.start
         profiled = self.enableIntervalProfiling and (self.iteration % self.profilingLogInterval == 0
                                                      or self.iteration == self.iterationCount - 1)
         step = self._profiledStep if profiled else (self._trainStepMulti if self.viewsPerRank > 1 else self._trainStep)
@@ -1847,7 +1876,9 @@ class GaussianTrainer:
             try:
                 if depth is not None:
                     self._depthStep = self._depthInputs(targetDepth, depthMask, depthAlign)
-                lent.set(depth_gradient=0 if depth is None else 1)
+                lent.set(depth_gradient=0 if depth is None and not normalOn else 1)
+                if normalOn:
+                    self._normalStep = self._normalInputs(camera, targetRGB, targetNormal, normalMask)
                 if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
                     lent.set(mcmc=self._mcmcParams())
                 if self.filter_3d:
@@ -1867,7 +1898,7 @@ class GaussianTrainer:
                         self._collectiveOverflowCheck()
                 return self._retryOnOverflow(lambda: step(camera, targetRGB, stepCameras, viewKey), recover=not self._exchange)
             finally:
-                self._depthStep = None
+                self._depthStep = self._normalStep = None
 
     def _depthInputs(self, targetDepth, depthMask, depthAlign):
         """The step's depth target and mask on the device and its gs_depth_loss_params."""
@@ -1898,6 +1929,45 @@ class GaussianTrainer:
         r._measure("train.loss.depth", lambda: r.depthLoss(
             res.depth, None if self._cotAlpha is None else res.alpha, d["target"], d["mask"], d["params"],
             out=dict(loss=lossOut, cotDepth=self._cotDepth, cotAlpha=self._cotAlpha)))
+
+    def _normalInputs(self, camera, targetRGB, targetNormal, normalMask):
+        """The step's normal prior, mask and edge image on the device and its gs_normal_loss_params.  The first step that runs
+        the term allocates what it needs: the two cotangent images (where depth= has not) and the three terms."""
+        r, cfg = self.gaussRender, self.normal
+        tn = nm = None
+        if targetNormal is not None:
+            tn = r._t(targetNormal)
+            if tn.numel() != 3 * r.H * r.W:
+                raise ValueError(f"trainStep: targetNormal is [H, W, 3] = [{r.H}, {r.W}, 3]")
+        if normalMask is not None:
+            nm = normalMask if torch.is_tensor(normalMask) else torch.as_tensor(np.ascontiguousarray(normalMask))
+            if nm.dtype not in (torch.uint8, torch.bool) or nm.numel() != r.H * r.W:
+                raise ValueError(f"trainStep: normalMask is a uint8 or bool [H, W] = [{r.H}, {r.W}] image, or None")
+            nm = nm.to(device=r.device, dtype=torch.uint8).contiguous()
+        l1, cos, smooth = cfg.weights_at(self.iteration, self.iterationCount)
+        params = r.normalLossParams(camera, l1, cos, smooth, cfg.alpha_min, cfg.max_jump, cfg.edge_gamma,
+                                    accumulate=self._depthStep is not None)
+        edge = r._t(targetRGB) if cfg.edge_gamma > 0.0 and smooth > 0.0 else None
+        if self._cotDepth is None:
+            self._cotDepth = r._empty(r.H, r.W)
+        if self._cotAlpha is None:      # (with depth= in the accumulated mode too: its term then writes the zeros this one adds to)
+            self._cotAlpha = r._empty(r.H, r.W)
+        if self._normalTerms is None:
+            self._normalTerms = r._empty(3)
+        return dict(camera=camera, target=tn, mask=nm, edge=edge, params=params)
+
+    def _normalLoss(self, res, lossOut):
+        """gs_normal_loss behind the colour loss that wrote lossOut, and behind the depth term where there is one (its cotangents
+        are then added to): lossOut[0], self._normalTerms and the step's two cotangents."""
+        r, d = self.gaussRender, self._normalStep
+        r._measure("train.loss.normal", lambda: r.normalLoss(
+            res.depth, res.alpha, d["camera"], d["target"], d["mask"], d["edge"], d["params"],
+            out=dict(loss=lossOut, terms=self._normalTerms, cotDepth=self._cotDepth, cotAlpha=self._cotAlpha)))
+
+    @property
+    def lastNormalTerms(self):
+        """(L_l1, L_cos, L_s) of the last step that ran the normal term, a device tensor; None before the first."""
+        return self._normalTerms
 
     def _compositeTarget(self, targetRGB, targetAlpha, b):
         """The step's target: targetRGB over b by targetAlpha, in the trainer's own buffer (allocated once)."""
@@ -2037,7 +2107,7 @@ class GaussianTrainer:
         in self._cot -- with depth= also the depth term and the depth and alpha cotangents; the forward is repeated once if it overflowed on the view's first visit, and once without depth cuts if
         it missed under them."""
         r, m = self.gaussRender, self.model
-        wd = self._depthStep is not None          # (without a depth term the step renders no depth image)
+        wd = self._depthStep is not None or self._normalStep is not None      # (without a depth or normal term the step renders no depth image)
         res = r._measure("train.forward", lambda: r.renderForward(m.getParams(), camera, viewKey=viewKey, wantDepth=wd))
         if viewKey is not None and viewKey not in self._checked_views:
             # first visit of a view: its pair count is unknown -- wait for the forward once and make sure it fitted
@@ -2048,8 +2118,7 @@ class GaussianTrainer:
         r._measure("train.loss.total", lambda: r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim,
                                                                       out=dict(loss=lossOut, cotColor=self._cot),
                                                                       targetKey=self._lossTargetKey(viewKey)))
-        if wd:
-            self._depthLoss(res, lossOut)
+        self._depthTerms(res, lossOut)
         # depth cuts (renderer.renderForward): nothing that changes state has been queued yet; the loss kernel above
         # keeps the GPU busy while the host learns whether the forward has to be repeated in full
         if viewKey is not None and r.forwardMissed():
@@ -2057,8 +2126,14 @@ class GaussianTrainer:
             res = r.renderForward(m.getParams(), camera, viewKey=viewKey, depthCuts=False, wantDepth=wd)
             r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim, out=dict(loss=lossOut, cotColor=self._cot),
                                   targetKey=self._lossTargetKey(viewKey))
-            if wd:
-                self._depthLoss(res, lossOut)
+            self._depthTerms(res, lossOut)
+
+    def _depthTerms(self, res, lossOut):
+        """The terms on the render's depth and alpha images, behind the colour loss: the depth term, then the normal term."""
+        if self._depthStep is not None:
+            self._depthLoss(res, lossOut)
+        if self._normalStep is not None:
+            self._normalLoss(res, lossOut)
 
     def _geometryAdam(self, lr: dict, scale: float):
         """Adam on the geometry slice after the all-reduce; the xyz segment's gradient = reduced + the view-direction terms the
@@ -2149,7 +2224,7 @@ class GaussianTrainer:
 
     def _depthCots(self) -> dict:
         """The backward's depth and alpha cotangents: none without a depth term (the calls are then today's)."""
-        if self._depthStep is None:
+        if self._depthStep is None and self._normalStep is None:
             return {}
         return dict(cotDepth=self._cotDepth, cotAlpha=self._cotAlpha)
 

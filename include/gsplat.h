@@ -965,6 +965,72 @@ int gs_depth_loss(gs_ctx* ctx, const gs_depth_loss_params* p /*HOST*/, const flo
 int gs_depth_normalize(gs_ctx* ctx, long long n_pixels, const float* depth /*DEVICE [n]*/, const float* alpha /*DEVICE [n]*/,
                        float alpha_min, float* out /*DEVICE [n]*/);
 
+/* Normal regularisation from the render's depth and alpha images (tests/normal_loss_numpy.py restates it):
+ * the normals of the expected depth image z = D / a, supervised by a normal prior (DN-Splatter's and MonoSDF's L1 and cosine
+ * terms) and smoothed (a cosine term between neighbours, weighted by the edges of an image), as the methods that extract meshes
+ * from splats train.  The call hands the fused backwards the cotangents of D and a, as gs_depth_loss does.
+ *
+ * Rays and depth.  A pinhole camera with OpenCV axes (x right, y down, z forward) and camera.py's pixel convention: pixel (i, j),
+ * column i and row j, has rx = ((i + 0.5) - cx) / fx and ry = ((j + 0.5) - cy) / fy.  A pixel is DEPTH-VALID iff a >= alpha_min,
+ * a > 0 and D > 0; its expected depth is z = D / a.
+ *
+ * The normal.  A pixel has a normal iff it is interior (1 <= i <= W - 2, 1 <= j <= H - 2), it and its four neighbours are
+ * depth-valid and, with max_jump > 0, max(|z+ - z-|, |zd - zu|) <= max_jump z (depth edges are left out).  With the right / left
+ * neighbours' z+, z- and the lower / upper neighbours' zd, zu:
+ *   A = z+ - z-,  S = (z+ + z-) / fx,  B = zd - zu,  T = (zd + zu) / fy
+ *   m = (A T, B S, -(A T rx + B S ry + S T)),  n = m / |m|   (no normal if |m| = 0)
+ * which is (P_down - P_up) x (P_right - P_left) of the back-projected points, written so that only A and B cancel.  It faces the
+ * camera: n . (rx, ry, 1) < 0.
+ *
+ * The terms.  Nt is the target normal in camera space, OpenCV axes, facing the camera; it is normalised here, and a target of
+ * squared norm < 0.25 is a hole.  mask: uint8, non-zero = the pixel takes part in the prior terms, NULL = all; the term's own
+ * mask, not gs_set_loss_mask's.  Vp = the pixels with a normal, a target that is no hole and the mask set; the pairs are the
+ * horizontally or vertically adjacent pixels that both have a normal (neither mask nor target enters).
+ *   L_l1  = sum_Vp |n - Nt|_1 / max(#Vp, 1e-6)                 (its gradient: sign 0 on a tie)
+ *   L_cos = sum_Vp (1 - n . Nt) / max(#Vp, 1e-6)
+ *   L_s   = sum_pairs w_pq (1 - n_p . n_q) / max(#pairs, 1e-6),  w_pq = exp(-edge_gamma mean_c |I_p - I_q|)
+ * I is edge_image (the trainer passes the step's target colour); w_pq is exactly 1 with edge_image NULL or edge_gamma = 0.  The
+ * smoothness term is the cosine form on purpose: an L1 total variation has its kink exactly where the term drives the scene
+ * (n_p = n_q).  normal_out[3] = (L_l1, L_cos, L_s); loss[0] += lambda_l1 L_l1 + lambda_cos L_cos + lambda_smooth L_s (read and
+ * written: the call is queued behind the loss that wrote it; loss[1..3] are left alone).  target_normals NULL: the prior terms
+ * are skipped, L_l1 = L_cos = 0, whatever their weights.
+ *
+ * Cotangents.  g_n of a pixel is the derivative by its normal of the weighted sum: from its own prior terms and its four pairs.
+ *   g_m = (g_n - n (n . g_n)) / |m|
+ *   g_A = g_m . (T, 0, -T rx),  g_T = g_m . (A, 0, -(A rx + S)),  g_B = g_m . (0, S, -S ry),  g_S = g_m . (0, B, -(B ry + T))
+ *   q+ = g_A + g_S / fx,  q- = -g_A + g_S / fx,  qd = g_B + g_T / fy,  qu = -g_B + g_T / fy
+ * and a pixel GATHERS what it is to its neighbours: g_z(i, j) = q+(i-1, j) + q-(i+1, j) + qd(i, j-1) + qu(i, j+1),
+ * cot_depth = g_z / a, cot_alpha = -g_z D / a^2, both exactly 0 where the pixel is not depth-valid.  Border pixels have no normal
+ * but do receive cotangents.  accumulate = 0: EVERY element of both images is written, zeros included.  accumulate = 1: the values
+ * are added to what the images hold (a gs_depth_loss queued before this call wrote them).
+ *
+ * Five launches (normals; per-block partial sums, in double, the counts exact; one workgroup that finishes them; q; the gather),
+ * every one a grid-stride loop, no float atomics -- two calls on the same inputs give the same bits --, no wait.  The first call
+ * allocates the workspace in the ctx (7 floats per pixel and 20 KB of partials); a later one only when a larger image needs more
+ * (it then waits for the stream).  H and W are the params' own.  GS_ERR_INVALID_ARG with the reason in gs_last_error: a NULL
+ * params, render_depth, render_alpha, loss, normal_out, cot_depth or cot_alpha; fx or fy not positive and finite, cx or cy not
+ * finite, H or W <= 0; a weight, alpha_min, max_jump or edge_gamma negative or not finite; accumulate other than 0 or 1.
+ * No reference call site (the reference app has no normal term). */
+typedef struct gs_normal_loss_params {
+    float fx, fy, cx, cy;
+    int H, W;
+    float lambda_l1, lambda_cos, lambda_smooth;
+    float alpha_min;
+    float max_jump;
+    float edge_gamma;
+    int accumulate;
+} gs_normal_loss_params;
+int gs_normal_loss(gs_ctx* ctx, const gs_normal_loss_params* p /*HOST*/, const float* render_depth /*DEVICE [H,W]*/,
+                   const float* render_alpha /*DEVICE [H,W]*/, const float* target_normals /*DEVICE [H,W,3] or NULL*/,
+                   const unsigned char* mask /*DEVICE [H,W] or NULL = all*/, const float* edge_image /*DEVICE [H,W,3] or NULL*/,
+                   float* loss /*DEVICE [4], read and written*/, float* normal_out /*DEVICE [3]*/,
+                   float* cot_depth /*DEVICE [H,W]*/, float* cot_alpha /*DEVICE [H,W]*/);
+/* The forward alone, for a viewer: out = the normal above, the zero vector where a pixel has none.  intrinsics = (fx, fy, cx, cy).
+ * One launch on the ctx stream, allocates nothing.  GS_ERR_INVALID_ARG: a NULL pointer, and what gs_normal_loss refuses of the
+ * camera, the size, alpha_min and max_jump. */
+int gs_depth_normals(gs_ctx* ctx, const float* intrinsics /*HOST [4]*/, int H, int W, const float* depth /*DEVICE [H,W]*/,
+                     const float* alpha /*DEVICE [H,W]*/, float alpha_min, float max_jump, float* out /*DEVICE [H,W,3]*/);
+
 /* Held-out evaluation (tests/metrics_numpy.py restates both calls): the sums behind the PSNR and the SSIM
  * that 3DGS papers report, of a render against its target, in one pass and without a statistic map in device memory.  Both images
  * are clamped to [0, 1] first, as Inria's render.py / metrics.py do; r and g below are the clamped render and target.  mask:
