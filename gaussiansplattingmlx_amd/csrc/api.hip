@@ -17,39 +17,24 @@ int fail(gs_ctx* c, int code, const std::string& msg)
     return code;
 }
 
-template <class T>
-int dev_alloc(gs_ctx* c, T** p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    GS_HIP_CHECK(c, hipMalloc((void**)p, count * sizeof(T)));
-    c->ws_bytes += count * sizeof(T);
-    return GS_OK;
-}
-
-template <class T>
-void dev_free(T*& p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
+// what a regrow of the per-Gaussian workspace replaces
 void free_gaussian_ws(gs_ctx* c)
 {
-    dev_free(c->packed12); dev_free(c->gradAcc16);
-    dev_free(c->depthKey[0]); dev_free(c->depthKey[1]); dev_free(c->depthVal[0]); dev_free(c->depthVal[1]);
-    dev_free(c->tilesTouched); dev_free(c->tileRect); dev_free(c->tilePieces); dev_free(c->waveSeg); dev_free(c->scanPrefix); dev_free(c->scanTmp); dev_free(c->blockSums);
-    dev_free(c->visPerBlock); dev_free(c->dropPerBlock);
-    dev_free(c->bucketId);
-    dev_free(c->densifyTiles);
-    c->densifyTileCap = 0;
+    ctx_free(c, c->packed12); ctx_free(c, c->gradAcc16);
+    for (int i = 0; i < 2; i++) { ctx_free(c, c->depthKey[i]); ctx_free(c, c->depthVal[i]); }
+    ctx_free(c, c->tilesTouched); ctx_free(c, c->tileRect); ctx_free(c, c->tilePieces); ctx_free(c, c->waveSeg);
+    ctx_free(c, c->scanPrefix); ctx_free(c, c->scanTmp); ctx_free(c, c->blockSums);
+    ctx_free(c, c->visPerBlock); ctx_free(c, c->dropPerBlock);
+    ctx_free(c, c->bucketId);
+    ctx_free(c, c->densifyTiles);
+    c->densifyInts = 0;
 }
 
+// ... and of the per-pair workspace (the checkpoint arena, segState, is not part of it: ensure_arena)
 void free_pair_ws(gs_ctx* c)
 {
-    // (the checkpoint arena, segState, is not part of it: ensure_arena / gs_ctx_destroy)
-    dev_free(c->pairKey[0]); dev_free(c->pairKey[1]); dev_free(c->pairVal[0]); dev_free(c->pairVal[1]);
-    dev_free(c->segSlot); dev_free(c->itemBlock); dev_free(c->itemRow);
+    for (int i = 0; i < 2; i++) { ctx_free(c, c->pairKey[i]); ctx_free(c, c->pairVal[i]); }
+    ctx_free(c, c->segSlot); ctx_free(c, c->itemBlock); ctx_free(c, c->itemRow);
 }
 
 // The checkpoint arena of the fused blend (blend_v2.hip): slots are taken as they are written, so the arena is sized
@@ -64,11 +49,7 @@ int ensure_arena(gs_ctx* c)
     if (want > c->segCap * 4) want = c->segCap * 4;
     if (want < c->qslotWanted) want = c->qslotWanted;
     if (want <= c->qslotCap) return GS_OK;
-    GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (c->segState) { c->ws_bytes -= (size_t)c->qslotCap * 5 * 64 * sizeof(float); dev_free(c->segState); }
-    const int rc = dev_alloc(c, &c->segState, (size_t)want * 5 * 64);
-    if (rc) { c->qslotCap = 0; return rc; }
-    c->qslotCap = want;
+    if (const int rc = ctx_grow(c, &c->segState, &c->qslotCap, want, 5 * 64)) return rc;
     c->fwd.valid = false;
     return GS_OK;
 }
@@ -82,24 +63,23 @@ int ensure_capacity(gs_ctx* c, int N, long long M)
         free_gaussian_ws(c);
         const size_t n = (size_t)N;
         int rc;
-        if ((rc = dev_alloc(c, &c->packed12, n * 12))) return rc;
-        if ((rc = dev_alloc(c, &c->gradAcc16, n * 16))) return rc;
+        if ((rc = ctx_alloc(c, &c->packed12, n * 12))) return rc;
+        if ((rc = ctx_alloc(c, &c->gradAcc16, n * 16))) return rc;
         for (int i = 0; i < 2; i++) {
-            if ((rc = dev_alloc(c, &c->depthKey[i], n))) return rc;
-            if ((rc = dev_alloc(c, &c->depthVal[i], n))) return rc;
+            if ((rc = ctx_alloc(c, &c->depthKey[i], n))) return rc;
+            if ((rc = ctx_alloc(c, &c->depthVal[i], n))) return rc;
         }
-        if ((rc = dev_alloc(c, &c->tilesTouched, n))) return rc;
-        if ((rc = dev_alloc(c, &c->tileRect, n))) return rc;
-        if ((rc = dev_alloc(c, &c->tilePieces, n))) return rc;
-        if ((rc = dev_alloc(c, &c->waveSeg, (n / 64 + 8) * GS_EXPAND_SLICES))) return rc;
-        if ((rc = dev_alloc(c, &c->scanPrefix, (n / 64 + 16) * GS_EXPAND_SLICES))) return rc;
-        if ((rc = dev_alloc(c, &c->scanTmp, (n / 64 + 16) * GS_EXPAND_SLICES / 1024 + 8))) return rc;
+        if ((rc = ctx_alloc(c, &c->tilesTouched, n))) return rc;
+        if ((rc = ctx_alloc(c, &c->tileRect, n))) return rc;
+        if ((rc = ctx_alloc(c, &c->tilePieces, n))) return rc;
+        if ((rc = ctx_alloc(c, &c->waveSeg, (n / 64 + 8) * GS_EXPAND_SLICES))) return rc;
+        if ((rc = ctx_alloc(c, &c->scanPrefix, (n / 64 + 16) * GS_EXPAND_SLICES))) return rc;
+        if ((rc = ctx_alloc(c, &c->scanTmp, (n / 64 + 16) * GS_EXPAND_SLICES / 1024 + 8))) return rc;
         const size_t nb = n / GS_SCAN_BLOCK + 2;
-        if ((rc = dev_alloc(c, &c->blockSums, nb))) return rc;
-        if ((rc = dev_alloc(c, &c->visPerBlock, n / 128 + 2))) return rc;
-        dev_free(c->dropPerBlock);
-        if ((rc = dev_alloc(c, &c->dropPerBlock, n / 128 + 2))) return rc;
-        if ((rc = dev_alloc(c, &c->bucketId, n + 16))) return rc;
+        if ((rc = ctx_alloc(c, &c->blockSums, nb))) return rc;
+        if ((rc = ctx_alloc(c, &c->visPerBlock, n / 128 + 2))) return rc;
+        if ((rc = ctx_alloc(c, &c->dropPerBlock, n / 128 + 2))) return rc;
+        if ((rc = ctx_alloc(c, &c->bucketId, n + 16))) return rc;
         c->capN = N;
         grewN = true;
     }
@@ -108,20 +88,20 @@ int ensure_capacity(gs_ctx* c, int N, long long M)
         free_pair_ws(c);
         int rc;
         for (int i = 0; i < 2; i++) {
-            if ((rc = dev_alloc(c, &c->pairKey[i], (size_t)M))) return rc;
-            if ((rc = dev_alloc(c, &c->pairVal[i], (size_t)M))) return rc;
+            if ((rc = ctx_alloc(c, &c->pairKey[i], (size_t)M))) return rc;
+            if ((rc = ctx_alloc(c, &c->pairVal[i], (size_t)M))) return rc;
         }
         if (c->fast16) {
             // saved-state slots: sum over pixel blocks of ceil(list/SEG)-1 <= (pairs seen by pixel blocks)/SEG
             const long long blocksPerTile = (long long)(c->tileW / 16) * (c->tileH / 16);
             c->segCap = M / GS_SEG_LEN * blocksPerTile + 16;
             c->itemCap = c->segCap + c->numPixBlocks;
-            if ((rc = dev_alloc(c, &c->segSlot, (size_t)c->segCap * 4))) return rc;
+            if ((rc = ctx_alloc(c, &c->segSlot, (size_t)c->segCap * 4))) return rc;
             // (entries are only ever read where this forward wrote them; zeroed once so that a backward run on a
             // forward that overflowed -- host errors off -- reads slot 0, never an address out of bounds)
             GS_HIP_CHECK(c, hipMemset(c->segSlot, 0, (size_t)c->segCap * 4 * sizeof(uint32_t)));
-            if ((rc = dev_alloc(c, &c->itemBlock, (size_t)c->itemCap))) return rc;
-            if ((rc = dev_alloc(c, &c->itemRow, (size_t)c->itemCap))) return rc;
+            if ((rc = ctx_alloc(c, &c->itemBlock, (size_t)c->itemCap))) return rc;
+            if ((rc = ctx_alloc(c, &c->itemRow, (size_t)c->itemCap))) return rc;
         }
         c->capM = M;
         grewM = true;
@@ -130,12 +110,12 @@ int ensure_capacity(gs_ctx* c, int N, long long M)
         const long long big = c->capM > c->capN ? c->capM : c->capN;
         const int nb = gs_div_up(big, GS_SORT_TILE) + 1;
         if (nb > c->nbCap) {
-            dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk);
-            int rc = dev_alloc(c, &c->hist, (size_t)256 * nb);
+            ctx_free(c, c->hist); ctx_free(c, c->wideCnt); ctx_free(c, c->wideChunk);
+            int rc = ctx_alloc(c, &c->hist, (size_t)256 * nb);
             if (rc) return rc;
             if (c->T <= GS_WIDE_BINS) {      // the one-pass tile sort's count tables (binning.hip)
-                if ((rc = dev_alloc(c, &c->wideCnt, (size_t)GS_WIDE_BINS * nb))) return rc;
-                if ((rc = dev_alloc(c, &c->wideChunk, (size_t)GS_WIDE_BINS * (nb / GS_WIDE_CHUNK + 2)))) return rc;
+                if ((rc = ctx_alloc(c, &c->wideCnt, (size_t)GS_WIDE_BINS * nb))) return rc;
+                if ((rc = ctx_alloc(c, &c->wideChunk, (size_t)GS_WIDE_BINS * (nb / GS_WIDE_CHUNK + 2)))) return rc;
             }
             c->nbCap = nb;
         }
@@ -282,7 +262,7 @@ int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* co
                                           "gs_render_forward)");
     GsStageTimer t(c, GS_STAGE_BLEND_BWD);
     c->absgradN = -1;
-    if (!c->fast16) return launch_blend_backward(c, c->fwd.bg, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+    if (!c->fast16) return launch_blend_backward(c, c->fwd.modes.bg, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
     if (const int rc = launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
                                                 c->fwd.outAlpha, absgrad))
         return rc;
@@ -312,7 +292,7 @@ int sh_views_args(gs_ctx* c, const char* who, int N, int K, int R, const float* 
 {
     if (N < 0 || K < 1 || R < 1 || R > 16 || !cam_centers || own_bad)
         return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": bad N/K/R");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
+    if ((c->modes.degree + 1) * (c->modes.degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
     if (N > 0 && (!xyz || !color_cot_all || !dc || (K > 1 && !rest) || own_null))
         return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": null buffer");
     return GS_OK;
@@ -354,7 +334,7 @@ int sh_in_arena(gs_ctx* c, const char* who, int N, int K, const float* dc, const
 // correction's setter -- a step never allocates
 int ensure_corrected_image(gs_ctx* c)
 {
-    return c->correctedImage ? GS_OK : dev_alloc(c, &c->correctedImage, (size_t)3 * c->H * c->W);
+    return c->correctedImage ? GS_OK : ctx_alloc(c, &c->correctedImage, (size_t)3 * c->H * c->W);
 }
 
 // gs_copy_overflow_flag: a one-thread kernel, not hipMemcpyAsync -- the runtime's device-to-device copy is a blit kernel
@@ -389,45 +369,51 @@ struct RealGeomScope {
 
 }  // namespace
 
+// the context's allocator (gs_mem.h): the one place the library's own buffers reach HIP's
+static int hip_device_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+static int hip_device_free(void* p) { return (int)hipFree(p); }
+static int hip_pinned_alloc(void** p, size_t bytes, unsigned flags) { return (int)hipHostMalloc(p, bytes, flags); }
+static int hip_pinned_free(void* p) { return (int)hipHostFree(p); }
+const GsMemBackend* gs_hip_mem_backend()
+{
+    static const GsMemBackend hip = {hip_device_alloc, hip_device_free, hip_pinned_alloc, hip_pinned_free};
+    return &hip;
+}
+
 namespace gs {
 
-int refuse_pose_correction(gs_ctx* c, const char* who)
+int refuse_modes(gs_ctx* c, const char* who, std::initializer_list<GsMode> unserved)
 {
-    if (!c->poseDelta && !c->fwd.poseDelta) return GS_OK;
-    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a pose correction is set (single-device steps only)");
-}
-
-int refuse_absgrad(gs_ctx* c, const char* who)
-{
-    if (!c->absgrad) return GS_OK;
-    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": absgrad is on (gs_set_absgrad): only gs_render_backward and "
-                                       "gs_render_backward_adam accumulate the absolute sums");
-}
-
-int refuse_adc_stats(gs_ctx* c, const char* who)
-{
-    if (!c->adcGradSum) return GS_OK;
-    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": the ADC statistic is set (gs_set_adc_stats): only gs_render_backward and "
-                                       "gs_render_backward_adam accumulate it");
-}
-
-int refuse_sparse_adam(gs_ctx* c, const char* who)
-{
-    if (!c->sparseAdam) return GS_OK;
-    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": sparse Adam is on (gs_set_sparse_adam): single-device steps through "
-                                       "gs_render_backward_adam or gs_adam_step_visible only");
-}
-
-int refuse_filter3d(gs_ctx* c, const char* who)
-{
-    if (!c->filter3d && !(c->fwd.valid && c->fwd.filter3d)) return GS_OK;
-    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": a 3-D filter is set (single-device steps only)");
-}
-
-int refuse_fisheye(gs_ctx* c, const char* who)
-{
-    if (!c->fisheye && !(c->fwd.valid && c->fwd.fisheye)) return GS_OK;
-    return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": the fisheye camera model is set (gs_set_camera_model; pinhole cameras only)");
+    const GsRenderModes &now = c->modes, &ran = c->fwd.modes;
+    const bool fwd = c->fwd.valid;
+    for (const GsMode m : unserved) {
+        const char* why = nullptr;
+        switch (m) {
+        case GS_MODE_POSE:
+            if (now.poseDelta || ran.poseDelta) why = ": a pose correction is set (single-device steps only)";
+            break;
+        case GS_MODE_FILTER3D:
+            if (now.filter3d || (fwd && ran.filter3d)) why = ": a 3-D filter is set (single-device steps only)";
+            break;
+        case GS_MODE_FISHEYE:
+            if (now.fisheye || (fwd && ran.fisheye)) why = ": the fisheye camera model is set (gs_set_camera_model; pinhole cameras only)";
+            break;
+        case GS_MODE_ABSGRAD:
+            if (c->absgrad) why = ": absgrad is on (gs_set_absgrad): only gs_render_backward and gs_render_backward_adam accumulate the "
+                                  "absolute sums";
+            break;
+        case GS_MODE_SPARSE_ADAM:
+            if (c->sparseAdam) why = ": sparse Adam is on (gs_set_sparse_adam): single-device steps through gs_render_backward_adam or "
+                                     "gs_adam_step_visible only";
+            break;
+        case GS_MODE_ADC_STATS:
+            if (c->adcGradSum) why = ": the ADC statistic is set (gs_set_adc_stats): only gs_render_backward and gs_render_backward_adam "
+                                     "accumulate it";
+            break;
+        }
+        if (why) return fail(c, GS_ERR_INVALID_ARG, std::string(who) + why);
+    }
+    return GS_OK;
 }
 
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena)
@@ -457,12 +443,13 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return GS_ERR_NO_DEVICE;
     gs_ctx* c = new gs_ctx();
+    c->mem.backend = gs_hip_mem_backend();
     c->device = device;
     c->W = W; c->H = H; c->tileW = tile_w; c->tileH = tile_h;
     c->gridW = (W + tile_w - 1) / tile_w; c->gridH = (H + tile_h - 1) / tile_h;
     c->T = c->gridW * c->gridH;
-    c->degree = c->maxDegree = sh_degree; c->whiteBg = white_bg ? 1 : 0;
-    c->bg.mode = c->whiteBg ? GS_BG_WHITE : GS_BG_BLACK;
+    c->modes.degree = c->maxDegree = sh_degree; c->whiteBg = white_bg ? 1 : 0;
+    c->modes.bg.mode = c->whiteBg ? GS_BG_WHITE : GS_BG_BLACK;
     c->fast16 = (tile_w % 16 == 0) && (tile_h % 16 == 0);
     c->blocksX = gs_div_up(W, 16); c->blocksY = gs_div_up(H, 16);
     c->real.tileW = tile_w; c->real.tileH = tile_h; c->real.gridW = c->gridW; c->real.gridH = c->gridH; c->real.T = c->T;
@@ -511,8 +498,8 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
     c->numPixBlocks = c->blocksX * c->blocksY;
     c->opBlocks = c->real.fast16 ? c->numPixBlocks : c->real.T * gs_div_up(tile_w, 16) * gs_div_up(tile_h, 16);
     const size_t maxBlocks = (size_t)(c->opBlocks > c->numPixBlocks ? c->opBlocks : c->numPixBlocks);
-    if (dev_alloc(c, &c->blockWorkOwn, maxBlocks) || dev_alloc(c, &c->blockOrder, maxBlocks + 8) || dev_alloc(c, &c->fwdQueue, GS_QUEUES * GS_QUEUE_STRIDE) || dev_alloc(c, &c->bwdQueue, GS_QUEUES * GS_QUEUE_STRIDE) ||
-        dev_alloc(c, &c->segBase, (size_t)c->numPixBlocks) || dev_alloc(c, &c->finalT, P))
+    if (ctx_alloc(c, &c->blockWorkOwn, maxBlocks) || ctx_alloc(c, &c->blockOrder, maxBlocks + 8) || ctx_alloc(c, &c->fwdQueue, GS_QUEUES * GS_QUEUE_STRIDE) || ctx_alloc(c, &c->bwdQueue, GS_QUEUES * GS_QUEUE_STRIDE) ||
+        ctx_alloc(c, &c->segBase, (size_t)c->numPixBlocks) || ctx_alloc(c, &c->finalT, P))
         return bail(GS_ERR_HIP);
     c->blockWork = c->blockWorkOwn;
     {
@@ -520,16 +507,16 @@ int gs_ctx_create(int device, int W, int H, int tile_w, int tile_h, int sh_degre
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             c->numCUs = prop.multiProcessorCount;
     }
-    if (dev_alloc(c, &c->superCut, (size_t)c->T + 16) || dev_alloc(c, &c->tileRanges, (size_t)c->T * 2) || dev_alloc(c, &c->tileCounts, (size_t)c->T) ||
-        dev_alloc(c, &c->lastContrib, P) ||
-        dev_alloc(c, &c->lossPartials, (size_t)(c->lossPartialBlocks = gs_div_up(W, 16) * gs_div_up(H, 16) * 3) * 4 + 16) || dev_alloc(c, &c->windowDev, 121) ||
-        dev_alloc(c, &c->counters, GS_CNT_COUNT) || dev_alloc(c, &c->rowTotal, 256) ||
-        dev_alloc(c, &c->sortBits, GS_SMALL_SORT_BLOCKS) || dev_alloc(c, &c->wideTotal, GS_WIDE_BINS) ||
-        dev_alloc(c, &c->bucketStart, 520) || dev_alloc(c, &c->sortSplit[0], 256) || dev_alloc(c, &c->sortSplit[1], 256))
+    if (ctx_alloc(c, &c->superCut, (size_t)c->T + 16) || ctx_alloc(c, &c->tileRanges, (size_t)c->T * 2) || ctx_alloc(c, &c->tileCounts, (size_t)c->T) ||
+        ctx_alloc(c, &c->lastContrib, P) ||
+        ctx_alloc(c, &c->lossPartials, (size_t)(c->lossPartialBlocks = gs_div_up(W, 16) * gs_div_up(H, 16) * 3) * 4 + 16) || ctx_alloc(c, &c->windowDev, 121) ||
+        ctx_alloc(c, &c->counters, GS_CNT_COUNT) || ctx_alloc(c, &c->rowTotal, 256) ||
+        ctx_alloc(c, &c->sortBits, GS_SMALL_SORT_BLOCKS) || ctx_alloc(c, &c->wideTotal, GS_WIDE_BINS) ||
+        ctx_alloc(c, &c->bucketStart, 520) || ctx_alloc(c, &c->sortSplit[0], 256) || ctx_alloc(c, &c->sortSplit[1], 256))
         return bail(GS_ERR_HIP);
-    if (hipHostMalloc((void**)&c->countersHost, sizeof(uint32_t) * GS_CNT_COUNT) != hipSuccess) return bail(GS_ERR_HIP);
+    if (ctx_alloc_pinned(c, &c->countersHost, GS_CNT_COUNT)) return bail(GS_ERR_HIP);
     // the depth cuts' miss word: host memory the forward kernel writes directly, read after the fwdDone event
-    if (hipHostMalloc((void**)&c->missHost, 64, hipHostMallocMapped) != hipSuccess) return bail(GS_ERR_HIP);
+    if (ctx_alloc_pinned(c, &c->missHost, 16, hipHostMallocMapped)) return bail(GS_ERR_HIP);
     for (int i = 0; i < 16; i++) c->missHost[i] = 0;
     if (hipHostGetDevicePointer((void**)&c->missDev, c->missHost, 0) != hipSuccess) return bail(GS_ERR_HIP);
     if (hipEventCreateWithFlags(&c->fwdDone, hipEventDisableTiming) != hipSuccess) return bail(GS_ERR_HIP);
@@ -549,25 +536,10 @@ int gs_ctx_destroy(gs_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)gs_dp_shutdown(c);
-    free_gaussian_ws(c);
-    free_pair_ws(c);
-    dev_free(c->segState);
-    dev_free(c->hist); dev_free(c->wideCnt); dev_free(c->wideChunk); dev_free(c->wideTotal); dev_free(c->rowTotal); dev_free(c->sortBits); dev_free(c->bucketStart); dev_free(c->sortSplit[0]); dev_free(c->sortSplit[1]); dev_free(c->tileRanges); dev_free(c->tileCounts); dev_free(c->superCut);
-    dev_free(c->lastContrib); dev_free(c->lossPartials); dev_free(c->depthLossWs); dev_free(c->normalWs); dev_free(c->normalPartials); dev_free(c->metricsWs); dev_free(c->windowDev);
-    dev_free(c->counters); dev_free(c->blockWorkOwn); dev_free(c->blockOrder); dev_free(c->fwdQueue); dev_free(c->bwdQueue); dev_free(c->segBase); dev_free(c->finalT);
+    c->mem.freeAll();      // every device and pinned buffer the context still owns
     for (auto& e : c->profPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    if (c->countersHost) (void)hipHostFree(c->countersHost);
-    if (c->missHost) (void)hipHostFree(c->missHost);
     if (c->fwdDone) (void)hipEventDestroy(c->fwdDone);
     if (c->densifyDone) (void)hipEventDestroy(c->densifyDone);
-    if (c->densifyPlanHost) (void)hipHostFree(c->densifyPlanHost);
-    dev_free(c->densifyPlan);
-    dev_free(c->poseCam); dev_free(c->posePartials);
-    dev_free(c->f3dCams); dev_free(c->f3dMax);
-    dev_free(c->visMask); dev_free(c->visRadii);
-    dev_free(c->correctedImage); dev_free(c->expoPartials); dev_free(c->bgPartials);
-    dev_free(c->densifyTable);
-    mcmc_free(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return GS_OK;
@@ -616,7 +588,7 @@ int gs_ctx_reserve(gs_ctx* c, int max_gaussians, long long max_pairs)
     return rc;
 }
 
-size_t gs_workspace_bytes(const gs_ctx* c) { return c ? c->ws_bytes : 0; }
+size_t gs_workspace_bytes(const gs_ctx* c) { return c ? c->mem.deviceBytes : 0; }
 
 int gs_sync(gs_ctx* c)
 {
@@ -659,7 +631,7 @@ int gs_projection_forward(gs_ctx* c, int N, int K, const float* scales, const fl
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (N < 0 || K < 1 || !cam) return fail(c, GS_ERR_INVALID_ARG, "gs_projection_forward: bad N/K/cam");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
+    if ((c->modes.degree + 1) * (c->modes.degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
     if (N > 0 && (!scales || !rotations || !means3d || !shs || !means2d || !depths || !color || !cov2d || !conic ||
                   !radii || !rect_min || !rect_max))
         return fail(c, GS_ERR_INVALID_ARG, "gs_projection_forward: null buffer");
@@ -675,7 +647,7 @@ int gs_projection_backward(gs_ctx* c, int N, int K, const float* scales, const f
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (N < 0 || K < 1 || !cam) return fail(c, GS_ERR_INVALID_ARG, "gs_projection_backward: bad N/K/cam");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
+    if ((c->modes.degree + 1) * (c->modes.degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
     if (N > 0 && (!scales || !rotations || !means3d || !shs || !cot_depths || !cot_means2d || !cot_cov2d ||
                   !cot_color || !cot_conic || !grad_scales || !grad_rotations || !grad_means3d || !grad_shs ||
                   !grad_cam_center_point))
@@ -808,7 +780,7 @@ int gs_blend_forward(gs_ctx* c, int N, const float* packed, float* out_color, fl
     c->fwd.valid = false; c->fwd.bwdPrepared = false;
     int rc = launch_pack11_to_12(c, N, packed);
     if (rc) return rc;
-    return launch_blend_forward(c, c->bg, out_color, out_depth, out_alpha, last_contrib);
+    return launch_blend_forward(c, c->modes.bg, out_color, out_depth, out_alpha, last_contrib);
 }
 
 int gs_blend_backward(gs_ctx* c, int N, const float* packed, const float* cot_color, const float* cot_depth,
@@ -827,7 +799,7 @@ int gs_blend_backward(gs_ctx* c, int N, const float* packed, const float* cot_co
     c->absgradN = -1;                                       // (the accumulator's rows are rewritten)
     int rc = launch_pack11_to_12(c, N, packed);
     if (rc) return rc;
-    if ((rc = launch_blend_backward(c, c->bg, N, cot_color, cot_depth, cot_alpha, out_alpha, last_contrib))) return rc;
+    if ((rc = launch_blend_backward(c, c->modes.bg, N, cot_color, cot_depth, cot_alpha, out_alpha, last_contrib))) return rc;
     return launch_gradacc_to_packed11(c, N, grad_packed);
 }
 
@@ -930,31 +902,20 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (N < 0 || K < 1 || !cam) return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: bad N/K/cam");
-    if ((c->degree + 1) * (c->degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
+    if ((c->modes.degree + 1) * (c->modes.degree + 1) > K) return fail(c, GS_ERR_SIZE_MISMATCH, "K smaller than (degree+1)^2");
     // (out_depth may be NULL: no depth image is computed, and the backward of this forward takes no depth cotangent)
     if (!out_color || !out_alpha) return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: null output");
     if (N > 0 && (!xyz || !features_dc || (K > 1 && !features_rest) || !scales || !rotation || !opacity))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: null parameter tensor");
-    if (c->fisheye && c->poseDelta)
+    if (c->modes.fisheye && c->modes.poseDelta)
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: the fisheye camera model has no pose refinement (gs_set_pose_correction is set)");
-    if (c->fisheye && c->filter3d)
+    if (c->modes.fisheye && c->modes.filter3d)
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: the fisheye camera model has no 3-D filter (gs_set_filter3d is set)");
     c->fwd.valid = false;
     c->visN = -1;
     const bool keepRadii = c->sparseAdam || c->adcGradSum != nullptr;      // (the ADC statistic reads the radii in the backward)
     if (keepRadii && N > c->visCap) {           // sparse Adam's mask and radii: grown by the first forward that needs more rows
-        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        if (c->visMask) c->ws_bytes -= (size_t)c->visCap * (sizeof(unsigned char) + sizeof(float));
-        dev_free(c->visMask); dev_free(c->visRadii);
-        c->visCap = 0;
-        const int cap = N > c->capN ? N : c->capN;
-        if (const int arc = dev_alloc(c, &c->visMask, (size_t)cap)) return arc;
-        if (const int arc = dev_alloc(c, &c->visRadii, (size_t)cap)) {      // (both or neither: visCap describes the pair)
-            c->ws_bytes -= (size_t)cap * sizeof(unsigned char);
-            dev_free(c->visMask);
-            return arc;
-        }
-        c->visCap = cap;
+        if (const int arc = ctx_grow_pair(c, &c->visMask, &c->visRadii, &c->visCap, N > c->capN ? N : c->capN)) return arc;
     }
     if (keepRadii && !radii) radii = c->visRadii;          // (the mask is taken from the radii the projection writes)
     c->binIsBlockLists = c->virt.nbx != 0;
@@ -970,16 +931,9 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.missChecked = !c->fwd.cutsActive;
     if (c->fwd.cutsActive) c->missHost[0] = 0;
     const CamParams cp = make_cam(cam, c->W, c->H);
-    if (c->poseDelta) {         // pose refinement: the corrected camera, composed on the device, for every kernel of this step
-        const long long need = pose_partials_floats(N);
-        if (need > c->posePartialsCap) {
-            GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-            dev_free(c->posePartials);
-            c->posePartialsCap = 0;
-            if (const int arc = dev_alloc(c, &c->posePartials, (size_t)need)) return arc;
-            c->posePartialsCap = need;
-        }
-        if (const int prc = launch_pose_camera(c, cp, c->poseDelta)) return prc;
+    if (c->modes.poseDelta) {         // pose refinement: the corrected camera, composed on the device, for every kernel of this step
+        if (const int arc = ctx_grow(c, &c->posePartials, &c->posePartialsCap, pose_partials_floats(N))) return arc;
+        if (const int prc = launch_pose_camera(c, cp, c->modes.poseDelta)) return prc;
     }
     c->segBaseWanted = c->fast16 && N > 0;
     c->segBaseDone = false;
@@ -998,7 +952,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     {
         GsStageTimer t(c, GS_STAGE_BLEND_FWD);
         rc = c->fast16 ? launch_blend_forward_v2(c, out_color, out_depth, out_alpha)
-                       : launch_blend_forward(c, c->bg, out_color, out_depth, out_alpha, c->lastContrib);
+                       : launch_blend_forward(c, c->modes.bg, out_color, out_depth, out_alpha, c->lastContrib);
         if (rc) return rc;
     }
     if (c->fwd.cutsActive) GS_HIP_CHECK(c, hipEventRecord(c->fwdDone, c->stream));
@@ -1012,13 +966,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
     c->fwd.rot = rotation; c->fwd.opacity = opacity;
     c->fwd.outColor = out_color; c->fwd.outDepth = out_depth; c->fwd.outAlpha = out_alpha;
     c->fwd.cam = cp;
-    c->fwd.poseDelta = c->poseDelta;
-    c->fwd.poseGrad = c->poseGrad;
-    c->fwd.antialias = c->antialias;
-    c->fwd.fisheye = c->fisheye;
-    c->fwd.degree = c->degree;
-    c->fwd.bg = c->bg;
-    c->fwd.filter3d = c->filter3d;
+    c->fwd.modes = c->modes;      // whole: what this forward ran under is what its backward runs under
     c->fwd.radii = keepRadii ? radii : nullptr;      // (a caller's buffer is remembered only where a backward will read it)
     if (c->sparseAdam) c->visN = N;
     return GS_OK;
@@ -1031,7 +979,7 @@ int gs_set_sparse_adam(gs_ctx* c, int enable)
     if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: enable is 0 or 1");
     if (enable && c->mcmcOn)
         return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: the MCMC strategy is set (its noise and regularisers act on every Gaussian)");
-    if (enable && c->filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: a 3-D filter is set (gs_set_filter3d)");
+    if (enable && c->modes.filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_sparse_adam: a 3-D filter is set (gs_set_filter3d)");
     // (the mask of the last forward made under the setting stays readable when the setting goes off: every forward drops it first)
     c->sparseAdam = enable == 1;
     return GS_OK;
@@ -1160,7 +1108,7 @@ int gs_set_antialiasing(gs_ctx* c, int enable)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (enable != 0 && enable != 1) return fail(c, GS_ERR_INVALID_ARG, "gs_set_antialiasing: enable is 0 or 1");
-    c->antialias = enable == 1;
+    c->modes.antialias = enable == 1;
     return GS_OK;
 }
 
@@ -1170,7 +1118,7 @@ int gs_set_sh_degree(gs_ctx* c, int degree)
     if (!c) return GS_ERR_INVALID_ARG;
     if (degree < 0 || degree > c->maxDegree)
         return fail(c, GS_ERR_INVALID_ARG, "gs_set_sh_degree: degree is 0 .. the sh_degree the context was created with");
-    c->degree = degree;
+    c->modes.degree = degree;
     return GS_OK;
 }
 
@@ -1178,7 +1126,7 @@ int gs_get_sh_degree(gs_ctx* c, int* degree)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!degree) return fail(c, GS_ERR_INVALID_ARG, "gs_get_sh_degree: null pointer");
-    *degree = c->degree;
+    *degree = c->modes.degree;
     return GS_OK;
 }
 
@@ -1188,7 +1136,7 @@ int gs_set_camera_model(gs_ctx* c, int model)
     if (!c) return GS_ERR_INVALID_ARG;
     if (model != GS_CAMERA_PINHOLE && model != GS_CAMERA_FISHEYE)
         return fail(c, GS_ERR_INVALID_ARG, "gs_set_camera_model: model is GS_CAMERA_PINHOLE or GS_CAMERA_FISHEYE");
-    c->fisheye = model == GS_CAMERA_FISHEYE;
+    c->modes.fisheye = model == GS_CAMERA_FISHEYE;
     return GS_OK;
 }
 
@@ -1196,7 +1144,7 @@ int gs_get_camera_model(gs_ctx* c, int* model)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!model) return fail(c, GS_ERR_INVALID_ARG, "gs_get_camera_model: null pointer");
-    *model = c->fisheye ? GS_CAMERA_FISHEYE : GS_CAMERA_PINHOLE;
+    *model = c->modes.fisheye ? GS_CAMERA_FISHEYE : GS_CAMERA_PINHOLE;
     return GS_OK;
 }
 
@@ -1211,7 +1159,7 @@ int gs_set_background(gs_ctx* c, const float* rgb)
             return fail(c, GS_ERR_INVALID_ARG, "gs_set_background: the three values must be finite");
         bg.mode = GS_BG_COLOUR; bg.r = rgb[0]; bg.g = rgb[1]; bg.b = rgb[2];
     }
-    c->bg = bg;
+    c->modes.bg = bg;
     return GS_OK;
 }
 
@@ -1219,8 +1167,8 @@ int gs_get_background(gs_ctx* c, float rgb[3])
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!rgb) return fail(c, GS_ERR_INVALID_ARG, "gs_get_background: null buffer");
-    if (c->bg.mode == GS_BG_COLOUR) { rgb[0] = c->bg.r; rgb[1] = c->bg.g; rgb[2] = c->bg.b; }
-    else rgb[0] = rgb[1] = rgb[2] = c->bg.mode == GS_BG_WHITE ? 1.0f : 0.0f;
+    if (c->modes.bg.mode == GS_BG_COLOUR) { rgb[0] = c->modes.bg.r; rgb[1] = c->modes.bg.g; rgb[2] = c->modes.bg.b; }
+    else rgb[0] = rgb[1] = rgb[2] = c->modes.bg.mode == GS_BG_WHITE ? 1.0f : 0.0f;
     return GS_OK;
 }
 
@@ -1237,11 +1185,11 @@ int gs_set_filter3d_cameras(gs_ctx* c, int V, const gs_camera* cams)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (V < 0 || (V > 0 && !cams)) return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d_cameras: V >= 0 and V cameras");
-    if (V > 0) { if (const int rc = refuse_fisheye(c, "gs_set_filter3d_cameras")) return rc; }
+    if (V > 0) { if (const int rc = refuse_modes(c, "gs_set_filter3d_cameras", {GS_MODE_FISHEYE})) return rc; }
     GS_HIP_CHECK(c, hipSetDevice(c->device));
     if (V == 0) {
         GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a width kernel may still be reading the table)
-        dev_free(c->f3dCams);
+        ctx_free(c, c->f3dCams);
         c->f3dCamCount = c->f3dCamCap = 0;
         return GS_OK;
     }
@@ -1249,12 +1197,10 @@ int gs_set_filter3d_cameras(gs_ctx* c, int V, const gs_camera* cams)
         if (!(cams[v].focal_x > 0.0f) || !(cams[v].fov_x > 0.0f) || !(cams[v].fov_y > 0.0f))
             return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d_cameras: focal_x, fov_x and fov_y are > 0");
     GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    if (!c->f3dMax) { if (const int rc = dev_alloc(c, &c->f3dMax, 1)) return rc; }
-    if (V > c->f3dCamCap) {
-        dev_free(c->f3dCams);
-        c->f3dCamCount = c->f3dCamCap = 0;
-        if (const int rc = dev_alloc(c, &c->f3dCams, (size_t)V * GS_F3D_CAM_FLOATS)) return rc;
-        c->f3dCamCap = V;
+    if (!c->f3dMax) { if (const int rc = ctx_alloc(c, &c->f3dMax, 1)) return rc; }
+    if (V > c->f3dCamCap) {      // (the capacity counts cameras, the buffer rows of GS_F3D_CAM_FLOATS)
+        c->f3dCamCount = 0;
+        if (const int rc = ctx_grow(c, &c->f3dCams, &c->f3dCamCap, V, GS_F3D_CAM_FLOATS)) return rc;
     }
     std::vector<float> rows((size_t)V * GS_F3D_CAM_FLOATS, 0.0f);
     for (int v = 0; v < V; v++) {
@@ -1294,8 +1240,8 @@ int gs_set_filter3d(gs_ctx* c, const float* filter)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (filter && c->mcmcOn) return fail(c, GS_ERR_INVALID_ARG, "gs_set_filter3d: the MCMC strategy is set (the reference strategy only)");
-    if (filter) { if (const int rc = refuse_sparse_adam(c, "gs_set_filter3d")) return rc; }
-    c->filter3d = filter;
+    if (filter) { if (const int rc = refuse_modes(c, "gs_set_filter3d", {GS_MODE_SPARSE_ADAM})) return rc; }
+    c->modes.filter3d = filter;
     return GS_OK;
 }
 
@@ -1328,8 +1274,8 @@ int gs_set_mcmc(gs_ctx* c, const gs_mcmc_params* params)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!params) { c->mcmcOn = false; return GS_OK; }
-    if (c->filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_mcmc: a 3-D filter is set (gs_set_filter3d: the reference strategy only)");
-    if (const int rc = refuse_sparse_adam(c, "gs_set_mcmc")) return rc;
+    if (c->modes.filter3d) return fail(c, GS_ERR_INVALID_ARG, "gs_set_mcmc: a 3-D filter is set (gs_set_filter3d: the reference strategy only)");
+    if (const int rc = refuse_modes(c, "gs_set_mcmc", {GS_MODE_SPARSE_ADAM})) return rc;
     if (const char* e = mcmc_params_error(params)) return fail(c, GS_ERR_INVALID_ARG, e);
     c->mcmc = *params;
     c->mcmcOn = true;
@@ -1410,9 +1356,9 @@ int gs_set_pose_correction(gs_ctx* c, const float* delta, float* grad_delta)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (!delta != !grad_delta) return fail(c, GS_ERR_INVALID_ARG, "gs_set_pose_correction: delta and grad_delta are both set or both NULL");
-    if (delta && !c->poseCam) { const int arc = dev_alloc(c, &c->poseCam, 1); if (arc) return arc; }
-    c->poseDelta = delta;
-    c->poseGrad = grad_delta;
+    if (delta && !c->poseCam) { const int arc = ctx_alloc(c, &c->poseCam, 1); if (arc) return arc; }
+    c->modes.poseDelta = delta;
+    c->modes.poseGrad = grad_delta;
     return GS_OK;
 }
 
@@ -1422,7 +1368,7 @@ int gs_set_exposure(gs_ctx* c, const float* M, float* grad)
     if (!M != !grad) return fail(c, GS_ERR_INVALID_ARG, "gs_set_exposure: M and grad are both set or both NULL");
     if (M && c->bgGrid) return fail(c, GS_ERR_INVALID_ARG, "gs_set_exposure: a bilateral grid is set (the two corrections are exclusive)");
     // (once per ctx, here: a step never allocates)
-    if (M && !c->expoPartials) { const int arc = dev_alloc(c, &c->expoPartials, (size_t)exposure_partials_doubles()); if (arc) return arc; }
+    if (M && !c->expoPartials) { const int arc = ctx_alloc(c, &c->expoPartials, (size_t)exposure_partials_doubles()); if (arc) return arc; }
     if (M) { const int arc = ensure_corrected_image(c); if (arc) return arc; }
     c->expoM = M;
     c->expoGrad = grad;
@@ -1495,13 +1441,7 @@ int gs_set_bilateral_grid(gs_ctx* c, const float* grid, float* grad, int grid_w,
             c->bgChunksH = grid_h;
         }
         const long long need = bilateral_partials_floats(grid_w, grid_h, grid_l, c->bgChunks);
-        if (need > c->bgPartialsCap) {
-            GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-            dev_free(c->bgPartials);
-            c->bgPartialsCap = 0;
-            if (const int arc = dev_alloc(c, &c->bgPartials, (size_t)need)) return arc;
-            c->bgPartialsCap = need;
-        }
+        if (const int arc = ctx_grow(c, &c->bgPartials, &c->bgPartialsCap, need)) return arc;
         if (const int arc = ensure_corrected_image(c)) return arc;
     }
     c->bgGrid = grid;
@@ -1587,7 +1527,7 @@ int gs_render_backward_adam(gs_ctx* c, const float* cot_color, const float* cot_
     if (!cot_color || !lr || n_arena < 0 || (N > 0 && (!params_base || !m_base || !v_base)))
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_adam: null buffer");
     if (const int rc = forward_in_arena(c, "gs_render_backward_adam", params_base, n_arena)) return rc;
-    if (c->sparseAdam && (c->visN != N || c->fwd.filter3d))
+    if (c->sparseAdam && (c->visN != N || c->fwd.modes.filter3d))
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_adam: sparse Adam is on, but the forward was not made under it "
                                           "(gs_set_sparse_adam comes before gs_render_forward)");
     if (const int rc = blend_backward_of_forward(c, cot_color, cot_depth, cot_alpha, c->absgrad, c->adamGate)) return rc;
@@ -1601,12 +1541,9 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
                                 float* color_cot)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_begin")) return rc;
-    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_begin")) return rc;
-    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_begin")) return rc;
-    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_begin")) return rc;
-    if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_begin")) return rc;
-    if (const int rc = refuse_adc_stats(c, "gs_render_backward_dp_begin")) return rc;
+    if (const int rc = refuse_modes(c, "gs_render_backward_dp_begin", {GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_SPARSE_ADAM,
+                                                                   GS_MODE_ABSGRAD, GS_MODE_ADC_STATS}))
+        return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && !color_cot)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_backward_dp_begin: null buffer");
@@ -1619,10 +1556,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
 int gs_render_backward_dp_finish(gs_ctx* c, float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish")) return rc;
-    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish")) return rc;
-    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_finish")) return rc;
-    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_finish")) return rc;
+    if (const int rc = refuse_modes(c, "gs_render_backward_dp_finish", {GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_SPARSE_ADAM})) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N, K = c->fwd.K;
@@ -1637,10 +1571,7 @@ int gs_render_backward_dp_finish_geom(gs_ctx* c, float* grad_xyz, float* grad_sc
                                       float* xyz_own)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_finish_geom")) return rc;
-    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_finish_geom")) return rc;
-    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_finish_geom")) return rc;
-    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_finish_geom")) return rc;
+    if (const int rc = refuse_modes(c, "gs_render_backward_dp_finish_geom", {GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_SPARSE_ADAM})) return rc;
     if (!c->fwd.valid || !c->fwd.blendBackwardDone)
         return fail(c, GS_ERR_NO_FORWARD, "gs_render_backward_dp_finish_geom: no gs_render_backward_dp_begin on this context");
     const int N = c->fwd.N;
@@ -1655,12 +1586,9 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
                                float* grad_xyz, float* grad_scales, float* grad_rotation, float* grad_opacity, float* xyz_own)
 {
     if (!c) return GS_ERR_INVALID_ARG;
-    if (const int rc = refuse_pose_correction(c, "gs_render_backward_dp_geom")) return rc;
-    if (const int rc = refuse_filter3d(c, "gs_render_backward_dp_geom")) return rc;
-    if (const int rc = refuse_fisheye(c, "gs_render_backward_dp_geom")) return rc;
-    if (const int rc = refuse_sparse_adam(c, "gs_render_backward_dp_geom")) return rc;
-    if (const int rc = refuse_absgrad(c, "gs_render_backward_dp_geom")) return rc;
-    if (const int rc = refuse_adc_stats(c, "gs_render_backward_dp_geom")) return rc;
+    if (const int rc = refuse_modes(c, "gs_render_backward_dp_geom", {GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_SPARSE_ADAM,
+                                                                  GS_MODE_ABSGRAD, GS_MODE_ADC_STATS}))
+        return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
     if (!cot_color || (N > 0 && (!color_cot || !grad_xyz || !grad_scales || !grad_rotation || !grad_opacity || !xyz_own)))
@@ -1677,7 +1605,7 @@ int gs_sh_grad_from_views_adam_dir(gs_ctx* c, int N, int K, int R, const float* 
 {
     if (!c) return GS_ERR_INVALID_ARG;
     const char* who = "gs_sh_grad_from_views_adam_dir";
-    if (const int rc = refuse_sparse_adam(c, who)) return rc;
+    if (const int rc = refuse_modes(c, who, {GS_MODE_SPARSE_ADAM})) return rc;
     if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest, n_arena < 0,
                                      !params_base || !m_base || !v_base || !xyz_add))
         return rc;
@@ -1719,7 +1647,7 @@ int gs_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* xyz,
 {
     if (!c) return GS_ERR_INVALID_ARG;
     const char* who = "gs_sh_grad_from_views_adam";
-    if (const int rc = refuse_sparse_adam(c, who)) return rc;
+    if (const int rc = refuse_modes(c, who, {GS_MODE_SPARSE_ADAM})) return rc;
     if (const int rc = sh_views_args(c, who, N, K, R, xyz, color_cot_all, cam_centers, features_dc, features_rest, n_arena < 0,
                                      !params_base || !m_base || !v_base))
         return rc;
@@ -1780,7 +1708,7 @@ int gs_depth_loss(gs_ctx* c, const gs_depth_loss_params* p, const float* render_
     { const int orc = deferred_overflow(c); if (orc) return orc; }
     if (!c->depthLossWs) {      // the first call: a step never allocates after it
         GS_HIP_CHECK(c, hipSetDevice(c->device));
-        if (const int rc = dev_alloc(c, &c->depthLossWs, (size_t)depth_loss_ws_doubles())) return rc;
+        if (const int rc = ctx_alloc(c, &c->depthLossWs, (size_t)depth_loss_ws_doubles())) return rc;
     }
     GsStageTimer t(c, GS_STAGE_LOSS);
     return launch_depth_loss(c, p->mode, p->lambda, p->alpha_min, p->scale, p->offset, render_depth, render_alpha, target, mask,
@@ -1841,16 +1769,9 @@ int gs_normal_loss(gs_ctx* c, const gs_normal_loss_params* p, const float* rende
     const long long want = normal_loss_ws_floats((long long)p->H * p->W);
     if (want > c->normalWsFloats || !c->normalPartials) {      // the first call, or a larger image: a step never allocates after it
         GS_HIP_CHECK(c, hipSetDevice(c->device));
-        if (c->normalWs) {
-            GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a queued call still works in the old buffer)
-            c->ws_bytes -= (size_t)c->normalWsFloats * sizeof(float);
-            dev_free(c->normalWs);
-        }
-        c->normalWsFloats = 0;
-        if (const int rc = dev_alloc(c, &c->normalWs, (size_t)want)) return rc;
-        c->normalWsFloats = want;
+        if (const int rc = ctx_grow(c, &c->normalWs, &c->normalWsFloats, want)) return rc;
         if (!c->normalPartials)
-            if (const int rc = dev_alloc(c, &c->normalPartials, (size_t)normal_loss_ws_doubles())) return rc;
+            if (const int rc = ctx_alloc(c, &c->normalPartials, (size_t)normal_loss_ws_doubles())) return rc;
     }
     GsStageTimer t(c, GS_STAGE_LOSS);
     return launch_normal_loss(c, *p, render_depth, render_alpha, target_normals, mask, edge_image, loss, normal_out, cot_depth,
@@ -1865,15 +1786,7 @@ int ensure_metrics_ws(gs_ctx* c, int H, int W)
     const long long want = metrics_ws_doubles(H, W);
     if (want <= c->metricsWsDoubles) return GS_OK;
     GS_HIP_CHECK(c, hipSetDevice(c->device));
-    if (c->metricsWs) {
-        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (a queued call still sums the old buffer)
-        c->ws_bytes -= (size_t)c->metricsWsDoubles * sizeof(double);
-        dev_free(c->metricsWs);
-    }
-    c->metricsWsDoubles = 0;
-    if (const int rc = dev_alloc(c, &c->metricsWs, (size_t)want)) return rc;
-    c->metricsWsDoubles = want;
-    return GS_OK;
+    return ctx_grow(c, &c->metricsWs, &c->metricsWsDoubles, want);
 }
 }  // namespace
 

@@ -1378,7 +1378,7 @@ int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* 
     BlendFwdArgs a;
     a.W = c->W; a.H = c->H; a.tileW = c->tileW; a.tileH = c->tileH; a.gridW = c->gridW; a.blocksX = c->blocksX;
     a.nItems = c->numPixBlocks * 4;
-    a.bgc = c->bg;
+    a.bgc = c->modes.bg;
     a.rec12 = reinterpret_cast<const float4*>(c->packed12); a.sortedIdx = c->sortedRaw; a.idxMask = c->idxMask;
     a.tileRanges = c->tileRanges; a.segBase = c->segBase; a.segCap = (uint32_t)c->segCap;
     a.statePlanes = c->renderOnly ? 0 : c->fwd.statePlanes;
@@ -1440,7 +1440,7 @@ int launch_blend_backward_v2(gs_ctx* c, int N, const float* cotColor, const floa
     }
     BlendBwdArgs a;
     a.W = c->W; a.H = c->H; a.tileW = c->tileW; a.tileH = c->tileH; a.gridW = c->gridW; a.blocksX = c->blocksX;
-    a.bgc = c->fwd.bg;
+    a.bgc = c->fwd.modes.bg;
     a.rec12 = reinterpret_cast<const float4*>(c->packed12); a.sortedIdx = c->sortedRaw; a.idxMask = c->idxMask;
     a.tileRanges = c->tileRanges; a.blockWork = c->fwd.blockWork;
     a.itemBlock = c->itemBlock; a.itemRow = c->itemRow; a.counters = c->counters;

@@ -479,14 +479,7 @@ int launch_densify_gather(gs_ctx* c, int total, int K, const float* xyz, const f
 static int densify_scan(gs_ctx* c, int N, const int* actions, const int* outputCounts, int* offsets, uint32_t** cntOut)
 {
     const int nTiles = gs_div_up(N, DN_SCAN_TILE);
-    if (nTiles > c->densifyTileCap) {
-        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));      // (kernels of an earlier event may still read the old scratch)
-        if (c->densifyTiles) GS_HIP_CHECK(c, hipFree(c->densifyTiles));
-        c->densifyTiles = nullptr;
-        c->densifyTileCap = 0;
-        GS_HIP_CHECK(c, hipMalloc(&c->densifyTiles, sizeof(int) * (size_t)(5 * nTiles + 8)));
-        c->densifyTileCap = nTiles;
-    }
+    if (const int rc = ctx_grow(c, &c->densifyTiles, &c->densifyInts, 5LL * nTiles + 8)) return rc;
     // scratch: [nTiles] tile sums -> offsets | [8] counts: [0..3] action histogram, [4] total | [nTiles][4] histogram per tile
     uint32_t* cnt = reinterpret_cast<uint32_t*>(c->densifyTiles + nTiles);
     uint32_t* tileHist = cnt + 8;
@@ -504,8 +497,8 @@ static int densify_scan(gs_ctx* c, int N, const int* actions, const int* outputC
 int launch_densify_plan(gs_ctx* c, int N, const int* actions, const int* outputCounts, int* offsets)
 {
     if (!c->densifyPlan) {
-        GS_HIP_CHECK(c, hipMalloc((void**)&c->densifyPlan, 8 * sizeof(uint32_t)));
-        GS_HIP_CHECK(c, hipHostMalloc((void**)&c->densifyPlanHost, 8 * sizeof(uint32_t), hipHostMallocMapped));
+        if (const int rc = ctx_alloc(c, &c->densifyPlan, 8)) return rc;
+        if (const int rc = ctx_alloc_pinned(c, &c->densifyPlanHost, 8, hipHostMallocMapped)) return rc;
         GS_HIP_CHECK(c, hipHostGetDevicePointer((void**)&c->densifyPlanHostDev, c->densifyPlanHost, 0));
         GS_HIP_CHECK(c, hipEventCreateWithFlags(&c->densifyDone, hipEventDisableTiming));
     }
@@ -576,7 +569,7 @@ int launch_densify_gather_planned_packed(gs_ctx* c, int cap, int K, const float*
                                          const int* noiseMode, unsigned long long noiseSeed, float* outBase, const int order[6])
 {
     if (cap == 0) return GS_OK;
-    if (!c->densifyTable) GS_HIP_CHECK(c, hipMalloc((void**)&c->densifyTable, 8 * sizeof(float*)));
+    if (!c->densifyTable) { if (const int rc = ctx_alloc(c, &c->densifyTable, 8)) return rc; }
     hipLaunchKernelGGL(dn_packed_table_kernel, dim3(1), dim3(1), 0, c->stream, c->densifyPlan, outBase, K, order[0], order[1],
                        order[2], order[3], order[4], order[5], c->densifyTable, cap);
     const float scaleReduction = (float)(-log(1.6));                    // Float(-log(1.6)), :866

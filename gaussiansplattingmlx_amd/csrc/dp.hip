@@ -218,13 +218,13 @@ int dp_create(gs_ctx* c, ncclComm_t comm, bool own, int rank, int world, Rccl* l
     GS_HIP_CHECK(c, hipStreamCreateWithFlags(&d->sComm, hipStreamNonBlocking));
     hipEvent_t* evs[] = {&d->evFlag, &d->evGate, &d->evCc, &d->evGather, &d->evGeom, &d->evReduce};
     for (hipEvent_t* e : evs) GS_HIP_CHECK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    GS_HIP_CHECK(c, hipMalloc((void**)&d->words, 4 * sizeof(uint32_t)));
+    int rc;
+    if ((rc = ctx_alloc(c, &d->words, 4))) return rc;
     GS_HIP_CHECK(c, hipMemset(d->words, 0, 4 * sizeof(uint32_t)));
-    GS_HIP_CHECK(c, hipMalloc((void**)&d->need, 2 * sizeof(unsigned long long)));
-    GS_HIP_CHECK(c, hipHostMalloc((void**)&d->hostWords, 16 * sizeof(unsigned long long)));
-    GS_HIP_CHECK(c, hipMalloc((void**)&d->repl, (2 * GS_REPL_BLOCKS + 8) * sizeof(double)));
-    GS_HIP_CHECK(c, hipMalloc((void**)&d->planDev, 16 * sizeof(double)));
-    GS_HIP_CHECK(c, hipHostMalloc((void**)&d->planHost, 32 * sizeof(double)));
+    if ((rc = ctx_alloc(c, &d->need, 2)) || (rc = ctx_alloc_pinned(c, &d->hostWords, 16)) ||
+        (rc = ctx_alloc(c, &d->repl, 2 * GS_REPL_BLOCKS + 8)) || (rc = ctx_alloc(c, &d->planDev, 16)) ||
+        (rc = ctx_alloc_pinned(c, &d->planHost, 32)))
+        return rc;
     GS_HIP_CHECK(c, hipEventCreateWithFlags(&d->evRepl, hipEventDisableTiming));
     c->adamGate = d->words;         // from now on every optimizer kernel of the ctx tests the step's COMMON word
     c->gateSeen = d->words + 1;     // ... and one that finds it raised says so (gs_dp_check_overflow)
@@ -337,15 +337,10 @@ int gs_dp_shutdown(gs_ctx* c)
     for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
     for (auto& st : d->timed) for (hipEvent_t e : st.e) (void)hipEventDestroy(e);
     if (d->sComm) (void)hipStreamDestroy(d->sComm);
-    if (d->words) (void)hipFree(d->words);
-    if (d->need) (void)hipFree(d->need);
-    if (d->repl) (void)hipFree(d->repl);
-    if (d->planDev) (void)hipFree(d->planDev);
-    if (d->xyzOwn) (void)hipFree(d->xyzOwn);
-    if (d->xyzAdd) (void)hipFree(d->xyzAdd);
-    if (d->planHost) (void)hipHostFree(d->planHost);
     if (d->evRepl) (void)hipEventDestroy(d->evRepl);
-    if (d->hostWords) (void)hipHostFree(d->hostWords);
+    // (the context outlives its communicator: these go now, not with gs_ctx_destroy)
+    ctx_free(c, d->words); ctx_free(c, d->need); ctx_free(c, d->repl); ctx_free(c, d->planDev);
+    ctx_free(c, d->xyzOwn); ctx_free(c, d->xyzAdd); ctx_free(c, d->planHost); ctx_free(c, d->hostWords);
     delete d;
     c->dp = nullptr;
     return GS_OK;
@@ -376,12 +371,9 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
 {
     if (!c) return GS_ERR_INVALID_ARG;
     GsDp* d = c->dp;
-    if (const int rc = gs::refuse_pose_correction(c, "gs_dp_step")) return rc;
-    if (const int rc = gs::refuse_filter3d(c, "gs_dp_step")) return rc;
-    if (const int rc = gs::refuse_fisheye(c, "gs_dp_step")) return rc;
-    if (const int rc = gs::refuse_absgrad(c, "gs_dp_step")) return rc;
-    if (const int rc = gs::refuse_adc_stats(c, "gs_dp_step")) return rc;
-    if (const int rc = gs::refuse_sparse_adam(c, "gs_dp_step")) return rc;
+    if (const int rc = gs::refuse_modes(c, "gs_dp_step", {gs::GS_MODE_POSE, gs::GS_MODE_FILTER3D, gs::GS_MODE_FISHEYE, gs::GS_MODE_ABSGRAD,
+                                                          gs::GS_MODE_ADC_STATS, gs::GS_MODE_SPARSE_ADAM}))
+        return rc;
     if (!d) { c->err = "gs_dp_step: no communicator (gs_dp_init / gs_dp_attach)"; return GS_ERR_INVALID_ARG; }
     if (!a || (mode != GS_DP_ALLREDUCE && mode != GS_DP_SH_COMPRESSED)) { c->err = "gs_dp_step: bad mode / arguments"; return GS_ERR_INVALID_ARG; }
     if (!c->fwd.valid || c->fwd.consumed) { c->err = "gs_dp_step: no gs_render_forward on this context"; return GS_ERR_NO_FORWARD; }
@@ -462,15 +454,8 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
     // gradient's view-direction term is rebuilt for all views by the SH kernel below, which has the rows in hand
     const long long xyzFloats = (3LL * N + 3) & ~3LL;
     if (xyzFloats > d->xyzCap) {
-        GS_HIP_CHECK(c, hipStreamSynchronize(c->stream));       // (kernels of an earlier step may still read the old buffers)
-        if (d->xyzOwn) GS_HIP_CHECK(c, hipFree(d->xyzOwn));
-        if (d->xyzAdd) GS_HIP_CHECK(c, hipFree(d->xyzAdd));
-        d->xyzOwn = d->xyzAdd = nullptr; d->xyzCap = 0;
-        const long long cap = xyzFloats + xyzFloats / 2;
-        GS_HIP_CHECK(c, hipMalloc((void**)&d->xyzOwn, cap * sizeof(float)));
-        GS_HIP_CHECK(c, hipMalloc((void**)&d->xyzAdd, cap * sizeof(float)));
-        GS_HIP_CHECK(c, hipMemset(d->xyzAdd, 0, cap * sizeof(float)));      // (the pad behind 3 N is read by the Adam kernel's last float4)
-        d->xyzCap = cap;
+        if ((rc = ctx_grow_pair(c, &d->xyzOwn, &d->xyzAdd, &d->xyzCap, xyzFloats + xyzFloats / 2))) return rc;
+        GS_HIP_CHECK(c, hipMemset(d->xyzAdd, 0, d->xyzCap * sizeof(float)));      // (the pad behind 3 N is read by the Adam kernel's last float4)
     } else if (xyzFloats > 3LL * N) {
         GS_HIP_CHECK(c, hipMemsetAsync(d->xyzAdd + 3LL * N, 0, (xyzFloats - 3LL * N) * sizeof(float), c->stream));     // (N moves with every densify event)
     }

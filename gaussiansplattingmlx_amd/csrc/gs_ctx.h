@@ -2,12 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "../../include/gsplat.h"
 #include "gs_math.h"
+#include "gs_mem.h"
 
 // device counters held in ctx->counters (u32 each)
 enum {
@@ -131,14 +134,29 @@ struct GsRealGeom {          // the caller's tile grid (what the op-level entry 
     bool fast16 = false;
 };
 
+// What a forward runs under, and its backward with it.  gs_ctx holds it twice: `modes`, what the setters write for the next
+// forward, and `fwd.modes`, what the last forward ran under -- copied whole by gs_render_forward, so a field added here is
+// snapshotted without another line
+struct GsRenderModes {
+    // pose refinement (gs_set_pose_correction): caller-owned device delta[6] / grad_delta[6] (where the backward writes
+    // dL/d delta), nullptr = off
+    const float* poseDelta = nullptr;
+    float* poseGrad = nullptr;
+    bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode
+    bool fisheye = false;                // gs_set_camera_model: GS_CAMERA_FISHEYE (also read by the op-level projection)
+    int degree = 0;                      // the active SH degree (gs_set_sh_degree), 0 .. gs_ctx::maxDegree
+    GsBackground bg;                     // gs_set_background: what the blend composites over (unset: whiteBg's black or white)
+    const float* filter3d = nullptr;     // gs_set_filter3d: the caller-owned device widths [>= N], nullptr = off
+};
+
 struct gs_ctx {
     int device = 0;
     GsDp* dp = nullptr;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
-    int W = 0, H = 0, tileW = 16, tileH = 16, gridW = 0, gridH = 0, T = 0, degree = 0, whiteBg = 0;
+    int W = 0, H = 0, tileW = 16, tileH = 16, gridW = 0, gridH = 0, T = 0, whiteBg = 0;
     int tileBits = 1;
-    GsBackground bg;             // gs_set_background: what the following forwards composite over (unset: whiteBg's black or white)
+    GsRenderModes modes;         // the settings of the following forwards (fwd.modes: what the last one ran under)
     bool fast16 = false;
     GsVirtGeom virt;             // block lists (above); virt.nbx != 0 <=> tileW .. T describe the block grid, `real` the caller's
     GsRealGeom real;
@@ -151,7 +169,7 @@ struct gs_ctx {
     long long capM = 0;
     bool pairsReserved = false;  // caller sized capM itself: no host check of M per call
     bool reserving = false;      // inside gs_ctx_reserve with a pair reserve (pairsReserved is set once it has succeeded)
-    size_t ws_bytes = 0;
+    GsMem mem;                   // every device and pinned buffer below that the context owns (ctx_alloc .. ctx_grow, below)
 
     // per-Gaussian workspace
     float* packed12 = nullptr;       // [capN,12] means2d, conic, colour, opacity, depth, pad 
@@ -213,10 +231,8 @@ struct gs_ctx {
     uint32_t* missDev = nullptr;         // device address of missHost
     hipEvent_t fwdDone = nullptr;        // recorded after the forward blend when cuts were active
     const uint32_t* workHint = nullptr;  // = the caller's block-work buffer: sweep lengths of an earlier forward of this view
-    // pose refinement (gs_set_pose_correction): caller-owned device delta[6] / grad_delta[6], nullptr = off; the composed
-    // camera of the last posed forward (pose_camera_kernel) and the backward's wave partials ([16 x waves], grown on demand)
-    const float* poseDelta = nullptr;
-    float* poseGrad = nullptr;
+    // pose refinement (modes.poseDelta): the composed camera of the last posed forward (pose_camera_kernel) and the backward's
+    // wave partials ([16 x waves], grown on demand)
     gs::CamParams* poseCam = nullptr;
     float* posePartials = nullptr;
     long long posePartialsCap = 0;
@@ -237,9 +253,7 @@ struct gs_ctx {
     int bgChunks = 0, bgChunksW = 0, bgChunksH = 0;
     float* bgPartials = nullptr;
     long long bgPartialsCap = 0;
-    bool antialias = false;              // gs_set_antialiasing: the anti-aliased mode for the following forwards
-    bool fisheye = false;                // gs_set_camera_model: GS_CAMERA_FISHEYE for the following forwards and the op-level projection
-    int maxDegree = 0;                   // gs_ctx_create's sh_degree; `degree` is the active one (gs_set_sh_degree), 0 .. maxDegree
+    int maxDegree = 0;                   // gs_ctx_create's sh_degree; modes.degree is the active one (gs_set_sh_degree), 0 .. maxDegree
     int shBandSkip = 1;                  // GS_TUNE_SH_BAND_SKIP: 1 = a lower-degree fused Adam step takes the BANDS form (projection.hip)
     bool absgrad = false;                // gs_set_absgrad: the fused backward also sums |g_x|, |g_y| per Gaussian
     int absgradN = -1;                   // N of the last backward that left (Ax, Ay) in gradAcc16's columns 12, 13; -1: none to read
@@ -257,16 +271,14 @@ struct gs_ctx {
     float* adcGradSum = nullptr;
     float* adcCount = nullptr;
     float* adcMaxRadius = nullptr;
-    // 3-D smoothing filter (gs_set_filter3d): the caller-owned device widths [>= N] of the following forwards, nullptr = off; the
-    // training cameras' table for gs_compute_filter3d (GS_F3D_CAM_FLOATS floats per camera) and the max word of its never-seen
-    // rule, both allocated or grown by gs_set_filter3d_cameras only
-    const float* filter3d = nullptr;
+    // 3-D smoothing filter (modes.filter3d): the training cameras' table for gs_compute_filter3d (GS_F3D_CAM_FLOATS floats per
+    // camera) and the max word of its never-seen rule, both allocated or grown by gs_set_filter3d_cameras only
     float* f3dCams = nullptr;
     int f3dCamCount = 0, f3dCamCap = 0;
     uint32_t* f3dMax = nullptr;
     bool mcmcOn = false;                 // gs_set_mcmc: the MCMC strategy's step in gs_render_backward_adam, with these parameters
     gs_mcmc_params mcmc = {};
-    void* mcmcWs = nullptr;              // mcmc.hip: the event's scratch (grown on demand) and its pinned read-back words
+    char* mcmcWs = nullptr;              // mcmc.hip: the event's scratch (grown on demand) and its pinned read-back words
     size_t mcmcWsBytes = 0;
     long long* mcmcHost = nullptr;
     float* gradNormAccum = nullptr;      // caller-owned [N]: the projection backward adds |grad xyz| (gs_set_grad_norm_accum)
@@ -336,9 +348,9 @@ struct gs_ctx {
     double* metricsWs = nullptr;      // gs_image_metrics / gs_colour_moments: [metricsWsDoubles] per-block partials, allocated at the
     long long metricsWsDoubles = 0;   //   first call, regrown only for a larger image (metrics.hip metrics_ws_doubles)
     float* windowDev = nullptr;       // [121] default SSIM window
-    // densify scan scratch: [densifyTileCap] tile sums + 8 counters, grown on demand
+    // densify scan scratch: [densifyInts] 5 ints per scan tile (sum, histogram) + 8 counters, grown on demand
     int* densifyTiles = nullptr;
-    int densifyTileCap = 0;
+    long long densifyInts = 0;
     // the planned densify event (densify.hip): its plan words on the device, their copy in pinned host memory, the event behind them
     uint32_t* densifyPlan = nullptr;
     uint32_t* densifyPlanHost = nullptr;
@@ -383,13 +395,8 @@ struct gs_ctx {
                     *opacity = nullptr;
         const float *outColor = nullptr, *outDepth = nullptr, *outAlpha = nullptr;
         gs::CamParams cam;
-        const float* poseDelta = nullptr;  // the correction this forward was composed with (nullptr: none) ...
-        float* poseGrad = nullptr;         // ... and where its backward writes dL/d delta
-        bool antialias = false;            // the anti-aliased mode this forward ran in (its backward's mode)
-        bool fisheye = false;              // the camera model this forward ran in (its backward's model)
-        int degree = 0;                    // the active SH degree this forward ran with (its backward's)
-        GsBackground bg;                   // the background this forward composited over (its backward's)
-        const float* filter3d = nullptr;   // the 3-D filter widths this forward ran with (its backward's; nullptr: none)
+        GsRenderModes modes;               // what this forward ran under: its backward's pose correction, anti-aliasing, camera
+                                           // model, SH degree, background and 3-D filter
         const float* radii = nullptr;      // where this forward's projection wrote its radii (nullptr: nowhere)
         uint32_t* cutStore = nullptr;  // the view's cut words at the time of this forward (nullptr: none kept)
         bool cutsActive = false;     // this forward binned under depth cuts
@@ -412,6 +419,65 @@ struct gs_ctx {
             return GS_ERR_HIP;                                                               \
         }                                                                                    \
     } while (0)
+
+// ---- the context's memory: every device and pinned buffer of gs_ctx and GsDp goes through these (gs_mem.h keeps the record,
+// gs_workspace_bytes reports its device bytes, gs_ctx_destroy frees what is left) ------------------------------------------
+const GsMemBackend* gs_hip_mem_backend();      // api.hip: hipMalloc / hipFree / hipHostMalloc / hipHostFree
+
+static inline int ctx_mem_error(gs_ctx* c, const char* expr, int e)
+{
+    c->err = std::string(expr) + ": " + hipGetErrorString((hipError_t)e);
+    return GS_ERR_HIP;
+}
+// count elements of device memory (a count of 0 allocates 1); GS_ERR_HIP with the failing expression in c->err
+template <class T>
+int ctx_alloc(gs_ctx* c, T** p, size_t count)
+{
+    if (count == 0) count = 1;
+    const int e = c->mem.alloc((void**)p, count * sizeof(T));
+    return e ? ctx_mem_error(c, "hipMalloc((void**)p, count * sizeof(T))", e) : GS_OK;
+}
+// ... of pinned host memory: recorded and freed with the context, not counted in gs_workspace_bytes
+template <class T>
+int ctx_alloc_pinned(gs_ctx* c, T** p, size_t count, unsigned flags = hipHostMallocDefault)
+{
+    const int e = c->mem.alloc((void**)p, count * sizeof(T), true, flags);
+    return e ? ctx_mem_error(c, "hipHostMalloc((void**)p, count * sizeof(T), flags)", e) : GS_OK;
+}
+// forgets, frees and nulls p (device or pinned).  A pointer the context does not own is left alone and reported
+template <class T>
+void ctx_free(gs_ctx* c, T*& p)
+{
+    if (!c->mem.free((void*)p)) {
+        c->err = "ctx_free: a pointer the context does not own";
+        fprintf(stderr, "gsplat: %s (%p)\n", c->err.c_str(), (void*)p);
+        return;
+    }
+    p = nullptr;
+}
+// grow on demand (GsMem::grow): nothing while want <= *cap; otherwise waits for the context's stream if the buffer exists,
+// frees it, and allocates `want` units of `per` elements each.  *cap is 0 while *p is null
+template <class T, class Cap>
+int ctx_grow(gs_ctx* c, T** p, Cap* cap, long long want, size_t per = 1)
+{
+    const char* expr = "hipMalloc((void**)p, count * sizeof(T))";
+    const int e = c->mem.grow((void**)p, cap, want, per * sizeof(T), [&] {
+        const hipError_t w = hipStreamSynchronize(c->stream);
+        if (w != hipSuccess) expr = "hipStreamSynchronize(c->stream)";
+        return (int)w;
+    });
+    return e ? ctx_mem_error(c, expr, e) : GS_OK;
+}
+// two buffers that one capacity describes: both hold `want` afterwards, or neither exists
+template <class A, class B, class Cap>
+int ctx_grow_pair(gs_ctx* c, A** a, B** b, Cap* cap, long long want)
+{
+    Cap capB = *cap;
+    int rc = ctx_grow(c, a, cap, want);
+    if (rc == GS_OK) rc = ctx_grow(c, b, &capB, want);
+    if (rc) { ctx_free(c, *a); ctx_free(c, *b); *cap = 0; }
+    return rc;
+}
 
 static inline int gs_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 // does the depth sort of n records take the splitter buckets or the two-launch passes (binning.hip, depth_sort)?
@@ -446,13 +512,11 @@ struct GsStageTimer {
 // ---- internal launchers (defined in the .hip files) -------------------------
 namespace gs {
 
-// api.hip: refusals that api.hip and dp.hip share (host code; `who` is the entry point's name, in front of the message)
-int refuse_pose_correction(gs_ctx* c, const char* who);      // GS_ERR_INVALID_ARG while a pose correction is bound
-int refuse_fisheye(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while the fisheye model is set (or the forward ran in it)
-int refuse_filter3d(gs_ctx* c, const char* who);             // GS_ERR_INVALID_ARG while a 3-D filter is set (or the forward ran with one)
-int refuse_absgrad(gs_ctx* c, const char* who);              // GS_ERR_INVALID_ARG while absgrad is on (gs_set_absgrad)
-int refuse_sparse_adam(gs_ctx* c, const char* who);          // GS_ERR_INVALID_ARG while sparse Adam is on (gs_set_sparse_adam)
-int refuse_adc_stats(gs_ctx* c, const char* who);            // GS_ERR_INVALID_ARG while the ADC statistic is set (gs_set_adc_stats)
+// api.hip: the refusal that api.hip and dp.hip share (host code).  GS_ERR_INVALID_ARG with the message of the first of `unserved`
+// that is in force -- set now or, for pose, filter and fisheye, what the last forward ran with; `who` is the entry point's name, in
+// front of the message
+enum GsMode { GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_ABSGRAD, GS_MODE_SPARSE_ADAM, GS_MODE_ADC_STATS };
+int refuse_modes(gs_ctx* c, const char* who, std::initializer_list<GsMode> unserved);
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
 CamParams make_cam(const gs_camera* cam, int W, int H);
@@ -633,7 +697,6 @@ int launch_mcmc_random(gs_ctx* c, unsigned long long seed, int iteration, int st
                        double* uniforms);
 int mcmc_relocate(gs_ctx* c, int N, int K, const McmcRows& rows, const gs_mcmc_params& p, long long stats[4]);
 int mcmc_grow(gs_ctx* c, int N, int capacity, int K, const McmcRows& rows, const gs_mcmc_params& p, int* nOut);
-void mcmc_free(gs_ctx* c);
 // knn.hip
 int launch_dist_topk(gs_ctx* c, int N, int k, int qBegin, int qCount, const float* xyz, float* out);
 // ply.hip

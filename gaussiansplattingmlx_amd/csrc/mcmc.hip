@@ -296,13 +296,6 @@ int launch_mcmc_random(gs_ctx* c, unsigned long long seed, int iteration, int st
     return GS_OK;
 }
 
-void mcmc_free(gs_ctx* c)
-{
-    if (c->mcmcWs) (void)hipFree(c->mcmcWs);
-    if (c->mcmcHost) (void)hipHostFree(c->mcmcHost);
-    c->mcmcWs = nullptr; c->mcmcHost = nullptr; c->mcmcWsBytes = 0;
-}
-
 namespace {
 
 struct McmcWs {
@@ -330,13 +323,10 @@ int mcmc_ws(gs_ctx* c, int N, McmcWs& w)
     size_t total = 0;
     for (size_t s : sz) total += s;
     if (total > c->mcmcWsBytes) {
-        if (c->mcmcWs) { GS_HIP_CHECK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->mcmcWs); c->mcmcWs = nullptr; c->mcmcWsBytes = 0; }
-        const size_t want = total + total / 2;
-        GS_HIP_CHECK(c, hipMalloc(&c->mcmcWs, want));
-        c->mcmcWsBytes = want;
+        if (const int rc = ctx_grow(c, &c->mcmcWs, &c->mcmcWsBytes, (long long)(total + total / 2))) return rc;
     }
-    if (!c->mcmcHost) GS_HIP_CHECK(c, hipHostMalloc((void**)&c->mcmcHost, 4 * sizeof(long long), hipHostMallocDefault));
-    char* b = static_cast<char*>(c->mcmcWs);
+    if (!c->mcmcHost) { if (const int rc = ctx_alloc_pinned(c, &c->mcmcHost, 4)) return rc; }
+    char* b = c->mcmcWs;
     w.cdf = reinterpret_cast<double*>(b); b += sz[0];
     w.cand = reinterpret_cast<int*>(b); b += sz[1];
     w.dead = reinterpret_cast<int*>(b); b += sz[2];

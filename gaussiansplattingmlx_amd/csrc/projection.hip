@@ -1236,13 +1236,13 @@ int launch_projection_forward(gs_ctx* c, int N, int K, const float* scales, cons
                               float* cov2d, float* conic, float* radii, float* rectMin, float* rectMax)
 {
     if (N == 0) return GS_OK;
-    if (c->fisheye)
+    if (c->modes.fisheye)
         hipLaunchKernelGGL(proj_fwd_op_fisheye_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
-                           c->degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii,
+                           c->modes.degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii,
                            rectMin, rectMax);
     else
     hipLaunchKernelGGL(proj_fwd_op_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
-                       c->degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii,
+                       c->modes.degree, cam, scales, rot, means3d, shs, means2d, depths, color, cov2d, conic, radii,
                        rectMin, rectMax);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
@@ -1255,13 +1255,13 @@ int launch_projection_backward(gs_ctx* c, int N, int K, const float* scales, con
                                float* gCam)
 {
     if (N == 0) return GS_OK;
-    if (c->fisheye)
+    if (c->modes.fisheye)
         hipLaunchKernelGGL(proj_bwd_op_fisheye_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
-                           c->degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor,
+                           c->modes.degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor,
                            cotConic, gScales, gRot, gMeans, gShs, gCam);
     else
     hipLaunchKernelGGL(proj_bwd_op_kernel, dim3(gs_div_up(N, PROJ_THREADS)), dim3(PROJ_THREADS), 0, c->stream, N, K,
-                       c->degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor,
+                       c->modes.degree, cam, scales, rot, means3d, shs, cotDepths, cotMeans2d, cotCov2d, cotColor,
                        cotConic, gScales, gRot, gMeans, gShs, gCam);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
@@ -1291,7 +1291,7 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
     // kernel (16385 .. 655 k Gaussians, not the context's first forward).  Elsewhere the split costs more than it hides
     // (measured): one projection kernel as before.  GS_TUNE_COLOUR_RIDERS = 2 forces the split (A/B).
     // pose refinement: the camera lives on the device, and only this kernel reads it -- no riders, no self-colour split
-    const bool posed = c->poseDelta != nullptr;
+    const bool posed = c->modes.poseDelta != nullptr;
     c->rider.on = !posed && K == GS_RIDER_K && (c->colourRiders == 2 || (c->colourRiders == 1 && depth_sort_takes_splitters(c, N)));
     // where no rider travels (the LSD depth sort's and the one-workgroup sort's kernels are no hosts): geometry first, then
     // the wave's own colours with the rows of unseen Gaussians left out -- faster than the interleaved one-kernel form at
@@ -1317,7 +1317,7 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
     ColourRider a = {};
     a.xyz = xyz; a.fdc = fdc; a.frest = frest; a.packed12 = c->packed12; a.tilesTouched = c->tilesTouched;
     a.cam[0] = cam.cam[0]; a.cam[1] = cam.cam[1]; a.cam[2] = cam.cam[2];
-    a.N = N; a.degree = c->degree; a.unit0 = 0; a.units = gs_div_up(N, 64);
+    a.N = N; a.degree = c->modes.degree; a.unit0 = 0; a.units = gs_div_up(N, 64);
     if (c->rider.on) {
         c->rider.args = a;
         c->rider.args.units = 0;
@@ -1332,10 +1332,10 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
         [&](auto TWO_PHASE, auto COLOUR, auto SELF, auto AA, auto F3D, auto POSE, auto FISHEYE) {
             if constexpr (proj_fwd_form_exists(TWO_PHASE, COLOUR, SELF, POSE, F3D, FISHEYE)) {
                 hipLaunchKernelGGL((proj_fwd_fused_kernel<TWO_PHASE, COLOUR, SELF, AA, F3D, POSE, FISHEYE>), dim3(gs_div_up(N, PROJ_FUSED_THREADS)),
-                                   dim3(PROJ_FUSED_THREADS), dynLds, c->stream, N, K, c->degree, cam, c->tileW, c->tileH,
+                                   dim3(PROJ_FUSED_THREADS), dynLds, c->stream, N, K, c->modes.degree, cam, c->tileW, c->tileH,
                                    c->gridW, c->gridH, xyz, fdc, frest, scales, rot, opacity, c->packed12, radii, c->tileRect,
                                    c->tilesTouched, c->depthKey[0], c->depthVal[0], c->visPerBlock, c->counters, pflags, a, c->virt, cc,
-                                   pieces, c->filter3d, c->poseCam);
+                                   pieces, c->modes.filter3d, c->poseCam);
                 return GS_OK;
             } else {      // unreachable: rider.on and selfColour each imply !posed and exclude one another, and api.hip refuses a
                           // fisheye forward under a pose correction or a 3-D filter, so the form exists;
@@ -1344,7 +1344,7 @@ int launch_projection_fused_forward(gs_ctx* c, int N, int K, const float* xyz, c
                 return GS_ERR_INVALID_ARG;
             }
         },
-        !colour || twoPhase, colour, selfColour, c->antialias, c->filter3d != nullptr, posed, c->fisheye);
+        !colour || twoPhase, colour, selfColour, c->modes.antialias, c->modes.filter3d != nullptr, posed, c->modes.fisheye);
     if (rc) return rc;
     c->visBlocks = gs_div_up(N, PROJ_FUSED_THREADS);
     GS_HIP_CHECK(c, hipGetLastError());
@@ -1388,14 +1388,14 @@ struct ProjBwdGrads { float *xyz, *fdc, *frest, *scales, *rot, *opacity; };
 static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, const AdamFuse& adam)
 {
     const int N = c->fwd.N, K = c->fwd.K;
-    if (N == 0) return c->fwd.poseDelta && mode != 1 ? launch_pose_grad(c, 0) : GS_OK;
-    const bool f3d = c->fwd.filter3d != nullptr;       // (the filter this backward's forward ran with; no data-parallel form: api.hip refuses)
+    if (N == 0) return c->fwd.modes.poseDelta && mode != 1 ? launch_pose_grad(c, 0) : GS_OK;
+    const bool f3d = c->fwd.modes.filter3d != nullptr;       // (the filter this backward's forward ran with; no data-parallel form: api.hip refuses)
     if (f3d && mode == 1) mode = 0;
-    const bool pose = c->fwd.poseDelta && mode != 1;
+    const bool pose = c->fwd.modes.poseDelta && mode != 1;
     const bool mcmc = mode == 2 && !f3d && c->mcmcOn;
     const bool sparse = mode == 2 && !f3d && !mcmc && c->sparseAdam;      // (api.hip has checked that the forward left its mask)
     ProjBwdArgs a = {};
-    a.N = N; a.K = K; a.degree = c->fwd.degree;      // (the degree this backward's forward ran with: gs_set_sh_degree)
+    a.N = N; a.K = K; a.degree = c->fwd.modes.degree;      // (the degree this backward's forward ran with: gs_set_sh_degree)
     a.cam = c->fwd.cam; a.dcam = c->poseCam;
     a.xyz = c->fwd.xyz; a.fdc = c->fwd.fdc; a.frest = c->fwd.frest; a.scalesRaw = c->fwd.scales; a.rotRaw = c->fwd.rot;
     a.opacityRaw = c->fwd.opacity; a.gradAcc16 = c->gradAcc16;
@@ -1404,7 +1404,7 @@ static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, con
     a.adam = adam;
     a.posePartials = c->posePartials;
     if (mcmc) a.mc = mcmc_fuse(c->mcmc, N, adam.lr[0]);
-    a.filter3d = c->fwd.filter3d;
+    a.filter3d = c->fwd.modes.filter3d;
     a.visMask = c->visMask;
     // the band-limited form: a plain fused Adam step below the degree K allows (GS_TUNE_SH_BAND_SKIP 0: the full-row form, whose
     // inactive columns meet exact zero gradients); at degree 0 it uses no LDS
@@ -1424,7 +1424,7 @@ static int launch_proj_bwd_fused(gs_ctx* c, int mode, const ProjBwdGrads& g, con
                 return GS_ERR_INVALID_ARG;
             }
         },
-        mode == 2, mode == 1, pose, c->fwd.antialias, mcmc, f3d, sparse, c->fwd.fisheye, bands);
+        mode == 2, mode == 1, pose, c->fwd.modes.antialias, mcmc, f3d, sparse, c->fwd.modes.fisheye, bands);
     if (rc) return rc;
     GS_HIP_CHECK(c, hipGetLastError());
     return pose ? launch_pose_grad(c, N) : GS_OK;
@@ -1480,7 +1480,7 @@ int launch_sh_grad_from_views(gs_ctx* c, int N, int K, int R, const float* xyz, 
     AdamFuse none = {};
     fill_gathered_gate(c, N, mgAll, none);
     hipLaunchKernelGGL(sh_grad_from_views_kernel<false>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                       lds, c->stream, N, K, c->degree, v, xyz, mgAll, cc_block_floats(c, N), gFdc, gFrest, nullptr, nullptr, none);
+                       lds, c->stream, N, K, c->modes.degree, v, xyz, mgAll, cc_block_floats(c, N), gFdc, gFrest, nullptr, nullptr, none);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }
@@ -1502,7 +1502,7 @@ int launch_sh_grad_from_views_adam(gs_ctx* c, int N, int K, int R, const float* 
     a.gate = c->adamGate;
     fill_gathered_gate(c, N, mgAll, a);
     hipLaunchKernelGGL(sh_grad_from_views_kernel<true>, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS),
-                       lds, c->stream, N, K, c->degree, v, xyz, mgAll, cc_block_floats(c, N), nullptr, nullptr, fdcParam, frestParam, a);
+                       lds, c->stream, N, K, c->modes.degree, v, xyz, mgAll, cc_block_floats(c, N), nullptr, nullptr, fdcParam, frestParam, a);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }
@@ -1518,7 +1518,7 @@ int launch_projection_geom_backward(gs_ctx* c, float* gXyz, float* gScales, floa
                                c->packed12, colorCot, c->counters + GS_CNT_OVERFLOW, c->overflowRider);
             return GS_OK;
         },
-        c->fwd.antialias);
+        c->fwd.modes.antialias);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }
@@ -1544,7 +1544,7 @@ int launch_sh_views_dir_adam(gs_ctx* c, int N, int K, int R, const float* xyz, c
     a.gate = c->adamGate;
     fill_gathered_gate(c, N, mgAll, a);
     hipLaunchKernelGGL(sh_views_dir_adam_kernel, dim3(gs_div_up(N, PROJ_FUSED_THREADS)), dim3(PROJ_FUSED_THREADS), lds, c->stream, N,
-                       K, c->degree, v, xyz, mgAll, cc_block_floats(c, N), fdcParam, frestParam, xyzAdd, c->gradNormAccum, a);
+                       K, c->modes.degree, v, xyz, mgAll, cc_block_floats(c, N), fdcParam, frestParam, xyzAdd, c->gradNormAccum, a);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }
@@ -1734,7 +1734,7 @@ int launch_pose_grad(gs_ctx* c, int N)
 {
     const int parts = (int)(pose_partials_floats(N) / 16);
     hipLaunchKernelGGL(pose_grad_kernel, dim3(1), dim3(256), 0, c->stream, N > 0 ? parts : 0, c->posePartials, c->fwd.cam,
-                       c->fwd.poseDelta, c->fwd.poseGrad);
+                       c->fwd.modes.poseDelta, c->fwd.modes.poseGrad);
     GS_HIP_CHECK(c, hipGetLastError());
     return GS_OK;
 }

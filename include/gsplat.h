@@ -101,7 +101,8 @@ int gs_ctx_set_stream(gs_ctx* ctx, void* hip_stream);
  *     gs_forward_missed that sees the flag returns GS_ERR_WORKSPACE_OVERFLOW (gs_last_error names the M needed) and
  *     keeps returning it until gs_sync has reported it once or gs_ctx_reserve has been called again. */
 int gs_ctx_reserve(gs_ctx* ctx, int max_gaussians, long long max_pairs);
-/* Bytes of device workspace currently held. */
+/* Bytes of device workspace currently held: every device buffer the context owns, including the on-demand ones of the
+ * densify, MCMC and data-parallel paths (pinned host memory is not counted). */
 size_t gs_workspace_bytes(const gs_ctx* ctx);
 /* Wait for the stream and report deferred errors (GS_ERR_WORKSPACE_OVERFLOW of any forward since the last report). [sync] */
 int gs_sync(gs_ctx* ctx);

@@ -120,6 +120,25 @@ def test_c_header_is_plain_c_and_the_cpp_host_links(tmp_path, lib):
         assert res.returncode == 10
 
 
+def test_context_memory_record_under_sanitizers(tmp_path):
+    """csrc/gs_mem.h, the record behind ctx_alloc / ctx_free / ctx_grow, driven by host/ctx_mem_check.cpp with a counting
+    malloc / free backend: the device bytes always equal the sum of the live device allocations and never count pinned ones,
+    a grow within the capacity touches nothing, a failed allocation leaves pointer null / capacity 0 / bytes unchanged and
+    every other buffer is still freed, a pointer the record does not know is refused rather than freed, and after freeAll
+    the backend has nothing outstanding.  Built with AddressSanitizer (LeakSanitizer with it) and UBSan, run as a plain
+    executable."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if not shutil.which("gcc") or not shutil.which("g++"):
+        pytest.skip("no host compiler")
+    exe = tmp_path / "ctx_mem_check"
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", root, os.path.join(root, "host", "ctx_mem_check.cpp"), "-o", str(exe)], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and "ctx_mem_check ok" in res.stdout, (res.returncode, res.stdout, res.stderr)
+
+
 def test_cut_policy():
     """renderer.CutPolicy (pure host logic): no cuts while the view's cuts are empty -- they are written by the
     preparation of a backward, a view that was only rendered has none -- a view whose cuts leave out too little sits
