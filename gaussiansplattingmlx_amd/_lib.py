@@ -55,6 +55,13 @@ class gs_normal_loss_params(C.Structure):
         [("accumulate", C.c_int)]
 
 
+class gs_distortion_params(C.Structure):
+    _fields_ = [("map", C.c_int), ("near", C.c_float), ("far", C.c_float)]
+
+
+GS_DISTORTION_NDC, GS_DISTORTION_LINEAR = 0, 1
+
+
 class gs_lens(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "dst_fx", "dst_fy", "dst_cx", "dst_cy")]
 
@@ -127,6 +134,12 @@ _SIGS = {
     "gs_render_features": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gs_render_features_backward": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gs_feature_channel_group": (C.c_int, []),
+    "gs_blend_distortion": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(gs_distortion_params), _vp, _vp]),
+    "gs_blend_distortion_backward": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(gs_distortion_params), _vp, _vp, _vp]),
+    "gs_render_distortion": (C.c_int, [_vp, C.POINTER(gs_distortion_params), _vp, _vp]),
+    "gs_render_distortion_backward": (C.c_int, [_vp, C.POINTER(gs_distortion_params), _vp, _vp, _vp]),
+    "gs_distortion_loss": (C.c_int, [_vp, C.c_float, C.c_longlong, _vp, _vp, _vp, _vp]),
+    "gs_arm_distortion": (C.c_int, [_vp, C.POINTER(gs_distortion_params), _vp, _vp]),
     "gs_ssim_window": (C.c_int, [C.c_int, C.c_float, _vp]),
     "gs_ssim_forward": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp] * 9),
     "gs_ssim_backward": (C.c_int, [_vp] + [C.c_int] * 4 + [_vp] * 11),

@@ -32,6 +32,7 @@ SOURCES = {
     "filter3d.hip": ["-ffp-contract=off"],
     "contrib.hip": ["-ffp-contract=off"],
     "features.hip": ["-ffp-contract=off"],
+    "distortion.hip": ["-ffp-contract=off"],
     "background.hip": ["-ffp-contract=off"],
     "depth_loss.hip": ["-ffp-contract=off"],
     "normal_loss.hip": ["-ffp-contract=off"],

@@ -250,6 +250,14 @@ int backward_preflight(gs_ctx* c, const char* who, bool wantsDepth)
     return GS_OK;
 }
 
+// the armed distortion term's backward into the context's own accumulator rows (gs_arm_distortion): between the blend backward
+// that fills them and their readers (a stage of its own, inside the blend-backward stage's interval)
+int distortion_backward_of_forward(gs_ctx* c)
+{
+    GsStageTimer t(c, GS_STAGE_DISTORTION_BWD);
+    return launch_blend_distortion_backward(c, c->distortion.params, c->distortion.cot, c->distortion.totals, c->gradAcc16);
+}
+
 // the blend backward of the last fused forward: the first stage of every backward entry point
 // absgrad (gs_set_absgrad; gs_render_backward and gs_render_backward_adam only): the ABSGRAD instantiation, which leaves (Ax, Ay)
 // in columns 12 and 13 of gradAcc16, and behind it the AbsGS statistic into the grad-norm accumulator (gate: the overflow word
@@ -262,10 +270,18 @@ int blend_backward_of_forward(gs_ctx* c, const float* cot_color, const float* co
                                           "gs_render_forward)");
     GsStageTimer t(c, GS_STAGE_BLEND_BWD);
     c->absgradN = -1;
-    if (!c->fast16) return launch_blend_backward(c, c->fwd.modes.bg, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+    if (!c->fast16) {
+        const int rc = launch_blend_backward(c, c->fwd.modes.bg, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outAlpha, c->lastContrib);
+        return rc || !c->distortion.armed ? rc : distortion_backward_of_forward(c);
+    }
     if (const int rc = launch_blend_backward_v2(c, c->fwd.N, cot_color, cot_depth, cot_alpha, c->fwd.outColor, c->fwd.outDepth,
                                                 c->fwd.outAlpha, absgrad))
         return rc;
+    // the distortion term (gs_arm_distortion) adds its cotangents to the rows the blend backward has filled, in front of
+    // everything that reads them: the ADC statistic below sees the term in columns 0 and 1
+    if (c->distortion.armed) {
+        if (const int rc = distortion_backward_of_forward(c)) return rc;
+    }
     // the ADC statistic (gs_set_adc_stats), from the signed mean gradient in columns 0 and 1 -- the absolute sums under absgrad
     if (c->adcGradSum) {
         if (const int rc = launch_adc_accum(c, c->fwd.N, c->gradAcc16, c->fwd.radii, absgrad, gate, c->adcGradSum, c->adcCount,
@@ -409,6 +425,10 @@ int refuse_modes(gs_ctx* c, const char* who, std::initializer_list<GsMode> unser
         case GS_MODE_ADC_STATS:
             if (c->adcGradSum) why = ": the ADC statistic is set (gs_set_adc_stats): only gs_render_backward and gs_render_backward_adam "
                                      "accumulate it";
+            break;
+        case GS_MODE_DISTORTION:
+            if (c->distortion.armed) why = ": the distortion term is armed (gs_arm_distortion): only gs_render_backward and "
+                                           "gs_render_backward_adam run its backward (single-device steps only)";
             break;
         }
         if (why) return fail(c, GS_ERR_INVALID_ARG, std::string(who) + why);
@@ -850,6 +870,67 @@ int gs_blend_features_backward(gs_ctx* c, int N, int C, const float* packed, con
 
 int gs_feature_channel_group(void) { return feature_channel_group(); }
 
+// ---- depth distortion loss (include/gsplat.h gs_blend_distortion ..; distortion.hip) -----------------------------------------
+// what every distortion entry point asks of its params
+static int distortion_params_check(gs_ctx* c, const char* who, const gs_distortion_params* p)
+{
+    if (!p) return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": null params");
+    if (p->map != GS_DISTORTION_NDC && p->map != GS_DISTORTION_LINEAR)
+        return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": map is GS_DISTORTION_NDC or GS_DISTORTION_LINEAR");
+    if (p->map == GS_DISTORTION_NDC && !(isfinite(p->near) && isfinite(p->far) && p->near > 0.0f && p->far > p->near))
+        return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": near and far are finite with 0 < near < far");
+    return GS_OK;
+}
+
+// the op-level pair's preconditions: gs_blend_contrib's
+static int blend_distortion_preflight(gs_ctx* c, const char* who, int N, const float* packed, const gs_distortion_params* p)
+{
+    if (!c->binValid) return fail(c, GS_ERR_NO_FORWARD, std::string(who) + ": call gs_tile_bin first");
+    if (c->binIsBlockLists) return fail(c, GS_ERR_NO_FORWARD, std::string(who) + ": the last binning on this context was a fused forward's block lists (tile size not a multiple of 16); call gs_tile_bin");
+    if (N != c->binN) return fail(c, GS_ERR_SIZE_MISMATCH, std::string(who) + ": N differs from the binned N");
+    if (N > 0 && !packed) return fail(c, GS_ERR_INVALID_ARG, std::string(who) + ": null buffer");
+    return distortion_params_check(c, who, p);
+}
+
+int gs_blend_distortion(gs_ctx* c, int N, const float* packed, const gs_distortion_params* params, float* out_distort,
+                        float* out_totals)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (const int prc = blend_distortion_preflight(c, "gs_blend_distortion", N, packed, params)) return prc;
+    if (!out_distort || !out_totals) return fail(c, GS_ERR_INVALID_ARG, "gs_blend_distortion: null buffer");
+    RealGeomScope real(c);
+    c->fwd.valid = false; c->fwd.bwdPrepared = false;      // as gs_blend_forward: the ctx's packed records are overwritten
+    if (const int rc = launch_pack11_to_12(c, N, packed)) return rc;
+    return launch_blend_distortion(c, *params, out_distort, out_totals);
+}
+
+int gs_blend_distortion_backward(gs_ctx* c, int N, const float* packed, const gs_distortion_params* params, const float* cot,
+                                 const float* totals, float* rows16)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (const int prc = blend_distortion_preflight(c, "gs_blend_distortion_backward", N, packed, params)) return prc;
+    if (!cot || !totals || (N > 0 && !rows16)) return fail(c, GS_ERR_INVALID_ARG, "gs_blend_distortion_backward: null buffer");
+    RealGeomScope real(c);
+    c->fwd.valid = false; c->fwd.bwdPrepared = false;
+    if (const int rc = launch_pack11_to_12(c, N, packed)) return rc;
+    return launch_blend_distortion_backward(c, *params, cot, totals, rows16);
+}
+
+int gs_distortion_loss(gs_ctx* c, float weight, long long n_pixels, const float* distort, const unsigned char* mask, float* loss,
+                       float* cot_out)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (n_pixels < 0) return fail(c, GS_ERR_INVALID_ARG, "gs_distortion_loss: negative n_pixels");
+    if (!isfinite(weight)) return fail(c, GS_ERR_INVALID_ARG, "gs_distortion_loss: weight is finite");
+    if (!distort || !loss || !cot_out) return fail(c, GS_ERR_INVALID_ARG, "gs_distortion_loss: null buffer");
+    if (!c->distortionWs) {      // the first call: a step never allocates after it
+        GS_HIP_CHECK(c, hipSetDevice(c->device));
+        if (const int rc = ctx_alloc(c, &c->distortionWs, (size_t)distortion_loss_ws_doubles())) return rc;
+    }
+    GsStageTimer t(c, GS_STAGE_LOSS);
+    return launch_distortion_loss(c, weight, n_pixels, distort, mask, loss, cot_out);
+}
+
 // ---- SSIM -----------------------------------------------------------------------------------------
 int gs_ssim_window(int K, float sigma, float* window)
 {
@@ -913,6 +994,7 @@ int gs_render_forward(gs_ctx* c, int N, int K, const float* xyz, const float* fe
         return fail(c, GS_ERR_INVALID_ARG, "gs_render_forward: the fisheye camera model has no 3-D filter (gs_set_filter3d is set)");
     c->fwd.valid = false;
     c->visN = -1;
+    c->distortion.armed = false;         // (gs_arm_distortion arms the term for one forward)
     const bool keepRadii = c->sparseAdam || c->adcGradSum != nullptr;      // (the ADC statistic reads the radii in the backward)
     if (keepRadii && N > c->visCap) {           // sparse Adam's mask and radii: grown by the first forward that needs more rows
         if (const int arc = ctx_grow_pair(c, &c->visMask, &c->visRadii, &c->visCap, N > c->capN ? N : c->capN)) return arc;
@@ -1509,6 +1591,39 @@ int gs_render_features_backward(gs_ctx* c, int C, const float* cot, float* grad_
     return launch_blend_features_backward(c, C, cot, grad_features);
 }
 
+// read the forward's records and lists, write nothing of the context's: a backward and further calls may follow
+int gs_render_distortion(gs_ctx* c, const gs_distortion_params* params, float* out_distort, float* out_totals)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    { const int prc = backward_preflight(c, "gs_render_distortion", false); if (prc) return prc; }
+    if (const int rc = distortion_params_check(c, "gs_render_distortion", params)) return rc;
+    if (!out_distort || !out_totals) return fail(c, GS_ERR_INVALID_ARG, "gs_render_distortion: null buffer");
+    return launch_blend_distortion(c, *params, out_distort, out_totals);
+}
+
+int gs_render_distortion_backward(gs_ctx* c, const gs_distortion_params* params, const float* cot, const float* totals, float* rows16)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    { const int prc = backward_preflight(c, "gs_render_distortion_backward", false); if (prc) return prc; }
+    if (const int rc = distortion_params_check(c, "gs_render_distortion_backward", params)) return rc;
+    if (!cot || !totals || (c->fwd.N > 0 && !rows16)) return fail(c, GS_ERR_INVALID_ARG, "gs_render_distortion_backward: null buffer");
+    return launch_blend_distortion_backward(c, *params, cot, totals, rows16);
+}
+
+int gs_arm_distortion(gs_ctx* c, const gs_distortion_params* params, const float* cot, const float* totals)
+{
+    if (!c) return GS_ERR_INVALID_ARG;
+    if (!params && !cot && !totals) { c->distortion.armed = false; return GS_OK; }
+    { const int prc = backward_preflight(c, "gs_arm_distortion", false); if (prc) return prc; }
+    if (const int rc = distortion_params_check(c, "gs_arm_distortion", params)) return rc;
+    if (!cot || !totals) return fail(c, GS_ERR_INVALID_ARG, "gs_arm_distortion: null buffer (all three NULL disarms)");
+    c->distortion.armed = true;
+    c->distortion.params = *params;
+    c->distortion.cot = cot;
+    c->distortion.totals = totals;
+    return GS_OK;
+}
+
 int gs_contrib_actions(gs_ctx* c, int N, const float* score, float threshold, int* actions, int* output_counts)
 {
     if (!c) return GS_ERR_INVALID_ARG;
@@ -1542,7 +1657,7 @@ int gs_render_backward_dp_begin(gs_ctx* c, const float* cot_color, const float* 
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_modes(c, "gs_render_backward_dp_begin", {GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_SPARSE_ADAM,
-                                                                   GS_MODE_ABSGRAD, GS_MODE_ADC_STATS}))
+                                                                   GS_MODE_ABSGRAD, GS_MODE_ADC_STATS, GS_MODE_DISTORTION}))
         return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_begin", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;
@@ -1587,7 +1702,7 @@ int gs_render_backward_dp_geom(gs_ctx* c, const float* cot_color, const float* c
 {
     if (!c) return GS_ERR_INVALID_ARG;
     if (const int rc = refuse_modes(c, "gs_render_backward_dp_geom", {GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_SPARSE_ADAM,
-                                                                  GS_MODE_ABSGRAD, GS_MODE_ADC_STATS}))
+                                                                  GS_MODE_ABSGRAD, GS_MODE_ADC_STATS, GS_MODE_DISTORTION}))
         return rc;
     { const int prc = backward_preflight(c, "gs_render_backward_dp_geom", cot_depth != nullptr); if (prc) return prc; }
     const int N = c->fwd.N;

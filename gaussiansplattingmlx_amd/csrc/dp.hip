@@ -372,7 +372,7 @@ int gs_dp_step(gs_ctx* c, int mode, const gs_dp_step_args* a)
     if (!c) return GS_ERR_INVALID_ARG;
     GsDp* d = c->dp;
     if (const int rc = gs::refuse_modes(c, "gs_dp_step", {gs::GS_MODE_POSE, gs::GS_MODE_FILTER3D, gs::GS_MODE_FISHEYE, gs::GS_MODE_ABSGRAD,
-                                                          gs::GS_MODE_ADC_STATS, gs::GS_MODE_SPARSE_ADAM}))
+                                                          gs::GS_MODE_ADC_STATS, gs::GS_MODE_SPARSE_ADAM, gs::GS_MODE_DISTORTION}))
         return rc;
     if (!d) { c->err = "gs_dp_step: no communicator (gs_dp_init / gs_dp_attach)"; return GS_ERR_INVALID_ARG; }
     if (!a || (mode != GS_DP_ALLREDUCE && mode != GS_DP_SH_COMPRESSED)) { c->err = "gs_dp_step: bad mode / arguments"; return GS_ERR_INVALID_ARG; }

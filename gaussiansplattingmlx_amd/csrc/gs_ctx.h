@@ -345,6 +345,15 @@ struct gs_ctx {
     float* normalWs = nullptr;        // gs_normal_loss: [normalWsFloats] the normals and q, 7 floats per pixel, allocated at the first
     long long normalWsFloats = 0;     //   call, regrown only for a larger image; normalPartials: [normal_loss_ws_doubles()]
     double* normalPartials = nullptr;
+    double* distortionWs = nullptr;   // gs_distortion_loss: [distortion_loss_ws_doubles()] per-block partial sums, allocated at the first call
+    // gs_arm_distortion: the distortion term of the current forward (host state only: an unarmed backward launches nothing more);
+    // cot [H, W] and totals [H, W, 3] are the caller's, read by the distortion backward behind the blend backward
+    struct {
+        bool armed = false;
+        gs_distortion_params params = {};
+        const float* cot = nullptr;
+        const float* totals = nullptr;
+    } distortion;
     double* metricsWs = nullptr;      // gs_image_metrics / gs_colour_moments: [metricsWsDoubles] per-block partials, allocated at the
     long long metricsWsDoubles = 0;   //   first call, regrown only for a larger image (metrics.hip metrics_ws_doubles)
     float* windowDev = nullptr;       // [121] default SSIM window
@@ -515,7 +524,8 @@ namespace gs {
 // api.hip: the refusal that api.hip and dp.hip share (host code).  GS_ERR_INVALID_ARG with the message of the first of `unserved`
 // that is in force -- set now or, for pose, filter and fisheye, what the last forward ran with; `who` is the entry point's name, in
 // front of the message
-enum GsMode { GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_ABSGRAD, GS_MODE_SPARSE_ADAM, GS_MODE_ADC_STATS };
+enum GsMode { GS_MODE_POSE, GS_MODE_FILTER3D, GS_MODE_FISHEYE, GS_MODE_ABSGRAD, GS_MODE_SPARSE_ADAM, GS_MODE_ADC_STATS,
+              GS_MODE_DISTORTION };
 int refuse_modes(gs_ctx* c, const char* who, std::initializer_list<GsMode> unserved);
 int forward_in_arena(gs_ctx* c, const char* who, const float* params_base, long long n_arena);      // the forward's six tensors
 
@@ -620,6 +630,15 @@ int launch_contrib_actions(gs_ctx* c, int N, const float* score, float threshold
 int launch_blend_features(gs_ctx* c, int C, const float* features, float* out);
 int launch_blend_features_backward(gs_ctx* c, int C, const float* cot, float* grad);
 int feature_channel_group();
+
+// distortion.hip: the depth distortion image D [H, W] and the pixels' totals (A, mu, S) [H, W, 3] over the lists of the last
+// binning (both fully written), their gradient into rows of 16 floats in gradAcc16's column order (accumulates), and the
+// term's loss sum and cotangent image
+int launch_blend_distortion(gs_ctx* c, const gs_distortion_params& p, float* outDistort, float* outTotals);
+int launch_blend_distortion_backward(gs_ctx* c, const gs_distortion_params& p, const float* cot, const float* totals, float* rows16);
+long long distortion_loss_ws_doubles();
+int launch_distortion_loss(gs_ctx* c, float weight, long long n, const float* distort, const unsigned char* mask, float* loss,
+                           float* cotOut);
 
 // blend_v2.hip (fused fast path)
 int launch_blend_forward_v2(gs_ctx* c, float* outColor, float* outDepth, float* outAlpha);

@@ -13,7 +13,8 @@ It hands the blend backward the cotangents of D and a.  This module holds the tr
 restates the kernels in numpy.
 
 Not here: normals rendered from the Gaussians' own axes and 2DGS's consistency between them and the depth
-normals, the distortion loss, median depth, fisheye cameras, data-parallel and multi-view steps.
+normals, median depth, fisheye cameras, data-parallel and multi-view steps.  The depth distortion loss these methods train with
+beside it is distortion.py's (GaussianTrainer(distortion=DistortionConfig(...))).
 """
 from __future__ import annotations
 

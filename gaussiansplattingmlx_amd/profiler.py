@@ -21,6 +21,7 @@ DEVICE_SECTIONS = {
     "bwd.globalTileComposite": ("blend_bwd",),
     "bwd.projectionScreenFused": ("proj_bwd",),
     "train.optimizer.applySingle": ("adam",),
+    "train.backward.distortion": ("distortion_bwd",),     # inside bwd.globalTileComposite's interval, which includes it
 }
 
 

@@ -117,6 +117,7 @@ class GaussianRenderer:
         self._exposure = (None, None)  # setExposure's tensors while the library holds their addresses
         self._bilateral = (None, None)  # setBilateralGrid's, likewise
         self._loss_mask = None         # setLossMask's uint8 device tensor, likewise
+        self._distortion_armed = None  # armDistortion's (cot, totals), likewise, until the next arming
         if antialiased:
             self.setAntialiased(True)
 
@@ -421,6 +422,115 @@ class GaussianRenderer:
         return self._features_backward("renderFeaturesVJP", N, cot, grad,
                                        lambda C_, ct, g: self.lib.gs_render_features_backward(self.ctx, C_, ct, g))
 
+    # -- depth distortion loss (include/gsplat.h gs_blend_distortion; distortion.py) ------------
+    @staticmethod
+    def distortionParams(map="ndc", near: float = 0.2, far: float = 1000.0):
+        """gs_distortion_params: the depth map by name (distortion.MAPS) and the "ndc" map's planes."""
+        from .distortion import MAPS
+        if map not in MAPS:
+            raise ValueError(f"distortionParams: unknown map {map!r} (one of {', '.join(MAPS)})")
+        return _lib.gs_distortion_params(MAPS.index(map), float(near), float(far))
+
+    def _distortion_params(self, params):
+        if params is None:
+            return self.distortionParams()
+        return params if isinstance(params, _lib.gs_distortion_params) else self.distortionParams(**params)
+
+    def _image_arg(self, who, name, t, per_pixel=1):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.numel() == self.H * self.W * per_pixel):
+            raise ValueError(f"{who}: {name} must be a contiguous float32 device tensor of {self.H} x {self.W}"
+                             + (f" x {per_pixel}" if per_pixel > 1 else "") + " elements")
+
+    def _distortion_forward(self, who, params, out, totals, call):
+        out = self._empty(self.H, self.W) if out is None else out
+        totals = self._empty(self.H, self.W, 3) if totals is None else totals
+        self._image_arg(who, "out", out)
+        self._image_arg(who, "totals", totals, 3)
+        p = self._distortion_params(params)
+        self._check(call(C.byref(p), _p(out), _p(totals)))
+        return out, totals
+
+    def _distortion_backward(self, who, N, params, cot, totals, rows, call):
+        self._image_arg(who, "cot", cot)
+        self._image_arg(who, "totals", totals, 3)
+        if rows is None:
+            rows = torch.zeros((N, 16), dtype=torch.float32, device=self.device)
+        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous()
+                and tuple(rows.shape) == (N, 16)):
+            raise ValueError(f"{who}: rows must be a contiguous float32 device tensor [{N}, 16]")
+        p = self._distortion_params(params)
+        self._check(call(C.byref(p), _p(cot), _p(totals), _p(rows)))
+        return rows
+
+    def blendDistortion(self, packedGaussians, params=None, out=None, totals=None):
+        """(D [H, W], totals [H, W, 3]) of the view whose lists the last buildGlobalTileSliceInfo built: the depth distortion
+        D = sum_{i<j} w_i w_j (m_i - m_j)^2 of every pixel (2DGS eq. 13, gsplat's distloss) with blendContrib's weights, and
+        the pixel's (A, mu, S), the backward's input.  params: distortionParams(...), a dict of its arguments, or None for its
+        defaults.  Every pixel of both is written (None allocates); the same bits on every run."""
+        packed = self._t(packedGaussians)
+        N = int(packed.shape[0])
+        return self._distortion_forward("blendDistortion", params, out, totals,
+                                        lambda p, o, t: self.lib.gs_blend_distortion(self.ctx, N, _p(packed), p, o, t))
+
+    def blendDistortionVJP(self, packedGaussians, cot, totals, params=None, rows=None):
+        """The gradient of sum_p cot[p] D[p] with respect to the packed records, as rows [N, 16] in the column order of the blend
+        backward's accumulator (dmx dmy dc00 dc01 | dc10 dc11 dr dg | db dop ddepth): columns 0 .. 5, 9 and 10 ACCUMULATE
+        (rows=None: zeros are allocated), the others are not touched.  totals: what blendDistortion returned."""
+        packed = self._t(packedGaussians)
+        N = int(packed.shape[0])
+        return self._distortion_backward("blendDistortionVJP", N, params, cot, totals, rows,
+                                         lambda p, c, t, r: self.lib.gs_blend_distortion_backward(self.ctx, N, _p(packed), p, c, t, r))
+
+    def renderDistortion(self, params=None, out=None, totals=None):
+        """blendDistortion for the view of the last renderForward / renderChecked, on that forward's own records and lists (its
+        anti-aliased opacity, 3-D filter and pose correction included).  Consumes nothing: a renderBackward may follow."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "renderDistortion: no renderForward on this renderer")
+        return self._distortion_forward("renderDistortion", params, out, totals,
+                                        lambda p, o, t: self.lib.gs_render_distortion(self.ctx, p, o, t))
+
+    def renderDistortionVJP(self, cot, totals, params=None, rows=None):
+        """blendDistortionVJP for the view of the last renderForward / renderChecked.  ACCUMULATES into rows [N, 16]."""
+        if getattr(self, "_fused", None) is None:
+            raise GsplatError(5, "renderDistortionVJP: no renderForward on this renderer")
+        N = int(self._fused["params"]["xyz"].shape[0])
+        return self._distortion_backward("renderDistortionVJP", N, params, cot, totals, rows,
+                                         lambda p, c, t, r: self.lib.gs_render_distortion_backward(self.ctx, p, c, t, r))
+
+    def distortionLoss(self, distort, weight: float, mask=None, loss=None, cot=None):
+        """gs_distortion_loss on a distortion image [H, W]: returns (loss, cot) with loss[0] += weight (1 / (H W)) sum_p v_p D_p
+        and cot [H, W] = weight v_p / (H W), v = mask / 255 of an optional uint8 device tensor [H, W] (None: 1).  loss: the
+        float tensor a lossForwardBackward has written (zeros of one element without it); cot=None allocates."""
+        self._image_arg("distortionLoss", "distort", distort)
+        if mask is not None and not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.uint8
+                                     and mask.is_contiguous() and mask.numel() == self.H * self.W):
+            raise ValueError(f"distortionLoss: mask is a contiguous uint8 device tensor [{self.H}, {self.W}], or None")
+        if loss is None:
+            loss = torch.zeros(1, device=self.device)
+        if not (isinstance(loss, torch.Tensor) and loss.is_cuda and loss.dtype == torch.float32 and loss.numel() >= 1):
+            raise ValueError("distortionLoss: loss is a float32 device tensor of at least one element")
+        cot = self._empty(self.H, self.W) if cot is None else cot
+        self._image_arg("distortionLoss", "cot", cot)
+        self._check(self.lib.gs_distortion_loss(self.ctx, C.c_float(weight), self.H * self.W, _p(distort), _p(mask), _p(loss),
+                                                _p(cot)))
+        return loss, cot
+
+    def armDistortion(self, cot=None, totals=None, params=None):
+        """Arms the distortion term for the current forward: the next renderBackward / renderBackwardAdam of it adds
+        renderDistortionVJP(cot, totals) to the library's own accumulator rows, behind the blend backward and in front of the
+        ADC statistic and the projection backward.  cot and totals None: disarms (a new renderForward disarms too).  The two
+        tensors are held until then."""
+        if cot is None and totals is None:
+            self._check(self.lib.gs_arm_distortion(self.ctx, None, None, None))
+            self._distortion_armed = None
+            return
+        self._image_arg("armDistortion", "cot", cot)
+        self._image_arg("armDistortion", "totals", totals, 3)
+        p = self._distortion_params(params)
+        self._check(self.lib.gs_arm_distortion(self.ctx, C.byref(p), _p(cot), _p(totals)))
+        self._distortion_armed = (cot, totals)      # (the library holds their addresses)
+
     # -- render / forward (GaussianRenderer.swift:736-934) ---------------------------------------------------
     def render(self, imageWidth, imageHeight, means2d, cov2d, color, opacity, depths, radii, conic, rect,
                inputIsDepthSorted: bool = False):
@@ -579,7 +689,7 @@ class GaussianRenderer:
         self._check(self.lib.gs_copy_last_contrib(self.ctx, _p(out)))
         return out
 
-    STAGES = ("proj_fwd", "bin", "blend_fwd", "loss", "blend_bwd", "proj_bwd", "adam")
+    STAGES = ("proj_fwd", "bin", "blend_fwd", "loss", "blend_bwd", "proj_bwd", "adam", "distortion_bwd")
 
     def profile(self, stages=True):
         """stages: True = all, False/None = off, or an iterable of stage names."""

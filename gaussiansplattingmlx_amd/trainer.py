@@ -535,6 +535,7 @@ _FEATURES = {
     "sh_schedule": ((".sh_schedule", "an SHDegreeSchedule"), "sh_schedule", (), False),
     "depth": ((".depth_loss", "a DepthConfig"), "depth", (), False),
     "normal": ((".normal_loss", "a NormalConfig"), "normal", (), False),
+    "distortion": ((".distortion", "a DistortionConfig"), "distortion", (), False),
     "background": ((".background", "a BackgroundConfig"), "background", (), False),
     "sparse_adam": (None, "sparse_adam", (
         ("mcmc", "sparse_adam: the reference strategy only (strategy='mcmc' moves every Gaussian every step)"),
@@ -584,7 +585,8 @@ class GaussianTrainer:
                  exposure_opt: bool = False, exposure_lr=(0.01, 0.001), bilateral_grid: bool = False,
                  bilateral_grid_shape=(16, 16, 8), bilateral_grid_lr: float = 2e-3, bilateral_grid_tv: float = 10.0,
                  filter_3d: bool = False, filter_cameras=None, filter_3d_interval: int = 100, contrib_prune=None,
-                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None, sh_schedule=None, normal=None):
+                 absgrad=None, sparse_adam: bool = False, background=None, depth=None, adc=None, sh_schedule=None, normal=None,
+                 distortion=None):
         """exchange_impl: who issues the collectives of a data-parallel step.  "torch": torch.distributed on
         process_group (RCCL when its backend is nccl; gloo for CPU rehearsals).  "native": the library itself
         (gs_dp_step: RCCL on its own side stream, the same event ordering) -- process_group is then only used to hand
@@ -726,6 +728,18 @@ class GaussianTrainer:
         single-device steps with one view only.  Before normal.start, and with None (the default): no kernel, launch, buffer
         or result differs.
 
+        distortion: the depth distortion loss (distortion.DistortionConfig, include/gsplat.h gs_render_distortion /
+        gs_arm_distortion; 2DGS eq. 13, gsplat's distloss, which GOF, PGSR and RaDe-GS train with too).
+        From iteration distortion.start on every step, once its forward is final -- behind the depth-cut miss check, so on the
+        lists of the forward the backward runs on --, renders the distortion image D (renderDistortion), adds
+        weight mean(v D) to loss[0] under the step's lossMask (distortionLoss; v = 1 without one) and arms the term
+        (armDistortion): the step's usual backward then adds the term's gradient to the per-Gaussian rows between the blend
+        backward and the projection backward (+ Adam), in front of the ADC statistic.  distortionTerm() is the last mean D.
+        The forward need not render a depth image.  Pinhole cameras only.  It composes with every strategy, depth=, normal=,
+        sparse_adam, sh_schedule, the per-view corrections, absgrad (whose absolute sums stay the colour and depth terms'),
+        an anti-aliased renderer and fuse_adam on or off; single-device steps with one view only.  Before distortion.start,
+        and with None (the default): no kernel, launch, buffer, setter call or result differs.
+
         strategy="adc", adc: adaptive density control, the densification of the original 3DGS (adc.ADCConfig, include/gsplat.h
         gs_set_adc_stats; Inria's densify_and_prune and reset_opacity, gsplat's DefaultStrategy) with the
         settings `adc` -- required, for its scene_extent (adc.scene_extent(cameras)).  The trainer owns three [N] accumulators
@@ -770,6 +784,9 @@ class GaussianTrainer:
         self._bgTarget = None
         self._bgSource = None
         self.sh_schedule, self.depth, self.normal = admit("sh_schedule", sh_schedule), admit("depth", depth), admit("normal", normal)
+        self.distortion = admit("distortion", distortion)
+        self._distortionStep = None     # the running step's distortion term, from iteration distortion.start on (as _normalStep)
+        self._distortionBufs = None     # (D, totals, cot) on the device, allocated by the first step that runs the term
         self.background = admit("background", background)
         if not isinstance(sparse_adam, bool):
             raise ValueError("sparse_adam is True or False")
@@ -1856,6 +1873,10 @@ class GaussianTrainer:
             raise ValueError("trainStep: normal= takes pinhole cameras only (the normals of a depth image are taken along "
                              "pinhole rays; a fisheye camera is not served)")
         normalOn = normal is not None and self.iteration >= normal.start
+        distortion = self.distortion
+        if distortion is not None and getattr(camera, "model", "pinhole") != "pinhole":
+            raise ValueError("trainStep: distortion= takes pinhole cameras only (the depth of a fisheye record is a ray length, "
+                             "which the maps are not defined on; a fisheye camera is not served)")
         profiled = self.enableIntervalProfiling and (self.iteration % self.profilingLogInterval == 0
                                                      or self.iteration == self.iterationCount - 1)
         step = self._profiledStep if profiled else (self._trainStepMulti if self.viewsPerRank > 1 else self._trainStep)
@@ -1879,7 +1900,9 @@ class GaussianTrainer:
                 lent.set(depth_gradient=0 if depth is None and not normalOn else 1)
                 if normalOn:
                     self._normalStep = self._normalInputs(camera, targetRGB, targetNormal, normalMask)
-                if self.mcmc is not None:       # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
+                if distortion is not None and self.iteration >= distortion.start:
+                    self._distortionStep = self._distortionInputs()
+                if self.mcmc is not None:      # the strategy's step in the fused backward + Adam (the unfused step calls the ops)
                     lent.set(mcmc=self._mcmcParams())
                 if self.filter_3d:
                     lent.set(filter_3d=self._filter)
@@ -1898,7 +1921,33 @@ class GaussianTrainer:
                         self._collectiveOverflowCheck()
                 return self._retryOnOverflow(lambda: step(camera, targetRGB, stepCameras, viewKey), recover=not self._exchange)
             finally:
-                self._depthStep = self._normalStep = None
+                self._depthStep = self._normalStep = self._distortionStep = None
+
+    def _distortionInputs(self):
+        """The step's gs_distortion_params and weight.  The first step that runs the term allocates its three images: D, the
+        pixels' totals and the cotangent."""
+        r, cfg = self.gaussRender, self.distortion
+        if self._distortionBufs is None:
+            self._distortionBufs = (r._empty(r.H, r.W), r._empty(r.H, r.W, 3), r._empty(r.H, r.W))
+        return dict(params=cfg.params(), weight=float(cfg.weight))
+
+    def _distortionLoss(self, lossOut):
+        """The distortion term of the step's FINAL forward (behind the depth-cut miss check: its lists are the ones the backward
+        sweeps): D and the totals, weight mean(v D) into lossOut[0] under the step's loss mask, and the term armed for the
+        step's backward."""
+        r, d = self.gaussRender, self._distortionStep
+        D, totals, cot = self._distortionBufs
+
+        def body():
+            r.renderDistortion(d["params"], D, totals)
+            r.distortionLoss(D, d["weight"], r.lossMask, lossOut, cot)
+            r.armDistortion(cot, totals, d["params"])
+        r._measure("train.loss.distortion", body)
+
+    def distortionTerm(self):
+        """The mean of the distortion image D over all pixels (no mask, no weight) of the last step that ran the term, a 0-dim
+        device tensor; None before the first."""
+        return None if self._distortionBufs is None else self._distortionBufs[0].mean()
 
     def _depthInputs(self, targetDepth, depthMask, depthAlign):
         """The step's depth target and mask on the device and its gs_depth_loss_params."""
@@ -2127,6 +2176,8 @@ class GaussianTrainer:
             r.lossForwardBackward(res.render, targetRGB, self.lambda_dssim, out=dict(loss=lossOut, cotColor=self._cot),
                                   targetKey=self._lossTargetKey(viewKey))
             self._depthTerms(res, lossOut)
+        if self._distortionStep is not None:       # on the final forward's lists: not in _depthTerms, which runs before the check
+            self._distortionLoss(lossOut)
 
     def _depthTerms(self, res, lossOut):
         """The terms on the render's depth and alpha images, behind the colour loss: the depth term, then the normal term."""

@@ -295,6 +295,73 @@ int gs_render_features(gs_ctx* ctx, int C, const float* features /*DEVICE [N,C]*
 int gs_render_features_backward(gs_ctx* ctx, int C, const float* cot /*DEVICE [H,W,C]*/,
                                 float* grad_features /*DEVICE [N,C], accumulates*/);
 
+/* The depth distortion loss (not in the reference): 2DGS's eq. 13, gsplat's `distloss`, which GOF, PGSR
+ * and RaDe-GS train with as well.  It pulls the blend weights of a ray together in depth.  Per pixel, over the entries i of its
+ * list up to its stop, with gs_blend_contrib's weights w_i = T_i alpha_i (its rule to the bit: clamp at 0.99, the pixel stops
+ * after the entry that brings T below 1e-4, no background) and the mapped depth m_i = map(z_i) of the record's depth (column 10):
+ *   D = sum_{i<j} w_i w_j (m_i - m_j)^2 = A S,    A = sum w_i,  mu = sum w_i m_i / A,  S = sum w_i (m_i - mu)^2
+ * -- 2DGS's convention: every unordered pair once, the weights not normalised.  (A, mu, S) are carried with the weighted Welford
+ * update A' = A + w, mu' = mu + (w / A') (m - mu), S' = S + w (m - mu) (m - mu'), which cancels nothing on thin distributions
+ * (A M2 - M1^2 and 2DGS's running prefix form both do, in float32); it runs on m - c, c the m of the pixel's first weighted
+ * entry, so that the running mean is as small as the deviations (the reported mu is c + mu).  The derivatives by the totals,
+ *   dD/dw_i = g_i = A (m_i - mu)^2 + S,   dD/dm_i = 2 w_i A (m_i - mu),   dD/dalpha_i = T_i g_i - R_i / (1 - alpha_i),
+ *   R_i = sum_{j>i} g_j w_j = 2 D - sum_{j<=i} g_j w_j,
+ * go from alpha_i into mean, conic and opacity with gs_blend_backward's derivatives and clamp rule (the clamp passes the gradient
+ * iff raw <= 0.99, the floor of 1 - alpha is 1e-6) and from m_i into the record's depth through map'(z).
+ *   GS_DISTORTION_NDC     m = far / (far - near) (1 - near / z)     2DGS's map; its defaults are near 0.2, far 1000
+ *   GS_DISTORTION_LINEAR  m = z                                     gsplat's; near and far are not read
+ * Forward: out_distort DEVICE [H, W] = D and out_totals DEVICE [H, W, 3] = (A, mu, S), the backward's input; every pixel is
+ * written (zeros where nothing blends; the caller does not clear) without atomics: the same bits on every run.
+ * Backward: cot DEVICE [H, W] is dL/dD (finite), totals what the forward wrote; rows16 DEVICE [N, 16] ACCUMULATES with float
+ * atomics in the column order of the blend backward's accumulator,
+ *   dmx dmy dc00 dc01 | dc10 dc11 dr dg | db dop ddepth . | . . . .
+ * of which columns 0 .. 5, 9 and 10 are added to (dc10 = dc01); the colour columns and columns 11 .. 15 are not touched, nor
+ * are rows of Gaussians in no list or behind every pixel's stop.  One pass over the tile lists of the last gs_tile_bin /
+ * gs_tile_bin_cut each.  Preconditions and codes as gs_blend_contrib; GS_ERR_INVALID_ARG also for a NULL params or buffer, a map
+ * out of range, or -- GS_DISTORTION_NDC -- near, far not finite or not 0 < near < far.  Every tile size gs_ctx_create accepts is
+ * supported.  No sync, no allocation. */
+enum { GS_DISTORTION_NDC = 0, GS_DISTORTION_LINEAR = 1 };
+typedef struct gs_distortion_params {
+    int map;
+    float near, far;
+} gs_distortion_params;
+int gs_blend_distortion(gs_ctx* ctx, int N, const float* packed /*[N,11]*/, const gs_distortion_params* params /*HOST*/,
+                        float* out_distort /*DEVICE [H,W]*/, float* out_totals /*DEVICE [H,W,3]*/);
+int gs_blend_distortion_backward(gs_ctx* ctx, int N, const float* packed /*[N,11]*/, const gs_distortion_params* params /*HOST*/,
+                                 const float* cot /*DEVICE [H,W]*/, const float* totals /*DEVICE [H,W,3]*/,
+                                 float* rows16 /*DEVICE [N,16], accumulates*/);
+/* gs_blend_distortion / gs_blend_distortion_backward (2DGS eq. 13 / gsplat distloss) for the last gs_render_forward's view, on
+ * that forward's own records and lists (its anti-aliased opacity, 3-D filter and pose correction included; trimmed rects and
+ * depth cuts as for gs_render_features).  rows16 is DEVICE [N of the forward, 16].  Refuse what gs_render_features refuses, with
+ * the same codes.  Consume nothing: a backward and further calls on the same forward may follow, the render outputs and
+ * gs_last_stats are untouched.  No sync, no allocation. */
+int gs_render_distortion(gs_ctx* ctx, const gs_distortion_params* params /*HOST*/, float* out_distort /*DEVICE [H,W]*/,
+                         float* out_totals /*DEVICE [H,W,3]*/);
+int gs_render_distortion_backward(gs_ctx* ctx, const gs_distortion_params* params /*HOST*/, const float* cot /*DEVICE [H,W]*/,
+                                  const float* totals /*DEVICE [H,W,3]*/, float* rows16 /*DEVICE [N,16], accumulates*/);
+/* The distortion term of a step's loss (2DGS eq. 13 as a loss, gsplat's distloss().mean()):
+ *   L = weight (1 / n_pixels) sum_p v_p D_p,    cot_out[p] = dL/dD_p = weight v_p / n_pixels,
+ * v_p = (float)mask[p] / 255.0f as gs_set_loss_mask's weights (255 is exactly 1, 0 exactly 0; it is this call's own argument),
+ * 1 with mask NULL; divided by all n_pixels, as the masked colour loss is.  loss[0] += L (read and written: the call is queued
+ * behind the loss that wrote it).  Every element of cot_out is written.  Two launches, the sum in double over per-block
+ * partials finished in a fixed order, no float atomics: two calls on the same inputs give the same bits.  The first call
+ * allocates 4 KB of workspace, no later one allocates; no wait.  GS_ERR_INVALID_ARG: n_pixels < 0, a weight that is not finite,
+ * a NULL distort, loss or cot_out; n_pixels == 0: nothing is launched. */
+int gs_distortion_loss(gs_ctx* ctx, float weight, long long n_pixels, const float* distort /*DEVICE [n]*/,
+                       const unsigned char* mask /*DEVICE [n] or NULL*/, float* loss /*DEVICE, accumulates into [0]*/,
+                       float* cot_out /*DEVICE [n]*/);
+/* Arms the distortion term (2DGS eq. 13 / gsplat distloss) for the current forward: the next gs_render_backward or
+ * gs_render_backward_adam of it runs gs_render_distortion_backward(params, cot, totals) into the context's own accumulator rows,
+ * directly behind the blend backward that fills them and in front of the ADC statistic (gs_set_adc_stats) and the projection
+ * backward that read them -- the signed 2-D mean gradient ADC averages then includes the term, as gsplat's means2d.grad does.
+ * Columns 12 and 13 of the rows (the AbsGS sums of gs_set_absgrad) stay the colour and depth terms' alone.  The depth column is
+ * read by the projection backward of every forward, so the forward need not have rendered a depth image.  cot and totals are
+ * DEVICE [H, W] and [H, W, 3], read when the backward runs.  params, cot and totals all NULL: disarms.  A new gs_render_forward
+ * disarms too.  The gs_render_backward_dp* family refuses an armed context (GS_ERR_INVALID_ARG): single-device steps only.
+ * Refuses what gs_render_features refuses, with the same codes; params as for gs_blend_distortion.  Launches nothing. */
+int gs_arm_distortion(gs_ctx* ctx, const gs_distortion_params* params /*HOST*/, const float* cot /*DEVICE [H,W]*/,
+                      const float* totals /*DEVICE [H,W,3]*/);
+
 /* Per-view camera pose refinement (not in the reference; DESIGN.md "Pose refinement").  delta DEVICE [6] = (w, tau), float32,
  * a correction of the camera-to-world pose in the camera's own OpenCV frame (x right, y down, z forward):
  *   c2w' = c2w [[R(w), tau], [0, 1]],  R(w) Rodrigues' rotation (its series near w = 0: R(0) = I exactly),
@@ -1287,6 +1354,8 @@ typedef enum gs_stage {
     GS_STAGE_BLEND_BWD = 4,
     GS_STAGE_PROJ_BWD = 5,
     GS_STAGE_ADAM = 6,
+    GS_STAGE_DISTORTION_BWD = 7,   /* the armed distortion backward (gs_arm_distortion); it runs inside GS_STAGE_BLEND_BWD's
+                                      interval, which then includes it */
     GS_STAGE_COUNT = 8
 } gs_stage;
 /* stage_mask: bit s set = record stage s (clears what was recorded); 0 = stop.  Each recorded stage costs two
